@@ -13,7 +13,7 @@ A "step" = PASSES (default 16) passes of the pipeline over a batch of FRAMES_PER
 timed region, like apps/local_laplacian/process.cpp:31-39 where the first call pays the copies and `benchmark()` times
 calls + device_sync).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 `--gpus N` is the whole command for any N: when the script is not already running under a launcher it starts N ranks of
 itself under `python -m torch.distributed.run` (one process per GPU, rendezvous on 127.0.0.1) and refuses when fewer than
@@ -45,6 +45,19 @@ ALG_BYTES_PER_PX = 12         # SURVEY.md §8(d) primary figure: 6 B read + 6 B 
 
 
 HEADLINE_KIND = "noise"
+DUMP_BUDGET_VALUES = 8 << 20  # float32 values written by --dump-outputs over all ranks: 32 MiB, under the 64 MB cap
+
+
+def dump_outputs(out_dir, frame_ids, outs, total_frames):
+    """--dump-outputs: the output frames of this rank as the last timed step left them (u16, what the caller receives), as
+    float32 at a fixed sample of flat positions (seed 0, the same in every run and build: the frames are ~25 M values each),
+    one DIR/local_laplacian_frame<NNN>.npy per global frame index."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = C * H * W
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_BUDGET_VALUES // total_frames), replace=False))
+    for i, o in zip(frame_ids, outs):
+        np.save(os.path.join(out_dir, f"local_laplacian_frame{i:03d}.npy"), o.numpy().reshape(-1)[idx].astype(np.float32))
 
 
 def synth_frame(seed, w=W, h=H, kind="smooth"):
@@ -222,7 +235,12 @@ def main():
                     help="replicas of each frame queue (more queues of the same kind)")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("HLMI_BENCH_STREAMS", "2")),
                     help="with --partitions 0: plain HIP streams the frames of a step are spread over")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed seeded sample of every output frame of the last step as "
+                         "float32 DIR/local_laplacian_frame<NNN>.npy (inputs are seeded: runs with the same arguments compare)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from halide_amd import launcher
     launcher.ensure_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:])   # N > 1 and no launcher yet: start N ranks, exit
@@ -341,6 +359,8 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
     elapsed = sharding.max_over_ranks(elapsed, dist, "cuda")
+    if args.dump_outputs:   # before the untimed legs below rewrite the outputs
+        dump_outputs(args.dump_outputs, mine, outs, world * FRAMES_PER_STEP)
 
     # --- per-kernel durations: HIP events around every launch on the launch stream, in a separate untimed pass on ONE
     #     stream (kernels of different frames must not overlap while a single kernel is being timed)

@@ -105,7 +105,37 @@ def natural_image():
     return True
 
 
+def reference_runtime(ref_root):
+    """tests/golden/reference_runtime.json: what the reference's runtime header and RunGen say about this library, for the
+    CPU tests (tests/test_reference_consumers.py, tests/test_abi_layout.py) on a box without the reference checkout — the values of the
+    halide_error_code_t enumerators include/hlmi_abi.h declares, compiled against the reference's src/runtime/HalideRuntime.h,
+    the `--describe` output of oracle/_ref/<name>.rungen (the reference's RunGen reading this library's metadata) and what
+    tests/test_abi_layout.py's probe prints for the reference header."""
+    import re
+    import subprocess
+    import tempfile
+    names = sorted(set(re.findall(r"\b(halide_error_code_\w+) =", open(os.path.join(ROOT, "include", "hlmi_abi.h")).read())))
+    with tempfile.TemporaryDirectory() as td:
+        src = os.path.join(td, "p.cpp")
+        with open(src, "w") as f:
+            f.write('#include <cstdio>\n#include "HalideRuntime.h"\nint main() {\n')
+            f.write("".join(f'  printf("{n} %d\\n", (int){n});\n' for n in names) + "  return 0;\n}\n")
+        subprocess.run(["g++", "-std=c++17", "-I", os.path.join(ref_root, "src", "runtime"), src, "-o", os.path.join(td, "p")], check=True)
+        out = subprocess.run([os.path.join(td, "p")], check=True, capture_output=True, text=True).stdout
+    codes = {n: int(v) for n, v in (line.split() for line in out.splitlines())}
+    describe = {n: subprocess.run([os.path.join(ROOT, "oracle", "_ref", f"{n}.rungen"), "--describe"], check=True,
+                                  capture_output=True, text=True).stdout for n in ("local_laplacian", "camera_pipe")}
+    import test_abi_layout
+    layout, layout_codes = test_abi_layout._probe("HalideRuntime.h", os.path.join(ref_root, "src", "runtime"))
+    with open(os.path.join(ROOT, "tests", "golden", "reference_runtime.json"), "w") as f:
+        json.dump({"error_codes": codes, "rungen_describe": describe, "abi_layout": layout, "abi_layout_codes": layout_codes},
+                  f, indent=1)
+
+
 if __name__ == "__main__":
+    if "--reference-runtime" in sys.argv:   # make_golden.py --reference-runtime <reference checkout>, after `make -C oracle ref`
+        reference_runtime(sys.argv[sys.argv.index("--reference-runtime") + 1])
+        sys.exit(0)
     if "--natural" in sys.argv:
         print("natural image fixture:", natural_image())
         sys.exit(0)

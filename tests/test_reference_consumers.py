@@ -11,10 +11,14 @@
 * `device_interface_test` (tests/cpp): device_crop / device_slice / release_crop / buffer_copy /
   device_and_host_malloc / wrap_native through the reference's Halide::Runtime::Buffer, plus cross-stream ordering.
 
-A missing binary is a failure: they are built by __graft_entry__.build() and travel to the GPU box.
+A missing binary is a failure in the GPU tests: they are built by __graft_entry__.build() and travel to the GPU box.  The two
+CPU tests also hold where there is no reference checkout to build them from: what the binaries showed is pinned in
+tests/golden/reference_runtime.json (scripts/make_golden.py --reference-runtime), and each runs the binary too where it exists.
 """
+import json
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 import pytest
@@ -39,20 +43,47 @@ def _run(name, *args, timeout=600):
     return subprocess.run([_exe(name), *args], capture_output=True, text=True, timeout=timeout)
 
 
+with open(os.path.join(ROOT, "tests", "golden", "reference_runtime.json")) as f:
+    GOLDEN = json.load(f)
+
+
+def _own_error_codes():
+    """The halide_error_code_t values of include/hlmi_abi.h, the re-declaration the library is built against."""
+    with tempfile.TemporaryDirectory() as td:
+        src = os.path.join(td, "p.cpp")
+        with open(src, "w") as f:
+            f.write('#include <cstdio>\n#include "hlmi_abi.h"\nint main() {\n')
+            f.write("".join(f'  printf("{n} %d\\n", (int){n});\n' for n in GOLDEN["error_codes"]) + "  return 0;\n}\n")
+        subprocess.run(["g++", "-std=c++17", "-I", os.path.join(ROOT, "include"), src, "-o", os.path.join(td, "p")], check=True)
+        out = subprocess.run([os.path.join(td, "p")], check=True, capture_output=True, text=True).stdout
+    return {n: int(v) for n, v in (line.split() for line in out.splitlines())}
+
+
 def test_error_codes_replay_with_the_reference_header():
-    """No GPU needed: every case fails in the prologue."""
-    r = _run("entry_protocol_ref", "errors")
-    assert r.returncode == 0 and "Success!" in r.stdout, r.stdout + r.stderr
+    """No GPU needed: every case fails in the prologue.  The codes the library returns are the values of include/hlmi_abi.h
+    (tests/test_entry_protocol.py replays the same cases through every entry point); those are the reference header's."""
+    assert _own_error_codes() == GOLDEN["error_codes"]
+    if os.path.exists(os.path.join(REF_BIN, "entry_protocol_ref")):
+        r = _run("entry_protocol_ref", "errors")
+        assert r.returncode == 0 and "Success!" in r.stdout, r.stdout + r.stderr
 
 
 def test_reference_rungen_describe_reads_our_metadata():
-    r = _run("local_laplacian.rungen", "--describe")
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert 'Filter name: "local_laplacian"' in r.stdout
-    assert 'Input "input" is of type Buffer<uint16> with 3 dimensions' in r.stdout
-    assert 'Input "levels" is of type int32' in r.stdout and 'Output "output" is of type Buffer<uint16> with 3 dimensions' in r.stdout
-    r = _run("camera_pipe.rungen", "--describe")
-    assert r.returncode == 0 and 'Input "matrix_3200" is of type Buffer<float32> with 2 dimensions' in r.stdout, r.stdout + r.stderr
+    """The reference's RunGen describes the metadata as the golden records; the library's own RunGen-compatible runner, which
+    reads the same <name>_metadata(), must print it byte for byte."""
+    want = GOLDEN["rungen_describe"]
+    assert 'Filter name: "local_laplacian"' in want["local_laplacian"]
+    assert 'Input "input" is of type Buffer<uint16> with 3 dimensions' in want["local_laplacian"]
+    assert 'Input "levels" is of type int32' in want["local_laplacian"]
+    assert 'Output "output" is of type Buffer<uint16> with 3 dimensions' in want["local_laplacian"]
+    assert 'Input "matrix_3200" is of type Buffer<float32> with 2 dimensions' in want["camera_pipe"]
+    for name, text in want.items():
+        r = subprocess.run([os.path.join(ROOT, "halide_amd", "bin", "hlmi_rungen"), f"--name={name}", "--describe"],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0 and r.stdout == text, r.stdout + r.stderr
+        if os.path.exists(os.path.join(REF_BIN, f"{name}.rungen")):
+            r = _run(f"{name}.rungen", "--describe")
+            assert r.returncode == 0 and r.stdout == text, r.stdout + r.stderr
 
 
 @pytest.mark.gpu
