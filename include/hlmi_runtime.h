@@ -151,7 +151,6 @@ size_t hlmi_kernel_timing_report(char *out, size_t cap);
  * The INTERFACE (what a deployment may set):
  *   HL_GPU_DEVICE            device ordinal, as in the reference's GPU runtimes (src/runtime/HalideRuntime.h:1019-1026)
  *   HLMI_ALLOC_CACHE_MB      cap of the device allocation cache (halide_reuse_device_allocations)
- *   HLMI_LL_GRAPH=1          local_laplacian: replay the launch chain as a HIP graph from the second identical call (opt-in)
  *   HLMI_LL_NO_LUT_CACHE=1, HLMI_CONV_NO_FILTER_CACHE=1, HLMI_CP_NO_SETUP_CACHE=1
  *                            recompute the remap table / bf16 filter image / camera_pipe set-up in every call instead of
  *                            memoising them per (device, parameters)

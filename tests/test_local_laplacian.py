@@ -381,14 +381,12 @@ def test_hip_8k_smooth_frame_matches_oracle(hl, oracle):
     o.device_free()
 
 
-# ---- HIP-graph replay of the launch chain (second call with the same buffers / shape / parameters captures, later ones replay)
+# ---- repeated calls into the same buffers
 @pytest.mark.gpu
-@pytest.mark.parametrize("graph", ["1", "0"])
-def test_hip_repeated_calls_replay_a_graph_and_follow_new_contents(hl, oracle, monkeypatch, graph):
-    """Five calls into the SAME pair of buffers: the first is eager, the second captures, the rest replay.  Between calls the
-    input's contents, then a parameter, then a switch change: every result must equal the oracle's for what that call was
-    given (a replayed graph may only ever repeat launches the eager path would have issued with identical arguments)."""
-    monkeypatch.setenv("HLMI_LL_GRAPH", graph)
+def test_hip_repeated_calls_follow_new_contents(hl, oracle, monkeypatch):
+    """Repeated calls into the SAME pair of buffers.  Between calls the input's contents, then a parameter, then a switch
+    change: every result must equal the oracle's for what that call was given (nothing of an earlier call's set-up may leak
+    into a later one)."""
     rng = np.random.default_rng(77)
     w, h = 512, 208
     imgs = [rng.integers(0, 65536, (3, h, w), dtype=np.uint16) for _ in range(3)]
@@ -401,20 +399,20 @@ def test_hip_repeated_calls_replay_a_graph_and_follow_new_contents(hl, oracle, m
         hl.local_laplacian(a, levels, alpha, beta, o)
         return o.numpy().copy()
     want = [oracle.local_laplacian(im, 8, alpha, 1.0) for im in imgs]
-    assert np.array_equal(call(imgs[0]), want[0])          # eager
-    assert np.array_equal(call(imgs[0]), want[0])          # captured + launched
-    assert np.array_equal(call(imgs[1]), want[1])          # replayed on new contents
+    assert np.array_equal(call(imgs[0]), want[0])
+    assert np.array_equal(call(imgs[0]), want[0])          # the same call again
+    assert np.array_equal(call(imgs[1]), want[1])          # new contents
     assert np.array_equal(call(imgs[2]), want[2])
-    # another parameter value: a different key (eager again), then back to the replayed one
+    # another parameter value, then back
     assert np.array_equal(call(imgs[2], beta=0.5), oracle.local_laplacian(imgs[2], 8, alpha, 0.5))
     assert np.array_equal(call(imgs[1]), want[1])
-    # a switch that changes the launch chain must not hit the graph captured without it
+    # a switch that changes the launch chain, then back
     monkeypatch.setenv("HLMI_LL_FUSE_FROM", "8")
     assert np.array_equal(call(imgs[0]), want[0])
     assert np.array_equal(call(imgs[0]), want[0])
     monkeypatch.delenv("HLMI_LL_FUSE_FROM")
     assert np.array_equal(call(imgs[2]), want[2])
-    # the pyramid debug hook sees the same bookkeeping after a replay as after an eager call
+    # the pyramid debug hook sees the last call's bookkeeping after repeated calls
     got4 = hl.debug_local_laplacian_outg(4)
     assert got4.size > 0 and np.isfinite(got4).all()
     a.device_free()
@@ -422,10 +420,9 @@ def test_hip_repeated_calls_replay_a_graph_and_follow_new_contents(hl, oracle, m
 
 
 @pytest.mark.gpu
-def test_hip_graph_replay_on_caller_streams(hl, oracle, monkeypatch):
-    """Two caller streams, one frame pair each, interleaved calls: keys differ by stream (and workspace), each stream
-    replays its own graph."""
-    monkeypatch.setenv("HLMI_LL_GRAPH", "1")      # opt-in: measured to buy nothing on MI355X (local_laplacian.hip)
+def test_hip_interleaved_caller_streams(hl, oracle):
+    """Two caller streams, one frame pair each, interleaved calls: each stream's frames come out right (every stream has its
+    own workspace)."""
     hip = hl.hip_runtime()
     import ctypes as C
     streams = []
@@ -498,12 +495,10 @@ def test_hip_emit_launch_geometries_match_oracle(hl, oracle, monkeypatch, units,
 
 
 @pytest.mark.gpu
-def test_hip_ll_mid_one_launch_for_levels_5_to_7_and_the_collapse_matches_oracle(hl, oracle, monkeypatch, on_stream):
-    """HLMI_LL_FUSE_MID=1 (opt-in, round 6): ll_down_multi and ll_up_multi as ONE launch, levels 5-7 handed from its producer blocks to
-    its consumer blocks through agent-coherent stores / loads and a count.  DIFFERENT frames go through the same workspace back to
-    back (a consumer that read a stale copy of the previous frame's levels would show here), on the device's stream and on a frame
-    queue, at sizes where the default chain is the five-launch one (levels 5-7 exist) and at sizes where a level is a single row."""
-    monkeypatch.setenv("HLMI_LL_FUSE_MID", "1")
+def test_hip_different_frames_back_to_back_through_one_workspace_match_oracle(hl, oracle, on_stream):
+    """DIFFERENT frames go through the same workspace back to back (a launch that read a stale part of the previous frame's levels
+    would show here), on the device's stream and on a frame queue, at sizes where the default chain makes levels 5-7 with
+    ll_down_multi and collapses them with ll_up_multi and at sizes where a level is a single row."""
     for (w, h) in [(1920, 1080), (520, 332), (2048, 64), (260, 40)]:
         for seed in range(3):
             inp = _rand_image(w, h, seed=100 * seed + w, kind="uniform" if seed != 1 else "smooth")
