@@ -145,6 +145,30 @@ void oracle_camera_pipe_setup(const float *m3200, const float *m7000 /* [3][4] r
     *strength_x32 = (uint8_t)s;
 }
 
+/* sharpen (:369-403) on curved, given as planar u8 [3][H + 2][W + 2] covering [-1, W] x [-1, H]: mask = i16(in) - i16(unsharp);
+ * mask * strength_x32 is int16 (x) uint8 -> int16 and wraps; / 32 floors; the sum is int16; u8_sat at the end.  Exported so that
+ * tests/test_reference_kats.py can drive every cast site with curved values no raw input reaches. */
+void oracle_camera_pipe_sharpen(const uint8_t *cv, int strength_x32, uint8_t *out, int W, int H, int out_sy, int out_sc) {
+    const int CW = W + 2, CH = H + 2;
+#define CV(x, y, c) cv[((size_t)(c) * CH + ((y) + 1)) * CW + ((x) + 1)]
+#pragma omp parallel for schedule(static)
+    for (int y = 0; y < H; y++) {
+        for (int x = 0; x < W; x++) {
+            for (int c = 0; c < 3; c++) {
+                uint8_t uy[3];
+                for (int d = -1; d <= 1; d++) uy[d + 1] = avg8(avg8(CV(x + d, y - 1, c), CV(x + d, y + 1, c)), CV(x + d, y, c));
+                uint8_t unsharp = avg8(avg8(uy[0], uy[2]), uy[1]);
+                int16_t mask = (int16_t)((int16_t)CV(x, y, c) - (int16_t)unsharp);
+                int16_t prod = (int16_t)(mask * (int16_t)strength_x32); /* int16 (x) uint8 -> int16, wraps */
+                int16_t q = (int16_t)o_fdiv(prod, 32);
+                int16_t s = (int16_t)((int16_t)CV(x, y, c) + q);
+                out[(size_t)y * out_sy + x + (size_t)c * out_sc] = (uint8_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
+            }
+        }
+    }
+#undef CV
+}
+
 int oracle_camera_pipe(const uint16_t *in, int in_w, int in_h, int in_sy, const float *m3200, const float *m7000,
                        float color_temp, float gamma, float contrast, float sharpen_strength, int blackLevel, int whiteLevel,
                        uint8_t *out, int W, int H, int out_sy, int out_sc) {
@@ -165,22 +189,7 @@ int oracle_camera_pipe(const uint16_t *in, int in_w, int in_h, int in_sy, const 
             for (int c = 0; c < 3; c++) cv[((size_t)c * CH + y) * CW + x] = o[c];
         }
     }
-#define CV(x, y, c) cv[((size_t)(c) * CH + ((y) + 1)) * CW + ((x) + 1)]
-#pragma omp parallel for schedule(static)
-    for (int y = 0; y < H; y++) {
-        for (int x = 0; x < W; x++) {
-            for (int c = 0; c < 3; c++) {
-                uint8_t uy[3];
-                for (int d = -1; d <= 1; d++) uy[d + 1] = avg8(avg8(CV(x + d, y - 1, c), CV(x + d, y + 1, c)), CV(x + d, y, c));
-                uint8_t unsharp = avg8(avg8(uy[0], uy[2]), uy[1]);
-                int16_t mask = (int16_t)((int16_t)CV(x, y, c) - (int16_t)unsharp);
-                int16_t prod = (int16_t)(mask * (int16_t)p.strength_x32); /* int16 (x) uint8 -> int16, wraps */
-                int16_t q = (int16_t)o_fdiv(prod, 32);
-                int16_t s = (int16_t)((int16_t)CV(x, y, c) + q);
-                out[(size_t)y * out_sy + x + (size_t)c * out_sc] = (uint8_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
-            }
-        }
-    }
+    oracle_camera_pipe_sharpen(cv, p.strength_x32, out, W, H, out_sy, out_sc);
     free(cv);
     return 0;
 }

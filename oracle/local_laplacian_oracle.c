@@ -115,6 +115,18 @@ static void downsample(const plane_t *f, plane_t *out) {
     free(dy.p);
 }
 
+/* Exported: one downsample step on a float plane that covers [X0, X0 + W) x [Y0, Y0 + H) in absolute coordinates, written for the
+ * output region [ox0, ox0 + OW) x [oy0, oy0 + OH) (tests/test_reference_kats.py).  -1 if that region reads outside the plane. */
+int oracle_ll_downsample(const float *in, int W, int H, int X0, int Y0, float *out, int ox0, int oy0, int OW, int OH) {
+    if (2 * ox0 - 1 < X0 || 2 * (ox0 + OW - 1) + 2 > X0 + W - 1 || 2 * oy0 - 1 < Y0 || 2 * (oy0 + OH - 1) + 2 > Y0 + H - 1) return -1;
+    plane_t f = {X0, X0 + W - 1, Y0, Y0 + H - 1, W, H, (float *)in}, o;
+    plane_alloc(&o, ox0, ox0 + OW - 1, oy0, oy0 + OH - 1);
+    downsample(&f, &o);
+    memcpy(out, o.p, sizeof(float) * (size_t)OW * (size_t)OH);
+    free(o.p);
+    return 0;
+}
+
 /* upsample (:276-282) evaluated at one point */
 static inline float upx_at(const plane_t *f, int x, int y) {
     float w = (float)(o_fmod(x, 2) * 2 + 1) * 0.25f;
@@ -161,6 +173,15 @@ void oracle_halide_pow_v(const float *x, const float *y, float *out, size_t n) {
 void oracle_lerp_v(const float *a, const float *b, const float *w, float *out, size_t n) {
 #pragma omp parallel for schedule(static)
     for (size_t i = 0; i < n; i++) out[i] = o_lerp(a[i], b[i], w[i]);
+}
+/* integer division / modulo with run-time divisors (tests/test_reference_kats.py) */
+void oracle_fdiv_v(const int32_t *a, const int32_t *b, int32_t *out, size_t n) {
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < n; i++) out[i] = o_fdiv(a[i], b[i]);
+}
+void oracle_fmod_v(const int32_t *a, const int32_t *b, int32_t *out, size_t n) {
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < n; i++) out[i] = o_fmod(a[i], b[i]);
 }
 
 /* Full pipeline.  in/out: planar u16 [3][H][W] with row stride `in_sy`/`out_sy` and plane stride

@@ -51,14 +51,20 @@ static inline float o_msub(float c, float a, float b) { return o_canon_fma ? fma
 /* a * b - c */
 static inline float o_mulsub(float a, float b, float c) { return o_canon_fma ? fmaf(a, b, -c) : a * b - c; }
 
-/* Halide integer division / modulo round toward -inf for positive divisors (src/IR.h:145-166). */
+/* Halide integer division / modulo (src/IR.h:145-166): Euclidean for either sign of b, so a % b is never negative and
+ * (a / b) * b + a % b == a; x / 0 == x % 0 == 0; INT_MIN / -1 wraps to INT_MIN (and INT_MIN % -1 == 0).  Every call site
+ * passes a constant divisor, so the b == 0 / b == -1 tests fold away there; C's own INT_MIN / -1 and x / 0 trap. */
 static inline int o_fdiv(int a, int b) {
+    if (b == 0) return 0;
+    if (b == -1) return (int)(0u - (unsigned)a);
     int q = a / b, r = a % b;
-    return (r < 0) ? q - 1 : q;
+    return (r < 0) ? q - ((b >> 31) | 1) : q; /* r < 0: one step down for b > 0, one step up for b < 0 */
 }
 static inline int o_fmod(int a, int b) {
+    if (b == 0 || b == -1) return 0;
     int r = a % b;
-    return (r < 0) ? r + b : r;
+    unsigned ab = b < 0 ? 0u - (unsigned)b : (unsigned)b; /* |b|, also for INT_MIN */
+    return (r < 0) ? (int)((unsigned)r + ab) : r;
 }
 static inline int o_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 /* clamp(a, lo, hi) = max(min(a, hi), lo)  (src/IROperator.cpp clamp) */

@@ -489,3 +489,52 @@ def bgu(r_sigma, s_sigma, splat_loc: np.ndarray, values: np.ndarray, slice_loc: 
     line = np.zeros((ncy, ncx, nz, 12), np.float32)
     assert _lib.oracle_bgu(*args, line.ctypes.data, C.cast(dims, C.c_void_p)) == 0
     return out, line, (cx0, cy0, ncx, ncy, nz, big)
+
+
+# ---- primitives with integer operands and single stages, for tests/test_reference_kats.py
+for _name in ("oracle_fdiv_v", "oracle_fmod_v"):
+    getattr(_lib, _name).argtypes = [_i32p, _i32p, _i32p, C.c_size_t]
+    getattr(_lib, _name).restype = None
+_lib.oracle_camera_pipe_sharpen.argtypes = [_u8p, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int]
+_lib.oracle_camera_pipe_sharpen.restype = None
+_lib.oracle_ll_downsample.argtypes = [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int]
+_lib.oracle_ll_downsample.restype = C.c_int
+
+
+def _int_binop(fn, a, b):
+    a, b = np.broadcast_arrays(np.asarray(a, np.int32), np.asarray(b, np.int32))
+    a, b = np.ascontiguousarray(a).ravel(), np.ascontiguousarray(b).ravel()
+    out = np.empty_like(a)
+    fn(a, b, out, a.size)
+    return out
+
+
+def fdiv(a, b) -> np.ndarray:
+    """o_fdiv element-wise on int32 arrays (Halide's integer a / b)."""
+    return _int_binop(_lib.oracle_fdiv_v, a, b)
+
+
+def fmod(a, b) -> np.ndarray:
+    """o_fmod element-wise on int32 arrays (Halide's integer a % b)."""
+    return _int_binop(_lib.oracle_fmod_v, a, b)
+
+
+def camera_pipe_sharpen(curved: np.ndarray, strength_x32: int) -> np.ndarray:
+    """camera_pipe's sharpen stage alone: curved u8 (3, H + 2, W + 2) covering [-1, W] x [-1, H] -> u8 (3, H, W)."""
+    curved = np.ascontiguousarray(curved, np.uint8)
+    h, w = curved.shape[1] - 2, curved.shape[2] - 2
+    out = np.zeros((3, h, w), np.uint8)
+    _lib.oracle_camera_pipe_sharpen(curved, int(strength_x32), out, w, h, w, w * h)
+    return out
+
+
+def ll_downsample(plane: np.ndarray, origin, out_origin, out_size) -> np.ndarray:
+    """One local_laplacian downsample step: plane f32 (H, W) whose [0, 0] sits at absolute `origin`; returns the (OH, OW)
+    result whose [0, 0] sits at `out_origin`."""
+    plane = np.ascontiguousarray(plane, np.float32)
+    ow, oh = out_size
+    out = np.zeros((oh, ow), np.float32)
+    r = _lib.oracle_ll_downsample(plane, plane.shape[1], plane.shape[0], int(origin[0]), int(origin[1]), out,
+                                  int(out_origin[0]), int(out_origin[1]), ow, oh)
+    assert r == 0, "the output region reads outside the plane"
+    return out

@@ -16,6 +16,8 @@ def _img(w, h, seed, kind="scene"):
 
 
 def test_oracle_cdf_is_the_luma_histogram_prefix_sum(oracle):
+    """Restates /root/reference/test/correctness/histogram.cpp:10-37: the histogram of a random image, built with a
+    clamp(cast<int>(v), 0, 255) scatter, equals a plain count of the same bins (here through the cumulative sum the pipeline keeps)."""
     inp = _img(61, 47, 1)
     _, cdf = oracle.hist(inp, return_cdf=True)
     f = inp.astype(np.float32)
