@@ -13,7 +13,7 @@ A "step" = PASSES (default 16) passes of the pipeline over a batch of FRAMES_PER
 timed region, like apps/local_laplacian/process.cpp:31-39 where the first call pays the copies and `benchmark()` times
 calls + device_sync).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 `--gpus N` is the whole command for any N: when the script is not already running under a launcher it starts N ranks of
 itself under `python -m torch.distributed.run` (one process per GPU, rendezvous on 127.0.0.1) and refuses when fewer than
@@ -23,9 +23,15 @@ with --gpus is an error, so `n_gpus` in the output is always the N asked for.
 
 Frames are independent units: ranks shard them with no data-path collective ("scaling": "weak");
 torch.distributed (RCCL) is used only for the barrier and the max-over-ranks of the elapsed time.
-Prints ONE JSON line on rank 0.  After the timed region rank 0 (N = 1 only) also measures the other BASELINE.json
-configs — bilateral_grid 1920x1080, nl_means 1920x1080x3, conv_layer bf16 N=16 — into `config.other_configs`, each with its
-roofline and a bounded oracle `cpu_baseline`.
+Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline figure needs: set-up, warm-up, the timed steps, `--dump-outputs`, the line
+(`value`, `ms_per_step`, the workload's `config`, the clock state of the timed region).  `--full` measures everything else
+after the timed region and adds it to the same line: per-kernel durations and the `roofline` of the dominant kernel, the live
+HBM copy ceiling, the reference driver's one-call protocol (`ms_per_call_one_stream`), the other input variants
+(`value_smooth`, `value_natural_tiled`, `config.variants`), the other BASELINE.json configs — bilateral_grid 1920x1080,
+nl_means 1920x1080x3, conv_layer bf16 N=16 — into `config.other_configs`, each with its roofline and a bounded oracle
+`cpu_baseline`, and the `cpu_baseline` of the headline workload.  The `--no-*` switches leave legs of `--full` out.
 """
 import argparse
 import json
@@ -221,10 +227,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20, help="timed steps (a step = --passes passes over the frames: 20 steps ≈ 0.27 s of GPU time)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--passes", type=int, default=PASSES, help="passes over the FRAMES_PER_STEP distinct frames that make one step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the bilateral_grid / nl_means / conv_layer_bf16 leg")
-    ap.add_argument("--no-ceiling", action="store_true", help="skip the live HBM copy-ceiling sweep (profiler runs)")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra input variants (uniform noise, 7680x4320)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure every other figure of the line: per-kernel durations and the "
+                         "roofline, the HBM copy ceiling, the one-call protocol, the input variants, the other BASELINE configs "
+                         "and the CPU baselines (off: the headline figure alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the bilateral_grid / nl_means / conv_layer_bf16 leg")
+    ap.add_argument("--no-ceiling", action="store_true", help="with --full: skip the live HBM copy-ceiling sweep (profiler runs)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the extra input variants (uniform noise, 7680x4320)")
     ap.add_argument("--partitions", type=int, default=int(os.environ.get("HLMI_BENCH_PARTITIONS", "4")),
                     help="frames of a step are spread over this many frame-queue streams (halide_hip_partition_stream: library "
                          "streams with a hardware queue each, launches sized for that many frames in flight; NOT CU "
@@ -269,6 +279,94 @@ def main():
     for a, o in zip(ins, outs):  # first call uploads the input and allocates the output on the device
         hl.local_laplacian(a, LEVELS, ALPHA, BETA, o)
     outs[-1].device_sync()
+
+    streams, keep, mode = [], [], "1 stream"
+    if args.partitions > 1:
+        spp = max(1, args.streams_per_partition)
+        streams = [hl.partition_stream(p, args.partitions, r) for r in range(spp) for p in range(args.partitions)]
+        mode = f"{args.partitions} frame-queue streams" + (f" x {spp}" if spp > 1 else "")
+        if not all(streams):
+            streams = []            # the device refused a CU mask: plain streams instead
+    if not streams and args.streams > 1:
+        keep = [torch.cuda.Stream() for _ in range(args.streams)]
+        streams, mode = [s.cuda_stream for s in keep], f"{args.streams} streams"
+
+    def one_pass(use_streams=True):
+        for i, (a, o) in enumerate(zip(ins, outs)):
+            if streams and use_streams:  # frame i goes to stream i % n
+                hl.set_stream(streams[i % len(streams)])
+            hl.local_laplacian(a, LEVELS, ALPHA, BETA, o)
+        if streams and use_streams:
+            hl.set_stream(None)
+
+    def step():
+        for _ in range(args.passes):
+            one_pass()
+
+    def barrier():
+        torch.cuda.synchronize()
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+
+    for _ in range(args.warmup):
+        step()
+    barrier()
+    sampler = ClockSampler(local_rank)
+    with sampler:
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        barrier()
+        elapsed = time.perf_counter() - t0
+    elapsed = sharding.max_over_ranks(elapsed, dist, "cuda")
+    if args.dump_outputs:   # before the untimed legs of --full rewrite the outputs
+        dump_outputs(args.dump_outputs, mine, outs, world * FRAMES_PER_STEP)
+
+    frames_per_step = FRAMES_PER_STEP * args.passes
+    frame_ms = elapsed / (args.steps * frames_per_step) * 1e3
+    extra = full_legs(args, hl, rank, local_rank, world, frames, ins, outs, streams, one_pass, frame_ms) if args.full else None
+
+    if rank == 0:
+        px_per_step = world * frames_per_step * W * H
+        value = px_per_step * args.steps / elapsed / 1e6
+        result = {
+            "metric": "megapixels/sec local_laplacian 8-level fp32 4K",
+            "value": round(value, 2), "unit": "Mpx/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            # `value` is measured on uniform noise, the input the reference's own benchmark protocol feeds (RunGen)
+            "value_input": "uniform full-range noise (tools/RunGen.h:482-505)",
+            # which canonical float form the library computes (hlmi_canon_fma(): 1 = mul+add pairs fused as LLVM contracts the
+            # reference's float operations, 0 = one rounding per operator) and the clock / power state during the timed region
+            "canon_fma": hl.canon_fma(),
+            "clock_state_timed_region": sampler.summary(),
+            "config": {"workload": "apps/local_laplacian J=8 levels=8 alpha=1/7 beta=1, u16 RGB planar 3840x2160",
+                       "frames_per_step_per_gpu": frames_per_step, "distinct_frames_per_gpu": FRAMES_PER_STEP,
+                       "passes_per_step": args.passes, "frame_ms": round(frame_ms, 4),
+                       # remap(x) depends on (levels, alpha) only: its 3585-entry table is memoised across calls, so 8 of the
+                       # reference's 9 stages run inside the timed region (HLMI_LL_NO_LUT_CACHE=1 re-runs it: +1 launch of ~4 us)
+                       "lut_cached": True,
+                       "streams_per_gpu": max(1, len(streams)), "frame_scheduling": mode,
+                       "boundary": "C ABI local_laplacian(halide_buffer_t*,int32,float,float,halide_buffer_t*)",
+                       "input": "uniform full-range noise, seeded per frame (SURVEY.md §8d (i): the reference's RunGen benchmark input); smooth / natural under `variants` (--full)",
+                       "rccl_ranks": rccl_ranks,
+                       "parallelism": f"frames sharded over {world} GPU(s), no data-path collective"},
+        }
+        if extra:
+            result["config"].update(extra.pop("config"))
+            result.update(extra)
+        print(json.dumps(result), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_legs(args, hl, rank, local_rank, world, frames, ins, outs, streams, one_pass, frame_ms):
+    """--full: every figure of the line beside the headline one, measured after the timed region (which it does not touch) on
+    the same process and buffers.  Returns the fields it adds to the line on rank 0 (None on the other ranks)."""
+    import numpy as np
+    import torch
 
     def run_variant(w, h, kind, nframes, steps):
         """Mpx/s of the same call on another input variant of configs[2], same stream scheduling, inputs
@@ -318,49 +416,6 @@ def main():
         a.device_free()
         o.device_free()
         return best, cs.summary()
-
-    streams, keep, mode = [], [], "1 stream"
-    if args.partitions > 1:
-        spp = max(1, args.streams_per_partition)
-        streams = [hl.partition_stream(p, args.partitions, r) for r in range(spp) for p in range(args.partitions)]
-        mode = f"{args.partitions} frame-queue streams" + (f" x {spp}" if spp > 1 else "")
-        if not all(streams):
-            streams = []            # the device refused a CU mask: plain streams instead
-    if not streams and args.streams > 1:
-        keep = [torch.cuda.Stream() for _ in range(args.streams)]
-        streams, mode = [s.cuda_stream for s in keep], f"{args.streams} streams"
-
-    def one_pass(use_streams=True):
-        for i, (a, o) in enumerate(zip(ins, outs)):
-            if streams and use_streams:  # frame i goes to stream i % n
-                hl.set_stream(streams[i % len(streams)])
-            hl.local_laplacian(a, LEVELS, ALPHA, BETA, o)
-        if streams and use_streams:
-            hl.set_stream(None)
-
-    def step():
-        for _ in range(args.passes):
-            one_pass()
-
-    def barrier():
-        torch.cuda.synchronize()
-        if dist is not None:
-            dist.barrier()
-        torch.cuda.synchronize()
-
-    for _ in range(args.warmup):
-        step()
-    barrier()
-    sampler = ClockSampler(local_rank)
-    with sampler:
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        barrier()
-        elapsed = time.perf_counter() - t0
-    elapsed = sharding.max_over_ranks(elapsed, dist, "cuda")
-    if args.dump_outputs:   # before the untimed legs below rewrite the outputs
-        dump_outputs(args.dump_outputs, mine, outs, world * FRAMES_PER_STEP)
 
     # --- per-kernel durations: HIP events around every launch on the launch stream, in a separate untimed pass on ONE
     #     stream (kernels of different frames must not overlap while a single kernel is being timed)
@@ -444,130 +499,103 @@ def main():
         # this GPU, no exchange step), enqueued back to back, one sync at the end
         other_configs.append(bench_apps.nl_means_batch32())
 
-    if rank == 0:
-        frames_per_step = FRAMES_PER_STEP * args.passes
-        px_per_step = world * frames_per_step * W * H
-        value = px_per_step * args.steps / elapsed / 1e6
-        frame_ms = elapsed / (args.steps * frames_per_step) * 1e3
-        # per-launch view: every launch of the chain is reported under its own name (ll_down_strip:1 ... ll_up:6 ...)
-        per_frame = {k["name"]: k["total_ms"] / (3 * FRAMES_PER_STEP) for k in kernels}
-        # dominant kernel = the launch with the longest average duration; its ALGORITHMIC bytes (compulsory reads +
-        # writes of that launch, declared next to the launch in halide_amd/csrc/local_laplacian.hip)
-        dom_rec = max(kernels, key=lambda k: k["avg_ms"])
-        dom = dom_rec["name"]
-        alg_bytes = dom_rec.get("alg_bytes") or ALG_BYTES_PER_PX * W * H
-        # duration: the kernel alone, back to back (comparable with rocprofv3's kernel trace); the event bracket of the chain is
-        # kept beside it as kernel_avg_ms_hip_events
-        kernel_ms = back_to_back_ms or dom_rec["avg_ms"]
-        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
-        # measured HBM traffic of that kernel (rocprofv3 PMC passes, FETCH_SIZE corrected x2 as
-        # MI355X_MICROARCH.md prescribes for wide coalesced reads + WRITE_SIZE), committed under profiles/
-        traffic = None
-        frame_traffic = None   # all launches of one frame: what the whole pipeline moves through HBM / MALL
-        traffic_source = None
-        tpath = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tpath):
-            import hashlib
-            with open(tpath) as f:
-                tj = json.load(f)
-            per_launch = tj.get("bytes_per_launch", {})
-            with open(os.path.join(ROOT, "halide_amd", "csrc", "local_laplacian.hip"), "rb") as f:
-                sha_now = hashlib.sha256(f.read()).hexdigest()
-            # NOT measured in this run: counters of a separate rocprofv3 PMC run (committed under profiles/).  Printed only while the
-            # kernel source is byte for byte the one that run profiled — a later edit of the kernels makes them stale
-            if tj.get("kernel_source_sha256") == sha_now:
-                traffic = per_launch.get(dom)      # the dominant kernel alone on a stream that owns the device: that geometry
-                # the whole frame: the counters of the geometry the headline loop ran — a frame queue's when it ran on frame queues
-                # (fewer seam rows and tile halos re-read than in the one-call geometry), else the device-wide ones
-                per_q = tj.get("bytes_per_launch_frame_queue") or {}
-                on_queues = args.partitions > 1 and bool(streams)
-                frame_set = per_q if (on_queues and all(k in per_q for k in per_frame)) else per_launch
-                if all(k in frame_set for k in per_frame):
-                    frame_traffic = int(sum(frame_set[k] for k in per_frame))
-                traffic_source = {"file": tj.get("source"), "git_head_when_collected": tj.get("git_head_when_collected"),
-                                  "measured_in_this_run": False,
-                                  "pipeline_traffic_geometry": "frame queue (" + str(tj.get("frame_queue_source")) + ")" if frame_set is per_q
-                                  else "one stream that owns the device"}
-            else:
-                traffic_source = {"file": tj.get("source"), "stale": "local_laplacian.hip changed since these counters were collected; traffic withheld"}
-        result = {
-            "metric": "megapixels/sec local_laplacian 8-level fp32 4K",
-            "value": round(value, 2), "unit": "Mpx/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            # `value` is measured on uniform noise, the input the reference's own benchmark protocol feeds (RunGen); the same call on
-            # the two other input classes of SURVEY.md §8d (details under config.variants): the smooth synthetic frame (rounds 1-5's
-            # headline input) and the reference checkout's one natural image, tiled
-            "value_input": "uniform full-range noise (tools/RunGen.h:482-505)",
-            "value_smooth": None if not variants else variants.get("smooth_3840x2160"),
-            "value_natural_tiled": None if not variants else variants.get("natural_tiled_3840x2160"),
-            # which canonical float form the library computes (hlmi_canon_fma(): 1 = mul+add pairs fused as LLVM contracts the
-            # reference's float operations, 0 = one rounding per operator) and the clock / power state during the timed region
-            "canon_fma": hl.canon_fma(),
-            "clock_state_timed_region": sampler.summary(),
-            # the reference driver's protocol beside the frames-in-flight `value`: one call + device_sync on the device's own
-            # stream, min over 10 samples (apps/local_laplacian/process.cpp:36-39) — ms per call and the Mpx/s that is
-            "ms_per_call_one_stream": None if not one_call else {k: round(v * 1e3, 4) for k, v in one_call.items()},
-            "mpx_per_s_one_call_one_stream": None if not one_call else {k: round(W * H / v / 1e6, 1) for k, v in one_call.items()},
-            "clock_state_one_call_one_stream": one_call_clock,
-            "config": {"workload": "apps/local_laplacian J=8 levels=8 alpha=1/7 beta=1, u16 RGB planar 3840x2160",
-                       "frames_per_step_per_gpu": frames_per_step, "distinct_frames_per_gpu": FRAMES_PER_STEP,
-                       "passes_per_step": args.passes, "frame_ms": round(frame_ms, 4),
-                       # remap(x) depends on (levels, alpha) only: its 3585-entry table is memoised across calls, so 8 of the
-                       # reference's 9 stages run inside the timed region (HLMI_LL_NO_LUT_CACHE=1 re-runs it: +1 launch of ~4 us)
-                       "lut_cached": True,
-                       "streams_per_gpu": max(1, len(streams)), "frame_scheduling": mode,
-                       "boundary": "C ABI local_laplacian(halide_buffer_t*,int32,float,float,halide_buffer_t*)",
-                       "input": "uniform full-range noise, seeded per frame (SURVEY.md §8d (i): the reference's RunGen benchmark input); smooth / natural under `variants`",
-                       "variants": variants,
-                       "other_configs": other_configs,
-                       "rccl_ranks": rccl_ranks,
-                       "parallelism": f"frames sharded over {world} GPU(s), no data-path collective"},
-            "roofline": {"bound": "hbm", "kernel": dom,
-                         # the three fractions of the 8 TB/s peak, first: (1) the dominant kernel on its algorithmic bytes over its
-                         # back-to-back duration (what profiles/*kernel_stats.csv gives for the same kernel); (2) the whole pipeline on
-                         # the compulsory 12 B/px over the frame time of the timed region; (3) the pipeline on its measured (PMC) bytes
-                         "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "pipeline_frac": round(ALG_BYTES_PER_PX * W * H / (frame_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "pipeline_traffic_frac": None if frame_traffic is None else
-                         round(frame_traffic / (frame_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": traffic,
-                         "traffic_source": traffic_source,
-                         # the same fraction on the bytes the kernel actually moved (PMC) instead of its algorithmic bytes
-                         "frac_moved": None if traffic is None else round(traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         "alg_bytes_per_launch": int(alg_bytes),
-                         "kernel_avg_ms": round(kernel_ms, 5),
-                         "kernel_avg_ms_method": f"{REPS} launches of the kernel alone, back to back on the device's stream, HIP events around "
-                                                 "the run, min of 3 rounds (hlmi_kernel_timing_only)",
-                         "kernel_avg_ms_hip_events": round(dom_rec["avg_ms"], 5),
-                         "pipeline_alg_bytes_per_frame": ALG_BYTES_PER_PX * W * H,
-                         # measured (PMC) bytes of all launches of a frame over the frame time: the pipeline's real HBM load
-                         "pipeline_traffic_per_frame": frame_traffic,
-                         # the same against the measured copy ceiling instead of the 8 TB/s spec figure
-                         "hbm_copy_ceiling_gbs": None if copy_ceiling is None else round(copy_ceiling, 1),
-                         "hbm_ceiling_detail": ceiling_detail,
-                         "pipeline_traffic_frac_of_copy_ceiling": None if (frame_traffic is None or not copy_ceiling) else
-                         round(frame_traffic / (frame_ms * 1e-3) / 1e9 / copy_ceiling, 4),
-                         # ... and against the float4-copy figure MI355X_MICROARCH.md measured (6.29 TB/s)
-                         "pipeline_traffic_frac_of_guide_copy_6290": None if frame_traffic is None else
-                         round(frame_traffic / (frame_ms * 1e-3) / 1e9 / 6290.0, 4),
-                         # HIP-event brackets around each launch on ONE stream: they include the gap to the previous launch and read
-                         # longer than the kernels run (rocprofv3's kernel trace, profiles/, has the durations) — relative weights
-                         "kernel_ms_hip_events_one_stream": {k: round(v, 5) for k, v in per_frame.items()},
-                         # per-launch figures (HIP events, PMC) are taken on ONE device-wide stream; the headline loop runs on four
-                         # frame queues, where the kernels use non-temporal frame accesses and a coarser launch geometry (same
-                         # bytes within 1 %)
-                         "notes": "the headline loop keeps four frames in flight on four hardware queues that all run on the whole "
-                                  "device (the CU masks of rounds 3-5 confined nothing: profiles/r06_cu_mask_probe.txt); the frame "
-                                  "time is the sum of the kernels' back-to-back floors (profiles/r06_partition_kernel_probe.txt); "
-                                  "profiles/r04_power_and_partition_scaling.txt read 1040 W with one queue busy, ~1370 W with two or four"},
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            result["cpu_baseline"] = cpu_baseline(frames[0])
-        print(json.dumps(result), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    if rank != 0:
+        return None
+    # per-launch view: every launch of the chain is reported under its own name (ll_down_strip:1 ... ll_up:6 ...)
+    per_frame = {k["name"]: k["total_ms"] / (3 * FRAMES_PER_STEP) for k in kernels}
+    # dominant kernel = the launch with the longest average duration; its ALGORITHMIC bytes (compulsory reads +
+    # writes of that launch, declared next to the launch in halide_amd/csrc/local_laplacian.hip)
+    dom_rec = max(kernels, key=lambda k: k["avg_ms"])
+    dom = dom_rec["name"]
+    alg_bytes = dom_rec.get("alg_bytes") or ALG_BYTES_PER_PX * W * H
+    # duration: the kernel alone, back to back (comparable with rocprofv3's kernel trace); the event bracket of the chain is
+    # kept beside it as kernel_avg_ms_hip_events
+    kernel_ms = back_to_back_ms or dom_rec["avg_ms"]
+    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+    # measured HBM traffic of that kernel (rocprofv3 PMC passes, FETCH_SIZE corrected x2 as
+    # MI355X_MICROARCH.md prescribes for wide coalesced reads + WRITE_SIZE), committed under profiles/
+    traffic = None
+    frame_traffic = None   # all launches of one frame: what the whole pipeline moves through HBM / MALL
+    traffic_source = None
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tpath):
+        import hashlib
+        with open(tpath) as f:
+            tj = json.load(f)
+        per_launch = tj.get("bytes_per_launch", {})
+        with open(os.path.join(ROOT, "halide_amd", "csrc", "local_laplacian.hip"), "rb") as f:
+            sha_now = hashlib.sha256(f.read()).hexdigest()
+        # NOT measured in this run: counters of a separate rocprofv3 PMC run (committed under profiles/).  Printed only while the
+        # kernel source is byte for byte the one that run profiled — a later edit of the kernels makes them stale
+        if tj.get("kernel_source_sha256") == sha_now:
+            traffic = per_launch.get(dom)      # the dominant kernel alone on a stream that owns the device: that geometry
+            # the whole frame: the counters of the geometry the headline loop ran — a frame queue's when it ran on frame queues
+            # (fewer seam rows and tile halos re-read than in the one-call geometry), else the device-wide ones
+            per_q = tj.get("bytes_per_launch_frame_queue") or {}
+            on_queues = args.partitions > 1 and bool(streams)
+            frame_set = per_q if (on_queues and all(k in per_q for k in per_frame)) else per_launch
+            if all(k in frame_set for k in per_frame):
+                frame_traffic = int(sum(frame_set[k] for k in per_frame))
+            traffic_source = {"file": tj.get("source"), "git_head_when_collected": tj.get("git_head_when_collected"),
+                              "measured_in_this_run": False,
+                              "pipeline_traffic_geometry": "frame queue (" + str(tj.get("frame_queue_source")) + ")" if frame_set is per_q
+                              else "one stream that owns the device"}
+        else:
+            traffic_source = {"file": tj.get("source"), "stale": "local_laplacian.hip changed since these counters were collected; traffic withheld"}
+    extra = {
+        # `value` is measured on uniform noise; the same call on the two other input classes of SURVEY.md §8d (details under
+        # config.variants): the smooth synthetic frame (rounds 1-5's headline input) and the reference checkout's one natural
+        # image, tiled
+        "value_smooth": None if not variants else variants.get("smooth_3840x2160"),
+        "value_natural_tiled": None if not variants else variants.get("natural_tiled_3840x2160"),
+        # the reference driver's protocol beside the frames-in-flight `value`: one call + device_sync on the device's own
+        # stream, min over 10 samples (apps/local_laplacian/process.cpp:36-39) — ms per call and the Mpx/s that is
+        "ms_per_call_one_stream": None if not one_call else {k: round(v * 1e3, 4) for k, v in one_call.items()},
+        "mpx_per_s_one_call_one_stream": None if not one_call else {k: round(W * H / v / 1e6, 1) for k, v in one_call.items()},
+        "clock_state_one_call_one_stream": one_call_clock,
+        "config": {"variants": variants, "other_configs": other_configs},
+        "roofline": {"bound": "hbm", "kernel": dom,
+                     # the three fractions of the 8 TB/s peak, first: (1) the dominant kernel on its algorithmic bytes over its
+                     # back-to-back duration (what profiles/*kernel_stats.csv gives for the same kernel); (2) the whole pipeline on
+                     # the compulsory 12 B/px over the frame time of the timed region; (3) the pipeline on its measured (PMC) bytes
+                     "frac": round(achieved / HBM_PEAK_GBS, 4),
+                     "pipeline_frac": round(ALG_BYTES_PER_PX * W * H / (frame_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                     "pipeline_traffic_frac": None if frame_traffic is None else
+                     round(frame_traffic / (frame_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "traffic": traffic,
+                     "traffic_source": traffic_source,
+                     # the same fraction on the bytes the kernel actually moved (PMC) instead of its algorithmic bytes
+                     "frac_moved": None if traffic is None else round(traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                     "alg_bytes_per_launch": int(alg_bytes),
+                     "kernel_avg_ms": round(kernel_ms, 5),
+                     "kernel_avg_ms_method": f"{REPS} launches of the kernel alone, back to back on the device's stream, HIP events around "
+                                             "the run, min of 3 rounds (hlmi_kernel_timing_only)",
+                     "kernel_avg_ms_hip_events": round(dom_rec["avg_ms"], 5),
+                     "pipeline_alg_bytes_per_frame": ALG_BYTES_PER_PX * W * H,
+                     # measured (PMC) bytes of all launches of a frame over the frame time: the pipeline's real HBM load
+                     "pipeline_traffic_per_frame": frame_traffic,
+                     # the same against the measured copy ceiling instead of the 8 TB/s spec figure
+                     "hbm_copy_ceiling_gbs": None if copy_ceiling is None else round(copy_ceiling, 1),
+                     "hbm_ceiling_detail": ceiling_detail,
+                     "pipeline_traffic_frac_of_copy_ceiling": None if (frame_traffic is None or not copy_ceiling) else
+                     round(frame_traffic / (frame_ms * 1e-3) / 1e9 / copy_ceiling, 4),
+                     # ... and against the float4-copy figure MI355X_MICROARCH.md measured (6.29 TB/s)
+                     "pipeline_traffic_frac_of_guide_copy_6290": None if frame_traffic is None else
+                     round(frame_traffic / (frame_ms * 1e-3) / 1e9 / 6290.0, 4),
+                     # HIP-event brackets around each launch on ONE stream: they include the gap to the previous launch and read
+                     # longer than the kernels run (rocprofv3's kernel trace, profiles/, has the durations) — relative weights
+                     "kernel_ms_hip_events_one_stream": {k: round(v, 5) for k, v in per_frame.items()},
+                     # per-launch figures (HIP events, PMC) are taken on ONE device-wide stream; the headline loop runs on four
+                     # frame queues, where the kernels use non-temporal frame accesses and a coarser launch geometry (same
+                     # bytes within 1 %)
+                     "notes": "the headline loop keeps four frames in flight on four hardware queues that all run on the whole "
+                              "device (the CU masks of rounds 3-5 confined nothing: profiles/r06_cu_mask_probe.txt); the frame "
+                              "time is the sum of the kernels' back-to-back floors (profiles/r06_partition_kernel_probe.txt); "
+                              "profiles/r04_power_and_partition_scaling.txt read 1040 W with one queue busy, ~1370 W with two or four"},
+    }
+    if world == 1 and not args.no_cpu_baseline:
+        extra["cpu_baseline"] = cpu_baseline(frames[0])
+    return extra
 
 
 if __name__ == "__main__":

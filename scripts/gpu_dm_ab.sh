@@ -1,7 +1,7 @@
 #!/bin/bash
 # ll_down_multi's tile edge at level 7 (4 = default: 486 workgroups; 8: 135; 2: 1.9 k): frame rate with four frames in flight, one call
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/r06mid
-F="--no-cpu-baseline --no-other-configs --no-variants --no-ceiling --steps 40 --warmup 3"
+F="--full --no-cpu-baseline --no-other-configs --no-variants --no-ceiling --steps 40 --warmup 3"
 L=$GRAFT_REPO_ROOT/halide_amd/lib
 run() {
   local envs=() ; while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift

@@ -1,7 +1,7 @@
 #!/bin/bash
 # wave priority (s_setprio 3) for ll_down01e or for ll_up0h, four frames in flight, alternating, 40 steps per point
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/r06mask
-F="--no-cpu-baseline --no-other-configs --no-variants --no-ceiling --steps 40 --warmup 3"
+F="--full --no-cpu-baseline --no-other-configs --no-variants --no-ceiling --steps 40 --warmup 3"
 L=$GRAFT_REPO_ROOT/halide_amd/lib
 run() {
   local envs=() ; while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
