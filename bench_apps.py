@@ -351,6 +351,35 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
              {"alg_bytes": 24 * W * H, "kernels_ms": kernels(call, o),
               "note": "bound by the sequential recurrence: 2 (W + H) dependent multiply-add steps per scan line"})
 
+    # ---- resize: the reference's two configurations (apps/resize/Makefile:53-79: 0.5 down on the full image, 4.0 up on the image reduced
+    #      by 0.125) at this project's usual size, every kernel and type, and 3840x2160 u8 cubic x 0.5.  Roofline: compulsory HBM bytes
+    #      (input read once + output written once).  Each line also times the same call on the general two-launch path
+    #      (hlmi_resize_general): the fused path must not be slower.  `--only resize` selects all of them, a variant's name that one.
+    if not only or any(n.startswith("resize") for n in only):
+        shapes = {"1536x2560 x0.5": (1536, 2560, 0.5), "192x320 x4": (192, 320, 4.0), "3840x2160 x0.5": (3840, 2160, 0.5)}
+        cases = [(k, t, tag) for tag in ("1536x2560 x0.5", "192x320 x4") for k in hl.RESIZE_KERNELS for t in ("uint8", "uint16", "float32")]
+        cases.append(("cubic", "uint8", "3840x2160 x0.5"))
+        for kernel, tname, tag in cases:
+            W, H, scale = shapes[tag]
+            name = f"resize_{kernel}_{tname}_{'up' if scale > 1 else 'down'}"
+            if only and "resize" not in only and name not in only:
+                continue
+            dt = np.dtype(tname)
+            img = rng.random((3, H, W), dtype=np.float32) if tname == "float32" else rng.integers(0, np.iinfo(dt).max + 1, (3, H, W)).astype(dt)
+            ow, oh = int(np.float32(W) * np.float32(scale)), int(np.float32(H) * np.float32(scale))
+            a, o = hl.Buffer(img), hl.Buffer(np.zeros((3, oh, ow), dt))
+            call = lambda: hl.resize(a, scale, o, kernel)
+            general = lambda: hl.debug_resize_general(name, a, scale, o)
+            iters = 50
+            t = timed(call, o, iters)
+            clock = last_clock[0]
+            tg = timed(general, o, iters)
+            last_clock[0] = clock
+            nbytes = dt.itemsize * 3 * (W * H + ow * oh)
+            emit(name, f"apps/resize {kernel} {tname} {tag}, 3 channels", t, ow * oh, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s",
+                 {"alg_bytes": nbytes, "kernels_ms": kernels(call, o), "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, o)},
+                  "fused_not_slower": bool(t <= tg)})
+
     # ---- lens_blur u8 stereo pair 768x1280 (the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
     if not only or "lens_blur" in only:
         W, H = 768, 1280

@@ -428,6 +428,10 @@ _interp = _bind("interpolate", [_BP, _BP])
 _iir = _bind("iir_blur", [_BP, C.c_float, _BP])
 _lens = _bind("lens_blur", [_BP, _BP, C.c_int32, C.c_int32, C.c_float, C.c_int32, _BP])
 _bgu = _bind("bgu", [C.c_float, C.c_int32, _BP, _BP, _BP, _BP])
+RESIZE_KERNELS = ("box", "linear", "cubic", "lanczos")
+_RESIZE_TYPES = {"float32": "float32", "uint8": "uint8", "uint16": "uint16"}
+_resize = {f"resize_{k}_{t}_{d}": _bind(f"resize_{k}_{t}_{d}", [_BP, C.c_float, _BP])
+           for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")}
 _cam = _bind("camera_pipe", [_BP, _BP, _BP, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _BP])
 
 
@@ -549,6 +553,33 @@ def interpolate(input, output) -> int:
 
 def iir_blur(input, alpha, output) -> int:
     return _check(_iir(_as_ptr(input), float(alpha), _as_ptr(output)))
+
+
+def resize_variant(input, scale_factor, interpolation="cubic", upsample=None) -> str:
+    """The AOT variant `resize` calls: element type from the buffer, kernel by name, direction from `upsample` (default:
+    scale_factor > 1, the rule of the reference's driver, apps/resize/resize.cpp:126)."""
+    if interpolation not in RESIZE_KERNELS:
+        raise ValueError(f"interpolation must be one of {RESIZE_KERNELS}, not {interpolation!r}")
+    raw = input.raw if isinstance(input, Buffer) else input.contents
+    tname = {(2, 32): "float32", (1, 8): "uint8", (1, 16): "uint16"}.get((raw.type.code, raw.type.bits))
+    if tname is None:
+        raise TypeError("resize takes float32, uint8 or uint16 buffers")
+    up = (float(scale_factor) > 1.0) if upsample is None else bool(upsample)
+    return f"resize_{interpolation}_{tname}_{'up' if up else 'down'}"
+
+
+def resize(input, scale_factor, output, interpolation="cubic", upsample=None) -> int:
+    """apps/resize: planar [W,H,C] f32 / u8 / u16 -> the same type at the output's size; output x, y are absolute coordinates."""
+    fn = _resize[resize_variant(input, scale_factor, interpolation, upsample)]
+    return _check(fn(_as_ptr(input), float(scale_factor), _as_ptr(output)))
+
+
+def debug_resize_general(variant: str, input, scale_factor, output) -> int:
+    """Test and measurement hook: the named resize variant on its general two-launch path, whatever the sizes."""
+    fn = lib.hlmi_resize_general
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, _BP, C.c_float, _BP]
+    return _check(fn(variant.encode(), _as_ptr(input), float(scale_factor), _as_ptr(output)))
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

@@ -10,7 +10,7 @@ using namespace hlmi;
 
 namespace {
 
-// fn: 0 halide_exp(x), 1 halide_log(x), 2 halide_pow(x, y), 3 fast_exp(x), 4 lerpf(x, y, w = z)
+// fn: 0 halide_exp(x), 1 halide_log(x), 2 halide_pow(x, y), 3 fast_exp(x), 4 lerpf(x, y, w = z), 5 halide_sin(x)
 __global__ __launch_bounds__(256) void dbg_math(int fn, const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ z,
                                                 float *__restrict__ out, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -21,7 +21,8 @@ __global__ __launch_bounds__(256) void dbg_math(int fn, const float *__restrict_
         case 1: r = dev::halide_log(x[i]); break;
         case 2: r = dev::halide_pow(x[i], y[i]); break;
         case 3: r = dev::fast_exp(x[i]); break;
-        default: r = dev::lerpf(x[i], y[i], z[i]); break;
+        case 4: r = dev::lerpf(x[i], y[i], z[i]); break;
+        default: r = dev::halide_sin(x[i]); break;
     }
     out[i] = r;
 }
@@ -30,7 +31,7 @@ __global__ __launch_bounds__(256) void dbg_math(int fn, const float *__restrict_
 
 // x, y, z, out: host pointers to n floats (y / z may be NULL where the function does not read them).  Returns 0, < 0 = HIP error.
 extern "C" int hlmi_debug_math(int fn, const float *x, const float *y, const float *z, float *out, size_t n) {
-    if (fn < 0 || fn > 4 || !x || !out || n == 0) return -1;
+    if (fn < 0 || fn > 5 || !x || !out || n == 0) return -1;
     float *d[4] = {nullptr, nullptr, nullptr, nullptr};
     const float *h[3] = {x, y, z};
     int rc = 0;

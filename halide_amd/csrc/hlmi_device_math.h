@@ -18,6 +18,8 @@
 //   log  -> halide_log + range_reduce_log                                     src/IROperator.cpp:847-919
 //   pow  -> exp(log|x|*y) + select chain                                      src/CodeGen_LLVM.cpp:3925-3941
 //   fast_exp                                                                  src/IROperator.cpp:1616-1643
+//   sin  -> halide_sin (this project's routine: the reference's CPU targets call libm's sinf, which no device routine can be
+//           bit-equal to; restated for the checker in tests/cpp/resize_check.c, the same in both canonical forms)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -126,6 +128,44 @@ __device__ __forceinline__ float fast_exp(float x_full) {
     float result = poly<6>(x, coeff);
     int biased = clampi((int)k_real + 127, 0, 255);
     return result * __uint_as_float((uint32_t)biased << 23);
+}
+
+// sin(x), SPECIFIED ON |x| <= 3 pi (1 + eps) ONLY: resize's lanczos window cuts its argument at |x| = 3 before multiplying by pi, and
+// nothing else calls it.  k = nearest integer to x * 2/pi (|k| <= 6), r = x - k pi/2 with pi/2 = P1 + P2 + P3: P1 and P2 carry 21 bits,
+// so k P1 and k P2 are exact, x - k P1 is exact and the second subtraction is an error-free two-sum (hi, lo); then the Taylor
+// polynomial of sin or cos on |r| <= pi/4 with a first-order correction for lo.  No fused operation in either canonical form: to the
+// pipelines it is one opaque function, as libm's is to the reference.  Largest error over every float in [2^-12, 9.5] of both signs:
+// 0.783 ulp (glibc's sinf: 0.561), tests/test_resize.py.
+__device__ __forceinline__ float halide_sin(float x) {
+    const float two_over_pi = 0x1.45f306p-1f;
+    const float P1 = 0x1.921fbp+0f, P2 = 0x1.5110bp-22f, P3 = 0x1.184698p-44f;
+    const float kf = rintf(x * two_over_pi);
+    const int k = (int)kf;
+    const float a = x - kf * P1;
+    const float b = kf * P2;
+    const float hi = a - b;
+    const float bb = hi - a;
+    float lo = (a - (hi - bb)) - (b + bb);
+    lo = lo - kf * P3;
+    const float z = hi * hi;
+    float r;
+    if (k & 1) {
+        float c = 0x1.1eed8ep-29f;                 // 1/12!
+        c = c * z - 0x1.27e4fcp-22f;               // 1/10!
+        c = c * z + 0x1.a01a02p-16f;               // 1/8!
+        c = c * z - 0x1.6c16c2p-10f;               // 1/6!
+        c = c * z + 0x1.555556p-5f;                // 1/4!
+        const float h = 0.5f * z, w = 1.0f - h;
+        r = w + (((1.0f - w) - h) + ((z * z) * c - hi * lo));
+    } else {
+        float s = -0x1.ae6456p-26f;                // 1/11!
+        s = s * z + 0x1.71de3ap-19f;               // 1/9!
+        s = s * z - 0x1.a01a02p-13f;               // 1/7!
+        s = s * z + 0x1.111112p-7f;                // 1/5!
+        s = s * z - 0x1.555556p-3f;                // 1/3!
+        r = hi + ((hi * z) * s + lo * (1.0f - 0.5f * z));
+    }
+    return (k & 2) ? -r : r;
 }
 
 }  // namespace dev

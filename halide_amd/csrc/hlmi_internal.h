@@ -197,6 +197,10 @@ extern const char *const kTargetString;  // "x86-64-linux-hip-gfx950" (canonical
 // conv_layer.hip: argument protocol shared by conv_layer and conv_layer_bf16
 int conv_check_args(void *uc, BufArg *args, int *CI, int *CO, int *W, int *H, int *N, bool *query);
 
+// resize.hip: the named resize variant ("resize_cubic_uint8_down", ...) on its general two-launch path whatever the sizes, for the
+// tests (fused == general bit for bit) and for bench_apps.py (fused is not slower).  Per call: no mode is kept anywhere.
+extern "C" int hlmi_resize_general(const char *variant, halide_buffer_t *input, float scale_factor, halide_buffer_t *output);
+
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;
     return (r != 0 && r < 0) ? q - 1 : q;

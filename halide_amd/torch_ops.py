@@ -15,6 +15,8 @@ Tensor axes are the Halide dimensions REVERSED (innermost last), as in the refer
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import numpy as np
 import torch
 
@@ -197,6 +199,24 @@ def iir_blur(input: torch.Tensor, alpha: float) -> torch.Tensor:
     return out
 
 
+def _resize_shape(input, scale_factor):
+    # apps/resize/resize.cpp:77-78: int out_width = in.width() * scale_factor (int * float in f32, truncated)
+    w, h = int(np.float32(input.shape[2]) * np.float32(scale_factor)), int(np.float32(input.shape[1]) * np.float32(scale_factor))
+    return (input.shape[0], h, w)
+
+
+@torch.library.custom_op("hlmi::resize", mutates_args=())
+def resize(input: torch.Tensor, scale_factor: float, interpolation: str = "cubic", upsample: Optional[bool] = None) -> torch.Tensor:
+    """apps/resize: (C, H, W) uint8 / uint16 / float32 -> (C, int(H * scale_factor), int(W * scale_factor)) of the same type;
+    interpolation box / linear / cubic / lanczos; `upsample` picks the _up or _down variant (default: scale_factor > 1)."""
+    if input.dim() != 3 or input.dtype not in (torch.uint8, torch.uint16, torch.float32):
+        raise TypeError("resize takes a (C, H, W) tensor of uint8, uint16 or float32")
+    out = torch.empty(_resize_shape(input, scale_factor), dtype=input.dtype, device=input.device)
+    with _Wrapped(input, out) as (a, o):
+        hl.resize(a, scale_factor, o, interpolation, upsample)
+    return out
+
+
 @torch.library.custom_op("hlmi::lens_blur", mutates_args=())
 def lens_blur(left_im: torch.Tensor, right_im: torch.Tensor, slices: int, focus_depth: int, blur_radius_scale: float,
               aperture_samples: int) -> torch.Tensor:
@@ -250,6 +270,11 @@ def _(input):
 @iir_blur.register_fake
 def _(input, alpha):
     return torch.empty_like(input)
+
+
+@resize.register_fake
+def _(input, scale_factor, interpolation="cubic", upsample=None):
+    return input.new_empty(_resize_shape(input, scale_factor))
 
 
 @lens_blur.register_fake

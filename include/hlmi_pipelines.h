@@ -146,6 +146,68 @@ int bgu(float r_sigma, int32_t s_sigma, struct halide_buffer_t *splat_loc, struc
         struct halide_buffer_t *slice_loc, struct halide_buffer_t *output);
 HLMI_DECLARE_AUX(bgu)
 
+/* apps/resize/resize_generator.cpp:61-63,249 — resampling to another size: planar [x, y, c] input and output of the variant's
+ * element type (f32 / u8 / u16), any channel count, any min on every dimension; the output's x, y are absolute coordinates, so
+ * an output crop equals that region of the full result.  4 kernels (box 1, linear 2, cubic 4, lanczos 6 taps) x 3 types x
+ * `_up` (resample x, then y; kernel unscaled) / `_down` (y, then x; kernel widened by 1 / scale_factor): the NAME decides, not
+ * the value of the factor.  Interleaved layouts, which the reference also specialises, are not supported: dim[0].stride != 1
+ * returns -8 as everywhere here.  Particular to this pipeline: with taps_f = ceil(T / scale_factor) (`_up`: T), a call with
+ * !(taps_f >= 1 && taps_f <= input extent) in x or in y returns -4 (the reference's clamped window would leave the input);
+ * this catches a non-finite or non-positive factor on the `_down` variants.  On `_up` variants such a factor reads in bounds
+ * and its result is unspecified.  The output's channel range must lie inside the input's (-4).  Bounds query: a query on the
+ * output leaves its dim[] as passed and sets its type; a query on the input sets its channels from the output and leaves
+ * x / y as passed (the required region is expressed through the input's own extents: the windows are clamped to them).
+ * float results are clamped to [0, 1], integer results saturate and truncate toward zero.  sin() of the lanczos kernel is this
+ * project's dev::halide_sin (the reference's CPU targets call libm).  No `_auto_schedule` twins: the reference's app has none. */
+int resize_box_float32_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_box_float32_up)
+int resize_box_float32_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_box_float32_down)
+int resize_box_uint8_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_box_uint8_up)
+int resize_box_uint8_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_box_uint8_down)
+int resize_box_uint16_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_box_uint16_up)
+int resize_box_uint16_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_box_uint16_down)
+int resize_linear_float32_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_linear_float32_up)
+int resize_linear_float32_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_linear_float32_down)
+int resize_linear_uint8_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_linear_uint8_up)
+int resize_linear_uint8_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_linear_uint8_down)
+int resize_linear_uint16_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_linear_uint16_up)
+int resize_linear_uint16_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_linear_uint16_down)
+int resize_cubic_float32_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_cubic_float32_up)
+int resize_cubic_float32_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_cubic_float32_down)
+int resize_cubic_uint8_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_cubic_uint8_up)
+int resize_cubic_uint8_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_cubic_uint8_down)
+int resize_cubic_uint16_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_cubic_uint16_up)
+int resize_cubic_uint16_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_cubic_uint16_down)
+int resize_lanczos_float32_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_lanczos_float32_up)
+int resize_lanczos_float32_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_lanczos_float32_down)
+int resize_lanczos_uint8_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_lanczos_uint8_up)
+int resize_lanczos_uint8_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_lanczos_uint8_down)
+int resize_lanczos_uint16_up(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_lanczos_uint16_up)
+int resize_lanczos_uint16_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(resize_lanczos_uint16_down)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,

@@ -249,7 +249,61 @@ def case_conv_layer_bf16(rng):
     return f"n={n} {ww}x{hh} ci={ci} co={co}", bool((err <= 2e-6 * mag.astype(np.float64) + 1e-6).all())
 
 
+_resize_checker = []
+
+
+def resize_checker():
+    """tests/cpp/resize_check.c as a shared object (oracle/ has no resize; the test suite builds the same file the same way)"""
+    if not _resize_checker:
+        import ctypes
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="resize_check"), "libresize_check.so")
+        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "cpp", "resize_check.c"), "-lm"],
+                       check=True)
+        lib = ctypes.CDLL(so)
+        lib.rc_set_canon(hl.canon_fma())
+        lib.rc_resize.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 6
+        _resize_checker.append(lib)
+    return _resize_checker[0]
+
+
+def fuzz_resize(rng):
+    """resize: random type, kernel, direction, factor in [0.05, 8], sizes, origins and crops, against tests/cpp/resize_check.c"""
+    import ctypes
+    kernel = str(rng.choice(hl.RESIZE_KERNELS))
+    tname = str(rng.choice(["float32", "uint8", "uint16"]))
+    up = bool(rng.integers(0, 2))
+    scale = float(f32(np.exp(rng.uniform(np.log(0.05), np.log(8.0)))))
+    taps = {"box": 1, "linear": 2, "cubic": 4, "lanczos": 6}[kernel]
+    need = taps if up else int(np.ceil(f32(taps) * (f32(1) / f32(scale))))
+    w, h, c = max(rdim(rng, 1, 700), need), max(rdim(rng, 1, 500), need), int(rng.integers(1, 5))
+    dt = np.dtype(tname)
+    inp = rng.random((c, h, w), dtype=f32) if tname == "float32" else rng.integers(0, np.iinfo(dt).max + 1, (c, h, w)).astype(dt)
+    in_min = [int(v) for v in rng.integers(-40, 41, 3)] if rng.random() < 0.5 else [0, 0, 0]
+    # the full output of the driver's size, or a crop of it / a region around it (windows are clamped, any region is legal)
+    fw, fh = max(1, min(int(f32(w) * f32(scale)), 1500)), max(1, min(int(f32(h) * f32(scale)), 1200))
+    x0, y0 = int(np.floor(in_min[0] * scale)), int(np.floor(in_min[1] * scale))
+    if rng.random() < 0.5:
+        ox, oy = x0 + int(rng.integers(-3, fw)), y0 + int(rng.integers(-3, fh))
+        ow, oh = int(rng.integers(1, fw + 1)), int(rng.integers(1, fh + 1))
+    else:
+        ox, oy, ow, oh = x0, y0, fw, fh
+    c0 = int(rng.integers(0, c))
+    oc = int(rng.integers(1, c - c0 + 1))
+    out_min = [ox, oy, in_min[2] + c0]
+    a, o = hl.Buffer(inp, mins=in_min), hl.Buffer(np.zeros((oc, oh, ow), dt), mins=out_min)
+    hl.resize(a, scale, o, kernel, upsample=up)
+    want = np.zeros((oc, oh, ow), dt)
+    i3 = lambda v: (ctypes.c_int * 3)(*[int(x) for x in v])
+    r = resize_checker().rc_resize(hl.RESIZE_KERNELS.index(kernel), ["float32", "uint8", "uint16"].index(tname), int(up), scale, inp.ctypes.data,
+                                   i3(in_min), i3((w, h, c)), want.ctypes.data, i3(out_min), i3((ow, oh, oc)))
+    desc = f"{kernel} {tname} {'up' if up else 'down'} x{scale!r} in {w}x{h}x{c} min {in_min} out {ow}x{oh}x{oc} min {out_min}"
+    return desc, r == 0 and same(o.numpy(), want)
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
+CASES["resize"] = fuzz_resize   # its checker is not oracle/'s
 
 
 def stress(args, only):
