@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "hlmi_pipelines.h"
 #include "hlmi_runtime.h"
@@ -188,6 +189,17 @@ bool launch_selected(const char *name);
         hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);                \
         if (hipGetLastError() != hipSuccess) return ::hlmi::launch_failed(uc, name);        \
     } while (0)
+
+// Run-time flags to template arguments, once: calls f(std::true_type / std::false_type ...) — one per flag, in order — and returns
+// what it returns.  f is a generic lambda that names the kernel instantiation (`kernel<A.value, B.value>`); all 2^n are instantiated.
+// HLMI_LAUNCH inside f returns from f on a failed launch, so f ends in `return 0` and the caller forwards the code.  Host only.
+template<typename F>
+int with_flags(F &&f) { return f(); }
+template<typename F, typename... Bs>
+int with_flags(F &&f, bool b, Bs... rest) {
+    return b ? with_flags([&](auto... t) { return f(std::true_type{}, t...); }, rest...)
+             : with_flags([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
 
 // ---------------------------------------------------------------------------------------------
 // metadata helper: every pipeline defines a static halide_filter_metadata_t

@@ -30,6 +30,14 @@
 //   ll_down0        level 0 -> 1, any K (chunks of 8 planes), vector or element-wise loads;  ll_down_strip:1
 //   ll_top, ll_up   outGPyramid[J-1], outGPyramid[j]: pointwise, data-dependent plane gathers
 //   ll_up0 / ll_up0f  outGPyramid[0] + recolour from the materialised level-1 planes
+//
+// Host path (after the kernels).  local_laplacian() reads: check arguments -> device and buffers -> ll_plan() -> workspace ->
+// the five stages -> mark_output_written.  ll_plan() fills an LlPlan on the caller's stack from the arguments, the switches
+// (ll_switches(), read once per call) and the two CU counts, without a HIP call: geometry, level table, workspace layout, which
+// kernels run (S, SU, d01, emit, fuse1, fuse2, strip2, nt, the two vectorisation predicates) and their launch geometry (RU, units,
+// LDS sizes).  LlBuffers holds the pointers (frames, remap table, the layout's regions in the arena).  A stage — ll_stage_table,
+// _down0, _down_rest, _up_coarse, _up0 — takes both, fills its kernel-argument struct and launches; run-time booleans become template
+// arguments through with_flags() (hlmi_internal.h), which instantiates every combination.
 #include "hlmi_device_math.h"
 #include "hlmi_internal.h"
 
@@ -57,8 +65,6 @@ struct Level {
     int ws;                  // row stride in floats (multiple of 4)
     size_t ps;               // plane stride in floats (multiple of 4)
     int rx0, rx1, ry0, ry1;  // R_j: region of outGPyramid[j] that is needed (absolute)
-    float *g;                // (K+1) planes
-    float *out;              // outGPyramid[j]
     // how level j is produced from level j-1 by the strip kernels
     bool odd;                // lane's source columns are 2P-1..2P+2 (odd source origin) instead of 2P-2..2P+1
     int nsx;                 // strips per row
@@ -2446,14 +2452,289 @@ LlSwitches ll_switches() {
 // RU + 2 = 302 tile rows (tests/test_index_arithmetic.py), so the switch is clamped to the proven range
 int dev_clamp_ru(int ru) { return ru < 1 ? 1 : (ru > 300 ? 300 : ru); }
 
-// last call's level table, for hlmi_debug_local_laplacian_outg (tests only)
-thread_local Level t_dbg_lv[J];
-thread_local hipStream_t t_dbg_stream = nullptr;
-thread_local bool t_dbg_out1_pending = false;  // the last call fused level 1's collapse: outGPyramid[1] was never stored
-thread_local bool t_dbg_out2_pending = false;  // ... and level 2's (ll_up0h phase 0)
-thread_local bool t_dbg_emit = false;         // ... by ll_up0h: level 1 holds its three planes only (ll_down01e)
-thread_local int t_dbg_K = 0;
-thread_local float t_dbg_Km1 = 0;
+// ---- the plan of one call: every decision the launches need — geometry, workspace layout, which kernels run and how they are
+// launched — made by ll_plan() before anything is enqueued.  It holds no pointer into the workspace (LlBuffers does); it lives on
+// local_laplacian()'s stack and the stages read it by reference.
+struct PairGeom {   // columns of a two-level walk (levels j+1 and j+2 from level j: ll_down01e / ll_down01f, ll_down_strip2)
+    int S2;         // level-(j+2) columns a wave produces per row
+    int Pbase;      // leftmost level-(j+1) column pair of strip 0
+    int nsx;        // strips per row
+};
+struct LlPlan {
+    Geometry gm;
+    Level lv[J];
+    size_t off_g[J], off_out[J], off_l0, ws_floats;   // workspace layout in floats (the remap table at 0); regions are multiples of 64
+    // the frames (pointers, strides, channel offsets, output box), beta and RU, the rows per wave of the level-0 kernel: complete
+    // after ll_plan(), read by every stage; the workspace pointers of the struct are ll_stage_up0's to set
+    Up0Args u0;
+    int nlut;
+    // chain shape
+    int S, SU;         // first level ll_down_multi makes / ll_up_multi collapses (J: none)
+    int up_low;        // the ll_up:j launches run from level min(SU, J - 1) - 1 down to this one
+    bool lut_cache;    // the remap table comes from the cache of tables
+    bool lut_lds;      // ... and fits the default 64 KB dynamic-LDS window
+    bool vec_frame;    // 4-byte accesses to the frames (ll_up0<VEC>; the condition of `fast`)
+    bool vec_in;       // 8-byte loads of the input (ll_down0<VEC>; the condition of `d01`)
+    bool b1;           // beta == 1
+    bool fast, fuse1, fuse2, emit, nt;
+    bool d01;          // levels 1 and 2 in one walk of the input (ll_down01e / ll_down01f), no ll_down_strip:1
+    bool strip2;       // levels 3 and 4 in one launch (ll_down_strip2), no ll_down_strip:2 / :3
+    // launch geometry
+    struct { PairGeom pg; bool exch; int nsy, nunits; size_t lds; } d0;   // ll_down0, or (d01: pg, exch) ll_down01e / ll_down01f
+    struct { PairGeom pg; int nsy, nunits; } s2;                          // ll_down_strip2 (strip2)
+    int units_strip;                                                      // unit target of the ll_down_strip launches
+    size_t up0_lds;                                                       // dynamic LDS of ll_up0h / ll_up0f / ll_up0
+};
+
+// the resolved pointers of one call: the remap table and where the plan's layout landed in the stream's arena
+struct LlBuffers {
+    float *lut, *outl0;
+    float *g[J], *outg[J];   // (K+1) planes of level j, outGPyramid[j]; [0] unused
+};
+
+PairGeom pair_geom(const Level &d, const Level &e) {   // d: level j+1, e: level j+2; e.odd == (d.lox & 1)
+    PairGeom g;
+    g.S2 = (d.odd || e.odd) ? 62 : 61;
+    const int lim = e.odd ? 2 * e.lox - 1 : 2 * e.lox - 2;   // leftmost pair must reach level-(j+2) column so2
+    g.Pbase = min(d.lox, lim);                                // same parity as so1 in either case
+    const int hi1 = d.lox + d.w - 1, hi2 = e.lox + e.w - 1;
+    const int x2_first = e.odd ? (g.Pbase + 1) / 2 + 0 : g.Pbase / 2 + 1;   // Pbase + 1 (resp. Pbase) is even: exact
+    g.nsx = max((hi2 - x2_first + g.S2) / g.S2, (hi1 - g.Pbase + 2 * g.S2) / (2 * g.S2));
+    return g;
+}
+
+// No HIP call, no lock, no allocation: a function of the checked arguments, the switches, the alignment of the two device pointers
+// and the CU counts the stream and the device are sized for.
+void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *output, int levels, float beta, const LlSwitches &sw,
+             int stream_cus, int device_cus) {
+    Up0Args &p = pl.u0;
+    const int ow = p.ow = output->dim[0].extent, oh = p.oh = output->dim[1].extent, nc = p.nc = output->dim[2].extent;
+    Geometry &gm = pl.gm;
+    gm.K = levels;
+    gm.half = (levels - 1) * 256;
+    gm.Km1 = (float)(levels - 1);
+    gm.inv_Km1 = 1.0f / gm.Km1;
+    gm.ix0 = input->dim[0].min, gm.ix1 = gm.ix0 + input->dim[0].extent - 1;
+    gm.iy0 = input->dim[1].min, gm.iy1 = gm.iy0 + input->dim[1].extent - 1;
+    const int ic0 = input->dim[2].min, ic1 = ic0 + input->dim[2].extent - 1, iw = gm.ix1 - gm.ix0 + 1;
+
+    // per-level boxes.  lo/hi: beyond them the level is constant; so: storage origin (<= lo) whose parity
+    // makes the strip kernels' 16-byte loads / 8-byte stores aligned (see ll_down0 / hpair).
+    Level *lv = pl.lv;
+    int lox = gm.ix0, hix = gm.ix1, loy = gm.iy0, hiy = gm.iy1, so = gm.ix0;
+    int rx0 = output->dim[0].min, rx1 = rx0 + ow - 1, ry0 = output->dim[1].min, ry1 = ry0 + oh - 1;
+    size_t ws_floats = (size_t)(2 * gm.half + 1 + 63) & ~(size_t)63;
+    for (int j = 0; j < J; j++) {
+        Level &L = lv[j];
+        L.lox = so, L.loy = loy, L.w = hix - so + 1, L.h = hiy - loy + 1;
+        L.ws = (L.w + 3) & ~3;
+        L.ps = ((size_t)L.ws * L.h + 3) & ~(size_t)3;
+        L.rx0 = rx0, L.rx1 = rx1, L.ry0 = ry0, L.ry1 = ry1;
+        if (j >= 1) {
+            pl.off_g[j] = ws_floats;
+            ws_floats += ((size_t)(levels + 1) * L.ps + 63) & ~(size_t)63;
+            pl.off_out[j] = ws_floats;
+            ws_floats += (L.ps + 63) & ~(size_t)63;
+        }
+        // next level
+        const bool odd = (so & 1) != 0;
+        const int par = odd ? (floor_div(so + 1, 2) & 1) : ((floor_div(so, 2) + 1) & 1);
+        lox = floor_div(lox - 2, 2), hix = floor_div(hix + 2, 2);
+        loy = floor_div(loy - 2, 2), hiy = floor_div(hiy + 2, 2);
+        so = lox - ((lox - par) & 1);
+        if (j + 1 < J) {
+            lv[j + 1].odd = odd;
+            lv[j + 1].nsx = (hix - so + 1 + STRIP - 1) / STRIP;
+        }
+        rx0 = floor_div(rx0 - 1, 2), rx1 = floor_div(rx1 + 1, 2);
+        ry0 = floor_div(ry0 - 1, 2), ry1 = floor_div(ry1 + 1, 2);
+    }
+    p.in = dev_ptr<uint16_t>(input), p.out = dev_ptr<uint16_t>(output);
+    const uintptr_t din = (uintptr_t)p.in, dout = (uintptr_t)p.out;
+    const long in_sy = p.in_sy = input->dim[1].stride, in_sc = input->dim[2].stride;
+    const long out_sy = p.out_sy = output->dim[1].stride, out_sc = p.out_sc = output->dim[2].stride;
+    p.ox0 = output->dim[0].min, p.oy0 = output->dim[1].min;
+    p.beta = beta, pl.b1 = (beta == 1.0f);
+    const int oc0 = output->dim[2].min;
+    bool same = (nc == 3);
+    for (int ch = 0; ch < 3; ch++) {
+        // clamped channels feeding `gray` (repeat_edge clamps the channel coordinate too, :28)
+        p.gco[ch] = (long)((ch < ic0 ? ic0 : (ch > ic1 ? ic1 : ch)) - ic0) * in_sc;
+        p.cco[ch] = ch < nc ? (long)(oc0 + ch - ic0) * in_sc : 0;
+        if (p.cco[ch] != p.gco[ch]) same = false;
+    }
+    p.same_ch = same ? 1 : 0;
+    pl.lut_cache = !sw.no_lut_cache.value_or(0);
+    const bool lut_lds = pl.lut_lds = levels <= 15;  // LUT must fit the default 64 KB dynamic-LDS window
+    const int nlut = pl.nlut = 2 * gm.half + 1;
+    const size_t lut_sh = lut_lds ? sizeof(float) * nlut : 0;
+
+    // levels >= S are produced / collapsed by the two multi-level kernels (S = 4: 2 launches instead of 7)
+    const int S = pl.S = [&] {
+        const int v = sw.fuse_from.value_or(4);
+        return (v >= J - 5 && v <= J - 2) ? v : J;
+    }();
+    // the collapse (outGPyramid[J-1] .. outGPyramid[SU]) is ONE launch (ll_up_multi); opt-in: on the large levels its per-pixel overhead exceeds the saved launches
+    // Default 3 when the down pass fuses from 4: outGPyramid[3] joins the collapse launch (one ll_up launch and its ~4.5 us of
+    // dependent-launch latency less: 110.8 -> 108.9 us per frame on one stream); from level 2 the kernel's per-pixel overhead
+    // costs more than the launch it saves (114.2).  0: SU = S.
+    const int SU = pl.SU = [&] {
+        const int v = sw.upchain_from.value_or(S == 4 ? 3 : 0);   // (S == 3: SU = S)
+        return (v >= 1 && v <= J - 2) ? v : S;
+    }();
+    // ---- which kernels run: decided before the workspace is sized (the re-cut dataflow's outLPyramid[0] plane is only requested
+    // by the calls that fill it)
+    const bool partitioned = stream_cus < device_cus;
+    bool vec_frame = (din % 4 == 0) && (dout % 4 == 0) && in_sy % 2 == 0 && out_sy % 2 == 0 && out_sc % 2 == 0 &&
+                     ((p.ox0 - gm.ix0) % 2 == 0) && !sw.no_vec.value_or(0);
+    for (int ch = 0; ch < 3; ch++) vec_frame = vec_frame && p.gco[ch] % 2 == 0 && p.cco[ch] % 2 == 0;
+    pl.vec_frame = vec_frame;
+    const bool vec_in = pl.vec_in = (din % 8 == 0) && in_sy % 4 == 0 && p.gco[0] % 4 == 0 && p.gco[1] % 4 == 0 && p.gco[2] % 4 == 0 &&
+                                    iw % 4 == 0 && !sw.no_vec.value_or(0);
+    const bool fast = pl.fast = vec_frame && same && nc == 3 && (ow & 1) == 0 && (p.ox0 & 1) == 0 &&
+                                (double)(levels + 1) * (4.0 * (double)lv[1].ps) < 4.0e9;
+    // the fused collapse needs level 2 to be a stored level of its own (SU >= 2 always holds: SU >= S >= 4 or the
+    // opt-in up-chain, which starts at >= 1 and then owns level 1 itself)
+    const bool fuse1 = pl.fuse1 = fast && SU >= 2;
+    // ll_down01f / ll_down01e: levels 1 and 2 from the input in one walk (levels == KCH planes in registers, 8-byte input loads);
+    // the ll_down_strip:1 launch is skipped
+    const bool d01 = pl.d01 = levels == KCH && lut_lds && vec_in;
+    // The default for the common geometry: ll_down01e emits outLPyramid[0] and three planes of level 1, ll_up0h collapses
+    // (HLMI_LL_EMIT=0: the round-3 pair ll_down01f / ll_up0f with the materialised K + 1 level-1 planes)
+    const bool emit = pl.emit = d01 && fast && fuse1 && lv[1].ws < (1 << 24) && sw.emit.value_or(1);   // ws: ll_up0h's 24-bit row products
+    // rows per wave of ll_up0f / ll_up0: taller tiles re-read less of level 1 (18 coarse rows per 16 output rows, 34 per 32) but keep
+    // a wave busy longer.  On a frame-queue stream (`partitioned`: one of several library queues with frames in flight, runtime.cpp),
+    // where several frames share the memory system and the frame rate is set by
+    // bytes, 32 rows measure 2.7 % faster (84.8 vs 82.6 Gpx/s); on a stream that owns the device 16 rows do (72.7 vs 68.2).
+    // ll_up0h has no data-dependent gathers to amortise over a tall tile: short tiles (more, smaller workgroups) are faster on a
+    // stream that owns the device (31.7 us at 8 rows per wave against 33.5 / 38.4 at 16 / 32); with four frames in flight 8 / 12 / 16 /
+    // 24 / 32 rows measure 107.8 / 110.1 / 111.2 / 112.3 / 112.3 Gpx/s (profiles/r06_frame_queue_geometry.txt), and next to ONE
+    // resident ll_down01e workgroup per CU 32 rows beat 24 / 40 / 48 / 64 (profiles/r06_coresidency_ab.txt)
+    const int RU = p.RU = dev_clamp_ru(sw.ru.value_or(emit ? (partitioned ? 32 : 8) : fuse1 ? (partitioned ? 32 : 16) : 8));
+    // non-temporal frame / outLPyramid[0] accesses: +6-7 % frames per second with four frames in flight, -2-3 % on a stream that owns the device
+    pl.nt = sw.nt.value_or(partitioned ? 1 : 0) != 0;
+    // ll_up0h also collapses level 2 (into an LDS tile) when level 3 is a stored level of its own: the ll_up:2 launch goes
+    // (with four frames in flight: 79.4 -> 76.4 us per frame; on a stream that
+    // owns the device the tile redundancy used to cost what the launch saved — 109 -> 111 us in round 4 — until round 5's batched
+    // tile phases: 104.1 -> 98.7 us per frame, 115 -> 110.6 for one call + sync)
+    pl.fuse2 = emit && SU >= 3 && SU < J && sw.fuse_up2.value_or(1);
+    pl.up_low = fuse1 ? (pl.fuse2 ? 3 : 2) : 1;
+    // levels 3 and 4 from level 2 in one launch (ll_down_strip2) when the chain would otherwise run ll_down_strip:2 and :3
+    // (one stream: 111.6 -> 105.1 us per frame back to back, 123 -> 116.6 for one call + sync; four frame queues 75-77 -> 72-76)
+    pl.strip2 = d01 && S == 4;
+
+    // ---- workspace: the levels and outLPyramid[0] of the re-cut dataflow (input width x output rows)
+    pl.off_l0 = ws_floats;
+    if (emit) ws_floats += ((size_t)iw * (size_t)oh + 63) & ~(size_t)63;
+    pl.ws_floats = ws_floats;
+
+    // ---- launch geometry
+    constexpr int WPB = D0_THREADS / 64;
+    if (!d01) {
+        const Level &d = lv[1];
+        // two waves per SIMD with (almost) equal row counts: the kernel is VALU-bound, so balance is what counts
+        const int target = sw.units0.value_or(8 * device_cus);
+        pl.d0.nsy = max(1, min(max(target / d.nsx, (d.h + 63) / 64), max(1, d.h / 2)));
+        pl.d0.nunits = d.nsx * pl.d0.nsy;
+        pl.d0.lds = (lut_lds ? sizeof(float) * ((nlut + 1) & ~1) : 0) + sizeof(float2) * D0_THREADS * (KCH + 1);
+    } else {
+        const Level &e = lv[2];
+        const PairGeom pg = pl.d0.pg = pair_geom(lv[1], e);
+        // ll_down01f: sized for the whole device on every stream (fewer, taller units measured 2-3 % slower: 101.5 vs 98.9 us per
+        // frame).  ll_down01e on a frame-queue stream (several frames in flight, the launches of different frames fill the device
+        // together): fewer and taller units — fewer seam rows walked twice, less per-workgroup set-up — measure 10 % more frames
+        // per second than the 2048 units of a launch that has the device to itself (round 6, four queues: 2048 / 1536 / 1024 /
+        // 896..384 / 256 units -> 109.4 / 110.2 / 111.3 / 112.1-112.5 / 103.3 Gpx/s, profiles/r06_frame_queue_geometry.txt; with
+        // one workgroup per CU — below — 640 units = 160 workgroups of 55 level-2 rows measure best),
+        // while on a stream that owns the device one round of resident waves is what counts (52.7 us against 57.1)
+        const int target2 = sw.units0.value_or(emit && partitioned ? 10 * stream_cus : 8 * device_cus);
+        // EXCH: a workgroup = 4 vertically adjacent units exchanging their seam rows through LDS.  With n level-2 rows
+        // per wave a workgroup owns R = 4 n - 1 rows (the bottom wave walks the two seam rows of the next workgroup
+        // itself and owns one row less); n = the smallest that keeps the launch within `target2` resident waves.
+        bool exch = sw.d01_exch.value_or(1) != 0;
+        int nwy = 0;
+        auto ceil_div = [](int x, int y) { return (x + y - 1) / y; };
+        if (exch) {
+            const int nwy_max = max(1, target2 / (WPB * pg.nsx));
+            const int n = max(2, (ceil_div(e.h, nwy_max) + 1 + 3) / 4);
+            nwy = ceil_div(e.h, 4 * n - 1);
+            exch = e.h / nwy >= 4;     // every workgroup gets at least 4 rows; smaller images take the plain units
+        }
+        pl.d0.exch = exch;
+        if (exch) {
+            pl.d0.nsy = nwy;
+            pl.d0.nunits = pg.nsx * nwy * WPB;
+        } else {
+            pl.d0.nsy = max(1, min(max(target2 / pg.nsx, (e.h + 31) / 32), e.h));
+            pl.d0.nunits = pg.nsx * pl.d0.nsy;
+        }
+        size_t sh2 = sizeof(float) * ((nlut + 1) & ~1) + sizeof(float2) * D01_STATE * (WPB + (exch ? WPB - 1 : 0));
+        // With frames in flight (a frame-queue stream) ll_down01e asks for so much LDS that only ONE of its workgroups fits a
+        // CU (2 x 77 KB would): the other half of the CU's registers and 77 KB of its LDS stay free for the workgroups of the
+        // OTHER frames' kernels — ll_up0h above all, which waits for memory while this one computes.  Four frames in flight,
+        // 40 steps, alternating A/B on three boxes: 110.3-114.5 -> 113.5-114.1 Gpx/s with the 512 units / 24 rows above,
+        // 115.8-121.8 with 640 units and 32 rows per ll_up0h wave (profiles/r06_coresidency_ab.txt).  On a stream that owns
+        // the device the second workgroup is what hides this kernel's own latencies (84.7 -> 74.7 Gpx/s without it).
+        // HLMI_LL_D01_PAD_LDS: bytes of unused LDS to add instead (experiments; 0 = two workgroups per CU).
+        const int pad = sw.d01_pad_lds.value_or(emit && partitioned ? -1 : 0);
+        constexpr size_t kHalfCuLds = 160 * 1024 / 2;   // gfx950: 160 KB per CU
+        if (pad < 0) sh2 = max(sh2, kHalfCuLds + 2048);
+        else sh2 += (size_t)pad;
+        pl.d0.lds = sh2;
+    }
+    if (pl.strip2) {
+        pl.s2.pg = pair_geom(lv[3], lv[4]);
+        pl.s2.nsy = (lv[4].h + S2_RPU - 1) / S2_RPU;
+        pl.s2.nunits = (levels + 1) * pl.s2.pg.nsx * pl.s2.nsy;
+    }
+    // ll_down_strip: enough waves to fill the chip on the big levels, short strips on the small ones
+    pl.units_strip = 16 * device_cus;
+    pl.up0_lds = emit   ? sizeof(float) * ((size_t)U0_TS * (RU + 2) + (size_t)U0H_T2 * (RU / 2 + 4))
+                 : fast ? lut_sh + (fuse1 ? ((lut_lds && (nlut & 1)) ? 4 : 0) + sizeof(float) * U0_TS * (RU + 2) : 0)
+                        : lut_sh;
+}
+
+// last call's plan and pointers, for hlmi_debug_local_laplacian_outg (tests only)
+struct LlLastCall {
+    LlPlan pl;
+    LlBuffers b;
+    hipStream_t stream;
+    bool out1_pending;  // the last call fused level 1's collapse: outGPyramid[1] was never stored
+    bool out2_pending;  // ... and level 2's (ll_up0h phase 0)
+};
+thread_local LlLastCall t_dbg = {};
+
+// ---- kernel arguments of the stages between the two big kernels
+StripArgs strip_args(const LlPlan &pl, const LlBuffers &b, int j) {   // level j -> j + 1
+    const Level &sl = pl.lv[j], &d = pl.lv[j + 1];
+    const int cols = d.nsx * (pl.gm.K + 1);
+    StripArgs a;
+    a.src = b.g[j], a.slox = sl.lox, a.sloy = sl.loy, a.sw = sl.w, a.sh = sl.h, a.sws = sl.ws, a.sps = sl.ps;
+    a.dst = b.g[j + 1], a.Xs = d.lox, a.dloy = d.loy, a.dw = d.w, a.dh = d.h, a.dws = d.ws, a.dps = d.ps;
+    a.nsx = d.nsx;
+    a.nsy = max(1, min(max(pl.units_strip / cols, (d.h + 31) / 32), max(1, d.h / 2)));
+    a.nunits = cols * a.nsy;
+    return a;
+}
+CoarseArgs coarse_args(const LlPlan &pl, const LlBuffers &b, int from) {
+    CoarseArgs ca;
+    for (int dl = 0; from + dl < J; dl++) {
+        const Level &L = pl.lv[from + dl];
+        DevLevel &D = ca.lv[dl];
+        D.g = b.g[from + dl], D.out = b.outg[from + dl], D.lox = L.lox, D.loy = L.loy, D.w = L.w, D.h = L.h, D.ws = L.ws, D.ps = (unsigned)L.ps;
+        D.rx0 = L.rx0, D.ry0 = L.ry0, D.rw = L.rx1 - L.rx0 + 1, D.rh = L.ry1 - L.ry0 + 1;
+    }
+    ca.K = pl.gm.K, ca.Km1 = pl.gm.Km1;
+    return ca;
+}
+UpArgs up_args(const LlPlan &pl, const LlBuffers &b, int j) {   // outGPyramid[j] from level j and outGPyramid[j + 1]
+    const Level &a = pl.lv[j], &c = pl.lv[j + 1];
+    UpArgs u;
+    u.g = b.g[j], u.ws = a.ws, u.ps = a.ps, u.lox = a.lox, u.loy = a.loy, u.gc = b.g[j + 1], u.outc = b.outg[j + 1], u.cws = c.ws, u.cps = c.ps;
+    u.clox = c.lox, u.cloy = c.loy, u.rx0 = a.rx0, u.ry0 = a.ry0, u.rw = a.rx1 - a.rx0 + 1, u.rh = a.ry1 - a.ry0 + 1;
+    u.K = pl.gm.K, u.Km1 = pl.gm.Km1, u.out = b.outg[j];
+    return u;
+}
 
 // ---- cache of remap tables: the LUT is a function of (levels, alpha) only — a video stream calls with the same pair frame
 // after frame — so it is kept in memory of its own per (device, levels, alpha) and ll_remap_lut runs when the pair is new
@@ -2470,6 +2751,227 @@ struct LutImage {
 std::mutex g_lut_mu;
 LutImage g_lut[8];
 uint64_t g_lut_clock = 0;
+
+// ---- the stages of the chain, in launch order.  Each takes the plan, the resolved pointers and the stream, fills its
+// kernel-argument struct and launches; a non-zero return is the error code of the call.
+
+// stage 1: the remap table — b.lut becomes the cached table of (device, levels, alpha), computed now if the pair is new;
+// HLMI_LL_NO_LUT_CACHE: computed in the workspace in every call
+int ll_stage_table(void *uc, const DeviceCtx &ctx, const LlPlan &pl, float alpha, LlBuffers &b) {
+    hipStream_t st = ctx.stream;
+    const int levels = pl.gm.K, nlut = pl.nlut;
+    if (pl.lut_cache) {
+        uint32_t abits;
+        memcpy(&abits, &alpha, 4);
+        std::unique_lock<std::mutex> lock(g_lut_mu);
+        LutImage *hit = nullptr, *slot = &g_lut[0];
+        for (auto &e : g_lut) {
+            if (e.valid && e.device == ctx.device && e.levels == levels && e.alpha_bits == abits) hit = &e;
+        }
+        if (hit) {
+            hit->used = ++g_lut_clock;
+            if (hit->stream != st) HLMI_HIP(uc, wait_done(st, hit->ready));
+            b.lut = hit->dev;
+        } else {
+            for (auto &e : g_lut) {
+                if (!e.dev) { slot = &e; break; }
+                if (e.used < slot->used) slot = &e;
+            }
+            slot->valid = false;
+            if (slot->dev) {   // evicting (more than 8 (levels, alpha) pairs in use): launches on any stream may still read it
+                HLMI_HIP(uc, hipDeviceSynchronize());
+                (void)hipFree(slot->dev);
+                slot->dev = nullptr;
+            }
+            HLMI_HIP(uc, hipMalloc((void **)&slot->dev, sizeof(float) * ((size_t)nlut + 64)));
+            if (!slot->ready) HLMI_HIP(uc, hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
+            slot->device = ctx.device, slot->levels = levels, slot->alpha_bits = abits, slot->stream = st, slot->used = ++g_lut_clock;
+            b.lut = slot->dev;
+            HLMI_LAUNCH(uc, "ll_remap_lut", st, ll_remap_lut, dim3((nlut + 255) / 256), dim3(256), 0, b.lut, pl.gm.half, alpha);
+            HLMI_HIP(uc, record_done(slot->ready, st));
+            slot->valid = true;
+        }
+    } else {
+        HLMI_LAUNCH(uc, "ll_remap_lut", st, ll_remap_lut, dim3((nlut + 255) / 256), dim3(256), 0, b.lut, pl.gm.half, alpha);
+    }
+    return 0;
+}
+
+// stage 2: level 0 -> 1 (ll_down0), or levels 0 -> 1 -> 2 in one walk (ll_down01e / ll_down01f)
+int ll_stage_down0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st) {
+    const Geometry &gm = pl.gm;
+    const Up0Args &f = pl.u0;   // the frames
+    const Level &d = pl.lv[1], &e = pl.lv[2];
+    const int levels = gm.K, iw = gm.ix1 - gm.ix0 + 1;
+    Levels lev;
+    for (int k = 0; k < MAX_K; k++) lev.v[k] = (float)k * gm.inv_Km1;
+    constexpr int WPB = D0_THREADS / 64;
+    dim3 block(D0_THREADS);
+    // algorithmic bytes: the input read once (u16 x 3 channels), the K+1 level-1 planes written once
+    const double d0_bytes = 6.0 * iw * (gm.iy1 - gm.iy0 + 1) + 4.0 * (levels + 1) * d.w * d.h;
+    if (!pl.d01) {
+        dim3 grid((pl.d0.nunits + WPB - 1) / WPB);
+        timing_note_bytes(d0_bytes);
+        return with_flags([&](auto O, auto V, auto L, auto B) -> int {
+            HLMI_LAUNCH(uc, "ll_down0", st, (ll_down0<O.value, V.value, L.value, B.value>), grid, block, pl.d0.lds, f.in, f.in_sy,
+                        f.gco[0], f.gco[1], f.gco[2], gm, lev, f.beta, b.lut, b.g[1], d.lox, d.loy, d.w, d.h, d.ws, d.ps, d.nsx,
+                        pl.d0.nsy, pl.d0.nunits);
+            return 0;
+        }, d.odd, pl.vec_in, pl.lut_lds, pl.b1);
+    }
+    D01Args a;
+    a.in = f.in, a.in_sy = f.in_sy, a.co0 = f.gco[0], a.co1 = f.gco[1], a.co2 = f.gco[2], a.beta = f.beta, a.lut_g = b.lut;
+    a.g1 = b.g[1], a.so1 = d.lox, a.loy1 = d.loy, a.w1 = d.w, a.h1 = d.h, a.ws1 = d.ws, a.ps1 = d.ps;
+    a.g2 = b.g[2], a.so2 = e.lox, a.loy2 = e.loy, a.w2 = e.w, a.h2 = e.h, a.ws2 = e.ws, a.ps2 = e.ps;
+    a.S2 = pl.d0.pg.S2, a.Pbase = pl.d0.pg.Pbase, a.nsx = pl.d0.pg.nsx, a.nsy = pl.d0.nsy, a.nunits = pl.d0.nunits;
+    a.nsy_magic = a.nsy == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)a.nsy + 1ull);   // 0: nsy == 1
+    a.rows_base = e.h / a.nsy, a.rows_rem = e.h % a.nsy;
+    dim3 grid((a.nunits + WPB - 1) / WPB);
+    if (pl.emit) {
+        // input read once; outLPyramid[0] (4 B per output pixel), three level-1 planes and K + 1 level-2 planes written
+        timing_note_bytes(6.0 * iw * (gm.iy1 - gm.iy0 + 1) + 4.0 * iw * f.oh + 4.0 * 3.0 * d.w * d.h + 4.0 * (levels + 1) * e.w * e.h);
+        D01EArgs ae;
+        ae.d = a, ae.outl0 = b.outl0, ae.oy0 = f.oy0, ae.oh = f.oh;
+        ae.nsx_magic = a.nsx == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)a.nsx + 1ull);
+        return with_flags([&](auto O0, auto O1, auto B, auto EX, auto NT) -> int {
+            HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0.value, O1.value, B.value, EX.value, NT.value>), grid, block, pl.d0.lds, ae, gm, lev);
+            return 0;
+        }, d.odd, e.odd, pl.b1, pl.d0.exch, pl.nt);
+    }
+    timing_note_bytes(d0_bytes + 4.0 * (levels + 1) * e.w * e.h);
+    return with_flags([&](auto O0, auto O1, auto B, auto EX) -> int {
+        HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01f<O0.value, O1.value, B.value, EX.value>), grid, block, pl.d0.lds, a, gm, lev);
+        return 0;
+    }, d.odd, e.odd, pl.b1, pl.d0.exch);
+}
+
+// stage 3: the levels between: ll_down_strip2 (3 and 4 from 2), ll_down_strip:j (j + 1 from j), then ll_down_multi (S + 1 .. J - 1 from S)
+int ll_stage_down_rest(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st) {
+    const Level *lv = pl.lv;
+    const int levels = pl.gm.K, S = pl.S;
+    if (pl.strip2) {
+        const Level &sl = lv[2], &d = lv[3], &e = lv[4];
+        Strip2Args a;
+        a.src = b.g[2], a.slox = sl.lox, a.sloy = sl.loy, a.sw = sl.w, a.sh = sl.h, a.sws = sl.ws, a.sps = sl.ps;
+        a.g1 = b.g[3], a.so1 = d.lox, a.loy1 = d.loy, a.w1 = d.w, a.h1 = d.h, a.ws1 = d.ws, a.ps1 = d.ps;
+        a.g2 = b.g[4], a.so2 = e.lox, a.loy2 = e.loy, a.w2 = e.w, a.h2 = e.h, a.ws2 = e.ws, a.ps2 = e.ps;
+        a.S2 = pl.s2.pg.S2, a.Pbase = pl.s2.pg.Pbase, a.nsx = pl.s2.pg.nsx, a.nsy = pl.s2.nsy, a.nunits = pl.s2.nunits;
+        timing_note_bytes(4.0 * (levels + 1) * ((double)sl.w * sl.h + (double)d.w * d.h + (double)e.w * e.h));
+        dim3 grid((a.nunits + 3) / 4), block(256);
+        if (int r = with_flags([&](auto O0, auto O1) -> int {
+                HLMI_LAUNCH(uc, "ll_down_strip2:2", st, (ll_down_strip2<O0.value, O1.value>), grid, block, 0, a);
+                return 0;
+            }, d.odd, e.odd)) return r;
+    }
+    for (int j = 1; j + 1 < J; j++) {
+        if (pl.strip2 && (j == 2 || j == 3)) continue;
+        if (j == S) {
+            const CoarseArgs ca = coarse_args(pl, b, S);
+            long total = 0;
+            for (int dl = 1; S + dl < J; dl++) total += (long)(levels + 1) * lv[S + dl].w * lv[S + dl].h;
+            const int ntx = (lv[J - 1].w + DM_T - 1) / DM_T, nty = (lv[J - 1].h + DM_T - 1) / DM_T;
+            dim3 grid((unsigned)(ntx * nty * (levels + 1))), block(256);
+            char nm[32];
+            snprintf(nm, sizeof nm, "ll_down_multi:%d", S);
+            timing_note_bytes(4.0 * ((double)(levels + 1) * lv[S].w * lv[S].h + (double)total));
+            if (J - 1 - S == 4) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<4>), grid, block, 0, ca, ntx, nty);
+            else if (J - 1 - S == 3) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<3>), grid, block, 0, ca, ntx, nty);
+            else if (J - 1 - S == 2) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<2>), grid, block, 0, ca, ntx, nty);
+            else HLMI_LAUNCH(uc, nm, st, (ll_down_multi<1>), grid, block, 0, ca, ntx, nty);
+            break;
+        }
+        if (j == 1 && pl.d01) continue;   // level 2 came out of ll_down01e / ll_down01f
+        const StripArgs sa = strip_args(pl, b, j);
+        dim3 grid((sa.nunits + 3) / 4), block(256);
+        char nm[32];
+        snprintf(nm, sizeof nm, "ll_down_strip:%d", j);
+        timing_note_bytes(4.0 * (levels + 1) * ((double)lv[j].w * lv[j].h + (double)lv[j + 1].w * lv[j + 1].h));
+        if (int r = with_flags([&](auto O) -> int {
+                HLMI_LAUNCH(uc, nm, st, (ll_down_strip<O.value>), grid, block, 0, sa);
+                return 0;
+            }, lv[j + 1].odd)) return r;
+    }
+    return 0;
+}
+
+// stage 4: the collapse of the coarse levels in one launch (ll_up_multi: outGPyramid[SU] from levels SU .. J - 1; none: ll_top,
+// outGPyramid[J - 1]), then an ll_up:j launch per level down to the first one the level-0 kernel does not collapse itself
+int ll_stage_up_coarse(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st) {
+    const Level *lv = pl.lv;
+    const int levels = pl.gm.K, SU = pl.SU;
+    if (SU < J) {
+        const CoarseArgs cu = coarse_args(pl, b, SU);
+        const int ntx = (cu.lv[0].rw + UM_T - 1) / UM_T, nty = (cu.lv[0].rh + UM_T - 1) / UM_T;
+        dim3 grid((unsigned)(ntx * nty)), block(256);
+        char nm[32];
+        snprintf(nm, sizeof nm, "ll_up_multi:%d", SU);
+        {   // per output pixel of level SU: 2 planes of g + inG read, outG written; coarser levels add 1/3
+            const double px = (double)cu.lv[0].rw * cu.lv[0].rh;
+            timing_note_bytes(4.0 * 4.0 * px * (SU + 1 < J ? 4.0 / 3.0 : 1.0));
+        }
+        switch (J - 1 - SU) {
+#define LL_UM(T) case T: HLMI_LAUNCH(uc, nm, st, (ll_up_multi<T>), grid, block, 0, cu, ntx); break;
+            LL_UM(1) LL_UM(2) LL_UM(3) LL_UM(4) LL_UM(5) LL_UM(6)
+#undef LL_UM
+        }
+    } else {
+        const Level &t = lv[J - 1];
+        int rw = t.rx1 - t.rx0 + 1, rh = t.ry1 - t.ry0 + 1;
+        HLMI_LAUNCH(uc, "ll_top", st, ll_top, dim3((rw + 63) / 64, rh), dim3(64), 0, b.g[J - 1], t.ws, t.ps, t.lox, t.loy, t.rx0,
+                    t.ry0, rw, rh, levels, pl.gm.Km1, b.outg[J - 1]);
+    }
+    for (int j = min(SU, J - 1) - 1; j >= pl.up_low; j--) {
+        const UpArgs ua = up_args(pl, b, j);
+        char nm[32];
+        snprintf(nm, sizeof nm, "ll_up:%d", j);
+        // per output: 2 planes of g_j + inG_j read, outG_j written; per coarse pixel: 2 planes of g_{j+1} + outG_{j+1}
+        timing_note_bytes(4.0 * (4.0 * ua.rw * ua.rh + 3.0 * (lv[j + 1].rx1 - lv[j + 1].rx0 + 1) * (lv[j + 1].ry1 - lv[j + 1].ry0 + 1)));
+        HLMI_LAUNCH(uc, nm, st, ll_up<false>, dim3((ua.rw + 255) / 256, ua.rh), dim3(256), 0, ua);
+    }
+    return 0;
+}
+
+// stage 5: level 0 — outGPyramid[0], recolour, u16 store (ll_up0h: from outLPyramid[0], collapsing levels 1 and 2 on the way;
+// ll_up0f / ll_up0: from the materialised level-1 planes)
+int ll_stage_up0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st) {
+    const Geometry &gm = pl.gm;
+    const Level *lv = pl.lv;
+    const Level &c = lv[1];
+    Up0Args p = pl.u0;
+    const int ow = p.ow, oh = p.oh, nc = p.nc;
+    p.lut_g = b.lut, p.g1 = b.g[1], p.out1 = b.outg[1];
+    p.lox1 = c.lox, p.loy1 = c.loy, p.ws1 = c.ws, p.ps1 = c.ps;
+    p.g2 = b.g[2], p.out2 = b.outg[2], p.lox2 = lv[2].lox, p.loy2 = lv[2].loy, p.ws2 = lv[2].ws, p.ps2 = lv[2].ps;
+    p.rx1_1 = c.rx1, p.rx0_1 = c.rx0, p.ry0_1 = c.ry0, p.ry1_1 = c.ry1;
+    dim3 grid((ow + 255) / 256, (oh + 2 * p.RU - 1) / (2 * p.RU)), block(256);
+    const double n1 = (double)(c.rx1 - c.rx0 + 1) * (c.ry1 - c.ry0 + 1), n2 = (double)(lv[2].rx1 - lv[2].rx0 + 1) * (lv[2].ry1 - lv[2].ry0 + 1);
+    if (pl.emit) {
+        // input read + output written (u16 x 3 channels), outLPyramid[0] read, three planes of level 1, per level-2 pixel two
+        // planes of g_2 + outG_2
+        timing_note_bytes(2.0 * (3 + nc) * ow * oh + 4.0 * ow * oh + 4.0 * 3.0 * n1 + 4.0 * 3.0 * n2);
+        Up0HArgs ph;
+        ph.u = p, ph.outl0 = b.outl0, ph.l0_ws = gm.ix1 - gm.ix0 + 1;
+        ph.fuse2 = pl.fuse2 ? 1 : 0;
+        ph.g3 = b.g[3], ph.out3 = b.outg[3], ph.lox3 = lv[3].lox, ph.loy3 = lv[3].loy, ph.ws3 = lv[3].ws, ph.ps3 = lv[3].ps;
+        return with_flags([&](auto NT) -> int {
+            HLMI_LAUNCH(uc, "ll_up0", st, ll_up0h<NT.value>, grid, block, pl.up0_lds, ph, gm);
+            return 0;
+        }, pl.nt);
+    }
+    // input read + output written (u16 x nc channels), 2 selected planes of g_1 read; unfused: + outG_1 read;
+    // fused: + inG_1 and, per level-2 pixel, 2 planes of g_2 + outG_2
+    timing_note_bytes(2.0 * (3 + nc) * ow * oh + 4.0 * 3.0 * n1 + (pl.fuse1 ? 4.0 * 3.0 * n2 : 0.0));
+    if (pl.fast) {
+        return with_flags([&](auto L, auto B, auto F) -> int {
+            HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0f<L.value, B.value, F.value>), grid, block, pl.up0_lds, p, gm);
+            return 0;
+        }, pl.lut_lds, pl.b1, pl.fuse1);
+    }
+    return with_flags([&](auto V, auto L) -> int {
+        HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0<V.value, L.value>), grid, block, pl.up0_lds, p, gm);
+        return 0;
+    }, pl.vec_frame, pl.lut_lds);
+}
 
 }  // namespace
 
@@ -2502,7 +3004,7 @@ extern "C" int local_laplacian(halide_buffer_t *input, int32_t levels, float alp
     if (levels > (1 << 20)) {   // (levels - 1) * 256 table entries and plane counts must stay inside 32-bit index arithmetic
         return report(uc, halide_error_code_param_too_large, "Parameter levels is %d but must be at most %d", levels, 1 << 20);
     }
-    const int ow = output->dim[0].extent, oh = output->dim[1].extent, nc = output->dim[2].extent;
+    const int nc = output->dim[2].extent;
     if (nc > 3) {
         // `color` is defined for c in [0,3) only (:84 reads input(x,y,c), whose extent the check above bounds)
         return report(uc, halide_error_code_constraint_violated, "Output buffer output has %d channels, at most 3 supported", nc);
@@ -2512,491 +3014,30 @@ extern "C" int local_laplacian(halide_buffer_t *input, int32_t levels, float alp
     if ((r = acquire_device(uc, &ctx))) return r;
     if ((r = input_to_device(uc, ctx, args[0]))) return r;
     if ((r = output_on_device(uc, ctx, args[1]))) return r;
-    if (ow == 0 || oh == 0 || nc == 0) {
+    if (output->dim[0].extent == 0 || output->dim[1].extent == 0 || nc == 0) {
         mark_output_written(output);
         return 0;
     }
 
-    Geometry gm;
-    gm.K = levels;
-    gm.half = (levels - 1) * 256;
-    gm.Km1 = (float)(levels - 1);
-    gm.inv_Km1 = 1.0f / gm.Km1;
-    gm.ix0 = input->dim[0].min, gm.ix1 = gm.ix0 + input->dim[0].extent - 1;
-    gm.iy0 = input->dim[1].min, gm.iy1 = gm.iy0 + input->dim[1].extent - 1;
-    const int ic0 = input->dim[2].min, ic1 = ic0 + input->dim[2].extent - 1;
+    LlPlan pl;
+    ll_plan(pl, input, output, levels, beta, sw, stream_cu_count(ctx.device, ctx.stream), stream_cu_count(ctx.device, nullptr));
 
-    // per-level boxes.  lo/hi: beyond them the level is constant; so: storage origin (<= lo) whose parity
-    // makes the strip kernels' 16-byte loads / 8-byte stores aligned (see ll_down0 / hpair).
-    Level lv[J];
-    int lox = gm.ix0, hix = gm.ix1, loy = gm.iy0, hiy = gm.iy1, so = gm.ix0;
-    int rx0 = output->dim[0].min, rx1 = rx0 + ow - 1, ry0 = output->dim[1].min, ry1 = ry0 + oh - 1;
-    size_t ws_floats = (size_t)(2 * gm.half + 1 + 63) & ~(size_t)63;
-    size_t off_g[J], off_out[J];
-    for (int j = 0; j < J; j++) {
-        Level &L = lv[j];
-        L.lox = so, L.loy = loy, L.w = hix - so + 1, L.h = hiy - loy + 1;
-        L.ws = (L.w + 3) & ~3;
-        L.ps = ((size_t)L.ws * L.h + 3) & ~(size_t)3;
-        L.rx0 = rx0, L.rx1 = rx1, L.ry0 = ry0, L.ry1 = ry1;
-        if (j >= 1) {
-            off_g[j] = ws_floats;
-            ws_floats += ((size_t)(levels + 1) * L.ps + 63) & ~(size_t)63;
-            off_out[j] = ws_floats;
-            ws_floats += (L.ps + 63) & ~(size_t)63;
-        }
-        // next level
-        const bool odd = (so & 1) != 0;
-        const int par = odd ? (floor_div(so + 1, 2) & 1) : ((floor_div(so, 2) + 1) & 1);
-        lox = floor_div(lox - 2, 2), hix = floor_div(hix + 2, 2);
-        loy = floor_div(loy - 2, 2), hiy = floor_div(hiy + 2, 2);
-        so = lox - ((lox - par) & 1);
-        if (j + 1 < J) {
-            lv[j + 1].odd = odd;
-            lv[j + 1].nsx = (hix - so + 1 + STRIP - 1) / STRIP;
-        }
-        rx0 = floor_div(rx0 - 1, 2), rx1 = floor_div(rx1 + 1, 2);
-        ry0 = floor_div(ry0 - 1, 2), ry1 = floor_div(ry1 + 1, 2);
-    }
-    const uint16_t *din = dev_ptr<uint16_t>(input);
-    uint16_t *dout = dev_ptr<uint16_t>(output);
-    const long in_sy = input->dim[1].stride, in_sc = input->dim[2].stride;
-    const long out_sy = output->dim[1].stride, out_sc = output->dim[2].stride;
-    // clamped channels feeding `gray` (repeat_edge clamps the channel coordinate too, :28)
-    long gco[3];
-    for (int c = 0; c < 3; c++) gco[c] = (long)((c < ic0 ? ic0 : (c > ic1 ? ic1 : c)) - ic0) * in_sc;
-    hipStream_t st = ctx.stream;
-    const bool lut_lds = levels <= 15;  // LUT must fit the default 64 KB dynamic-LDS window
-    const int nlut = 2 * gm.half + 1;
-    const size_t lut_sh = lut_lds ? sizeof(float) * nlut : 0;
-
-    // levels >= S are produced / collapsed by the two multi-level kernels (S = 4: 2 launches instead of 7)
-    const int S = [&] {
-        const int v = sw.fuse_from.value_or(4);
-        return (v >= J - 5 && v <= J - 2) ? v : J;
-    }();
-    // the collapse (outGPyramid[J-1] .. outGPyramid[SU]) is ONE launch (ll_up_multi); opt-in: on the large levels its per-pixel overhead exceeds the saved launches
-    // Default 3 when the down pass fuses from 4: outGPyramid[3] joins the collapse launch (one ll_up launch and its ~4.5 us of
-    // dependent-launch latency less: 110.8 -> 108.9 us per frame on one stream); from level 2 the kernel's per-pixel overhead
-    // costs more than the launch it saves (114.2).  0: SU = S.
-    const int SU = [&] {
-        const int v = sw.upchain_from.value_or(S == 4 ? 3 : 0);   // (S == 3: SU = S)
-        return (v >= 1 && v <= J - 2) ? v : S;
-    }();
-    // ---- which kernels run: decided before the workspace is sized (the re-cut dataflow's outLPyramid[0] plane is only requested
-    // by the calls that fill it)
-    Up0Args p;
-    bool vec, fast, fuse1;
-    const int stream_cus = stream_cu_count(ctx.device, ctx.stream);
-    const bool partitioned = stream_cus < stream_cu_count(ctx.device, nullptr);
-    {
-        p.in = din, p.in_sy = in_sy;
-        const int oc0 = output->dim[2].min;
-        bool same = (nc == 3);
-        for (int ch = 0; ch < 3; ch++) {
-            p.gco[ch] = gco[ch];
-            p.cco[ch] = ch < nc ? (long)(oc0 + ch - ic0) * in_sc : 0;
-            if (p.cco[ch] != p.gco[ch]) same = false;
-        }
-        p.same_ch = same ? 1 : 0;
-        p.out = dout, p.out_sy = out_sy, p.out_sc = out_sc;
-        p.ox0 = output->dim[0].min, p.oy0 = output->dim[1].min, p.ow = ow, p.oh = oh, p.nc = nc;
-        p.beta = beta;
-        vec = ((uintptr_t)din % 4 == 0) && ((uintptr_t)dout % 4 == 0) && in_sy % 2 == 0 && out_sy % 2 == 0 &&
-              out_sc % 2 == 0 && ((p.ox0 - gm.ix0) % 2 == 0) && !sw.no_vec.value_or(0);
-        for (int ch = 0; ch < 3; ch++) vec = vec && p.gco[ch] % 2 == 0 && p.cco[ch] % 2 == 0;
-        fast = vec && same && nc == 3 && (ow & 1) == 0 && (p.ox0 & 1) == 0 &&
-               (double)(levels + 1) * (4.0 * (double)lv[1].ps) < 4.0e9;
-        // the fused collapse needs level 2 to be a stored level of its own (SU >= 2 always holds: SU >= S >= 4 or the
-        // opt-in up-chain, which starts at >= 1 and then owns level 1 itself)
-        fuse1 = fast && SU >= 2;
-        // rows per wave: taller tiles re-read less of level 1 (18 coarse rows per 16 output rows, 34 per 32) but keep a wave
-        // busy longer.  On a frame-queue stream (`partitioned`: one of several library queues with frames in flight, runtime.cpp),
-        // where several frames share the memory system and the frame rate is set by
-        // bytes, 32 rows measure 2.7 % faster (84.8 vs 82.6 Gpx/s); on a stream that owns the device 16 rows do (72.7 vs 68.2).
-        p.RU = dev_clamp_ru(sw.ru.value_or(fuse1 ? (partitioned ? 32 : 16) : 8));
-    }
-    // ll_down01f / ll_down01e: levels 1 and 2 from the input in one walk (levels == KCH planes in registers, 8-byte input loads)
-    const bool d01_possible = levels == KCH && lut_lds &&
-                              ((uintptr_t)din % 8 == 0) && in_sy % 4 == 0 && gco[0] % 4 == 0 && gco[1] % 4 == 0 && gco[2] % 4 == 0 &&
-                              (gm.ix1 - gm.ix0 + 1) % 4 == 0 && !sw.no_vec.value_or(0);
-    // The default for the common geometry: ll_down01e emits outLPyramid[0] and three planes of level 1, ll_up0h collapses
-    // (HLMI_LL_EMIT=0: the round-3 pair ll_down01f / ll_up0f with the materialised K + 1 level-1 planes)
-    const bool emit = d01_possible && fast && fuse1 && lv[1].ws < (1 << 24) && sw.emit.value_or(1);   // ws: ll_up0h's 24-bit row products
-    // ll_up0h has no data-dependent gathers to amortise over a tall tile: short tiles (more, smaller workgroups) are faster on a
-    // stream that owns the device (31.7 us at 8 rows per wave against 33.5 / 38.4 at 16 / 32); with four frames in flight 8 / 12 / 16 /
-    // 24 / 32 rows measure 107.8 / 110.1 / 111.2 / 112.3 / 112.3 Gpx/s (profiles/r06_frame_queue_geometry.txt), and next to ONE
-    // resident ll_down01e workgroup per CU 32 rows beat 24 / 40 / 48 / 64 (profiles/r06_coresidency_ab.txt)
-    if (emit) p.RU = dev_clamp_ru(sw.ru.value_or(partitioned ? 32 : 8));
-    // non-temporal frame / outLPyramid[0] accesses: +6-7 % frames per second with four frames in flight, -2-3 % on a stream that owns the device
-    const bool nt = sw.nt.value_or(partitioned ? 1 : 0) != 0;
-    // ll_up0h also collapses level 2 (into an LDS tile) when level 3 is a stored level of its own: the ll_up:2 launch goes
-    // (with four frames in flight: 79.4 -> 76.4 us per frame; on a stream that
-    // owns the device the tile redundancy used to cost what the launch saved — 109 -> 111 us in round 4 — until round 5's batched
-    // tile phases: 104.1 -> 98.7 us per frame, 115 -> 110.6 for one call + sync)
-    const bool fuse2 = emit && SU >= 3 && SU < J && sw.fuse_up2.value_or(1);
-
-    // ---- workspace: the levels and outLPyramid[0] of the re-cut dataflow (input width x output rows)
-    const size_t off_l0 = ws_floats;
-    if (emit) ws_floats += ((size_t)(gm.ix1 - gm.ix0 + 1) * (size_t)oh + 63) & ~(size_t)63;
     void *ws = nullptr;
-    if ((r = get_workspace(uc, ctx, ws_floats * sizeof(float), &ws))) return r;
+    if ((r = get_workspace(uc, ctx, pl.ws_floats * sizeof(float), &ws))) return r;
     float *wsf = (float *)ws;
-    float *lut = wsf;
-    float *outl0 = wsf + off_l0;
-    for (int j = 1; j < J; j++) lv[j].g = wsf + off_g[j], lv[j].out = wsf + off_out[j];
-    lv[0].g = lv[0].out = nullptr;
-    for (int j = 0; j < J; j++) t_dbg_lv[j] = lv[j];
-    t_dbg_stream = ctx.stream;
+    LlBuffers b;
+    b.lut = wsf, b.outl0 = wsf + pl.off_l0;
+    b.g[0] = b.outg[0] = nullptr;
+    for (int j = 1; j < J; j++) b.g[j] = wsf + pl.off_g[j], b.outg[j] = wsf + pl.off_out[j];
+    // for the test hook: what this call leaves in the arena (the table's address is not needed there)
+    t_dbg.pl = pl, t_dbg.b = b, t_dbg.stream = ctx.stream;
+    t_dbg.out1_pending = pl.fuse1, t_dbg.out2_pending = pl.fuse2;
 
-    if (!sw.no_lut_cache.value_or(0)) {
-        uint32_t abits;
-        memcpy(&abits, &alpha, 4);
-        std::unique_lock<std::mutex> lock(g_lut_mu);
-        LutImage *hit = nullptr, *slot = &g_lut[0];
-        for (auto &e : g_lut) {
-            if (e.valid && e.device == ctx.device && e.levels == levels && e.alpha_bits == abits) hit = &e;
-        }
-        if (hit) {
-            hit->used = ++g_lut_clock;
-            if (hit->stream != st) HLMI_HIP(uc, wait_done(st, hit->ready));
-            lut = hit->dev;
-        } else {
-            for (auto &e : g_lut) {
-                if (!e.dev) { slot = &e; break; }
-                if (e.used < slot->used) slot = &e;
-            }
-            slot->valid = false;
-            if (slot->dev) {   // evicting (more than 8 (levels, alpha) pairs in use): launches on any stream may still read it
-                HLMI_HIP(uc, hipDeviceSynchronize());
-                (void)hipFree(slot->dev);
-                slot->dev = nullptr;
-            }
-            HLMI_HIP(uc, hipMalloc((void **)&slot->dev, sizeof(float) * ((size_t)nlut + 64)));
-            if (!slot->ready) HLMI_HIP(uc, hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
-            slot->device = ctx.device, slot->levels = levels, slot->alpha_bits = abits, slot->stream = st, slot->used = ++g_lut_clock;
-            lut = slot->dev;
-            HLMI_LAUNCH(uc, "ll_remap_lut", st, ll_remap_lut, dim3((nlut + 255) / 256), dim3(256), 0, lut, gm.half, alpha);
-            HLMI_HIP(uc, record_done(slot->ready, st));
-            slot->valid = true;
-        }
-    } else {
-        HLMI_LAUNCH(uc, "ll_remap_lut", st, ll_remap_lut, dim3((nlut + 255) / 256), dim3(256), 0, lut, gm.half, alpha);
+    hipStream_t st = ctx.stream;
+    if ((r = ll_stage_table(uc, ctx, pl, alpha, b)) || (r = ll_stage_down0(uc, pl, b, st)) || (r = ll_stage_down_rest(uc, pl, b, st)) ||
+        (r = ll_stage_up_coarse(uc, pl, b, st)) || (r = ll_stage_up0(uc, pl, b, st))) {
+        return r;
     }
-    {
-        const Level &c = lv[1];
-        p.lut_g = lut, p.g1 = c.g, p.out1 = c.out;
-        p.lox1 = c.lox, p.loy1 = c.loy, p.ws1 = c.ws, p.ps1 = c.ps;
-        p.g2 = lv[2].g, p.out2 = lv[2].out, p.lox2 = lv[2].lox, p.loy2 = lv[2].loy, p.ws2 = lv[2].ws, p.ps2 = lv[2].ps;
-        p.rx1_1 = c.rx1, p.rx0_1 = c.rx0, p.ry0_1 = c.ry0, p.ry1_1 = c.ry1;
-    }
-    // the stages of the chain between the two big kernels
-    auto strip_args = [&](int j, int target_units) {   // level j -> j + 1
-        const Level &sl = lv[j], &d = lv[j + 1];
-        const int cols = d.nsx * (levels + 1);
-        StripArgs a;
-        a.src = sl.g, a.slox = sl.lox, a.sloy = sl.loy, a.sw = sl.w, a.sh = sl.h, a.sws = sl.ws, a.sps = sl.ps;
-        a.dst = d.g, a.Xs = d.lox, a.dloy = d.loy, a.dw = d.w, a.dh = d.h, a.dws = d.ws, a.dps = d.ps;
-        a.nsx = d.nsx;
-        a.nsy = max(1, min(max(target_units / cols, (d.h + 31) / 32), max(1, d.h / 2)));
-        a.nunits = cols * a.nsy;
-        return a;
-    };
-    auto coarse_args = [&](int from) {
-        CoarseArgs ca;
-        for (int dl = 0; from + dl < J; dl++) {
-            const Level &L = lv[from + dl];
-            DevLevel &D = ca.lv[dl];
-            D.g = L.g, D.out = L.out, D.lox = L.lox, D.loy = L.loy, D.w = L.w, D.h = L.h, D.ws = L.ws, D.ps = (unsigned)L.ps;
-            D.rx0 = L.rx0, D.ry0 = L.ry0, D.rw = L.rx1 - L.rx0 + 1, D.rh = L.ry1 - L.ry0 + 1;
-        }
-        ca.K = levels, ca.Km1 = gm.Km1;
-        return ca;
-    };
-    auto up_args = [&](int j) {
-        const Level &a = lv[j], &c = lv[j + 1];
-        UpArgs u;
-        u.g = a.g, u.ws = a.ws, u.ps = a.ps, u.lox = a.lox, u.loy = a.loy, u.gc = c.g, u.outc = c.out, u.cws = c.ws, u.cps = c.ps;
-        u.clox = c.lox, u.cloy = c.loy, u.rx0 = a.rx0, u.ry0 = a.ry0, u.rw = a.rx1 - a.rx0 + 1, u.rh = a.ry1 - a.ry0 + 1;
-        u.K = levels, u.Km1 = gm.Km1, u.out = a.out;
-        return u;
-    };
-    t_dbg_K = levels, t_dbg_Km1 = gm.Km1;
-    t_dbg_emit = emit;
-    // ---- the launch chain of one frame
-    bool fuse_d2 = false;
-    {
-        const Level &d = lv[1];
-        // two waves per SIMD with (almost) equal row counts: the kernel is VALU-bound, so balance is what counts
-        const int target = sw.units0.value_or(8 * stream_cu_count(ctx.device, nullptr));
-        const int nsy = max(1, min(max(target / d.nsx, (d.h + 63) / 64), max(1, d.h / 2)));
-        const int nunits = d.nsx * nsy;
-        const int iw = gm.ix1 - gm.ix0 + 1;
-        const bool vec = ((uintptr_t)din % 8 == 0) && in_sy % 4 == 0 && gco[0] % 4 == 0 && gco[1] % 4 == 0 &&
-                         gco[2] % 4 == 0 && iw % 4 == 0 && !sw.no_vec.value_or(0);
-        Levels lev;
-        for (int k = 0; k < MAX_K; k++) lev.v[k] = (float)k * gm.inv_Km1;
-        const bool b1 = (beta == 1.0f);
-        const int variant = (d.odd ? 8 : 0) | (vec ? 4 : 0) | (lut_lds ? 2 : 0) | (b1 ? 1 : 0);
-        constexpr int WPB = D0_THREADS / 64;
-        dim3 grid((nunits + WPB - 1) / WPB), block(D0_THREADS);
-        const size_t d0_sh = (lut_lds ? sizeof(float) * ((nlut + 1) & ~1) : 0) + sizeof(float2) * D0_THREADS * (KCH + 1);
-        // algorithmic bytes: the input read once (u16 x 3 channels), the K+1 level-1 planes written once
-        const double d0_bytes = 6.0 * iw * (gm.iy1 - gm.iy0 + 1) + 4.0 * (levels + 1) * d.w * d.h;
-        auto launch_d0 = [&](auto kern) -> int {
-            timing_note_bytes(d0_bytes);
-            HLMI_LAUNCH(uc, "ll_down0", st, kern, grid, block, d0_sh, din, in_sy, gco[0], gco[1], gco[2], gm, lev, beta,
-                        lut, d.g, d.lox, d.loy, d.w, d.h, d.ws, d.ps, d.nsx, nsy, nunits);
-            return 0;
-        };
-#define LL_D0(O, V, L, B)                                             \
-    case ((O ? 8 : 0) | (V ? 4 : 0) | (L ? 2 : 0) | (B ? 1 : 0)):      \
-        r = launch_d0(&ll_down0<O, V, L, B>);                         \
-        break;
-        fuse_d2 = levels == KCH && vec && lut_lds;
-        if (fuse_d2) {
-            // ---- levels 1 AND 2 from the input in one walk (ll_down01f); the ll_down_strip:1 launch below is skipped
-            const Level &e = lv[2];
-            D01Args a;
-            a.in = din, a.in_sy = in_sy, a.co0 = gco[0], a.co1 = gco[1], a.co2 = gco[2], a.beta = beta, a.lut_g = lut;
-            a.g1 = d.g, a.so1 = d.lox, a.loy1 = d.loy, a.w1 = d.w, a.h1 = d.h, a.ws1 = d.ws, a.ps1 = d.ps;
-            a.g2 = e.g, a.so2 = e.lox, a.loy2 = e.loy, a.w2 = e.w, a.h2 = e.h, a.ws2 = e.ws, a.ps2 = e.ps;
-            const bool odd0 = d.odd, odd1 = e.odd;   // e.odd == (d.lox & 1)
-            a.S2 = (odd0 || odd1) ? 62 : 61;
-            const int lim = odd1 ? 2 * e.lox - 1 : 2 * e.lox - 2;    // leftmost pair must reach level-2 column so2
-            a.Pbase = min(d.lox, lim);                                // same parity as so1 in either case
-            const int hi1 = d.lox + d.w - 1, hi2 = e.lox + e.w - 1;
-            const int x2_first = odd1 ? (a.Pbase + 1) / 2 + 0 : a.Pbase / 2 + 1;   // Pbase + 1 (resp. Pbase) is even: exact
-            a.nsx = max((hi2 - x2_first + a.S2) / a.S2, (hi1 - a.Pbase + 2 * a.S2) / (2 * a.S2));
-            // ll_down01f: sized for the whole device on every stream (fewer, taller units measured 2-3 % slower: 101.5 vs 98.9 us per
-            // frame).  ll_down01e on a frame-queue stream (several frames in flight, the launches of different frames fill the device
-            // together): fewer and taller units — fewer seam rows walked twice, less per-workgroup set-up — measure 10 % more frames
-            // per second than the 2048 units of a launch that has the device to itself (round 6, four queues: 2048 / 1536 / 1024 /
-            // 896..384 / 256 units -> 109.4 / 110.2 / 111.3 / 112.1-112.5 / 103.3 Gpx/s, profiles/r06_frame_queue_geometry.txt; with
-            // one workgroup per CU — below — 640 units = 160 workgroups of 55 level-2 rows measure best),
-            // while on a stream that owns the device one round of resident waves is what counts (52.7 us against 57.1)
-            const int target2 = sw.units0.value_or(emit && partitioned ? 10 * stream_cus : 8 * stream_cu_count(ctx.device, nullptr));
-            // EXCH: a workgroup = 4 vertically adjacent units exchanging their seam rows through LDS.  With n level-2 rows
-            // per wave a workgroup owns R = 4 n - 1 rows (the bottom wave walks the two seam rows of the next workgroup
-            // itself and owns one row less); n = the smallest that keeps the launch within `target2` resident waves.
-            bool exch = sw.d01_exch.value_or(1) != 0;
-            int nwy = 0;
-            auto ceil_div = [](int x, int y) { return (x + y - 1) / y; };
-            if (exch) {
-                const int nwy_max = max(1, target2 / (WPB * a.nsx));
-                const int n = max(2, (ceil_div(e.h, nwy_max) + 1 + 3) / 4);
-                nwy = ceil_div(e.h, 4 * n - 1);
-                exch = e.h / nwy >= 4;     // every workgroup gets at least 4 rows; smaller images take the plain units
-            }
-            if (exch) {
-                a.nsy = nwy;
-                a.nunits = a.nsx * nwy * WPB;
-            } else {
-                a.nsy = max(1, min(max(target2 / a.nsx, (e.h + 31) / 32), e.h));
-                a.nunits = a.nsx * a.nsy;
-            }
-            a.nsy_magic = a.nsy == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)a.nsy + 1ull);   // 0: nsy == 1
-            a.rows_base = e.h / a.nsy, a.rows_rem = e.h % a.nsy;
-            dim3 grid2((a.nunits + WPB - 1) / WPB);
-            size_t sh2 = sizeof(float) * ((nlut + 1) & ~1) + sizeof(float2) * D01_STATE * (WPB + (exch ? WPB - 1 : 0));
-            // With frames in flight (a frame-queue stream) ll_down01e asks for so much LDS that only ONE of its workgroups fits a
-            // CU (2 x 77 KB would): the other half of the CU's registers and 77 KB of its LDS stay free for the workgroups of the
-            // OTHER frames' kernels — ll_up0h above all, which waits for memory while this one computes.  Four frames in flight,
-            // 40 steps, alternating A/B on three boxes: 110.3-114.5 -> 113.5-114.1 Gpx/s with the 512 units / 24 rows above,
-            // 115.8-121.8 with 640 units and 32 rows per ll_up0h wave (profiles/r06_coresidency_ab.txt).  On a stream that owns
-            // the device the second workgroup is what hides this kernel's own latencies (84.7 -> 74.7 Gpx/s without it).
-            // HLMI_LL_D01_PAD_LDS: bytes of unused LDS to add instead (experiments; 0 = two workgroups per CU).
-            {
-                const int pad = sw.d01_pad_lds.value_or(emit && partitioned ? -1 : 0);
-                constexpr size_t kHalfCuLds = 160 * 1024 / 2;   // gfx950: 160 KB per CU
-                if (pad < 0) sh2 = max(sh2, kHalfCuLds + 2048);
-                else sh2 += (size_t)pad;
-            }
-            if (emit) {
-                // input read once; outLPyramid[0] (4 B per output pixel), three level-1 planes and K + 1 level-2 planes written
-                timing_note_bytes(6.0 * iw * (gm.iy1 - gm.iy0 + 1) + 4.0 * iw * oh + 4.0 * 3.0 * d.w * d.h + 4.0 * (levels + 1) * e.w * e.h);
-                D01EArgs ae;
-                ae.d = a, ae.outl0 = outl0, ae.oy0 = output->dim[1].min, ae.oh = oh;
-                ae.nsx_magic = a.nsx == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)a.nsx + 1ull);
-#define LL_D01E(O0, O1, B)                                                                                                    \
-    do {                                                                                                                      \
-        if (exch && nt) HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0, O1, B, true, true>), grid2, block, sh2, ae, gm, lev);  \
-        else if (exch) HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0, O1, B, true, false>), grid2, block, sh2, ae, gm, lev);   \
-        else if (nt) HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0, O1, B, false, true>), grid2, block, sh2, ae, gm, lev);    \
-        else HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0, O1, B, false, false>), grid2, block, sh2, ae, gm, lev);          \
-    } while (0)
-                switch ((odd0 ? 4 : 0) | (odd1 ? 2 : 0) | (b1 ? 1 : 0)) {
-                    case 0: LL_D01E(false, false, false); break;
-                    case 1: LL_D01E(false, false, true); break;
-                    case 2: LL_D01E(false, true, false); break;
-                    case 3: LL_D01E(false, true, true); break;
-                    case 4: LL_D01E(true, false, false); break;
-                    case 5: LL_D01E(true, false, true); break;
-                    case 6: LL_D01E(true, true, false); break;
-                    default: LL_D01E(true, true, true); break;
-                }
-#undef LL_D01E
-            } else {
-            timing_note_bytes(d0_bytes + 4.0 * (levels + 1) * e.w * e.h);
-#define LL_D01(O0, O1, B)                                                                                              \
-    do {                                                                                                               \
-        if (exch) HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01f<O0, O1, B, true>), grid2, block, sh2, a, gm, lev);      \
-        else HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01f<O0, O1, B, false>), grid2, block, sh2, a, gm, lev);          \
-    } while (0)
-            switch ((odd0 ? 4 : 0) | (odd1 ? 2 : 0) | (b1 ? 1 : 0)) {
-                case 0: LL_D01(false, false, false); break;
-                case 1: LL_D01(false, false, true); break;
-                case 2: LL_D01(false, true, false); break;
-                case 3: LL_D01(false, true, true); break;
-                case 4: LL_D01(true, false, false); break;
-                case 5: LL_D01(true, false, true); break;
-                case 6: LL_D01(true, true, false); break;
-                default: LL_D01(true, true, true); break;
-            }
-#undef LL_D01
-            }
-        } else {
-            switch (variant) {
-                LL_D0(false, false, false, false) LL_D0(false, false, false, true) LL_D0(false, false, true, false)
-                LL_D0(false, false, true, true) LL_D0(false, true, false, false) LL_D0(false, true, false, true)
-                LL_D0(false, true, true, false) LL_D0(false, true, true, true) LL_D0(true, false, false, false)
-                LL_D0(true, false, false, true) LL_D0(true, false, true, false) LL_D0(true, false, true, true)
-                LL_D0(true, true, false, false) LL_D0(true, true, false, true) LL_D0(true, true, true, false)
-                LL_D0(true, true, true, true)
-            }
-        }
-#undef LL_D0
-        if (r) return r;
-    }
-    // levels 3 and 4 from level 2 in one launch (ll_down_strip2) when the chain below would run ll_down_strip:2 and :3
-    // (one stream: 111.6 -> 105.1 us per frame back to back, 123 -> 116.6 for one call + sync; four frame queues 75-77 -> 72-76)
-    const bool strip2 = fuse_d2 && S == 4;
-    if (strip2) {
-        const Level &sl = lv[2], &d = lv[3], &e = lv[4];
-        Strip2Args a;
-        a.src = sl.g, a.slox = sl.lox, a.sloy = sl.loy, a.sw = sl.w, a.sh = sl.h, a.sws = sl.ws, a.sps = sl.ps;
-        a.g1 = d.g, a.so1 = d.lox, a.loy1 = d.loy, a.w1 = d.w, a.h1 = d.h, a.ws1 = d.ws, a.ps1 = d.ps;
-        a.g2 = e.g, a.so2 = e.lox, a.loy2 = e.loy, a.w2 = e.w, a.h2 = e.h, a.ws2 = e.ws, a.ps2 = e.ps;
-        const bool odd0 = d.odd, odd1 = e.odd;                  // as for ll_down01f: e.odd == (d.lox & 1)
-        a.S2 = (odd0 || odd1) ? 62 : 61;
-        const int lim = odd1 ? 2 * e.lox - 1 : 2 * e.lox - 2;   // leftmost pair must reach level-(j+2) column so2
-        a.Pbase = min(d.lox, lim);
-        const int hi1 = d.lox + d.w - 1, hi2 = e.lox + e.w - 1;
-        const int x2_first = odd1 ? (a.Pbase + 1) / 2 + 0 : a.Pbase / 2 + 1;
-        a.nsx = max((hi2 - x2_first + a.S2) / a.S2, (hi1 - a.Pbase + 2 * a.S2) / (2 * a.S2));
-        a.nsy = (e.h + S2_RPU - 1) / S2_RPU;
-        a.nunits = (levels + 1) * a.nsx * a.nsy;
-        timing_note_bytes(4.0 * (levels + 1) * ((double)sl.w * sl.h + (double)d.w * d.h + (double)e.w * e.h));
-        dim3 grid((a.nunits + 3) / 4), block(256);
-        switch ((odd0 ? 2 : 0) | (odd1 ? 1 : 0)) {
-            case 0: HLMI_LAUNCH(uc, "ll_down_strip2:2", st, (ll_down_strip2<false, false>), grid, block, 0, a); break;
-            case 1: HLMI_LAUNCH(uc, "ll_down_strip2:2", st, (ll_down_strip2<false, true>), grid, block, 0, a); break;
-            case 2: HLMI_LAUNCH(uc, "ll_down_strip2:2", st, (ll_down_strip2<true, false>), grid, block, 0, a); break;
-            default: HLMI_LAUNCH(uc, "ll_down_strip2:2", st, (ll_down_strip2<true, true>), grid, block, 0, a); break;
-        }
-    }
-    for (int j = 1; j + 1 < J; j++) {
-        if (strip2 && (j == 2 || j == 3)) continue;
-        if (j == S) {
-            const CoarseArgs ca = coarse_args(S);
-            long total = 0;
-            for (int dl = 1; S + dl < J; dl++) total += (long)(levels + 1) * lv[S + dl].w * lv[S + dl].h;
-            const int ntx = (lv[J - 1].w + DM_T - 1) / DM_T, nty = (lv[J - 1].h + DM_T - 1) / DM_T;
-            dim3 grid((unsigned)(ntx * nty * (levels + 1))), block(256);
-            char nm[32];
-            snprintf(nm, sizeof nm, "ll_down_multi:%d", S);
-            timing_note_bytes(4.0 * ((double)(levels + 1) * lv[S].w * lv[S].h + (double)total));
-            if (J - 1 - S == 4) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<4>), grid, block, 0, ca, ntx, nty);
-            else if (J - 1 - S == 3) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<3>), grid, block, 0, ca, ntx, nty);
-            else if (J - 1 - S == 2) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<2>), grid, block, 0, ca, ntx, nty);
-            else HLMI_LAUNCH(uc, nm, st, (ll_down_multi<1>), grid, block, 0, ca, ntx, nty);
-            break;
-        }
-        if (j == 1 && fuse_d2) continue;   // level 2 came out of ll_down01f
-        // enough waves to fill the chip on the big levels, short strips on the small ones
-        const StripArgs sa = strip_args(j, 16 * stream_cu_count(ctx.device, nullptr));
-        dim3 grid((sa.nunits + 3) / 4), block(256);
-        char nm[32];
-        snprintf(nm, sizeof nm, "ll_down_strip:%d", j);
-        timing_note_bytes(4.0 * (levels + 1) * ((double)lv[j].w * lv[j].h + (double)lv[j + 1].w * lv[j + 1].h));
-        if (lv[j + 1].odd) HLMI_LAUNCH(uc, nm, st, (ll_down_strip<true>), grid, block, 0, sa);
-        else HLMI_LAUNCH(uc, nm, st, (ll_down_strip<false>), grid, block, 0, sa);
-    }
-    if (SU < J) {
-        const CoarseArgs cu = coarse_args(SU);
-        const int ntx = (cu.lv[0].rw + UM_T - 1) / UM_T, nty = (cu.lv[0].rh + UM_T - 1) / UM_T;
-        dim3 grid((unsigned)(ntx * nty)), block(256);
-        char nm[32];
-        snprintf(nm, sizeof nm, "ll_up_multi:%d", SU);
-        {   // per output pixel of level SU: 2 planes of g + inG read, outG written; coarser levels add 1/3
-            const double px = (double)cu.lv[0].rw * cu.lv[0].rh;
-            timing_note_bytes(4.0 * 4.0 * px * (SU + 1 < J ? 4.0 / 3.0 : 1.0));
-        }
-        switch (J - 1 - SU) {
-#define LL_UM(T) case T: HLMI_LAUNCH(uc, nm, st, (ll_up_multi<T>), grid, block, 0, cu, ntx); break;
-            LL_UM(1) LL_UM(2) LL_UM(3) LL_UM(4) LL_UM(5) LL_UM(6)
-#undef LL_UM
-        }
-    } else {
-        const Level &t = lv[J - 1];
-        int rw = t.rx1 - t.rx0 + 1, rh = t.ry1 - t.ry0 + 1;
-        HLMI_LAUNCH(uc, "ll_top", st, ll_top, dim3((rw + 63) / 64, rh), dim3(64), 0, t.g, t.ws, t.ps, t.lox, t.loy, t.rx0,
-                    t.ry0, rw, rh, levels, gm.Km1, t.out);
-    }
-    for (int j = min(SU, J - 1) - 1; j >= (fuse1 ? (fuse2 ? 3 : 2) : 1); j--) {
-        const UpArgs ua = up_args(j);
-        char nm[32];
-        snprintf(nm, sizeof nm, "ll_up:%d", j);
-        // per output: 2 planes of g_j + inG_j read, outG_j written; per coarse pixel: 2 planes of g_{j+1} + outG_{j+1}
-        timing_note_bytes(4.0 * (4.0 * ua.rw * ua.rh + 3.0 * (lv[j + 1].rx1 - lv[j + 1].rx0 + 1) * (lv[j + 1].ry1 - lv[j + 1].ry0 + 1)));
-        HLMI_LAUNCH(uc, nm, st, ll_up<false>, dim3((ua.rw + 255) / 256, ua.rh), dim3(256), 0, ua);
-    }
-    {
-        const Level &c = lv[1];
-        dim3 grid((ow + 255) / 256, (oh + 2 * p.RU - 1) / (2 * p.RU)), block(256);
-        // input read + output written (u16 x nc channels), 2 selected planes of g_1 read; unfused: + outG_1 read;
-        // fused: + inG_1 and, per level-2 pixel, 2 planes of g_2 + outG_2
-        const double n1 = (double)(c.rx1 - c.rx0 + 1) * (c.ry1 - c.ry0 + 1), n2 = (double)(lv[2].rx1 - lv[2].rx0 + 1) * (lv[2].ry1 - lv[2].ry0 + 1);
-        const double u0_bytes = 2.0 * (3 + nc) * ow * oh + 4.0 * 3.0 * n1 + (fuse1 ? 4.0 * 3.0 * n2 : 0.0);
-        if (emit) {
-            // input read + output written (u16 x 3 channels), outLPyramid[0] read, three planes of level 1, per level-2 pixel two
-            // planes of g_2 + outG_2
-            timing_note_bytes(2.0 * (3 + nc) * ow * oh + 4.0 * ow * oh + 4.0 * 3.0 * n1 + 4.0 * 3.0 * n2);
-            Up0HArgs ph;
-            ph.u = p, ph.outl0 = outl0, ph.l0_ws = gm.ix1 - gm.ix0 + 1;
-            ph.fuse2 = fuse2 ? 1 : 0;
-            ph.g3 = lv[3].g, ph.out3 = lv[3].out, ph.lox3 = lv[3].lox, ph.loy3 = lv[3].loy, ph.ws3 = lv[3].ws, ph.ps3 = lv[3].ps;
-            const size_t sh_h = sizeof(float) * ((size_t)U0_TS * (p.RU + 2) + (size_t)U0H_T2 * (p.RU / 2 + 4));
-            if (nt) HLMI_LAUNCH(uc, "ll_up0", st, ll_up0h<true>, grid, block, sh_h, ph, gm);
-            else HLMI_LAUNCH(uc, "ll_up0", st, ll_up0h<false>, grid, block, sh_h, ph, gm);
-        } else {
-            timing_note_bytes(u0_bytes);
-            if (fast) {
-                const bool b1 = (beta == 1.0f);
-                const size_t sh = lut_sh + (fuse1 ? ((lut_lds && (nlut & 1)) ? 4 : 0) + sizeof(float) * U0_TS * (p.RU + 2) : 0);
-#define LL_U0(L, B, F) HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0f<L, B, F>), grid, block, sh, p, gm)
-                if (fuse1) {
-                    if (lut_lds && b1) LL_U0(true, true, true);
-                    else if (lut_lds) LL_U0(true, false, true);
-                    else if (b1) LL_U0(false, true, true);
-                    else LL_U0(false, false, true);
-                } else {
-                    if (lut_lds && b1) LL_U0(true, true, false);
-                    else if (lut_lds) LL_U0(true, false, false);
-                    else if (b1) LL_U0(false, true, false);
-                    else LL_U0(false, false, false);
-                }
-#undef LL_U0
-            } else if (vec) {
-                if (lut_lds) HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0<true, true>), grid, block, lut_sh, p, gm);
-                else HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0<true, false>), grid, block, lut_sh, p, gm);
-            } else {
-                if (lut_lds) HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0<false, true>), grid, block, lut_sh, p, gm);
-                else HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0<false, false>), grid, block, lut_sh, p, gm);
-            }
-        }
-    }
-    t_dbg_out1_pending = fuse1, t_dbg_out2_pending = fuse2;
     mark_output_written(output);
     return 0;
 }
@@ -3011,8 +3052,8 @@ extern "C" int local_laplacian_auto_schedule(halide_buffer_t *input, int32_t lev
     return local_laplacian(input, levels, alpha, beta, output);
 }
 
-// Test hook: runs the DPP wave-shift probe on the current device; 1 = wave_shr:1 / wave_shl:1 behave as the
-// strip kernels assume, 0 = they do not, < 0 = HIP error.
+// Probe builds (HLMI_LL_PROBE=1): copies the 32 phase counters of g_probe to `out32` and clears them; 1, 0 = not a probe
+// build, < 0 = HIP error.
 extern "C" int hlmi_debug_ll_probe(unsigned long long *out32) {
 #if HLMI_LL_PROBE
     if (hipDeviceSynchronize() != hipSuccess) return -1;
@@ -3026,6 +3067,8 @@ extern "C" int hlmi_debug_ll_probe(unsigned long long *out32) {
 #endif
 }
 
+// Residency builds (HLMI_LL_RESIDENCY=1): copies the 16 histogram counters of g_res_hist to `out16` and clears them; 1, 0 = not
+// a residency build, < 0 = HIP error.
 extern "C" int hlmi_debug_ll_residency(unsigned long long *out16) {
 #if HLMI_LL_RESIDENCY
     if (hipDeviceSynchronize() != hipSuccess) return -1;
@@ -3039,6 +3082,8 @@ extern "C" int hlmi_debug_ll_residency(unsigned long long *out16) {
 #endif
 }
 
+// Test hook: runs the DPP wave-shift probe on the current device; 1 = wave_shr:1 / wave_shl:1 behave as the
+// strip kernels assume, 0 = they do not, < 0 = HIP error.
 extern "C" int hlmi_debug_dpp_probe(void) {
     int *flag = nullptr, h = 0;
     if (hipMalloc(&flag, sizeof(int)) != hipSuccess) return -1;
@@ -3072,43 +3117,37 @@ extern "C" int hlmi_debug_div3_check(const float *n, const float *d, int count) 
 // Test hook (tests/ only; not part of the reference ABI): copies outGPyramid[level] of the calling thread's
 // LAST local_laplacian call, restricted to R_level, to `dst` (row-major, rw x rh floats); returns 0, or -1.
 extern "C" int hlmi_debug_local_laplacian_outg(int level, float *dst, int cap_floats, int *rw_out, int *rh_out) {
-    auto dbg_up_args = [](const Level &a, const Level &c) {
-        UpArgs u;
-        u.g = a.g, u.ws = a.ws, u.ps = a.ps, u.lox = a.lox, u.loy = a.loy, u.gc = c.g, u.outc = c.out, u.cws = c.ws, u.cps = c.ps;
-        u.clox = c.lox, u.cloy = c.loy, u.rx0 = a.rx0, u.ry0 = a.ry0, u.rw = a.rx1 - a.rx0 + 1, u.rh = a.ry1 - a.ry0 + 1;
-        u.K = t_dbg_K, u.Km1 = t_dbg_Km1, u.out = a.out;
-        return u;
-    };
-    if (level < 1 || level >= J || !t_dbg_lv[level].out) return -1;
-    const Level &L = t_dbg_lv[level];
+    LlLastCall &c = t_dbg;
+    if (level < 1 || level >= J || !c.b.outg[level]) return -1;
+    const Level &L = c.pl.lv[level];
     int rw = L.rx1 - L.rx0 + 1, rh = L.ry1 - L.ry0 + 1;
     if (rw_out) *rw_out = rw;
     if (rh_out) *rh_out = rh;
     if (!dst) return 0;
     if ((long)rw * rh > cap_floats) return -1;
-    if ((level == 1 || level == 2) && t_dbg_out2_pending) {
+    // outGPyramid[j] by the stand-alone kernel; SEL: level j holds its three planes only
+    auto collapse = [&c](int j, bool sel) {
+        const UpArgs ua = up_args(c.pl, c.b, j);
+        with_flags([&](auto SEL) -> int {
+            hipLaunchKernelGGL(ll_up<SEL.value>, dim3((ua.rw + 255) / 256, ua.rh), dim3(256), 0, c.stream, ua);
+            return 0;
+        }, sel);
+        return hipGetLastError() == hipSuccess;
+    };
+    if ((level == 1 || level == 2) && c.out2_pending) {
         // ll_up0h kept outGPyramid[2] in LDS tiles: produce the plane with the stand-alone kernel (levels 2, 3 and outGPyramid[3] are
         // still in the arena); level 1's own stand-alone collapse below reads it
-        const Level &a = t_dbg_lv[2], &c = t_dbg_lv[3];
-        const int rw2 = a.rx1 - a.rx0 + 1, rh2 = a.ry1 - a.ry0 + 1;
-        hipLaunchKernelGGL(ll_up<false>, dim3((rw2 + 255) / 256, rh2), dim3(256), 0, t_dbg_stream, dbg_up_args(a, c));
-        if (hipGetLastError() != hipSuccess) return -1;
-        t_dbg_out2_pending = false;
+        if (!collapse(2, false)) return -1;
+        c.out2_pending = false;
     }
-    if (level == 1 && t_dbg_out1_pending) {
+    if (level == 1 && c.out1_pending) {
         // the fused ll_up0f / ll_up0h kept outGPyramid[1] in LDS: produce the plane now with the stand-alone kernel (its inputs are
         // still in the arena) so that the tests can compare every level
-        const Level &a = t_dbg_lv[1], &c = t_dbg_lv[2];
-        if (t_dbg_emit) {   // level 1 holds its three planes only (ll_down01e)
-            hipLaunchKernelGGL(ll_up<true>, dim3((rw + 255) / 256, rh), dim3(256), 0, t_dbg_stream, dbg_up_args(a, c));
-        } else {
-            hipLaunchKernelGGL(ll_up<false>, dim3((rw + 255) / 256, rh), dim3(256), 0, t_dbg_stream, dbg_up_args(a, c));
-        }
-        if (hipGetLastError() != hipSuccess) return -1;
-        t_dbg_out1_pending = false;
+        if (!collapse(1, c.pl.emit)) return -1;   // emit: level 1 holds its three planes only (ll_down01e)
+        c.out1_pending = false;
     }
-    if (hipStreamSynchronize(t_dbg_stream) != hipSuccess) return -1;
-    const float *src = L.out + (size_t)(L.ry0 - L.loy) * L.ws + (L.rx0 - L.lox);
+    if (hipStreamSynchronize(c.stream) != hipSuccess) return -1;
+    const float *src = c.b.outg[level] + (size_t)(L.ry0 - L.loy) * L.ws + (L.rx0 - L.lox);
     if (hipMemcpy2D(dst, sizeof(float) * rw, src, sizeof(float) * L.ws, sizeof(float) * rw, rh, hipMemcpyDeviceToHost) !=
         hipSuccess) {
         return -1;
