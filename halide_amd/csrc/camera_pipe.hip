@@ -459,8 +459,8 @@ const halide_filter_metadata_t cp_md = {1, 10, cp_args, kTargetString, "camera_p
 // ---- cache of set-up blocks ---------------------------------------------------------------------------------------
 // cp_setup's output (matrix, curve, strength) is a function of the two matrix buffers' contents and six scalars; a video
 // stream calls with the same ones frame after frame.  The block is kept per (matrix allocations and versions, scalars) in
-// memory of its own (the per-stream arena is shared with other pipelines) and the launch is skipped when nothing changed.
-// Matrices in memory the runtime does not own (version 0) are never cached.
+// the runtime's cache of derived device data (hlmi_internal.h; the per-stream arena is shared with other pipelines) and the
+// launch is skipped when nothing changed.  Matrices in memory the runtime does not own (version 0) are never cached.
 struct SetupKey {
     int device;
     uint64_t h3, v3, h7, v7;
@@ -468,17 +468,8 @@ struct SetupKey {
     float color_temp, gamma, contrast, sharpen;
     int black, white;
 };
-struct SetupImage {
-    SetupKey key;
-    bool valid = false;
-    CPSetup *dev = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ready = nullptr;
-    uint64_t used = 0;
-};
-std::mutex g_si_mu;
-SetupImage g_si[4];
-uint64_t g_si_clock = 0;
+static_assert(sizeof(SetupKey) <= DERIVED_KEY_BYTES, "key does not fit an entry");
+DerivedCache g_setups(4);
 
 }  // namespace
 
@@ -544,7 +535,6 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
     const long mo7 = (long)matrix_7000->dim[1].min * matrix_7000->dim[1].stride + matrix_7000->dim[0].min;
     const float *m3 = dev_ptr<float>(matrix_3200) - mo3;
     const float *m7 = dev_ptr<float>(matrix_7000) - mo7;
-    bool have_setup = false;
     SetupKey key;
     memset(&key, 0, sizeof key);
     key.device = ctx.device;
@@ -552,47 +542,13 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
     key.s3 = matrix_3200->dim[1].stride, key.s7 = matrix_7000->dim[1].stride, key.o3 = mo3, key.o7 = mo7;
     key.color_temp = color_temp, key.gamma = gamma, key.contrast = contrast, key.sharpen = sharpen_strength;
     key.black = blackLevel, key.white = whiteLevel;
-    const bool cacheable = key.v3 != 0 && key.v7 != 0 && !env_flag("HLMI_CP_NO_SETUP_CACHE");
-    std::unique_lock<std::mutex> si_lock(g_si_mu, std::defer_lock);
-    SetupImage *slot = nullptr;
-    if (cacheable) {
-        si_lock.lock();
-        for (auto &e : g_si) {
-            if (e.valid && memcmp(&e.key, &key, sizeof key) == 0) {
-                e.used = ++g_si_clock;
-                if (e.stream != st) HLMI_HIP(uc, wait_done(st, e.ready));
-                setup = e.dev, have_setup = true;
-                break;
-            }
-        }
-        if (!have_setup) {
-            slot = &g_si[0];
-            for (auto &e : g_si) {
-                if (!e.dev) { slot = &e; break; }
-                if (e.used < slot->used) slot = &e;
-            }
-            slot->valid = false;
-            if (slot->dev && slot->key.device != ctx.device) {
-                (void)hipFree(slot->dev);
-                slot->dev = nullptr;
-            }
-            if (!slot->dev) HLMI_HIP(uc, hipMalloc((void **)&slot->dev, setup_bytes));
-            else HLMI_HIP(uc, hipDeviceSynchronize());   // evicting a block (rare): launches on any stream may still read it
-            if (!slot->ready) HLMI_HIP(uc, hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
-            slot->key = key, slot->stream = st, slot->used = ++g_si_clock;
-            setup = slot->dev;
-        } else {
-            si_lock.unlock();
-        }
-    }
-    if (!have_setup) {
+    DerivedUse use;
+    if ((r = derived_acquire(uc, ctx, g_setups, &key, sizeof key, setup_bytes, key.v3 != 0 && key.v7 != 0 && !env_flag("HLMI_CP_NO_SETUP_CACHE"), &use))) return r;
+    if (use.ptr) setup = (CPSetup *)use.ptr;
+    if (use.fill) {
         HLMI_LAUNCH(uc, "cp_setup", st, cp_setup, dim3(1), dim3(1024), 0, m3, (long)matrix_3200->dim[1].stride, m7,
                     (long)matrix_7000->dim[1].stride, color_temp, gamma, contrast, sharpen_strength, blackLevel, whiteLevel, setup);
-        if (slot) {
-            HLMI_HIP(uc, record_done(slot->ready, st));
-            slot->valid = true;
-            si_lock.unlock();
-        }
+        use.filled(st);
     }
     const int nqx = floor_div(W, 2) + 2, nqy = floor_div(H, 2) + 2;
     const long o_sy = processed->dim[1].stride, o_sc = processed->dim[2].stride;
@@ -601,6 +557,7 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
         const int dwords = o_sy % 4 == 0 && o_sc % 4 == 0 && (uintptr_t)dout % 4 == 0;
         HLMI_LAUNCH(uc, "cp_fused", st, cp_fused_tile, dim3(((W + 63) / 64) * ((H + 2 * FTY - 1) / (2 * FTY))), dim3(256), 0, raw, in_sy, setup, dout, o_sy, o_sc,
                     W, H, dwords, (W + 63) / 64);
+        use.done(st);
         mark_output_written(processed);
         return 0;
     }
@@ -615,6 +572,7 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
     } else {
         HLMI_LAUNCH(uc, "cp_sharpen", st, cp_sharpen, dim3((W + 255) / 256, H), dim3(256), 0, cv, CW, CH, setup, dout, o_sy, o_sc, W, H);
     }
+    use.done(st);
     mark_output_written(processed);
     return 0;
 }

@@ -565,167 +565,16 @@ const halide_filter_argument_t conv_args[4] = {
 };
 const halide_filter_metadata_t conv_md = {1, 4, conv_args, kTargetString, "conv_layer_bf16"};
 
-// ---- cache of re-ordered filters -------------------------------------------------------------------------------
-// One entry per (device, filter allocation, version, layout).  An entry is read by the main kernel of every call that hits
-// it, on whatever stream that call runs: the entry therefore remembers its reader streams, and whoever re-fills or evicts the
-// entry first records an event behind everything those streams hold and orders its own stream behind all of them.  The
-// cache lock is held from the lookup until the caller's main kernel has been enqueued and recorded (FilterUse), so an
-// entry can never be re-filled between a hit and the launch that reads it.  Filters in memory the runtime does not own
-// (version 0: wrapped pointers, e.g. every torch tensor) are never cached: their image lives in the calling stream's own
-// scratch arena, where stream order alone protects it.
-constexpr int FI_READERS = 4;
-struct FilterImage {
-    int device = -1;
-    uint64_t handle = 0, version = 0;
-    int layout = 0;
-    size_t bytes = 0;
-    uint16_t *wb = nullptr;
-    hipStream_t stream = nullptr;  // stream the pre-pass ran on
-    hipEvent_t ready = nullptr;    // recorded behind the pre-pass
-    struct Reader {
-        hipStream_t s = nullptr;
-        hipEvent_t done = nullptr;
-        bool live = false;
-    } readers[FI_READERS];
-    bool overflow = false;         // more reader streams than slots: fall back to a device-wide wait
-    int pins = 0;                  // calls between their cache hit and the enqueue of their main kernel: not evictable meanwhile
-    uint64_t used = 0;
+// ---- cache of re-ordered filters: one entry per (device, filter allocation, version, layout) in the runtime's cache of
+// derived device data (hlmi_internal.h), read by the main kernel of every call that hits it.  Filters in memory the runtime
+// does not own (version 0: wrapped pointers, e.g. every torch tensor) are never cached: their image lives in the calling
+// stream's own scratch arena, where stream order alone protects it.
+struct FilterKey {
+    int device, layout;
+    uint64_t handle, version;
 };
-std::mutex g_fi_mu;
-FilterImage g_fi[8];
-uint64_t g_fi_clock = 0;
-
-// everything enqueued so far that reads `e.wb` happens before whatever `consumer` enqueues from now on
-void wait_for_readers(FilterImage &e, hipStream_t consumer) {
-    // consumer == nullptr: the entry lives on ANOTHER device than the calling thread's current one — no events are created
-    // or recorded from here (they would belong to the wrong device and poison the slot); one device-wide wait over there
-    bool sync_all = e.overflow || consumer == nullptr;
-    for (auto &r : e.readers) {
-        if (!r.live) continue;
-        if (consumer != nullptr && r.s != consumer) {
-            // the reader's event is recorded NOW, behind everything its stream has been given so far (a record per call
-            // put a barrier packet between consecutive kernels of a stream: ~3 us of every 30 us call)
-            bool ok = r.done || hipEventCreateWithFlags(&r.done, hipEventDisableTiming) == hipSuccess;
-            ok = ok && record_done(r.done, r.s) == hipSuccess && wait_done(consumer, r.done) == hipSuccess;
-            if (!ok) {
-                (void)hipGetLastError();
-                sync_all = true;   // e.g. the reader's stream was destroyed: nothing of it can still be pending, but be safe
-            }
-        }
-        r.live = false;
-    }
-    if (sync_all) {
-        int cur = -1;
-        (void)hipGetDevice(&cur);
-        if (cur != e.device && e.device >= 0) (void)hipSetDevice(e.device);
-        (void)hipDeviceSynchronize();
-        if (cur >= 0 && cur != e.device) (void)hipSetDevice(cur);
-        (void)hipGetLastError();
-    }
-    e.overflow = false;
-}
-
-// A use of a filter image by one call.  A cache HIT pins its entry (not evictable, not re-fillable) and lets go of the cache
-// lock at once — concurrent callers (the per-device workers of hlmi_run_batch, multi-stream hosts) enqueue their launches side
-// by side; done() — called after the main kernel has been enqueued — takes the lock again for a moment, records this stream
-// as a reader and unpins.  A MISS keeps the lock from the choice of the slot until done(): the entry is being (re)filled.
-// `fill` = the pre-pass has to run first.
-struct FilterUse {
-    std::unique_lock<std::mutex> lock;
-    FilterImage *entry = nullptr;   // null: the image is in the stream's scratch arena
-    bool fill = false, pinned = false;
-    uint16_t *wb = nullptr;
-    void filled(hipStream_t s) {    // the pre-pass has been enqueued on s
-        if (entry) (void)record_done(entry->ready, s);
-        fill = false;
-    }
-    void done(hipStream_t s) {      // the main kernel has been enqueued on s
-        if (entry) {
-            if (!lock.owns_lock()) lock = std::unique_lock<std::mutex>(g_fi_mu);
-            if (pinned) entry->pins--, pinned = false;
-            FilterImage::Reader *slot = nullptr;
-            for (auto &r : entry->readers) {
-                if (r.live && r.s == s) slot = &r;
-            }
-            if (!slot) {
-                for (auto &r : entry->readers) {
-                    if (!r.live) { slot = &r; break; }
-                }
-            }
-            if (slot) slot->s = s, slot->live = true;   // the stream is remembered; wait_for_readers records behind it when needed
-            else entry->overflow = true;
-        }
-        entry = nullptr;
-        if (lock.owns_lock()) lock.unlock();
-    }
-    ~FilterUse() {
-        if (!entry) return;
-        if (!lock.owns_lock()) lock = std::unique_lock<std::mutex>(g_fi_mu);
-        if (pinned) entry->pins--;
-        if (fill) entry->version = 0, entry->handle = 0;   // bailed out before the pre-pass: never match this entry
-        entry->overflow = true;                            // bailed out after it: an unrecorded reader may exist
-    }
-};
-
-int filter_image(void *uc, const DeviceCtx &ctx, const halide_buffer_t *filter, size_t bytes, int layout, FilterUse *use) {
-    const uint64_t version = buffer_version(filter);
-    if (version == 0 || env_flag("HLMI_CONV_NO_FILTER_CACHE")) {
-        void *ws = nullptr;
-        int r = get_workspace(uc, ctx, bytes, &ws);
-        if (r) return r;
-        use->wb = (uint16_t *)ws, use->fill = true, use->entry = nullptr;
-        return 0;
-    }
-    std::unique_lock<std::mutex> lock(g_fi_mu);
-    for (auto &e : g_fi) {
-        if (e.wb && e.device == ctx.device && e.handle == filter->device && e.version == version && e.layout == layout && e.bytes == bytes) {
-            e.used = ++g_fi_clock;
-            if (e.stream != ctx.stream && e.ready) HLMI_HIP(uc, wait_done(ctx.stream, e.ready));
-            e.pins++;
-            use->wb = e.wb, use->fill = false, use->entry = &e, use->pinned = true;
-            return 0;   // the lock is released here: the pin keeps the entry
-        }
-    }
-    FilterImage *slot = nullptr;
-    for (auto &e : g_fi) {
-        if (e.pins > 0) continue;   // in use by a call that has not enqueued its kernel yet
-        if (!e.wb) { slot = &e; break; }
-        if (!slot || e.used < slot->used) slot = &e;
-    }
-    if (!slot) {   // every entry is pinned by a concurrent call: this call re-orders its filter into the stream's arena
-        lock.unlock();
-        void *ws = nullptr;
-        int r = get_workspace(uc, ctx, bytes, &ws);
-        if (r) return r;
-        use->wb = (uint16_t *)ws, use->fill = true, use->entry = nullptr;
-        return 0;
-    }
-    if (slot->wb) {
-        // re-fill or evict: the old image may still be read on other streams (and was produced on slot->stream)
-        if (slot->device == ctx.device) {
-            wait_for_readers(*slot, ctx.stream);
-            if (slot->stream != ctx.stream && slot->ready && wait_done(ctx.stream, slot->ready) != hipSuccess) (void)hipGetLastError();
-        } else {
-            slot->overflow = true;
-            wait_for_readers(*slot, nullptr);   // another device: host-side wait for everything there
-        }
-        if (slot->bytes != bytes || slot->device != ctx.device) {
-            if (slot->device == ctx.device) HLMI_HIP(uc, hipStreamSynchronize(ctx.stream));   // the waits above have been enqueued: drain them before freeing
-            int cur = -1;
-            (void)hipGetDevice(&cur);
-            if (cur != slot->device) (void)hipSetDevice(slot->device);
-            (void)hipFree(slot->wb);
-            if (cur >= 0 && cur != slot->device) (void)hipSetDevice(cur);
-            slot->wb = nullptr;
-        }
-    }
-    if (!slot->wb) HLMI_HIP(uc, hipMalloc((void **)&slot->wb, bytes));
-    if (!slot->ready) HLMI_HIP(uc, hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
-    slot->device = ctx.device, slot->handle = filter->device, slot->version = version, slot->layout = layout, slot->bytes = bytes;
-    slot->stream = ctx.stream, slot->used = ++g_fi_clock;
-    use->wb = slot->wb, use->fill = true, use->entry = slot, use->lock = std::move(lock);
-    return 0;
-}
+static_assert(sizeof(FilterKey) <= DERIVED_KEY_BYTES, "key does not fit an entry");
+DerivedCache g_filters(8);
 
 }  // namespace
 
@@ -764,9 +613,14 @@ extern "C" int conv_layer_bf16(halide_buffer_t *input, halide_buffer_t *filter, 
         // allocation, version, layout) and the pre-pass re-runs only when the filter changed (uploaded again because the
         // caller set host_dirty, written by another pipeline, re-allocated).  Weights that stay resident — the
         // inference case — pay the re-ordering once.
-        FilterUse use;
-        if ((r = filter_image(uc, ctx, filter, wb_bytes, layout, &use))) return r;
-        uint16_t *wb = use.wb;
+        FilterKey key;
+        memset(&key, 0, sizeof key);
+        key.device = ctx.device, key.layout = layout, key.handle = filter->device, key.version = buffer_version(filter);
+        DerivedUse use;
+        if ((r = derived_acquire(uc, ctx, g_filters, &key, sizeof key, wb_bytes, key.version != 0 && !env_flag("HLMI_CONV_NO_FILTER_CACHE"), &use))) return r;
+        void *wb_mem = use.ptr;   // not cached: the image goes into the stream's arena
+        if (!wb_mem && (r = get_workspace(uc, ctx, wb_bytes, &wb_mem))) return r;
+        uint16_t *wb = (uint16_t *)wb_mem;
         if (use.fill) {
             timing_note_bytes(6.0 * 9 * g.CO * g.CI);
             const dim3 fgrid((pairs + 255) / 256), fblock(256);

@@ -157,6 +157,60 @@ inline hipStream_t event_stream(hipStream_t s) { return s == hipStreamLegacy ? n
 template<typename T>
 inline T *dev_ptr(const halide_buffer_t *b) { return reinterpret_cast<T *>((uintptr_t)b->device); }
 
+// ---- cache of derived device data: small results of a producing launch that are a function of a key only (the remap table of
+// local_laplacian, the set-up block of camera_pipe, the re-ordered bf16 filter of conv_layer_bf16), kept in memory of their own
+// so that a call with a known key skips the launch.  One instance per pipeline, each with its own lock and a fixed number of
+// slots, least recently used replaced first.  An entry is read by the launches of every call that hits it, on whatever stream
+// that call runs: the entry therefore remembers its reader streams, and whoever re-fills or evicts the entry first records an
+// event behind everything those streams hold and orders its own stream behind all of them (or waits for the whole device where
+// a stream is a caller's, which may be gone by then).  DESIGN.md section 1 has the invariants.
+constexpr int DERIVED_SLOTS = 8, DERIVED_READERS = 4;
+constexpr size_t DERIVED_KEY_BYTES = 96;
+struct DerivedEntry {
+    unsigned char key[DERIVED_KEY_BYTES];
+    size_t key_bytes = 0;          // 0: matches nothing
+    int device = -1;
+    size_t bytes = 0;
+    void *ptr = nullptr;
+    hipStream_t stream = nullptr;  // stream the producer ran on
+    hipEvent_t ready = nullptr;    // recorded behind the producer
+    struct Reader {
+        hipStream_t s = nullptr;
+        hipEvent_t done = nullptr;
+        bool live = false;
+    } readers[DERIVED_READERS];
+    bool overflow = false;         // more reader streams than slots: fall back to a device-wide wait
+    int pins = 0;                  // calls between their cache hit and the enqueue of their last reading launch: not evictable meanwhile
+    uint64_t used = 0;
+};
+struct DerivedCache {
+    const int capacity;            // slots in use, <= DERIVED_SLOTS
+    std::mutex mu;
+    DerivedEntry slots[DERIVED_SLOTS];
+    uint64_t clock = 0;
+    explicit DerivedCache(int n) : capacity(n) {}
+};
+// A use of an entry by one call.  A cache HIT pins its entry (not evictable, not re-fillable) and lets go of the cache lock at
+// once — concurrent callers (the per-device workers of hlmi_run_batch, multi-stream hosts) enqueue their launches side by side;
+// done() — called after the last launch that reads `ptr` has been enqueued — takes the lock again for a moment, records this
+// stream as a reader and unpins.  A MISS keeps the lock from the choice of the slot until done(): the entry is being (re)filled.
+struct DerivedUse {
+    void *ptr = nullptr;             // null: not cached — the caller produces into memory of its own (its workspace)
+    bool fill = true;                // the caller has to enqueue the producing launch on its stream first, then call filled()
+    void filled(hipStream_t s);      // the producer has been enqueued on s
+    void done(hipStream_t s);        // every launch of this call that reads ptr has been enqueued on s
+    ~DerivedUse();                   // the call bailed out between derived_acquire() and done()
+
+    std::unique_lock<std::mutex> lock;   // (which also keeps a use from being copied)
+    DerivedCache *cache = nullptr;
+    DerivedEntry *entry = nullptr;
+    bool pinned = false;
+};
+// `key` is compared as `key_bytes` (<= DERIVED_KEY_BYTES) opaque bytes: callers zero their key struct first and put the device in it.
+// !cacheable, or every slot pinned by a concurrent call: nothing is touched, use->ptr == nullptr and use->fill.
+int derived_acquire(void *uc, const DeviceCtx &ctx, DerivedCache &c, const void *key, size_t key_bytes, size_t bytes, bool cacheable,
+                    DerivedUse *use);
+
 // ---------------------------------------------------------------------------------------------
 // optional per-kernel HIP-event timing (include/hlmi_runtime.h: hlmi_kernel_timing_*)
 bool timing_enabled();

@@ -2737,62 +2737,32 @@ UpArgs up_args(const LlPlan &pl, const LlBuffers &b, int j) {   // outGPyramid[j
 }
 
 // ---- cache of remap tables: the LUT is a function of (levels, alpha) only — a video stream calls with the same pair frame
-// after frame — so it is kept in memory of its own per (device, levels, alpha) and ll_remap_lut runs when the pair is new
-// (one 4.5 us launch less per frame).  An entry is used by other streams behind the event recorded after its launch.
-struct LutImage {
-    int device = -1, levels = 0;
-    uint32_t alpha_bits = 0;
-    bool valid = false;
-    float *dev = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ready = nullptr;
-    uint64_t used = 0;
+// after frame — so it is kept per (device, levels, alpha) in the runtime's cache of derived device data (hlmi_internal.h) and
+// ll_remap_lut runs when the pair is new (one 4.5 us launch less per frame).
+struct LutKey {
+    int device, levels;
+    uint32_t alpha_bits;
 };
-std::mutex g_lut_mu;
-LutImage g_lut[8];
-uint64_t g_lut_clock = 0;
+static_assert(sizeof(LutKey) <= DERIVED_KEY_BYTES, "key does not fit an entry");
+DerivedCache g_luts(8);
 
 // ---- the stages of the chain, in launch order.  Each takes the plan, the resolved pointers and the stream, fills its
 // kernel-argument struct and launches; a non-zero return is the error code of the call.
 
 // stage 1: the remap table — b.lut becomes the cached table of (device, levels, alpha), computed now if the pair is new;
-// HLMI_LL_NO_LUT_CACHE: computed in the workspace in every call
-int ll_stage_table(void *uc, const DeviceCtx &ctx, const LlPlan &pl, float alpha, LlBuffers &b) {
-    hipStream_t st = ctx.stream;
-    const int levels = pl.gm.K, nlut = pl.nlut;
-    if (pl.lut_cache) {
-        uint32_t abits;
-        memcpy(&abits, &alpha, 4);
-        std::unique_lock<std::mutex> lock(g_lut_mu);
-        LutImage *hit = nullptr, *slot = &g_lut[0];
-        for (auto &e : g_lut) {
-            if (e.valid && e.device == ctx.device && e.levels == levels && e.alpha_bits == abits) hit = &e;
-        }
-        if (hit) {
-            hit->used = ++g_lut_clock;
-            if (hit->stream != st) HLMI_HIP(uc, wait_done(st, hit->ready));
-            b.lut = hit->dev;
-        } else {
-            for (auto &e : g_lut) {
-                if (!e.dev) { slot = &e; break; }
-                if (e.used < slot->used) slot = &e;
-            }
-            slot->valid = false;
-            if (slot->dev) {   // evicting (more than 8 (levels, alpha) pairs in use): launches on any stream may still read it
-                HLMI_HIP(uc, hipDeviceSynchronize());
-                (void)hipFree(slot->dev);
-                slot->dev = nullptr;
-            }
-            HLMI_HIP(uc, hipMalloc((void **)&slot->dev, sizeof(float) * ((size_t)nlut + 64)));
-            if (!slot->ready) HLMI_HIP(uc, hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
-            slot->device = ctx.device, slot->levels = levels, slot->alpha_bits = abits, slot->stream = st, slot->used = ++g_lut_clock;
-            b.lut = slot->dev;
-            HLMI_LAUNCH(uc, "ll_remap_lut", st, ll_remap_lut, dim3((nlut + 255) / 256), dim3(256), 0, b.lut, pl.gm.half, alpha);
-            HLMI_HIP(uc, record_done(slot->ready, st));
-            slot->valid = true;
-        }
-    } else {
-        HLMI_LAUNCH(uc, "ll_remap_lut", st, ll_remap_lut, dim3((nlut + 255) / 256), dim3(256), 0, b.lut, pl.gm.half, alpha);
+// HLMI_LL_NO_LUT_CACHE: computed in the workspace in every call.  `use` holds the table until the caller's done().
+int ll_stage_table(void *uc, const DeviceCtx &ctx, const LlPlan &pl, float alpha, LlBuffers &b, DerivedUse &use) {
+    const int nlut = pl.nlut;
+    LutKey key;
+    memset(&key, 0, sizeof key);
+    key.device = ctx.device, key.levels = pl.gm.K;
+    memcpy(&key.alpha_bits, &alpha, 4);
+    int r = derived_acquire(uc, ctx, g_luts, &key, sizeof key, sizeof(float) * ((size_t)nlut + 64), pl.lut_cache, &use);
+    if (r) return r;
+    if (use.ptr) b.lut = (float *)use.ptr;
+    if (use.fill) {
+        HLMI_LAUNCH(uc, "ll_remap_lut", ctx.stream, ll_remap_lut, dim3((nlut + 255) / 256), dim3(256), 0, b.lut, pl.gm.half, alpha);
+        use.filled(ctx.stream);
     }
     return 0;
 }
@@ -3034,10 +3004,12 @@ extern "C" int local_laplacian(halide_buffer_t *input, int32_t levels, float alp
     t_dbg.out1_pending = pl.fuse1, t_dbg.out2_pending = pl.fuse2;
 
     hipStream_t st = ctx.stream;
-    if ((r = ll_stage_table(uc, ctx, pl, alpha, b)) || (r = ll_stage_down0(uc, pl, b, st)) || (r = ll_stage_down_rest(uc, pl, b, st)) ||
+    DerivedUse table;
+    if ((r = ll_stage_table(uc, ctx, pl, alpha, b, table)) || (r = ll_stage_down0(uc, pl, b, st)) || (r = ll_stage_down_rest(uc, pl, b, st)) ||
         (r = ll_stage_up_coarse(uc, pl, b, st)) || (r = ll_stage_up0(uc, pl, b, st))) {
         return r;
     }
+    table.done(st);   // ll_stage_down0 and ll_stage_up0 read the table
     mark_output_written(output);
     return 0;
 }

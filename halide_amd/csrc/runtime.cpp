@@ -460,6 +460,126 @@ int stream_cu_count(int device, hipStream_t stream) {
     return stream ? c / share : c;
 }
 
+// ---- cache of derived device data (hlmi_internal.h) ----------------------------------------------
+// Streams the library made itself — a device's own stream and the frame queues — live as long as the process; the special handles
+// are no objects at all.  Any other stream is its caller's, who may have destroyed it since an entry remembered it: neither such a
+// handle nor an event recorded on such a stream is handed to the HIP runtime again.
+static bool stream_outlives_entries(int device, hipStream_t s) {
+    if (stream_is_special(s)) return true;
+    std::lock_guard<std::mutex> lock(g_mu);
+    return s == g_dev[device].stream || g_part_cus.count(s) != 0;
+}
+
+// everything enqueued so far that writes or reads `e.ptr` happens before whatever `consumer` enqueues from now on
+static void wait_for_users(DerivedEntry &e, hipStream_t consumer) {
+    // consumer == nullptr: the entry lives on ANOTHER device than the calling thread's current one — no events are created
+    // or recorded from here (they would belong to the wrong device and poison the slot); one device-wide wait over there
+    bool sync_all = e.overflow || consumer == nullptr;
+    if (!sync_all && e.stream != consumer) {   // the producer
+        if (!stream_outlives_entries(e.device, e.stream)) sync_all = true;
+        else if (e.ready && wait_done(consumer, e.ready) != hipSuccess) (void)hipGetLastError(), sync_all = true;
+    }
+    for (auto &r : e.readers) {
+        if (r.live && !sync_all && r.s != consumer) {
+            // the reader's event is recorded NOW, behind everything its stream has been given so far (a record per call
+            // put a barrier packet between consecutive kernels of a stream: ~3 us of every 30 us call)
+            bool ok = stream_outlives_entries(e.device, r.s) && (r.done || hipEventCreateWithFlags(&r.done, hipEventDisableTiming) == hipSuccess);
+            ok = ok && record_done(r.done, r.s) == hipSuccess && wait_done(consumer, r.done) == hipSuccess;
+            if (!ok) {
+                (void)hipGetLastError();
+                sync_all = true;   // a caller's stream, or an event call failed: wait for the whole device instead
+            }
+        }
+        r.live = false;
+    }
+    if (sync_all) {
+        int cur = -1;
+        (void)hipGetDevice(&cur);
+        if (cur != e.device && e.device >= 0) (void)hipSetDevice(e.device);
+        (void)hipDeviceSynchronize();
+        if (cur >= 0 && cur != e.device) (void)hipSetDevice(cur);
+        (void)hipGetLastError();
+    }
+    e.overflow = false;
+}
+
+void DerivedUse::filled(hipStream_t s) {
+    if (entry) (void)record_done(entry->ready, s);
+    fill = false;
+}
+
+void DerivedUse::done(hipStream_t s) {
+    if (entry) {
+        if (!lock.owns_lock()) lock = std::unique_lock<std::mutex>(cache->mu);
+        if (pinned) entry->pins--, pinned = false;
+        DerivedEntry::Reader *slot = nullptr;
+        for (auto &r : entry->readers) {
+            if (r.live && r.s == s) slot = &r;
+        }
+        if (!slot) {
+            for (auto &r : entry->readers) {
+                if (!r.live) { slot = &r; break; }
+            }
+        }
+        if (slot) slot->s = s, slot->live = true;   // the stream is remembered; wait_for_users records behind it when needed
+        else entry->overflow = true;
+    }
+    entry = nullptr;
+    if (lock.owns_lock()) lock.unlock();
+}
+
+DerivedUse::~DerivedUse() {
+    if (!entry) return;
+    if (!lock.owns_lock()) lock = std::unique_lock<std::mutex>(cache->mu);
+    if (pinned) entry->pins--;
+    if (fill) entry->key_bytes = 0;   // bailed out before the producer: never match this entry
+    entry->overflow = true;           // bailed out after it: an unrecorded reader may exist
+}
+
+int derived_acquire(void *uc, const DeviceCtx &ctx, DerivedCache &c, const void *key, size_t key_bytes, size_t bytes, bool cacheable,
+                    DerivedUse *use) {
+    use->ptr = nullptr, use->fill = true, use->entry = nullptr, use->cache = &c;
+    if (!cacheable || key_bytes == 0 || key_bytes > DERIVED_KEY_BYTES) return 0;
+    std::unique_lock<std::mutex> lock(c.mu);
+    DerivedEntry *const end = c.slots + c.capacity;
+    for (DerivedEntry *e = c.slots; e != end; e++) {
+        if (e->ptr && e->device == ctx.device && e->bytes == bytes && e->key_bytes == key_bytes && memcmp(e->key, key, key_bytes) == 0) {
+            e->used = ++c.clock;
+            if (e->stream != ctx.stream && e->ready) HLMI_HIP(uc, wait_done(ctx.stream, e->ready));
+            e->pins++;
+            use->ptr = e->ptr, use->fill = false, use->entry = e, use->pinned = true;
+            return 0;   // the lock is released here: the pin keeps the entry
+        }
+    }
+    DerivedEntry *slot = nullptr;
+    for (DerivedEntry *e = c.slots; e != end; e++) {
+        if (e->pins > 0) continue;   // in use by a call that has not enqueued its launches yet
+        if (!e->ptr) { slot = e; break; }
+        if (!slot || e->used < slot->used) slot = e;
+    }
+    if (!slot) return 0;   // every entry is pinned by a concurrent call: this call produces into memory of its own
+    if (slot->ptr) {
+        // re-fill or evict: the old contents may still be read on other streams (and were produced on slot->stream)
+        wait_for_users(*slot, slot->device == ctx.device ? ctx.stream : nullptr);   // another device: host-side wait for everything there
+        if (slot->bytes != bytes || slot->device != ctx.device) {
+            if (slot->device == ctx.device) HLMI_HIP(uc, hipStreamSynchronize(ctx.stream));   // the waits above have been enqueued: drain them before freeing
+            int cur = -1;
+            (void)hipGetDevice(&cur);
+            if (cur != slot->device) (void)hipSetDevice(slot->device);
+            (void)hipFree(slot->ptr);
+            if (cur >= 0 && cur != slot->device) (void)hipSetDevice(cur);
+            slot->ptr = nullptr;
+        }
+    }
+    slot->key_bytes = 0;
+    if (!slot->ptr) HLMI_HIP(uc, hipMalloc(&slot->ptr, bytes));
+    if (!slot->ready) HLMI_HIP(uc, hipEventCreateWithFlags(&slot->ready, hipEventDisableTiming));
+    memcpy(slot->key, key, key_bytes);
+    slot->key_bytes = key_bytes, slot->device = ctx.device, slot->bytes = bytes, slot->stream = ctx.stream, slot->used = ++c.clock;
+    use->ptr = slot->ptr, use->entry = slot, use->lock = std::move(lock);
+    return 0;
+}
+
 uint64_t buffer_version(const halide_buffer_t *buf) {
     if (!buf || !buf->device) return 0;
     std::lock_guard<std::mutex> lock(g_mu);

@@ -195,3 +195,109 @@ def test_bounds_query(hl):
     out = hl.Buffer(np.zeros((3, 1920, 2560), np.uint8))
     hl.camera_pipe(q, m3, m7, 3700.0, 2.0, 50.0, 1.0, 25, 1023, out)
     assert q.mins == [10, 6] and q.extents == [2572, 1932]
+
+
+def _foreign_copy(hl, arr):
+    """`arr` in device memory the runtime does not own (what a torch tensor is), wrapped: its version is 0"""
+    import ctypes
+    hip = hl.hip_runtime()
+    p = ctypes.c_void_p()
+    assert hip.hipMalloc(ctypes.byref(p), ctypes.c_size_t(arr.nbytes)) == 0
+    assert hip.hipMemcpy(p, ctypes.c_void_p(arr.ctypes.data), ctypes.c_size_t(arr.nbytes), 1) == 0   # host to device
+    return hl.Buffer.wrap_device(p.value, arr.dtype, arr.shape[::-1]), p
+
+
+def _launch_count(hl, name):
+    return sum(k["calls"] for k in hl.kernel_timing_report() if k["name"] == name)
+
+
+@pytest.mark.gpu
+def test_hip_setup_block_is_computed_once_per_matrices_and_scalars(hl, monkeypatch):
+    """cp_setup runs when (matrix allocations + versions, scalars) is new and is skipped when the block is cached, over the
+    steps of test_hip_setup_block_follows_the_matrices_and_scalars; with wrapped matrices (version 0) or
+    HLMI_CP_NO_SETUP_CACHE=1 it runs in every call.  Counted with the library's own launch record, one host thread, one stream."""
+    monkeypatch.delenv("HLMI_CP_NO_SETUP_CACHE", raising=False)
+    bi = hl.Buffer(_raw(200, 150, seed=12))
+    m3 = M3200 * np.float32(1.0625)                     # matrices no other test uses
+    m7 = M7000 * np.float32(0.9375)
+    b3, b7 = hl.Buffer(m3), hl.Buffer(m7)
+
+    def run(p, a3, a7):
+        bo = hl.Buffer(np.zeros((3, 120, 160), np.uint8))
+        hl.camera_pipe(bi, a3, a7, p["color_temp"], p["gamma"], p["contrast"], p["sharpen"], p["black"], p["white"], bo)
+        bo.device_sync()
+        bo.device_free()
+    p2 = dict(PARAMS, gamma=1.4, sharpen=3.0)
+    hl.kernel_timing(True)
+    hl.kernel_timing_reset()
+    try:
+        run(PARAMS, b3, b7), run(PARAMS, b3, b7)
+        assert _launch_count(hl, "cp_setup") == 1       # same scalars: skipped
+        run(p2, b3, b7)
+        assert _launch_count(hl, "cp_setup") == 2       # other scalars: runs
+        run(PARAMS, b3, b7)
+        assert _launch_count(hl, "cp_setup") == 2       # and back: skipped
+        m3[...] = m3 * np.float32(0.75)
+        b3.set_host_dirty()
+        run(PARAMS, b3, b7)
+        assert _launch_count(hl, "cp_setup") == 3       # matrix marked host-dirty: runs
+        b7.device_free()
+        b7 = hl.Buffer((m7 * np.float32(1.25)).astype(np.float32))
+        run(PARAMS, b3, b7)
+        assert _launch_count(hl, "cp_setup") == 4       # re-allocated matrix: runs
+        (w3, p3), (w7, p7) = _foreign_copy(hl, m3), _foreign_copy(hl, m7)
+        hl.kernel_timing_reset()
+        run(PARAMS, w3, w7), run(PARAMS, w3, w7), run(PARAMS, w3, w7)
+        assert _launch_count(hl, "cp_setup") == 3       # wrapped matrices: in every call
+        w3.device_detach(), w7.device_detach()
+        hl.hip_runtime().hipFree(p3), hl.hip_runtime().hipFree(p7)
+        monkeypatch.setenv("HLMI_CP_NO_SETUP_CACHE", "1")
+        hl.kernel_timing_reset()
+        run(PARAMS, b3, b7), run(PARAMS, b3, b7)
+        assert _launch_count(hl, "cp_setup") == 2       # cache switched off: in every call
+    finally:
+        hl.kernel_timing(False)
+        hl.kernel_timing_reset()
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_hip_setup_blocks_are_safe_across_threads_and_streams(hl, oracle):
+    """Four host threads with a stream each call camera_pipe with SIX scalar sets in random order (the cache of set-up blocks
+    holds four: blocks are evicted and re-filled while launches of other streams still read them); every output equals the
+    oracle's for its set."""
+    import ctypes
+    import threading
+    hip = hl.hip_runtime()
+    sets = [dict(PARAMS, gamma=1.0 + 0.25 * i, contrast=10.0 * i, sharpen=0.5 * i, black=20 + i) for i in range(6)]
+    raws = [_raw(200, 150, seed=30 + t) for t in range(4)]
+    want = [[_oracle(oracle, raws[t], 160, 120, p) for p in sets] for t in range(4)]
+    b3, b7 = hl.Buffer(M3200.copy()).copy_to_device(), hl.Buffer(M7000.copy()).copy_to_device()   # resident: cacheable
+    errors = []
+
+    def worker(t):
+        try:
+            stream = ctypes.c_void_p()
+            assert hip.hipStreamCreateWithFlags(ctypes.byref(stream), 1) == 0
+            hl.set_stream(stream.value)
+            r = np.random.default_rng(400 + t)
+            bi = hl.Buffer(raws[t])
+            for rep in range(40):
+                k = int(r.integers(0, len(sets)))
+                p = sets[k]
+                bo = hl.Buffer(np.zeros((3, 120, 160), np.uint8))
+                hl.camera_pipe(bi, b3, b7, p["color_temp"], p["gamma"], p["contrast"], p["sharpen"], p["black"], p["white"], bo)
+                if not np.array_equal(bo.numpy(), want[t][k]):
+                    errors.append(f"thread {t} rep {rep} set {k}: result is not this set's")
+                bo.device_free()
+            hl.set_stream(None)
+            assert hip.hipStreamSynchronize(stream) == 0
+        except Exception as e:  # noqa: BLE001
+            errors.append(f"thread {t}: {e!r}")
+
+    threads = [threading.Thread(target=worker, args=(t,)) for t in range(4)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors[:5]

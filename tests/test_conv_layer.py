@@ -198,6 +198,65 @@ def test_hip_bf16_filter_images_are_safe_across_threads_and_streams(hl, oracle, 
     assert not errors, errors[:5]
 
 
+def _foreign_copy(hl, arr):
+    """`arr` in device memory the runtime does not own (what a torch tensor is), wrapped: its version is 0"""
+    import ctypes
+    hip = hl.hip_runtime()
+    p = ctypes.c_void_p()
+    assert hip.hipMalloc(ctypes.byref(p), ctypes.c_size_t(arr.nbytes)) == 0
+    assert hip.hipMemcpy(p, ctypes.c_void_p(arr.ctypes.data), ctypes.c_size_t(arr.nbytes), 1) == 0   # host to device
+    return hl.Buffer.wrap_device(p.value, arr.dtype, arr.shape[::-1]), p
+
+
+def _launch_count(hl, name):
+    return sum(k["calls"] for k in hl.kernel_timing_report() if k["name"] == name)
+
+
+@pytest.mark.gpu
+def test_hip_bf16_filter_is_reordered_once_per_allocation_and_version(hl, monkeypatch):
+    """conv_filter_bf16 runs when (filter allocation, version) is new and is skipped when the image is cached, over the steps
+    of test_hip_bf16_filter_image_follows_the_filter_contents; with a wrapped filter (version 0) or
+    HLMI_CONV_NO_FILTER_CACHE=1 it runs in every call.  Counted with the library's own launch record, one host thread, one
+    stream."""
+    monkeypatch.delenv("HLMI_CONV_NO_FILTER_CACHE", raising=False)
+    inp, filt, bias = _data(2, 6, 10, 64, 128, seed=9)
+    bi, bf, bb = hl.Buffer(inp), hl.Buffer(filt), hl.Buffer(bias)
+
+    def run(f):
+        bo = hl.Buffer(np.zeros((2, 6, 10, 128), np.float32))
+        hl.conv_layer_bf16(bi, f, bb, bo)
+        bo.device_sync()
+        bo.device_free()
+    hl.kernel_timing(True)
+    hl.kernel_timing_reset()
+    try:
+        run(bf), run(bf)
+        assert _launch_count(hl, "conv_filter_bf16") == 1   # resident filter: re-ordered once
+        filt[...] = -filt
+        bf.set_host_dirty()
+        run(bf)
+        assert _launch_count(hl, "conv_filter_bf16") == 2   # rewritten and marked host-dirty: runs
+        run(bf)
+        assert _launch_count(hl, "conv_filter_bf16") == 2
+        bf.device_free()
+        bf = hl.Buffer((filt * np.float32(0.5)).astype(np.float32))
+        run(bf)
+        assert _launch_count(hl, "conv_filter_bf16") == 3   # a new allocation: runs
+        wf, pf = _foreign_copy(hl, filt)
+        hl.kernel_timing_reset()
+        run(wf), run(wf), run(wf)
+        assert _launch_count(hl, "conv_filter_bf16") == 3   # wrapped filter: in every call
+        wf.device_detach()
+        hl.hip_runtime().hipFree(pf)
+        monkeypatch.setenv("HLMI_CONV_NO_FILTER_CACHE", "1")
+        hl.kernel_timing_reset()
+        run(bf), run(bf)
+        assert _launch_count(hl, "conv_filter_bf16") == 2   # cache switched off: in every call
+    finally:
+        hl.kernel_timing(False)
+        hl.kernel_timing_reset()
+
+
 @pytest.mark.gpu
 def test_hip_rejects_non_dense_layout(hl):
     inp, filt, bias = _data(1, 4, 4, 32, 128, 0)

@@ -543,3 +543,118 @@ def test_hip_eight_4k_frames_in_flight_on_partitioned_and_plain_streams(hl, orac
     for s in plain:
         hip.hipStreamSynchronize(s)
         hip.hipStreamDestroy(s)
+
+
+# ---- the cache of remap tables (the runtime's cache of derived device data)
+def _launch_count(hl, name):
+    return sum(k["calls"] for k in hl.kernel_timing_report() if k["name"] == name)
+
+
+@pytest.mark.gpu
+def test_hip_remap_table_is_computed_once_per_levels_and_alpha(hl, oracle, monkeypatch):
+    """ll_remap_lut runs when (levels, alpha) is new and is skipped when the pair's table is cached; with
+    HLMI_LL_NO_LUT_CACHE=1 it runs in every call.  Counted with the library's own launch record, one host thread, one stream;
+    (6, 0.3125) and (6, 0.4375) are pairs no other test uses."""
+    monkeypatch.delenv("HLMI_LL_NO_LUT_CACHE", raising=False)
+    inp = _rand_image(96, 64, seed=61)
+    a = hl.Buffer(inp)
+
+    def run(alpha):
+        o = hl.Buffer(np.zeros_like(inp))
+        hl.local_laplacian(a, 6, alpha, 1.0, o)
+        res = o.numpy().copy()
+        o.device_free()
+        return res
+    hl.kernel_timing(True)
+    hl.kernel_timing_reset()
+    try:
+        first, again = run(0.3125), run(0.3125)
+        assert _launch_count(hl, "ll_remap_lut") == 1
+        other = run(0.4375)
+        assert _launch_count(hl, "ll_remap_lut") == 2
+        back = run(0.3125)
+        assert _launch_count(hl, "ll_remap_lut") == 2
+        monkeypatch.setenv("HLMI_LL_NO_LUT_CACHE", "1")
+        hl.kernel_timing_reset()
+        uncached = [run(0.3125), run(0.3125), run(0.4375)]
+        assert _launch_count(hl, "ll_remap_lut") == 3
+    finally:
+        hl.kernel_timing(False)
+        hl.kernel_timing_reset()
+    a.device_free()
+    want = oracle.local_laplacian(inp, 6, 0.3125, 1.0)
+    for got in (first, again, back, uncached[0], uncached[1]):
+        assert np.array_equal(got, want)
+    want2 = oracle.local_laplacian(inp, 6, 0.4375, 1.0)
+    assert np.array_equal(other, want2) and np.array_equal(uncached[2], want2)
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_hip_remap_tables_are_safe_across_threads_and_streams(hl, oracle):
+    """Four host threads with a stream each call local_laplacian with TEN (levels, alpha) pairs in random order (the cache of
+    remap tables holds eight: tables are evicted and re-filled while launches of other streams still read them); every output
+    equals the oracle's for its pair."""
+    import ctypes
+    import threading
+    hip = hl.hip_runtime()
+    pairs = [(3 + i % 4, float(np.float32(0.11 + 0.07 * i))) for i in range(10)]
+    inputs = [_rand_image(96, 64, seed=200 + t) for t in range(4)]
+    want = [[oracle.local_laplacian(inputs[t], lv, al, 1.0) for (lv, al) in pairs] for t in range(4)]
+    errors = []
+
+    def worker(t):
+        try:
+            stream = ctypes.c_void_p()
+            assert hip.hipStreamCreateWithFlags(ctypes.byref(stream), 1) == 0
+            hl.set_stream(stream.value)
+            r = np.random.default_rng(300 + t)
+            bi = hl.Buffer(inputs[t])
+            for rep in range(40):
+                k = int(r.integers(0, len(pairs)))
+                bo = hl.Buffer(np.zeros_like(inputs[t]))
+                hl.local_laplacian(bi, pairs[k][0], pairs[k][1], 1.0, bo)
+                if not np.array_equal(bo.numpy(), want[t][k]):
+                    errors.append(f"thread {t} rep {rep} pair {pairs[k]}: result is not this pair's")
+                bo.device_free()
+            hl.set_stream(None)
+            assert hip.hipStreamSynchronize(stream) == 0
+        except Exception as e:  # noqa: BLE001
+            errors.append(f"thread {t}: {e!r}")
+
+    threads = [threading.Thread(target=worker, args=(t,)) for t in range(4)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors[:5]
+
+
+@pytest.mark.gpu
+def test_hip_remap_table_is_evicted_after_its_streams_were_destroyed(hl, oracle):
+    """A caller may destroy its streams once their work is done.  The table of a (levels, alpha) pair that was produced on one
+    such stream and read on another is evicted later — nine other pairs on the library's own stream; the cache holds eight —
+    and recomputed: every output equals the oracle's."""
+    import ctypes as C
+    hip = hl.hip_runtime()
+    inp = _rand_image(96, 64, seed=62)
+
+    def run(levels, alpha):   # buffers of its own: no allocation remembers a stream beyond the call
+        return _run_hip(hl, inp, levels, alpha, 1.0).copy()
+    streams = []
+    for _ in range(2):
+        s = C.c_void_p()
+        assert hip.hipStreamCreateWithFlags(C.byref(s), 1) == 0
+        streams.append(s)
+    want = oracle.local_laplacian(inp, 5, 0.28125, 1.0)
+    for s in streams:
+        hl.set_stream(s.value)
+        assert np.array_equal(run(5, 0.28125), want)
+    hl.set_stream(None)
+    for s in streams:
+        assert hip.hipStreamSynchronize(s) == 0
+        assert hip.hipStreamDestroy(s) == 0
+    for i in range(9):
+        alpha = 0.53125 + i / 32.0
+        assert np.array_equal(run(7, alpha), oracle.local_laplacian(inp, 7, alpha, 1.0)), f"pair {i}"
+    assert np.array_equal(run(5, 0.28125), want)
