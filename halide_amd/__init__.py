@@ -403,41 +403,41 @@ def _as_ptr(b):
 
 # ---------------------------------------------------------------------------------------------------
 # pipelines — argument order and meaning exactly as in include/hlmi_pipelines.h
-def _bind(name, argtypes):
+def _bind(name):
+    """The entry point `name` with the argtypes its own `<name>_metadata()` states (one table per entry point in the library:
+    csrc/hlmi_internal.h); None when the library does not export it."""
     fn = getattr(lib, name, None)
-    if fn is None:
+    if fn is None or getattr(lib, name + "_metadata", None) is None:
         return None
+    md = metadata(name)
+    argtypes = []
+    for a in (md.arguments[i] for i in range(md.num_arguments)):
+        t = _BP if a.kind != 0 else {(2, 32): C.c_float, (0, 32): C.c_int32}.get((a.type.code, a.type.bits))
+        if t is None:
+            raise ImportError(f"{name}: no ctypes type for scalar argument {a.name.decode()} (type code {a.type.code}, {a.type.bits} bits)")
+        argtypes.append(t)
     fn.argtypes = argtypes
     fn.restype = C.c_int
     return fn
 
 
-_ll = _bind("local_laplacian", [_BP, C.c_int32, C.c_float, C.c_float, _BP])
-_bg = _bind("bilateral_grid", [_BP, C.c_float, _BP])
-_blur = _bind("halide_blur", [_BP, _BP])
-_nlm = _bind("nl_means", [_BP, C.c_int32, C.c_int32, C.c_float, _BP])
-_sc = _bind("stencil_chain", [_BP, _BP])
-_conv = _bind("conv_layer", [_BP, _BP, _BP, _BP])
-_conv_bf16 = _bind("conv_layer_bf16", [_BP, _BP, _BP, _BP])
-_dsc = _bind("depthwise_separable_conv", [_BP, _BP, _BP, _BP, _BP])
-_unsharp = _bind("unsharp", [_BP, _BP])
-_maxf = _bind("max_filter", [_BP, _BP])
-_hist = _bind("hist", [_BP, _BP])
-_harris = _bind("harris", [_BP, _BP])
-_interp = _bind("interpolate", [_BP, _BP])
-_iir = _bind("iir_blur", [_BP, C.c_float, _BP])
-_lens = _bind("lens_blur", [_BP, _BP, C.c_int32, C.c_int32, C.c_float, C.c_int32, _BP])
-_bgu = _bind("bgu", [C.c_float, C.c_int32, _BP, _BP, _BP, _BP])
+def metadata(name: str) -> halide_filter_metadata_t:
+    fn = getattr(lib, name + "_metadata")
+    fn.restype = C.POINTER(halide_filter_metadata_t)
+    return fn().contents
+
+
 RESIZE_KERNELS = ("box", "linear", "cubic", "lanczos")
 _RESIZE_TYPES = {"float32": "float32", "uint8": "uint8", "uint16": "uint16"}
-_resize = {f"resize_{k}_{t}_{d}": _bind(f"resize_{k}_{t}_{d}", [_BP, C.c_float, _BP])
-           for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")}
-_cam = _bind("camera_pipe", [_BP, _BP, _BP, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, _BP])
+_fn = {name: _bind(name) for name in
+       ["local_laplacian", "bilateral_grid", "halide_blur", "nl_means", "stencil_chain", "conv_layer", "conv_layer_bf16",
+        "depthwise_separable_conv", "unsharp", "max_filter", "hist", "harris", "interpolate", "iir_blur", "lens_blur", "bgu",
+        "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
     """apps/local_laplacian: u16 [W,H,3] -> u16 [W,H,3]; drivers pass alpha/(levels-1) (process.cpp:31)."""
-    return _check(_ll(_as_ptr(input), int(levels), float(alpha), float(beta), _as_ptr(output)))
+    return _check(_fn["local_laplacian"](_as_ptr(input), int(levels), float(alpha), float(beta), _as_ptr(output)))
 
 
 def debug_local_laplacian_outg(level: int) -> np.ndarray:
@@ -504,55 +504,55 @@ def membench(nbytes: int = 1 << 30, iters: int = 10, blocks: int = 0) -> dict:
 
 
 def bilateral_grid(input, r_sigma, output) -> int:
-    return _check(_bg(_as_ptr(input), float(r_sigma), _as_ptr(output)))
+    return _check(_fn["bilateral_grid"](_as_ptr(input), float(r_sigma), _as_ptr(output)))
 
 
 def halide_blur(input, blur_y) -> int:
-    return _check(_blur(_as_ptr(input), _as_ptr(blur_y)))
+    return _check(_fn["halide_blur"](_as_ptr(input), _as_ptr(blur_y)))
 
 
 def nl_means(input, patch_size, search_area, sigma, output) -> int:
-    return _check(_nlm(_as_ptr(input), int(patch_size), int(search_area), float(sigma), _as_ptr(output)))
+    return _check(_fn["nl_means"](_as_ptr(input), int(patch_size), int(search_area), float(sigma), _as_ptr(output)))
 
 
 def stencil_chain(input, output) -> int:
-    return _check(_sc(_as_ptr(input), _as_ptr(output)))
+    return _check(_fn["stencil_chain"](_as_ptr(input), _as_ptr(output)))
 
 
 def conv_layer(input, filter, bias, relu) -> int:
-    return _check(_conv(_as_ptr(input), _as_ptr(filter), _as_ptr(bias), _as_ptr(relu)))
+    return _check(_fn["conv_layer"](_as_ptr(input), _as_ptr(filter), _as_ptr(bias), _as_ptr(relu)))
 
 
 def conv_layer_bf16(input, filter, bias, relu) -> int:
-    return _check(_conv_bf16(_as_ptr(input), _as_ptr(filter), _as_ptr(bias), _as_ptr(relu)))
+    return _check(_fn["conv_layer_bf16"](_as_ptr(input), _as_ptr(filter), _as_ptr(bias), _as_ptr(relu)))
 
 
 def depthwise_separable_conv(input, depthwise_filter, pointwise_filter, bias, output) -> int:
-    return _check(_dsc(_as_ptr(input), _as_ptr(depthwise_filter), _as_ptr(pointwise_filter), _as_ptr(bias), _as_ptr(output)))
+    return _check(_fn["depthwise_separable_conv"](_as_ptr(input), _as_ptr(depthwise_filter), _as_ptr(pointwise_filter), _as_ptr(bias), _as_ptr(output)))
 
 
 def unsharp(input, output) -> int:
-    return _check(_unsharp(_as_ptr(input), _as_ptr(output)))
+    return _check(_fn["unsharp"](_as_ptr(input), _as_ptr(output)))
 
 
 def max_filter(input, output) -> int:
-    return _check(_maxf(_as_ptr(input), _as_ptr(output)))
+    return _check(_fn["max_filter"](_as_ptr(input), _as_ptr(output)))
 
 
 def hist(input, output) -> int:
-    return _check(_hist(_as_ptr(input), _as_ptr(output)))
+    return _check(_fn["hist"](_as_ptr(input), _as_ptr(output)))
 
 
 def harris(input, output) -> int:
-    return _check(_harris(_as_ptr(input), _as_ptr(output)))
+    return _check(_fn["harris"](_as_ptr(input), _as_ptr(output)))
 
 
 def interpolate(input, output) -> int:
-    return _check(_interp(_as_ptr(input), _as_ptr(output)))
+    return _check(_fn["interpolate"](_as_ptr(input), _as_ptr(output)))
 
 
 def iir_blur(input, alpha, output) -> int:
-    return _check(_iir(_as_ptr(input), float(alpha), _as_ptr(output)))
+    return _check(_fn["iir_blur"](_as_ptr(input), float(alpha), _as_ptr(output)))
 
 
 def resize_variant(input, scale_factor, interpolation="cubic", upsample=None) -> str:
@@ -570,7 +570,7 @@ def resize_variant(input, scale_factor, interpolation="cubic", upsample=None) ->
 
 def resize(input, scale_factor, output, interpolation="cubic", upsample=None) -> int:
     """apps/resize: planar [W,H,C] f32 / u8 / u16 -> the same type at the output's size; output x, y are absolute coordinates."""
-    fn = _resize[resize_variant(input, scale_factor, interpolation, upsample)]
+    fn = _fn[resize_variant(input, scale_factor, interpolation, upsample)]
     return _check(fn(_as_ptr(input), float(scale_factor), _as_ptr(output)))
 
 
@@ -583,18 +583,18 @@ def debug_resize_general(variant: str, input, scale_factor, output) -> int:
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:
-    return _check(_lens(_as_ptr(left_im), _as_ptr(right_im), int(slices), int(focus_depth), float(blur_radius_scale),
+    return _check(_fn["lens_blur"](_as_ptr(left_im), _as_ptr(right_im), int(slices), int(focus_depth), float(blur_radius_scale),
                         int(aperture_samples), _as_ptr(final)))
 
 
 def bgu(r_sigma, s_sigma, splat_loc, values, slice_loc, output) -> int:
     """apps/bgu: low-res f32 pair (splat_loc -> values) fitted per bilateral-grid cell, applied to the full-res slice_loc."""
-    return _check(_bgu(float(r_sigma), int(s_sigma), _as_ptr(splat_loc), _as_ptr(values), _as_ptr(slice_loc), _as_ptr(output)))
+    return _check(_fn["bgu"](float(r_sigma), int(s_sigma), _as_ptr(splat_loc), _as_ptr(values), _as_ptr(slice_loc), _as_ptr(output)))
 
 
 def camera_pipe(input, matrix_3200, matrix_7000, color_temp, gamma, contrast, sharpen_strength, black_level,
                 white_level, processed) -> int:
-    return _check(_cam(_as_ptr(input), _as_ptr(matrix_3200), _as_ptr(matrix_7000), float(color_temp), float(gamma),
+    return _check(_fn["camera_pipe"](_as_ptr(input), _as_ptr(matrix_3200), _as_ptr(matrix_7000), float(color_temp), float(gamma),
                        float(contrast), float(sharpen_strength), int(black_level), int(white_level),
                        _as_ptr(processed)))
 
@@ -654,12 +654,6 @@ def run_batch(name: str, frames, devices=None, streams_per_device: int = 1) -> i
 _batch_error: list = []
 _batch_active = [False]
 _batch_lock = threading.Lock()
-
-
-def metadata(name: str) -> halide_filter_metadata_t:
-    fn = getattr(lib, name + "_metadata")
-    fn.restype = C.POINTER(halide_filter_metadata_t)
-    return fn().contents
 
 
 def version() -> str:

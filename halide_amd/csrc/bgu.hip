@@ -326,23 +326,15 @@ __global__ __launch_bounds__(256) void bgu_slice_direct(const float *__restrict_
     for (int c = 0; c < 3; c++) op[c * q.o_sc] = clampf(dev::mad(m[4 * c + 2], s2, dev::mad2(m[4 * c], s0, m[4 * c + 1], s1)) + m[4 * c + 3], 0.0f, 1.0f);
 }
 
-const int64_t e0 = 0, e3 = 3, e192 = 192, e320 = 320, e1536 = 1536, e2560 = 2560;
-const int64_t *const est_lo[6] = {&e0, &e192, &e0, &e320, &e0, &e3};     // generator :676-687
-const int64_t *const est_hi[6] = {&e0, &e1536, &e0, &e2560, &e0, &e3};
-halide_scalar_value_t mk_i(int v) { halide_scalar_value_t s{}; s.u.i32 = v; return s; }
-halide_scalar_value_t mk_f(float v) { halide_scalar_value_t s{}; s.u.f32 = v; return s; }
-const halide_scalar_value_t est_r = mk_f(1.0f / 8.0f), est_s = mk_i(16);  // :674-675
-const halide_type_t ty_i32 = {(decltype(halide_type_t::code))0, 32, 0};
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
-const halide_filter_argument_t bgu_args[6] = {
-    {"r_sigma", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_r, nullptr},
-    {"s_sigma", halide_argument_kind_input_scalar, 0, ty_i32, nullptr, nullptr, nullptr, &est_s, nullptr},
-    {"splat_loc", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est_lo},
-    {"values", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est_lo},
-    {"slice_loc", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est_hi},
-    {"output", halide_argument_kind_output_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est_hi},
-};
-const halide_filter_metadata_t bgu_md = {1, 6, bgu_args, kTargetString, "bgu"};
+// estimates: generator :674-687
+const ArgTable bgu_table("bgu", {
+    scalar_f32("r_sigma").estimate(1.0 / 8.0),
+    scalar_i32("s_sigma").estimate(16),
+    in_buf("splat_loc", T_F32, 3, {0, 192, 0, 320, 0, 3}),
+    in_buf("values", T_F32, 3, {0, 192, 0, 320, 0, 3}),
+    in_buf("slice_loc", T_F32, 3, {0, 1536, 0, 2560, 0, 3}),
+    out_buf("output", T_F32, 3, {0, 1536, 0, 2560, 0, 3}),
+});
 
 int ceil_div_f(int a, int b) { return (int)ceilf((float)a / (float)b); }   // i32(ceil(f32(a) / b)), :275-278
 
@@ -351,8 +343,8 @@ int ceil_div_f(int a, int b) { return (int)ceilf((float)a / (float)b); }   // i3
 extern "C" int bgu(float r_sigma, int32_t s_sigma, halide_buffer_t *splat_loc, halide_buffer_t *values, halide_buffer_t *slice_loc,
                    halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[4] = {{"splat_loc", splat_loc, T_F32, 3, false}, {"values", values, T_F32, 3, false},
-                      {"slice_loc", slice_loc, T_F32, 3, false}, {"output", output, T_F32, 3, true}};
+    BufArg args[4];
+    bgu_table.bufs(args, {splat_loc, values, slice_loc, output});
     int r = check_not_null(uc, args, 4);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 4))) return r;
@@ -368,8 +360,7 @@ extern "C" int bgu(float r_sigma, int32_t s_sigma, halide_buffer_t *splat_loc, h
         answer_query(values, lmins, lext);
         return 0;
     }
-    for (int i = 0; i < 4; i++)
-        if ((r = check_shape(uc, args[i]))) return r;
+    if ((r = check_shapes(uc, args, 4))) return r;
     // the schedule bounds the output's channels to [0, 3) (:566, :648)
     if ((r = check_equal(uc, "output.min.2", output->dim[2].min, "0", 0)) || (r = check_equal(uc, "output.extent.2", output->dim[2].extent, "3", 3)))
         return r;
@@ -393,10 +384,7 @@ extern "C" int bgu(float r_sigma, int32_t s_sigma, halide_buffer_t *splat_loc, h
         }
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    for (int i = 0; i < 3; i++)
-        if ((r = input_to_device(uc, ctx, args[i]))) return r;
-    if ((r = output_on_device(uc, ctx, args[3]))) return r;
+    if ((r = to_device(uc, &ctx, args, 4))) return r;
     if (!work) {
         mark_output_written(output);
         return 0;
@@ -458,11 +446,4 @@ extern "C" int bgu(float r_sigma, int32_t s_sigma, halide_buffer_t *splat_loc, h
     return 0;
 }
 
-extern "C" int bgu_argv(void **a) {
-    return bgu(*(float *)a[0], *(int32_t *)a[1], (halide_buffer_t *)a[2], (halide_buffer_t *)a[3], (halide_buffer_t *)a[4], (halide_buffer_t *)a[5]);
-}
-extern "C" const halide_filter_metadata_t *bgu_metadata(void) { return &bgu_md; }
-extern "C" int bgu_auto_schedule(float r_sigma, int32_t s_sigma, halide_buffer_t *splat_loc, halide_buffer_t *values, halide_buffer_t *slice_loc,
-                                 halide_buffer_t *output) {
-    return bgu(r_sigma, s_sigma, splat_loc, values, slice_loc, output);
-}
+HLMI_ENTRY_AUTO(bgu, bgu_table.md)

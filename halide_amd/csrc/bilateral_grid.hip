@@ -413,23 +413,19 @@ __global__ __launch_bounds__(256) void bg_blur_slice(const float *__restrict__ i
     }
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560;
-const int64_t *const est[4] = {&e0, &ew, &e0, &eh};
-const halide_scalar_value_t est_rs = [] { halide_scalar_value_t v{}; v.u.f32 = 0.1f; return v; }();
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
 // estimates: generator :73-81
-const halide_filter_argument_t bg_args[3] = {
-    {"input", halide_argument_kind_input_buffer, 2, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-    {"r_sigma", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_rs, nullptr},
-    {"bilateral_grid", halide_argument_kind_output_buffer, 2, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-};
-const halide_filter_metadata_t bg_md = {1, 3, bg_args, kTargetString, "bilateral_grid"};
+const ArgTable bg_table("bilateral_grid", {
+    in_buf("input", T_F32, 2, {0, 1536, 0, 2560}),
+    scalar_f32("r_sigma").estimate(0.1),
+    out_buf("bilateral_grid", T_F32, 2, {0, 1536, 0, 2560}),
+});
 
 }  // namespace
 
 extern "C" int bilateral_grid(halide_buffer_t *input, float r_sigma, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_F32, 2, false}, {"bilateral_grid", output, T_F32, 2, true}};
+    BufArg args[2];
+    bg_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -440,7 +436,7 @@ extern "C" int bilateral_grid(halide_buffer_t *input, float r_sigma, halide_buff
         answer_query(output, mins, ext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     const int ow = output->dim[0].extent, oh = output->dim[1].extent;
     const int ox0 = output->dim[0].min, oy0 = output->dim[1].min;
     if ((r = check_covers(uc, args[0], 0, ox0, ow)) || (r = check_covers(uc, args[0], 1, oy0, oh))) return r;
@@ -456,9 +452,7 @@ extern "C" int bilateral_grid(halide_buffer_t *input, float r_sigma, halide_buff
     g.ZH = zmax + 1, g.ZD = zmax + 2;
 
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (ow == 0 || oh == 0) {
         mark_output_written(output);
         return 0;
@@ -541,10 +535,4 @@ extern "C" int bilateral_grid(halide_buffer_t *input, float r_sigma, halide_buff
     return 0;
 }
 
-extern "C" int bilateral_grid_argv(void **a) {
-    return bilateral_grid((halide_buffer_t *)a[0], *(float *)a[1], (halide_buffer_t *)a[2]);
-}
-extern "C" const halide_filter_metadata_t *bilateral_grid_metadata(void) { return &bg_md; }
-extern "C" int bilateral_grid_auto_schedule(halide_buffer_t *input, float r_sigma, halide_buffer_t *output) {
-    return bilateral_grid(input, r_sigma, output);
-}
+HLMI_ENTRY_AUTO(bilateral_grid, bg_table.md)

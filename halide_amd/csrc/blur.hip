@@ -55,21 +55,14 @@ __global__ __launch_bounds__(256) void blur3x3_u16(const uint16_t *__restrict__ 
     }
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560, ewi = 1538, ehi = 2562;
-const int64_t *const est_in[4] = {&e0, &ewi, &e0, &ehi};
-const int64_t *const est_out[4] = {&e0, &ew, &e0, &eh};
-const halide_type_t ty_u16 = {(decltype(halide_type_t::code))1, 16, 0};
-const halide_filter_argument_t blur_args[2] = {
-    {"input", halide_argument_kind_input_buffer, 2, ty_u16, nullptr, nullptr, nullptr, nullptr, est_in},
-    {"blur_y", halide_argument_kind_output_buffer, 2, ty_u16, nullptr, nullptr, nullptr, nullptr, est_out},
-};
-const halide_filter_metadata_t blur_md = {1, 2, blur_args, kTargetString, "halide_blur"};
+const ArgTable blur_table("halide_blur", {in_buf("input", T_U16, 2, {0, 1538, 0, 2562}), out_buf("blur_y", T_U16, 2, {0, 1536, 0, 2560})});
 
 }  // namespace
 
 extern "C" int halide_blur(halide_buffer_t *input, halide_buffer_t *blur_y) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_U16, 2, false}, {"blur_y", blur_y, T_U16, 2, true}};
+    BufArg args[2];
+    blur_table.bufs(args, {input, blur_y});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -81,15 +74,13 @@ extern "C" int halide_blur(halide_buffer_t *input, halide_buffer_t *blur_y) {
         answer_query(blur_y, omin, oext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     const int W = blur_y->dim[0].extent, H = blur_y->dim[1].extent;
     if ((r = check_covers(uc, args[0], 0, blur_y->dim[0].min, W + 2))) return r;
     if ((r = check_covers(uc, args[0], 1, blur_y->dim[1].min, H + 2))) return r;
 
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (W > 0 && H > 0) {
         const long in_sy = input->dim[1].stride, out_sy = blur_y->dim[1].stride;
         const uint16_t *din = dev_ptr<uint16_t>(input) + (long)(blur_y->dim[1].min - input->dim[1].min) * in_sy +
@@ -102,6 +93,4 @@ extern "C" int halide_blur(halide_buffer_t *input, halide_buffer_t *blur_y) {
     return 0;
 }
 
-extern "C" int halide_blur_argv(void **a) { return halide_blur((halide_buffer_t *)a[0], (halide_buffer_t *)a[1]); }
-extern "C" const halide_filter_metadata_t *halide_blur_metadata(void) { return &blur_md; }
-extern "C" int halide_blur_auto_schedule(halide_buffer_t *input, halide_buffer_t *blur_y) { return halide_blur(input, blur_y); }
+HLMI_ENTRY_AUTO(halide_blur, blur_table.md)

@@ -429,32 +429,19 @@ __global__ __launch_bounds__(256) void cp_sharpen4(const uint8_t *__restrict__ c
     }
 }
 
-const halide_type_t ty_u16 = {(decltype(halide_type_t::code))1, 16, 0};
-const halide_type_t ty_u8 = {(decltype(halide_type_t::code))1, 8, 0};
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
-const halide_type_t ty_i32 = {(decltype(halide_type_t::code))0, 32, 0};
-const int64_t e0 = 0, e2592 = 2592, e1968 = 1968, e4 = 4, e3 = 3;
-const int64_t *const est_in[4] = {&e0, &e2592, &e0, &e1968};
-const int64_t *const est_m[4] = {&e0, &e4, &e0, &e3};
-const int64_t *const est_out[6] = {&e0, &e2592, &e0, &e1968, &e0, &e3};
-halide_scalar_value_t fval(float f) { halide_scalar_value_t v{}; v.u.f32 = f; return v; }
-halide_scalar_value_t ival(int i) { halide_scalar_value_t v{}; v.u.i32 = i; return v; }
-const halide_scalar_value_t est_ct = fval(3700), est_gamma = fval(2.0f), est_contrast = fval(50), est_sharp = fval(1.0f),
-                            est_black = ival(25), est_white = ival(1023);
 // estimates: generator :430-439
-const halide_filter_argument_t cp_args[10] = {
-    {"input", halide_argument_kind_input_buffer, 2, ty_u16, nullptr, nullptr, nullptr, nullptr, est_in},
-    {"matrix_3200", halide_argument_kind_input_buffer, 2, ty_f32, nullptr, nullptr, nullptr, nullptr, est_m},
-    {"matrix_7000", halide_argument_kind_input_buffer, 2, ty_f32, nullptr, nullptr, nullptr, nullptr, est_m},
-    {"color_temp", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_ct, nullptr},
-    {"gamma", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_gamma, nullptr},
-    {"contrast", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_contrast, nullptr},
-    {"sharpen_strength", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_sharp, nullptr},
-    {"blackLevel", halide_argument_kind_input_scalar, 0, ty_i32, nullptr, nullptr, nullptr, &est_black, nullptr},
-    {"whiteLevel", halide_argument_kind_input_scalar, 0, ty_i32, nullptr, nullptr, nullptr, &est_white, nullptr},
-    {"processed", halide_argument_kind_output_buffer, 3, ty_u8, nullptr, nullptr, nullptr, nullptr, est_out},
-};
-const halide_filter_metadata_t cp_md = {1, 10, cp_args, kTargetString, "camera_pipe"};
+const ArgTable cp_table("camera_pipe", {
+    in_buf("input", T_U16, 2, {0, 2592, 0, 1968}),
+    in_buf("matrix_3200", T_F32, 2, {0, 4, 0, 3}),
+    in_buf("matrix_7000", T_F32, 2, {0, 4, 0, 3}),
+    scalar_f32("color_temp").estimate(3700),
+    scalar_f32("gamma").estimate(2),
+    scalar_f32("contrast").estimate(50),
+    scalar_f32("sharpen_strength").estimate(1),
+    scalar_i32("blackLevel").estimate(25),
+    scalar_i32("whiteLevel").estimate(1023),
+    out_buf("processed", T_U8, 3, {0, 2592, 0, 1968, 0, 3}),
+});
 
 // ---- cache of set-up blocks ---------------------------------------------------------------------------------------
 // cp_setup's output (matrix, curve, strength) is a function of the two matrix buffers' contents and six scalars; a video
@@ -477,8 +464,8 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
                            float gamma, float contrast, float sharpen_strength, int32_t blackLevel, int32_t whiteLevel,
                            halide_buffer_t *processed) {
     void *uc = nullptr;
-    BufArg args[4] = {{"input", input, T_U16, 2, false}, {"matrix_3200", matrix_3200, T_F32, 2, false},
-                      {"matrix_7000", matrix_7000, T_F32, 2, false}, {"processed", processed, T_U8, 3, true}};
+    BufArg args[4];
+    cp_table.bufs(args, {input, matrix_3200, matrix_7000, processed});
     int r = check_not_null(uc, args, 4);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 4))) return r;
@@ -496,8 +483,7 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
         answer_query(processed, omin, oext);
         return 0;
     }
-    for (int i = 0; i < 4; i++)
-        if ((r = check_shape(uc, args[i]))) return r;
+    if ((r = check_shapes(uc, args, 4))) return r;
     if ((r = check_equal(uc, "processed.min.2", processed->dim[2].min, "0", 0))) return r;          // bound(c, 0, 3), :454
     if ((r = check_equal(uc, "processed.extent.2", processed->dim[2].extent, "3", 3))) return r;
     if ((ox & 1) || (oy & 1)) {
@@ -511,10 +497,7 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
         if ((r = check_covers(uc, args[i], 0, 0, 4)) || (r = check_covers(uc, args[i], 1, 0, 3))) return r;
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    for (int i = 0; i < 3; i++)
-        if ((r = input_to_device(uc, ctx, args[i]))) return r;
-    if ((r = output_on_device(uc, ctx, args[3]))) return r;
+    if ((r = to_device(uc, &ctx, args, 4))) return r;
     if (W == 0 || H == 0) {
         mark_output_written(processed);
         return 0;
@@ -577,14 +560,4 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
     return 0;
 }
 
-extern "C" int camera_pipe_argv(void **a) {
-    return camera_pipe((halide_buffer_t *)a[0], (halide_buffer_t *)a[1], (halide_buffer_t *)a[2], *(float *)a[3], *(float *)a[4],
-                       *(float *)a[5], *(float *)a[6], *(int32_t *)a[7], *(int32_t *)a[8], (halide_buffer_t *)a[9]);
-}
-extern "C" const halide_filter_metadata_t *camera_pipe_metadata(void) { return &cp_md; }
-extern "C" int camera_pipe_auto_schedule(halide_buffer_t *input, halide_buffer_t *matrix_3200, halide_buffer_t *matrix_7000,
-                                         float color_temp, float gamma, float contrast, float sharpen_strength,
-                                         int32_t blackLevel, int32_t whiteLevel, halide_buffer_t *processed) {
-    return camera_pipe(input, matrix_3200, matrix_7000, color_temp, gamma, contrast, sharpen_strength, blackLevel, whiteLevel,
-                       processed);
-}
+HLMI_ENTRY_AUTO(camera_pipe, cp_table.md)

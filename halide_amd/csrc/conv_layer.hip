@@ -130,23 +130,16 @@ __global__ __launch_bounds__(256) void conv3x3_f32_mfma(const float *__restrict_
         }
 }
 
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
-const int64_t e0 = 0, e128 = 128, e3 = 3, e102 = 102, e82 = 82, e100 = 100, e80 = 80, e5 = 5;
-const int64_t *const est_in[8] = {&e0, &e128, &e0, &e102, &e0, &e82, &e0, &e5};
-const int64_t *const est_f[8] = {&e0, &e128, &e0, &e3, &e0, &e3, &e0, &e128};
-const int64_t *const est_b[2] = {&e0, &e128};
-const int64_t *const est_o[8] = {&e0, &e128, &e0, &e100, &e0, &e80, &e0, &e5};
-const halide_filter_argument_t conv_args[4] = {
-    {"input", halide_argument_kind_input_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_in},
-    {"filter", halide_argument_kind_input_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_f},
-    {"bias", halide_argument_kind_input_buffer, 1, ty_f32, nullptr, nullptr, nullptr, nullptr, est_b},
-    {"relu", halide_argument_kind_output_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_o},
-};
-const halide_filter_metadata_t conv_md = {1, 4, conv_args, kTargetString, "conv_layer"};
+const ArgTable conv_table = conv_arg_table("conv_layer", 100, 80, 5);   // estimates: generator :35-50
 
 }  // namespace
 
 namespace hlmi {
+
+ArgTable conv_arg_table(const char *name, int w, int h, int n) {
+    return {name, {in_buf("input", T_F32, 4, {0, 128, 0, w + 2, 0, h + 2, 0, n}), in_buf("filter", T_F32, 4, {0, 128, 0, 3, 0, 3, 0, 128}),
+                   in_buf("bias", T_F32, 1, {0, 128}), out_buf("relu", T_F32, 4, {0, 128, 0, w, 0, h, 0, n})}};
+}
 
 // Shared by conv_layer and conv_layer_bf16: argument protocol + the dense-layout constraints of the generator
 // (:35-50) generalised to runtime N, W, H, CI, CO.  Returns 0 and fills the extents, or an error code; *query is
@@ -176,8 +169,7 @@ int conv_check_args(void *uc, BufArg *args, int *CI, int *CO, int *W, int *H, in
         *query = true;
         return 0;
     }
-    for (int i = 0; i < 4; i++)
-        if ((r = check_shape(uc, args[i]))) return r;
+    if ((r = check_shapes(uc, args, 4))) return r;
     const int co = relu->dim[0].extent, w = relu->dim[1].extent, h = relu->dim[2].extent, n = relu->dim[3].extent;
     const int ci = input->dim[0].extent;
     char what[64];
@@ -212,17 +204,14 @@ int conv_check_args(void *uc, BufArg *args, int *CI, int *CO, int *W, int *H, in
 
 extern "C" int conv_layer(halide_buffer_t *input, halide_buffer_t *filter, halide_buffer_t *bias, halide_buffer_t *relu) {
     void *uc = nullptr;
-    BufArg args[4] = {{"input", input, T_F32, 4, false}, {"filter", filter, T_F32, 4, false}, {"bias", bias, T_F32, 1, false},
-                      {"relu", relu, T_F32, 4, true}};
+    BufArg args[4];
+    conv_table.bufs(args, {input, filter, bias, relu});
     CGeom g;
     bool query;
     int r = conv_check_args(uc, args, &g.CI, &g.CO, &g.W, &g.H, &g.N, &query);
     if (r || query) return r;
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    for (int i = 0; i < 3; i++)
-        if ((r = input_to_device(uc, ctx, args[i]))) return r;
-    if ((r = output_on_device(uc, ctx, args[3]))) return r;
+    if ((r = to_device(uc, &ctx, args, 4))) return r;
     g.npix = (long)g.W * g.H * g.N;
     if (g.npix > 0) {
         dim3 grid((unsigned)((g.npix + TP - 1) / TP), g.CO / TC);
@@ -233,11 +222,4 @@ extern "C" int conv_layer(halide_buffer_t *input, halide_buffer_t *filter, halid
     return 0;
 }
 
-extern "C" int conv_layer_argv(void **a) {
-    return conv_layer((halide_buffer_t *)a[0], (halide_buffer_t *)a[1], (halide_buffer_t *)a[2], (halide_buffer_t *)a[3]);
-}
-extern "C" const halide_filter_metadata_t *conv_layer_metadata(void) { return &conv_md; }
-extern "C" int conv_layer_auto_schedule(halide_buffer_t *input, halide_buffer_t *filter, halide_buffer_t *bias,
-                                        halide_buffer_t *relu) {
-    return conv_layer(input, filter, bias, relu);
-}
+HLMI_ENTRY_AUTO(conv_layer, conv_table.md)

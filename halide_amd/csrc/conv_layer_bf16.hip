@@ -550,20 +550,7 @@ __global__ __launch_bounds__(512) void conv3x3_bf16_p(const float *__restrict__ 
 // Bit-identical (15 tests), 0.0275-0.0279 against 0.0261-0.0262 ms per call: taking the staging out of the MFMA waves' instruction
 // streams does not put the matrix pipe under it either.
 
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
-// estimates: BASELINE.json configs[4] (N=16, 56x56 output, 128 -> 128 channels)
-const int64_t e0 = 0, e128 = 128, e3 = 3, e58 = 58, e56 = 56, e16 = 16;
-const int64_t *const est_in[8] = {&e0, &e128, &e0, &e58, &e0, &e58, &e0, &e16};
-const int64_t *const est_f[8] = {&e0, &e128, &e0, &e3, &e0, &e3, &e0, &e128};
-const int64_t *const est_b[2] = {&e0, &e128};
-const int64_t *const est_o[8] = {&e0, &e128, &e0, &e56, &e0, &e56, &e0, &e16};
-const halide_filter_argument_t conv_args[4] = {
-    {"input", halide_argument_kind_input_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_in},
-    {"filter", halide_argument_kind_input_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_f},
-    {"bias", halide_argument_kind_input_buffer, 1, ty_f32, nullptr, nullptr, nullptr, nullptr, est_b},
-    {"relu", halide_argument_kind_output_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_o},
-};
-const halide_filter_metadata_t conv_md = {1, 4, conv_args, kTargetString, "conv_layer_bf16"};
+const ArgTable conv_table = conv_arg_table("conv_layer_bf16", 56, 56, 16);   // estimates: BASELINE.json configs[4] (N=16, 56x56 output)
 
 // ---- cache of re-ordered filters: one entry per (device, filter allocation, version, layout) in the runtime's cache of
 // derived device data (hlmi_internal.h), read by the main kernel of every call that hits it.  Filters in memory the runtime
@@ -580,8 +567,8 @@ DerivedCache g_filters(8);
 
 extern "C" int conv_layer_bf16(halide_buffer_t *input, halide_buffer_t *filter, halide_buffer_t *bias, halide_buffer_t *relu) {
     void *uc = nullptr;
-    BufArg args[4] = {{"input", input, T_F32, 4, false}, {"filter", filter, T_F32, 4, false}, {"bias", bias, T_F32, 1, false},
-                      {"relu", relu, T_F32, 4, true}};
+    BufArg args[4];
+    conv_table.bufs(args, {input, filter, bias, relu});
     CGeom g;
     bool query;
     int r = conv_check_args(uc, args, &g.CI, &g.CO, &g.W, &g.H, &g.N, &query);
@@ -591,10 +578,7 @@ extern "C" int conv_layer_bf16(halide_buffer_t *input, halide_buffer_t *filter, 
                       "Constraint violated: conv_layer_bf16 needs input channels (%d) to be a multiple of %d", g.CI, KC);
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    for (int i = 0; i < 3; i++)
-        if ((r = input_to_device(uc, ctx, args[i]))) return r;
-    if ((r = output_on_device(uc, ctx, args[3]))) return r;
+    if ((r = to_device(uc, &ctx, args, 4))) return r;
     g.npix = (long)g.W * g.H * g.N;
     if (g.npix > 0) {
         const size_t wb_bytes = (size_t)9 * g.CO * g.CI * sizeof(uint16_t);
@@ -677,7 +661,4 @@ extern "C" int conv_layer_bf16(halide_buffer_t *input, halide_buffer_t *filter, 
     return 0;
 }
 
-extern "C" int conv_layer_bf16_argv(void **a) {
-    return conv_layer_bf16((halide_buffer_t *)a[0], (halide_buffer_t *)a[1], (halide_buffer_t *)a[2], (halide_buffer_t *)a[3]);
-}
-extern "C" const halide_filter_metadata_t *conv_layer_bf16_metadata(void) { return &conv_md; }
+HLMI_ENTRY(conv_layer_bf16, conv_table.md)

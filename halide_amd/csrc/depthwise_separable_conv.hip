@@ -260,31 +260,22 @@ __global__ __launch_bounds__(256) void dsc_fused_t(const float *__restrict__ in,
     }
 }
 
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
 // estimates: generator :78-99 (N=4, CI=32, CO=16, CM=1, 112x112; depthwise_filter.dim(0) estimate is CI/CO as written)
-const int64_t e0 = 0, e32 = 32, e112 = 112, e4 = 4, e2 = 2, e3 = 3, e16 = 16;
-const int64_t *const est_in[8] = {&e0, &e32, &e0, &e112, &e0, &e112, &e0, &e4};
-const int64_t *const est_dw[8] = {&e0, &e2, &e0, &e32, &e0, &e3, &e0, &e3};
-const int64_t *const est_pw[4] = {&e0, &e16, &e0, &e32};
-const int64_t *const est_b[2] = {&e0, &e16};
-const int64_t *const est_o[8] = {&e0, &e16, &e0, &e112, &e0, &e112, &e0, &e4};
-const halide_filter_argument_t dsc_args[5] = {
-    {"input", halide_argument_kind_input_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_in},
-    {"depthwise_filter", halide_argument_kind_input_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_dw},
-    {"pointwise_filter", halide_argument_kind_input_buffer, 2, ty_f32, nullptr, nullptr, nullptr, nullptr, est_pw},
-    {"bias", halide_argument_kind_input_buffer, 1, ty_f32, nullptr, nullptr, nullptr, nullptr, est_b},
-    {"output", halide_argument_kind_output_buffer, 4, ty_f32, nullptr, nullptr, nullptr, nullptr, est_o},
-};
-const halide_filter_metadata_t dsc_md = {1, 5, dsc_args, kTargetString, "depthwise_separable_conv"};
+const ArgTable dsc_table("depthwise_separable_conv", {
+    in_buf("input", T_F32, 4, {0, 32, 0, 112, 0, 112, 0, 4}),
+    in_buf("depthwise_filter", T_F32, 4, {0, 2, 0, 32, 0, 3, 0, 3}),
+    in_buf("pointwise_filter", T_F32, 2, {0, 16, 0, 32}),
+    in_buf("bias", T_F32, 1, {0, 16}),
+    out_buf("output", T_F32, 4, {0, 16, 0, 112, 0, 112, 0, 4}),
+});
 
 }  // namespace
 
 extern "C" int depthwise_separable_conv(halide_buffer_t *input, halide_buffer_t *depthwise_filter,
                                         halide_buffer_t *pointwise_filter, halide_buffer_t *bias, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[5] = {{"input", input, T_F32, 4, false}, {"depthwise_filter", depthwise_filter, T_F32, 4, false},
-                      {"pointwise_filter", pointwise_filter, T_F32, 2, false}, {"bias", bias, T_F32, 1, false},
-                      {"output", output, T_F32, 4, true}};
+    BufArg args[5];
+    dsc_table.bufs(args, {input, depthwise_filter, pointwise_filter, bias, output});
     int r = check_not_null(uc, args, 5);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 5))) return r;
@@ -312,8 +303,7 @@ extern "C" int depthwise_separable_conv(halide_buffer_t *input, halide_buffer_t 
         answer_query(output, z4, eo);
         return 0;
     }
-    for (int i = 0; i < 5; i++)
-        if ((r = check_shape(uc, args[i]))) return r;
+    if ((r = check_shapes(uc, args, 5))) return r;
     DGeom g;
     g.CI = input->dim[0].extent, g.W = input->dim[1].extent, g.H = input->dim[2].extent, g.N = output->dim[3].extent;
     g.CM = depthwise_filter->dim[0].extent, g.FW = depthwise_filter->dim[2].extent, g.FH = depthwise_filter->dim[3].extent;
@@ -334,10 +324,7 @@ extern "C" int depthwise_separable_conv(halide_buffer_t *input, halide_buffer_t 
         return report(uc, halide_error_code_constraint_violated, "depthwise_filter extents must be >= 1");
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    for (int i = 0; i < 4; i++)
-        if ((r = input_to_device(uc, ctx, args[i]))) return r;
-    if ((r = output_on_device(uc, ctx, args[4]))) return r;
+    if ((r = to_device(uc, &ctx, args, 5))) return r;
     g.ow = output->dim[1].extent, g.oh = output->dim[2].extent;
     if (g.ow > 0 && g.oh > 0 && g.N > 0 && g.CO > 0) {
         // in-bounds test of the generator (:36-37): 0 <= x < input.dim(1).extent(), i.e. W counts from the input's min
@@ -386,13 +373,4 @@ extern "C" int depthwise_separable_conv(halide_buffer_t *input, halide_buffer_t 
     return 0;
 }
 
-extern "C" int depthwise_separable_conv_argv(void **a) {
-    return depthwise_separable_conv((halide_buffer_t *)a[0], (halide_buffer_t *)a[1], (halide_buffer_t *)a[2],
-                                    (halide_buffer_t *)a[3], (halide_buffer_t *)a[4]);
-}
-extern "C" const halide_filter_metadata_t *depthwise_separable_conv_metadata(void) { return &dsc_md; }
-extern "C" int depthwise_separable_conv_auto_schedule(halide_buffer_t *input, halide_buffer_t *depthwise_filter,
-                                                      halide_buffer_t *pointwise_filter, halide_buffer_t *bias,
-                                                      halide_buffer_t *output) {
-    return depthwise_separable_conv(input, depthwise_filter, pointwise_filter, bias, output);
-}
+HLMI_ENTRY_AUTO(depthwise_separable_conv, dsc_table.md)

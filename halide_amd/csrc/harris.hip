@@ -93,22 +93,15 @@ __global__ __launch_bounds__(256) void harris_tile(const float *__restrict__ in,
     }
 }
 
-const int64_t e0 = 0, e3 = 3, ew = 1536, eh = 2560, ew6 = 1530, eh6 = 2554, ec = 3;
-const int64_t *const est_in[6] = {&e0, &ew, &e0, &eh, &e0, &ec};
-const int64_t *const est_out[4] = {&e3, &ew6, &e3, &eh6};
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
 // estimates: generator :64-72
-const halide_filter_argument_t r_args[2] = {
-    {"input", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est_in},
-    {"output", halide_argument_kind_output_buffer, 2, ty_f32, nullptr, nullptr, nullptr, nullptr, est_out},
-};
-const halide_filter_metadata_t r_md = {1, 2, r_args, kTargetString, "harris"};
+const ArgTable r_table("harris", {in_buf("input", T_F32, 3, {0, 1536, 0, 2560, 0, 3}), out_buf("output", T_F32, 2, {3, 1530, 3, 2554})});
 
 }  // namespace
 
 extern "C" int harris(halide_buffer_t *input, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_F32, 3, false}, {"output", output, T_F32, 2, true}};
+    BufArg args[2];
+    r_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -120,15 +113,13 @@ extern "C" int harris(halide_buffer_t *input, halide_buffer_t *output) {
         answer_query(output, omins, oext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     if (ow > 0 && oh > 0) {
         if ((r = check_covers(uc, args[0], 0, output->dim[0].min - 2, ow + 4)) || (r = check_covers(uc, args[0], 1, output->dim[1].min - 2, oh + 4)) ||
             (r = check_covers(uc, args[0], 2, 0, 3))) return r;
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (ow > 0 && oh > 0) {
         RGeom g;
         g.ix0 = input->dim[0].min, g.iy0 = input->dim[1].min, g.ox0 = output->dim[0].min, g.oy0 = output->dim[1].min;
@@ -142,6 +133,4 @@ extern "C" int harris(halide_buffer_t *input, halide_buffer_t *output) {
     return 0;
 }
 
-extern "C" int harris_argv(void **a) { return harris((halide_buffer_t *)a[0], (halide_buffer_t *)a[1]); }
-extern "C" const halide_filter_metadata_t *harris_metadata(void) { return &r_md; }
-extern "C" int harris_auto_schedule(halide_buffer_t *input, halide_buffer_t *output) { return harris(input, output); }
+HLMI_ENTRY_AUTO(harris, r_table.md)

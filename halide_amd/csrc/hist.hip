@@ -146,21 +146,15 @@ __global__ __launch_bounds__(256) void hist_apply(const uint8_t *__restrict__ in
     }
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560, ec = 3;
-const int64_t *const est[6] = {&e0, &ew, &e0, &eh, &e0, &ec};
-const halide_type_t ty_u8 = {(decltype(halide_type_t::code))1, 8, 0};
 // estimates: generator :58-65
-const halide_filter_argument_t h_args[2] = {
-    {"input", halide_argument_kind_input_buffer, 3, ty_u8, nullptr, nullptr, nullptr, nullptr, est},
-    {"output", halide_argument_kind_output_buffer, 3, ty_u8, nullptr, nullptr, nullptr, nullptr, est},
-};
-const halide_filter_metadata_t h_md = {1, 2, h_args, kTargetString, "hist"};
+const ArgTable h_table("hist", {in_buf("input", T_U8, 3, {0, 1536, 0, 2560, 0, 3}), out_buf("output", T_U8, 3, {0, 1536, 0, 2560, 0, 3})});
 
 }  // namespace
 
 extern "C" int hist(halide_buffer_t *input, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_U8, 3, false}, {"output", output, T_U8, 3, true}};
+    BufArg args[2];
+    h_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -172,7 +166,7 @@ extern "C" int hist(halide_buffer_t *input, halide_buffer_t *output) {
         answer_query(output, omins, oext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     const int W = input->dim[0].extent, H = input->dim[1].extent;
     const int ow = output->dim[0].extent, oh = output->dim[1].extent, oc = output->dim[2].extent;
     // the histogram's RDom starts at 0 (:31, :36) and reads channels 0..2
@@ -184,9 +178,7 @@ extern "C" int hist(halide_buffer_t *input, halide_buffer_t *output) {
         return report(uc, halide_error_code_constraint_violated, "Output buffer output: the three channels [0, 3) are produced together");
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (ow > 0 && oh > 0 && oc > 0) {
         void *ws = nullptr;
         if ((r = get_workspace(uc, ctx, HSUB * 256 * sizeof(int), &ws))) return r;
@@ -216,6 +208,4 @@ extern "C" int hist(halide_buffer_t *input, halide_buffer_t *output) {
     return 0;
 }
 
-extern "C" int hist_argv(void **a) { return hist((halide_buffer_t *)a[0], (halide_buffer_t *)a[1]); }
-extern "C" const halide_filter_metadata_t *hist_metadata(void) { return &h_md; }
-extern "C" int hist_auto_schedule(halide_buffer_t *input, halide_buffer_t *output) { return hist(input, output); }
+HLMI_ENTRY_AUTO(hist, h_table.md)

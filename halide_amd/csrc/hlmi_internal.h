@@ -4,12 +4,15 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 #include <type_traits>
+#include <utility>
 
 #include "hlmi_pipelines.h"
 #include "hlmi_runtime.h"
@@ -40,6 +43,9 @@ inline uint32_t buf_type_abi(const halide_buffer_t *b) {
 }
 const char *type_name(uint32_t abi, char tmp[16]);
 
+// internal helpers that need no entry in the dynamic symbol table: the C ABI is what the library exports
+#define HLMI_LOCAL __attribute__((visibility("hidden")))
+
 struct BufArg {
     const char *name;
     halide_buffer_t *buf;
@@ -47,6 +53,100 @@ struct BufArg {
     int dims;       // required dimensionality
     bool is_output;
 };
+
+// ---------------------------------------------------------------------------------------------
+// The argument table: the ONE place an entry point describes its arguments, one line each, in signature order.  The metadata
+// RunGen reads (layout: src/runtime/HalideRuntime.h:1937-1975; contents as emitted by src/CodeGen_C.cpp:760-912), the BufArg
+// array of the checks below, lens_blur's scalar ranges and the Python caller's argtypes all come from it.
+struct Arg {
+    const char *name;
+    int32_t kind;       // halide_argument_kind_*
+    uint32_t type;      // type_abi
+    int32_t dims;       // 0 for scalars
+    int n_est;          // buffers: 2 * dims (min, extent) estimates given, or 0
+    int64_t est[8];
+    unsigned has;       // scalars: bit DEF / MIN / MAX / EST set = sv[that] given
+    halide_scalar_value_t sv[4];
+    enum { DEF, MIN, MAX, EST };
+    Arg &set(int which, double v) {   // stored as the argument's own type (every scalar here is an int32 or a float)
+        has |= 1u << which;
+        if (type == T_F32) sv[which].u.f32 = (float)v;
+        else sv[which].u.i32 = (int32_t)v;
+        return *this;
+    }
+    double get(int which) const { return type == T_F32 ? (double)sv[which].u.f32 : (double)sv[which].u.i32; }
+    Arg &def(double v) { return set(DEF, v); }
+    Arg &range(double lo, double hi) { return set(MIN, lo).set(MAX, hi); }
+    Arg &estimate(double v) { return set(EST, v); }
+};
+// `est`: {min0, extent0, min1, extent1, ...} of the generator's set_estimates, or nothing where it declares none (ArgTable's
+// constructor refuses a line whose count is neither 0 nor 2 * dims)
+inline Arg make_arg(const char *name, int32_t kind, uint32_t type, int dims, std::initializer_list<int64_t> est = {}) {
+    Arg a = {name, kind, type, dims, (int)est.size(), {}, 0, {}};
+    std::copy_n(est.begin(), std::min<size_t>(est.size(), 8), a.est);
+    return a;
+}
+inline Arg in_buf(const char *name, uint32_t type, int dims, std::initializer_list<int64_t> est = {}) {
+    return make_arg(name, halide_argument_kind_input_buffer, type, dims, est);
+}
+inline Arg out_buf(const char *name, uint32_t type, int dims, std::initializer_list<int64_t> est = {}) {
+    return make_arg(name, halide_argument_kind_output_buffer, type, dims, est);
+}
+inline Arg scalar_f32(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_F32, 0); }
+inline Arg scalar_i32(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_I32, 0); }
+
+// One entry point's table and everything RunGen's structs point into, built once from the table and never per call.  Initialised
+// dynamically (the pointers lead into the object itself), which no consumer can observe: tests/cpp/rungen_registration.cpp calls
+// <name>_metadata() from a static initialiser of the EXECUTABLE, which runs after those of the library it links, and hlmi_rungen
+// comes in through dlopen, which returns after them.
+constexpr int MAX_ARGS = 10;
+struct HLMI_LOCAL ArgTable {
+    int n = 0;
+    Arg spec[MAX_ARGS];
+    halide_filter_argument_t args[MAX_ARGS];
+    const int64_t *est_ptrs[MAX_ARGS][8];
+    halide_filter_metadata_t md;   // version 1, kTargetString, `name`
+    ArgTable(const char *name, std::initializer_list<Arg> table);
+    ArgTable(const ArgTable &) = delete;   // (nor moved: args and md point into *this)
+    // the same arguments under another entry point's name (the resize variants of one element type)
+    halide_filter_metadata_t named(const char *name) const { return {md.version, md.num_arguments, md.arguments, md.target, name}; }
+    // the table's buffer arguments, in table order, bound to the pointers the entry point received
+    template<int N>
+    void bufs(BufArg (&out)[N], halide_buffer_t *const (&ptrs)[N]) const {
+        for (int i = 0, k = 0; i < n && k < N; i++) {
+            const Arg &a = spec[i];
+            if (a.kind != halide_argument_kind_input_scalar) out[k] = {a.name, ptrs[k], a.type, a.dims, a.kind == halide_argument_kind_output_buffer}, k++;
+        }
+    }
+};
+
+// <name>_argv from the signature of <name>: a pointer parameter takes a[i], any other parameter type P takes *(P *)a[i]
+// (src/CodeGen_C.cpp:688-694), so the casts cannot disagree with the signature.
+template<typename... P, size_t... I>
+int argv_call(int (*fn)(P...), void **a, std::index_sequence<I...>) {
+    auto arg = [](auto *tag, void *p) {
+        using T = std::remove_pointer_t<decltype(tag)>;
+        if constexpr (std::is_pointer<T>::value) return (T)p;
+        else return *(T *)p;
+    };
+    return fn(arg((P *)nullptr, a[I])...);
+}
+template<typename... P>
+int argv_call(int (*fn)(P...), void **a) { return argv_call(fn, a, std::index_sequence_for<P...>{}); }
+
+// The exported companions of entry point `name`: <name>_argv and <name>_metadata (`md`: a halide_filter_metadata_t, usually
+// table.md), and with HLMI_ENTRY_AUTO also <name>_auto_schedule, a second name for the same function (the reference's drivers
+// link both objects; an alias needs its target defined, which it is in the host pass only).
+#define HLMI_ENTRY(name, md)                                                       \
+    extern "C" int name##_argv(void **a) { return ::hlmi::argv_call(name, a); }    \
+    extern "C" const halide_filter_metadata_t *name##_metadata(void) { return &(md); }
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HLMI_ENTRY_AUTO(name, md) HLMI_ENTRY(name, md)
+#else
+#define HLMI_ENTRY_AUTO(name, md) \
+    HLMI_ENTRY(name, md)          \
+    extern "C" __typeof__(name) name##_auto_schedule __attribute__((alias(#name)));
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // The entry prologue.  The reference emits its argument checks in a fixed order (src/AddImageChecks.cpp:716-760,
@@ -64,6 +164,8 @@ struct BufArg {
 // not reported on the spot but RECORDED with their (phase, buffer rank, dimension, kind) key, and the one the
 // reference would have hit first is reported by checks_done() — which acquire_device() calls, so no kernel is ever
 // enqueued with unchecked arguments.  tests/test_entry_protocol.py pins the codes and the order.
+// An entry point fills its BufArg array from its table (ArgTable::bufs), runs the checks in its own order — check_shapes and
+// check_scalar_ranges are the loops several of them share — and ends the prologue with to_device().
 // step 0; also (re)starts the recording for this call and ranks the buffers by name
 int check_not_null(void *uc, const BufArg *args, int n);
 // step 2 (src/AddImageChecks.cpp:315-318, HalideRuntime.h:1851-1853)
@@ -76,6 +178,10 @@ int check_type_and_dims(void *uc, const BufArg *args, int n);
 // steps 4-6 for one buffer: dim[0].stride == 1 (src/Parameter.cpp:30-35), extents >= 0, sizes < 2^31.  Always
 // returns 0 (recorded).
 int check_shape(void *uc, const BufArg &a);
+HLMI_LOCAL int check_shapes(void *uc, const BufArg *args, int n);   // every buffer, in array order
+// step 1: the min / max the table's scalar lines declare, if any; `values` are the scalars the entry point received, in table
+// order like ArgTable::bufs' pointers
+HLMI_LOCAL int check_scalar_ranges(void *uc, const ArgTable &t, std::initializer_list<double> values);
 // step 5: [min, min+extent) of dimension d must cover [req_min, req_min+req_extent)
 // (src/AddImageChecks.cpp:393-418 -> halide_error_access_out_of_bounds).  Always returns 0 (recorded).
 int check_covers(void *uc, const BufArg &a, int d, int req_min, int req_extent);
@@ -113,6 +219,8 @@ int get_workspace(void *uc, const DeviceCtx &ctx, size_t bytes, void **ptr);
 // dirty-flag protocol for pipeline arguments (src/InjectHostDevBufferCopies.cpp:197-217,285-304)
 int input_to_device(void *uc, const DeviceCtx &ctx, const BufArg &a);
 int output_on_device(void *uc, const DeviceCtx &ctx, const BufArg &a);
+// acquire_device, then input_to_device for every input and output_on_device for every output, each in array order
+HLMI_LOCAL int to_device(void *uc, DeviceCtx *ctx, const BufArg *args, int n);
 void mark_output_written(halide_buffer_t *buf);  // device_dirty = 1, host_dirty = 0
 // A number that changes whenever the device contents of `buf` may have changed through this runtime (upload of a
 // host-dirty buffer, use as a pipeline output or copy target, re-allocation); unique across allocations, so
@@ -256,11 +364,11 @@ int with_flags(F &&f, bool b, Bs... rest) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// metadata helper: every pipeline defines a static halide_filter_metadata_t
-// (layout: src/runtime/HalideRuntime.h:1937-1975; contents as emitted by src/CodeGen_C.cpp:760-912)
 extern const char *const kTargetString;  // "x86-64-linux-hip-gfx950" (canonical-style target string)
 
-// conv_layer.hip: argument protocol shared by conv_layer and conv_layer_bf16
+// conv_layer.hip: argument table and protocol shared by conv_layer and conv_layer_bf16; the table's estimates are those of an
+// N x W x H output with 128 -> 128 channels
+HLMI_LOCAL ArgTable conv_arg_table(const char *name, int w, int h, int n);
 int conv_check_args(void *uc, BufArg *args, int *CI, int *CO, int *W, int *H, int *N, bool *query);
 
 // resize.hip: the named resize variant ("resize_cubic_uint8_down", ...) on its general two-launch path whatever the sizes, for the

@@ -386,17 +386,12 @@ __global__ __launch_bounds__(64 * (1 + NHELP)) void iir_cols_T(const float *__re
     pass(std::true_type{});
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560, ec = 3;
-const int64_t *const est[6] = {&e0, &ew, &e0, &eh, &e0, &ec};
-const halide_scalar_value_t est_alpha = [] { halide_scalar_value_t v{}; v.u.f32 = 0.1f; return v; }();
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
 // estimates: generator :166-173
-const halide_filter_argument_t ib_args[3] = {
-    {"input", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-    {"alpha", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_alpha, nullptr},
-    {"output", halide_argument_kind_output_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-};
-const halide_filter_metadata_t ib_md = {1, 3, ib_args, kTargetString, "iir_blur"};
+const ArgTable ib_table("iir_blur", {
+    in_buf("input", T_F32, 3, {0, 1536, 0, 2560, 0, 3}),
+    scalar_f32("alpha").estimate(0.1),
+    out_buf("output", T_F32, 3, {0, 1536, 0, 2560, 0, 3}),
+});
 
 }  // namespace
 
@@ -415,7 +410,8 @@ extern "C" int hlmi_debug_iir_probe(unsigned long long *out32) {   // 32 counter
 
 extern "C" int iir_blur(halide_buffer_t *input, float alpha, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_F32, 3, false}, {"output", output, T_F32, 3, true}};
+    BufArg args[2];
+    ib_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -430,7 +426,7 @@ extern "C" int iir_blur(halide_buffer_t *input, float alpha, halide_buffer_t *ou
         answer_query(output, z, e);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     const int W = input->dim[0].extent, H = input->dim[1].extent, C = input->dim[2].extent;
     char what[48];
     for (int d = 0; d < 3; d++) {   // every scan starts at coordinate 0 and spans the input; output = the same box
@@ -442,9 +438,7 @@ extern "C" int iir_blur(halide_buffer_t *input, float alpha, halide_buffer_t *ou
         if ((r = check_equal(uc, what, output->dim[d].extent, "input.extent", input->dim[d].extent))) return r;
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (W > 0 && H > 0 && C > 0) {
         const size_t plane = ((size_t)W * H + 63) & ~(size_t)63;
         void *ws = nullptr;
@@ -466,6 +460,4 @@ extern "C" int iir_blur(halide_buffer_t *input, float alpha, halide_buffer_t *ou
     return 0;
 }
 
-extern "C" int iir_blur_argv(void **a) { return iir_blur((halide_buffer_t *)a[0], *(float *)a[1], (halide_buffer_t *)a[2]); }
-extern "C" const halide_filter_metadata_t *iir_blur_metadata(void) { return &ib_md; }
-extern "C" int iir_blur_auto_schedule(halide_buffer_t *input, float alpha, halide_buffer_t *output) { return iir_blur(input, alpha, output); }
+HLMI_ENTRY_AUTO(iir_blur, ib_table.md)

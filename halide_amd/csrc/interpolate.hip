@@ -326,16 +326,8 @@ __global__ __launch_bounds__(256) void ip_final(InGeom g, Lvl d1, Lvl d2, Lvl up
     }
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560, e4 = 4, e3 = 3;
-const int64_t *const est_in[6] = {&e0, &ew, &e0, &eh, &e0, &e4};
-const int64_t *const est_out[6] = {&e0, &ew, &e0, &eh, &e0, &e3};
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
 // estimates: generator :204-211
-const halide_filter_argument_t ip_args[2] = {
-    {"input", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est_in},
-    {"output", halide_argument_kind_output_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est_out},
-};
-const halide_filter_metadata_t ip_md = {1, 2, ip_args, kTargetString, "interpolate"};
+const ArgTable ip_table("interpolate", {in_buf("input", T_F32, 3, {0, 1536, 0, 2560, 0, 4}), out_buf("output", T_F32, 3, {0, 1536, 0, 2560, 0, 3})});
 
 struct Box {
     int x0, x1, y0, y1;
@@ -345,7 +337,8 @@ struct Box {
 
 extern "C" int interpolate(halide_buffer_t *input, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_F32, 3, false}, {"output", output, T_F32, 3, true}};
+    BufArg args[2];
+    ip_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -362,7 +355,7 @@ extern "C" int interpolate(halide_buffer_t *input, halide_buffer_t *output) {
         answer_query(output, z, eo);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     const int W = input->dim[0].extent, H = input->dim[1].extent;
     // input.dim(2).set_bounds(0, 4) (:23); normalize.bound(x, 0, input.width()) etc. (:83-87)
     if ((r = check_equal(uc, "input.min.2", input->dim[2].min, "0", 0)) || (r = check_equal(uc, "input.extent.2", input->dim[2].extent, "4", 4)) ||
@@ -373,9 +366,7 @@ extern "C" int interpolate(halide_buffer_t *input, halide_buffer_t *output) {
         return r;
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (W > 0 && H > 0) {
         Box I[IL], D[IL];
         I[0] = {0, W - 1, 0, H - 1};
@@ -476,6 +467,4 @@ extern "C" int interpolate(halide_buffer_t *input, halide_buffer_t *output) {
     return 0;
 }
 
-extern "C" int interpolate_argv(void **a) { return interpolate((halide_buffer_t *)a[0], (halide_buffer_t *)a[1]); }
-extern "C" const halide_filter_metadata_t *interpolate_metadata(void) { return &ip_md; }
-extern "C" int interpolate_auto_schedule(halide_buffer_t *input, halide_buffer_t *output) { return interpolate(input, output); }
+HLMI_ENTRY_AUTO(interpolate, ip_table.md)

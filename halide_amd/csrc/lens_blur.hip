@@ -878,25 +878,16 @@ __global__ __launch_bounds__(256) void lb_final(LBGeom g, const uint32_t *__rest
     }
 }
 
-const int64_t e0 = 0, e192 = 192, e320 = 320, e3 = 3;
-const int64_t *const est_im[6] = {&e0, &e192, &e0, &e320, &e0, &e3};
-halide_scalar_value_t mk_i(int v) { halide_scalar_value_t s{}; s.u.i32 = v; return s; }
-halide_scalar_value_t mk_f(float v) { halide_scalar_value_t s{}; s.u.f32 = v; return s; }
 // defaults / ranges / estimates: generator :14-19, :158-166
-const halide_scalar_value_t s32 = mk_i(32), s13 = mk_i(13), s1 = mk_i(1), s64 = mk_i(64), fhalf = mk_f(0.5f), f0 = mk_f(0.0f), f1 = mk_f(1.0f);
-const halide_type_t ty_u8 = {(decltype(halide_type_t::code))1, 8, 0};
-const halide_type_t ty_i32 = {(decltype(halide_type_t::code))0, 32, 0};
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
-const halide_filter_argument_t lb_args[7] = {
-    {"left_im", halide_argument_kind_input_buffer, 3, ty_u8, nullptr, nullptr, nullptr, nullptr, est_im},
-    {"right_im", halide_argument_kind_input_buffer, 3, ty_u8, nullptr, nullptr, nullptr, nullptr, est_im},
-    {"slices", halide_argument_kind_input_scalar, 0, ty_i32, &s32, &s1, &s64, &s32, nullptr},
-    {"focus_depth", halide_argument_kind_input_scalar, 0, ty_i32, &s13, &s1, &s32, &s13, nullptr},
-    {"blur_radius_scale", halide_argument_kind_input_scalar, 0, ty_f32, &fhalf, &f0, &f1, &fhalf, nullptr},
-    {"aperture_samples", halide_argument_kind_input_scalar, 0, ty_i32, &s32, &s1, &s64, &s32, nullptr},
-    {"final", halide_argument_kind_output_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est_im},
-};
-const halide_filter_metadata_t lb_md = {1, 7, lb_args, kTargetString, "lens_blur"};
+const ArgTable lb_table("lens_blur", {
+    in_buf("left_im", T_U8, 3, {0, 192, 0, 320, 0, 3}),
+    in_buf("right_im", T_U8, 3, {0, 192, 0, 320, 0, 3}),
+    scalar_i32("slices").def(32).range(1, 64).estimate(32),
+    scalar_i32("focus_depth").def(13).range(1, 32).estimate(13),
+    scalar_f32("blur_radius_scale").def(0.5).range(0, 1).estimate(0.5),
+    scalar_i32("aperture_samples").def(32).range(1, 64).estimate(32),
+    out_buf("final", T_F32, 3, {0, 192, 0, 320, 0, 3}),
+});
 
 }  // namespace
 
@@ -906,17 +897,12 @@ extern "C" int hlmi_lens_blur_get_random_tag(void) { return g_rand_tag.load(); }
 extern "C" int lens_blur(halide_buffer_t *left_im, halide_buffer_t *right_im, int32_t slices, int32_t focus_depth,
                          float blur_radius_scale, int32_t aperture_samples, halide_buffer_t *final_) {
     void *uc = nullptr;
-    BufArg args[3] = {{"left_im", left_im, T_U8, 3, false}, {"right_im", right_im, T_U8, 3, false}, {"final", final_, T_F32, 3, true}};
+    BufArg args[3];
+    lb_table.bufs(args, {left_im, right_im, final_});
     int r = check_not_null(uc, args, 3);
     if (r) return r;
     // scalar ranges are checked before the image checks (src/Lower.cpp:189 vs :251); generator :14-19
-    struct { const char *name; double v, lo, hi; } pr[4] = {{"slices", (double)slices, 1, 64}, {"focus_depth", (double)focus_depth, 1, 32},
-                                                            {"blur_radius_scale", (double)blur_radius_scale, 0, 1},
-                                                            {"aperture_samples", (double)aperture_samples, 1, 64}};
-    for (auto &p : pr) {
-        if (!(p.v >= p.lo)) return report(uc, halide_error_code_param_too_small, "Parameter %s is %g but must be at least %g", p.name, p.v, p.lo);
-        if (!(p.v <= p.hi)) return report(uc, halide_error_code_param_too_large, "Parameter %s is %g but must be at most %g", p.name, p.v, p.hi);
-    }
+    if ((r = check_scalar_ranges(uc, lb_table, {(double)slices, (double)focus_depth, (double)blur_radius_scale, (double)aperture_samples}))) return r;
     if ((r = check_type_and_dims(uc, args, 3))) return r;
     if (any_bounds_query(args, 3)) {
         // every tap of the inputs is clamped (:27-28); propose the output's x / y region and the three channels
@@ -926,8 +912,7 @@ extern "C" int lens_blur(halide_buffer_t *left_im, halide_buffer_t *right_im, in
         answer_query(final_, mins, ext);
         return 0;
     }
-    for (int i = 0; i < 3; i++)
-        if ((r = check_shape(uc, args[i]))) return r;
+    if ((r = check_shapes(uc, args, 3))) return r;
     if ((r = check_equal(uc, "final.min.2", final_->dim[2].min, "0", 0))) return r;
     if (final_->dim[2].extent > 3) {
         return report(uc, halide_error_code_constraint_violated, "Output buffer final has %d channels, at most 3 are defined", final_->dim[2].extent);
@@ -942,9 +927,7 @@ extern "C" int lens_blur(halide_buffer_t *left_im, halide_buffer_t *right_im, in
         }
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0])) || (r = input_to_device(uc, ctx, args[1]))) return r;
-    if ((r = output_on_device(uc, ctx, args[2]))) return r;
+    if ((r = to_device(uc, &ctx, args, 3))) return r;
     if (ow == 0 || oh == 0 || nc == 0) {
         mark_output_written(final_);
         return 0;
@@ -1132,12 +1115,4 @@ extern "C" int lens_blur(halide_buffer_t *left_im, halide_buffer_t *right_im, in
     return 0;
 }
 
-extern "C" int lens_blur_argv(void **a) {
-    return lens_blur((halide_buffer_t *)a[0], (halide_buffer_t *)a[1], *(int32_t *)a[2], *(int32_t *)a[3], *(float *)a[4], *(int32_t *)a[5],
-                     (halide_buffer_t *)a[6]);
-}
-extern "C" const halide_filter_metadata_t *lens_blur_metadata(void) { return &lb_md; }
-extern "C" int lens_blur_auto_schedule(halide_buffer_t *left_im, halide_buffer_t *right_im, int32_t slices, int32_t focus_depth,
-                                       float blur_radius_scale, int32_t aperture_samples, halide_buffer_t *final_) {
-    return lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final_);
-}
+HLMI_ENTRY_AUTO(lens_blur, lb_table.md)

@@ -2394,22 +2394,14 @@ __global__ __launch_bounds__(256) void ll_up0h(Up0HArgs ph, Geometry gm) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-const int64_t est_zero = 0, est_w = 1536, est_h = 2560, est_c = 3;
-const int64_t *const buf_est[6] = {&est_zero, &est_w, &est_zero, &est_h, &est_zero, &est_c};
-const halide_scalar_value_t est_levels = [] { halide_scalar_value_t v{}; v.u.i32 = 8; return v; }();
-const halide_scalar_value_t est_one = [] { halide_scalar_value_t v{}; v.u.f32 = 1.0f; return v; }();
-const halide_type_t ty_u16 = {(decltype(halide_type_t::code))1, 16, 0};
-const halide_type_t ty_i32 = {(decltype(halide_type_t::code))0, 32, 0};
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
 // estimates: generator :92-98
-const halide_filter_argument_t ll_args[5] = {
-    {"input", halide_argument_kind_input_buffer, 3, ty_u16, nullptr, nullptr, nullptr, nullptr, buf_est},
-    {"levels", halide_argument_kind_input_scalar, 0, ty_i32, nullptr, nullptr, nullptr, &est_levels, nullptr},
-    {"alpha", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_one, nullptr},
-    {"beta", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_one, nullptr},
-    {"output", halide_argument_kind_output_buffer, 3, ty_u16, nullptr, nullptr, nullptr, nullptr, buf_est},
-};
-const halide_filter_metadata_t ll_md = {1, 5, ll_args, kTargetString, "local_laplacian"};
+const ArgTable ll_table("local_laplacian", {
+    in_buf("input", T_U16, 3, {0, 1536, 0, 2560, 0, 3}),
+    scalar_i32("levels").estimate(8),
+    scalar_f32("alpha").estimate(1),
+    scalar_f32("beta").estimate(1),
+    out_buf("output", T_U16, 3, {0, 1536, 0, 2560, 0, 3}),
+});
 
 // ---- run-time switches: environment variables, read by ll_switches() once per call — on EVERY call, since the parity tests flip
 // them between calls of one process.  Unset or empty: the default; otherwise atoi of the value.  All default to the fast path;
@@ -2948,7 +2940,8 @@ int ll_stage_up0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st)
 extern "C" int local_laplacian(halide_buffer_t *input, int32_t levels, float alpha, float beta, halide_buffer_t *output) {
     void *uc = nullptr;
     const LlSwitches sw = ll_switches();
-    BufArg args[2] = {{"input", input, T_U16, 3, false}, {"output", output, T_U16, 3, true}};
+    BufArg args[2];
+    ll_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -2960,7 +2953,7 @@ extern "C" int local_laplacian(halide_buffer_t *input, int32_t levels, float alp
         answer_query(output, mins, ext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     for (int d = 0; d < 3; d++) {
         if ((r = check_covers(uc, args[0], d, output->dim[d].min, output->dim[d].extent))) return r;
     }
@@ -2981,9 +2974,7 @@ extern "C" int local_laplacian(halide_buffer_t *input, int32_t levels, float alp
     }
 
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (output->dim[0].extent == 0 || output->dim[1].extent == 0 || nc == 0) {
         mark_output_written(output);
         return 0;
@@ -3014,15 +3005,7 @@ extern "C" int local_laplacian(halide_buffer_t *input, int32_t levels, float alp
     return 0;
 }
 
-extern "C" int local_laplacian_argv(void **a) {
-    return local_laplacian((halide_buffer_t *)a[0], *(int32_t *)a[1], *(float *)a[2], *(float *)a[3],
-                           (halide_buffer_t *)a[4]);
-}
-extern "C" const halide_filter_metadata_t *local_laplacian_metadata(void) { return &ll_md; }
-extern "C" int local_laplacian_auto_schedule(halide_buffer_t *input, int32_t levels, float alpha, float beta,
-                                             halide_buffer_t *output) {
-    return local_laplacian(input, levels, alpha, beta, output);
-}
+HLMI_ENTRY_AUTO(local_laplacian, ll_table.md)
 
 // Probe builds (HLMI_LL_PROBE=1): copies the 32 phase counters of g_probe to `out32` and clears them; 1, 0 = not a probe
 // build, < 0 = HIP error.

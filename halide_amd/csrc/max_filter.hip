@@ -198,21 +198,15 @@ __global__ __launch_bounds__(NT) void max_filter_tile(const float *__restrict__ 
     }
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560, ec = 3;
-const int64_t *const est[6] = {&e0, &ew, &e0, &eh, &e0, &ec};
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
 // estimates: generator :55-62
-const halide_filter_argument_t mf_args[2] = {
-    {"input", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-    {"output", halide_argument_kind_output_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-};
-const halide_filter_metadata_t mf_md = {1, 2, mf_args, kTargetString, "max_filter"};
+const ArgTable mf_table("max_filter", {in_buf("input", T_F32, 3, {0, 1536, 0, 2560, 0, 3}), out_buf("output", T_F32, 3, {0, 1536, 0, 2560, 0, 3})});
 
 }  // namespace
 
 extern "C" int max_filter(halide_buffer_t *input, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_F32, 3, false}, {"output", output, T_F32, 3, true}};
+    BufArg args[2];
+    mf_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -224,7 +218,7 @@ extern "C" int max_filter(halide_buffer_t *input, halide_buffer_t *output) {
         answer_query(output, mins, ext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     const int ow = output->dim[0].extent, oh = output->dim[1].extent, oc = output->dim[2].extent;
     if ((r = check_covers(uc, args[0], 2, output->dim[2].min, oc))) return r;
     if (ow > 0 && oh > 0 && oc > 0) {
@@ -238,9 +232,7 @@ extern "C" int max_filter(halide_buffer_t *input, halide_buffer_t *output) {
         }
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (ow > 0 && oh > 0 && oc > 0) {
         MFGeom g;
         g.ix0 = input->dim[0].min, g.iy0 = input->dim[1].min, g.W = input->dim[0].extent, g.H = input->dim[1].extent;
@@ -277,6 +269,4 @@ extern "C" int max_filter(halide_buffer_t *input, halide_buffer_t *output) {
     return 0;
 }
 
-extern "C" int max_filter_argv(void **a) { return max_filter((halide_buffer_t *)a[0], (halide_buffer_t *)a[1]); }
-extern "C" const halide_filter_metadata_t *max_filter_metadata(void) { return &mf_md; }
-extern "C" int max_filter_auto_schedule(halide_buffer_t *input, halide_buffer_t *output) { return max_filter(input, output); }
+HLMI_ENTRY_AUTO(max_filter, mf_table.md)

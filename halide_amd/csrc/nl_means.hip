@@ -251,28 +251,22 @@ __global__ __launch_bounds__(256) void nlm_generic(const float *__restrict__ in,
     for (int c = 0; c < 3; c++) out[(long)y * out_sy + x + (long)c * out_sc] = dev::clampf(acc[c] / acc[3], 0.0f, 1.0f);
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560, ec = 3;
-const int64_t *const est[6] = {&e0, &ew, &e0, &eh, &e0, &ec};
-const halide_scalar_value_t est7 = [] { halide_scalar_value_t v{}; v.u.i32 = 7; return v; }();
-const halide_scalar_value_t est_sigma = [] { halide_scalar_value_t v{}; v.u.f32 = 0.12f; return v; }();
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
-const halide_type_t ty_i32 = {(decltype(halide_type_t::code))0, 32, 0};
 // estimates: generator :76-82
-const halide_filter_argument_t nlm_args[5] = {
-    {"input", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-    {"patch_size", halide_argument_kind_input_scalar, 0, ty_i32, nullptr, nullptr, nullptr, &est7, nullptr},
-    {"search_area", halide_argument_kind_input_scalar, 0, ty_i32, nullptr, nullptr, nullptr, &est7, nullptr},
-    {"sigma", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, &est_sigma, nullptr},
-    {"non_local_means", halide_argument_kind_output_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-};
-const halide_filter_metadata_t nlm_md = {1, 5, nlm_args, kTargetString, "nl_means"};
+const ArgTable nlm_table("nl_means", {
+    in_buf("input", T_F32, 3, {0, 1536, 0, 2560, 0, 3}),
+    scalar_i32("patch_size").estimate(7),
+    scalar_i32("search_area").estimate(7),
+    scalar_f32("sigma").estimate(0.12),
+    out_buf("non_local_means", T_F32, 3, {0, 1536, 0, 2560, 0, 3}),
+});
 
 }  // namespace
 
 extern "C" int nl_means(halide_buffer_t *input, int32_t patch_size, int32_t search_area, float sigma,
                         halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_F32, 3, false}, {"non_local_means", output, T_F32, 3, true}};
+    BufArg args[2];
+    nlm_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -284,7 +278,7 @@ extern "C" int nl_means(halide_buffer_t *input, int32_t patch_size, int32_t sear
         answer_query(output, mins, ext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     if ((r = check_equal(uc, "non_local_means.min.2", output->dim[2].min, "0", 0))) return r;
     if ((r = check_equal(uc, "non_local_means.extent.2", output->dim[2].extent, "3", 3))) return r;
     if (patch_size < 1 || search_area < 1) {
@@ -296,9 +290,7 @@ extern "C" int nl_means(halide_buffer_t *input, int32_t patch_size, int32_t sear
         return report(uc, halide_error_code_access_out_of_bounds, "Input buffer input is empty but is accessed (clamped)");
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (ow == 0 || oh == 0) {
         mark_output_written(output);
         return 0;
@@ -329,11 +321,4 @@ extern "C" int nl_means(halide_buffer_t *input, int32_t patch_size, int32_t sear
     return 0;
 }
 
-extern "C" int nl_means_argv(void **a) {
-    return nl_means((halide_buffer_t *)a[0], *(int32_t *)a[1], *(int32_t *)a[2], *(float *)a[3], (halide_buffer_t *)a[4]);
-}
-extern "C" const halide_filter_metadata_t *nl_means_metadata(void) { return &nlm_md; }
-extern "C" int nl_means_auto_schedule(halide_buffer_t *input, int32_t patch_size, int32_t search_area, float sigma,
-                                      halide_buffer_t *output) {
-    return nl_means(input, patch_size, search_area, sigma, output);
-}
+HLMI_ENTRY_AUTO(nl_means, nlm_table.md)

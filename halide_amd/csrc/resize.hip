@@ -292,10 +292,18 @@ template<> constexpr uint32_t abi_of<float>() { return T_F32; }
 template<> constexpr uint32_t abi_of<uint8_t>() { return T_U8; }
 template<> constexpr uint32_t abi_of<uint16_t>() { return T_U16; }
 
+// one table per element type, shared by the eight variants of that type; no estimates: the generator sets none
+template<typename T>
+const ArgTable &rs_table() {
+    static const ArgTable t("resize", {in_buf("input", abi_of<T>(), 3), scalar_f32("scale_factor"), out_buf("output", abi_of<T>(), 3)});
+    return t;
+}
+
 template<typename T, int KIND, bool UP>
 int resize_entry(halide_buffer_t *input, float scale_factor, halide_buffer_t *output, bool general_only) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, abi_of<T>(), 3, false}, {"output", output, abi_of<T>(), 3, true}};
+    BufArg args[2];
+    rs_table<T>().bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -307,7 +315,7 @@ int resize_entry(halide_buffer_t *input, float scale_factor, halide_buffer_t *ou
         answer_query(input, mins, ext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     RGeom g;
     g.ix0 = input->dim[0].min, g.iy0 = input->dim[1].min, g.W = input->dim[0].extent, g.H = input->dim[1].extent;
     g.ox0 = output->dim[0].min, g.oy0 = output->dim[1].min, g.ow = output->dim[0].extent, g.oh = output->dim[1].extent;
@@ -323,9 +331,7 @@ int resize_entry(halide_buffer_t *input, float scale_factor, halide_buffer_t *ou
     }
     g.taps = (int)taps_f;
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (g.ow > 0 && g.oh > 0 && g.oc > 0) {
         g.in_sy = input->dim[1].stride, g.in_sc = input->dim[2].stride;
         g.out_sy = output->dim[1].stride, g.out_sc = output->dim[2].stride;
@@ -377,16 +383,6 @@ int resize_entry(halide_buffer_t *input, float scale_factor, halide_buffer_t *ou
     return 0;
 }
 
-// no estimates: the generator sets none
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0}, ty_u8 = {(decltype(halide_type_t::code))1, 8, 0},
-                    ty_u16 = {(decltype(halide_type_t::code))1, 16, 0};
-#define RS_ARGS(ty)                                                                                              \
-    {                                                                                                            \
-        {"input", halide_argument_kind_input_buffer, 3, ty, nullptr, nullptr, nullptr, nullptr, nullptr},        \
-            {"scale_factor", halide_argument_kind_input_scalar, 0, ty_f32, nullptr, nullptr, nullptr, nullptr, nullptr}, \
-            {"output", halide_argument_kind_output_buffer, 3, ty, nullptr, nullptr, nullptr, nullptr, nullptr},  \
-    }
-const halide_filter_argument_t rs_args_float32[3] = RS_ARGS(ty_f32), rs_args_uint8[3] = RS_ARGS(ty_u8), rs_args_uint16[3] = RS_ARGS(ty_u16);
 using float32 = float;
 using uint8 = uint8_t;
 using uint16 = uint16_t;
@@ -400,8 +396,7 @@ struct Variant {
 
 #define RS_VARIANT(kname, KIND, tname, dname, UP)                                                                                     \
     namespace {                                                                                                                       \
-    const halide_filter_metadata_t rs_md_##kname##_##tname##_##dname = {1, 3, rs_args_##tname, kTargetString,                         \
-                                                                        "resize_" #kname "_" #tname "_" #dname};                      \
+    const halide_filter_metadata_t rs_md_##kname##_##tname##_##dname = rs_table<tname>().named("resize_" #kname "_" #tname "_" #dname); \
     int rs_general_##kname##_##tname##_##dname(halide_buffer_t *i, float s, halide_buffer_t *o) {                                     \
         return resize_entry<tname, KIND, UP>(i, s, o, true);                                                                          \
     }                                                                                                                                 \
@@ -409,12 +404,7 @@ struct Variant {
     extern "C" int resize_##kname##_##tname##_##dname(halide_buffer_t *input, float scale_factor, halide_buffer_t *output) {          \
         return resize_entry<tname, KIND, UP>(input, scale_factor, output, false);                                                     \
     }                                                                                                                                 \
-    extern "C" int resize_##kname##_##tname##_##dname##_argv(void **a) {                                                              \
-        return resize_##kname##_##tname##_##dname((halide_buffer_t *)a[0], *(float *)a[1], (halide_buffer_t *)a[2]);                  \
-    }                                                                                                                                 \
-    extern "C" const halide_filter_metadata_t *resize_##kname##_##tname##_##dname##_metadata(void) {                                  \
-        return &rs_md_##kname##_##tname##_##dname;                                                                                    \
-    }
+    HLMI_ENTRY(resize_##kname##_##tname##_##dname, rs_md_##kname##_##tname##_##dname)
 #define RS_TYPES(kname, KIND)                \
     RS_VARIANT(kname, KIND, float32, up, true)    \
     RS_VARIANT(kname, KIND, float32, down, false) \

@@ -26,6 +26,27 @@ namespace hlmi {
 
 const char *const kTargetString = "x86-64-linux-hip-gfx950";
 
+ArgTable::ArgTable(const char *name, std::initializer_list<Arg> table) {
+    for (const Arg &s : table) {
+        if (n == MAX_ARGS || (s.n_est != 0 && s.n_est != 2 * s.dims) || s.n_est > 8) {
+            fprintf(stderr, "hlmi: malformed argument table line %s.%s\n", name, s.name);
+            abort();
+        }
+        const int i = n++;
+        spec[i] = s;
+        halide_filter_argument_t &a = args[i];
+        a = halide_filter_argument_t{};
+        a.name = s.name, a.kind = s.kind, a.dimensions = s.dims;
+        memcpy(&a.type, &s.type, 4);
+        const halide_scalar_value_t **sp[4] = {&a.scalar_def, &a.scalar_min, &a.scalar_max, &a.scalar_estimate};
+        for (int w = 0; w < 4; w++)
+            if (s.has & (1u << w)) *sp[w] = &spec[i].sv[w];
+        for (int e = 0; e < s.n_est; e++) est_ptrs[i][e] = &spec[i].est[e];
+        if (s.n_est) a.buffer_estimates = est_ptrs[i];
+    }
+    md = {1, n, args, kTargetString, name};
+}
+
 // ------------------------------------------------------------------------------------------------
 // hooks
 static void default_error_handler(void *, const char *msg) {
@@ -206,6 +227,28 @@ int check_shape(void *uc, const BufArg &a) {
             total = 1;  // keep the running product inside int64 for the remaining dimensions
         }
     }
+    return 0;
+}
+
+int check_shapes(void *uc, const BufArg *args, int n) {
+    for (int i = 0; i < n; i++)
+        if (int r = check_shape(uc, args[i])) return r;
+    return 0;
+}
+
+static int check_scalar_range(void *uc, const Arg &a, double v) {
+    if ((a.has & (1u << Arg::MIN)) && !(v >= a.get(Arg::MIN)))
+        return report(uc, halide_error_code_param_too_small, "Parameter %s is %g but must be at least %g", a.name, v, a.get(Arg::MIN));
+    if ((a.has & (1u << Arg::MAX)) && !(v <= a.get(Arg::MAX)))
+        return report(uc, halide_error_code_param_too_large, "Parameter %s is %g but must be at most %g", a.name, v, a.get(Arg::MAX));
+    return 0;
+}
+
+int check_scalar_ranges(void *uc, const ArgTable &t, std::initializer_list<double> values) {
+    const double *v = values.begin();
+    for (int i = 0; i < t.n && v != values.end(); i++)
+        if (t.spec[i].kind == halide_argument_kind_input_scalar)
+            if (int r = check_scalar_range(uc, t.spec[i], *v++)) return r;
     return 0;
 }
 
@@ -1062,6 +1105,15 @@ int output_on_device(void *uc, const DeviceCtx &ctx, const BufArg &a) {
         if (r) return r;
     }
     return note_use(uc, ctx, b->device, a.name, true);
+}
+
+int to_device(void *uc, DeviceCtx *ctx, const BufArg *args, int n) {
+    int r = acquire_device(uc, ctx);
+    for (int i = 0; i < n && !r; i++)
+        if (!args[i].is_output) r = input_to_device(uc, *ctx, args[i]);
+    for (int i = 0; i < n && !r; i++)
+        if (args[i].is_output) r = output_on_device(uc, *ctx, args[i]);
+    return r;
 }
 
 void mark_output_written(halide_buffer_t *b) {

@@ -156,20 +156,14 @@ __global__ __launch_bounds__(64 * NW) void stencil_fused8r(const uint16_t *__res
     }
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560;
-const int64_t *const est[4] = {&e0, &ew, &e0, &eh};
-const halide_type_t ty_u16 = {(decltype(halide_type_t::code))1, 16, 0};
-const halide_filter_argument_t sc_args[2] = {
-    {"input", halide_argument_kind_input_buffer, 2, ty_u16, nullptr, nullptr, nullptr, nullptr, est},
-    {"output", halide_argument_kind_output_buffer, 2, ty_u16, nullptr, nullptr, nullptr, nullptr, est},
-};
-const halide_filter_metadata_t sc_md = {1, 2, sc_args, kTargetString, "stencil_chain"};
+const ArgTable sc_table("stencil_chain", {in_buf("input", T_U16, 2, {0, 1536, 0, 2560}), out_buf("output", T_U16, 2, {0, 1536, 0, 2560})});
 
 }  // namespace
 
 extern "C" int stencil_chain(halide_buffer_t *input, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_U16, 2, false}, {"output", output, T_U16, 2, true}};
+    BufArg args[2];
+    sc_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -181,15 +175,13 @@ extern "C" int stencil_chain(halide_buffer_t *input, halide_buffer_t *output) {
         answer_query(output, mins, ext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     const int W = output->dim[0].extent, H = output->dim[1].extent;
     if (W > 0 && H > 0 && (input->dim[0].extent < 1 || input->dim[1].extent < 1)) {
         return report(uc, halide_error_code_access_out_of_bounds, "Input buffer input is empty but is accessed (clamped) at 0");
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (W == 0 || H == 0) {
         mark_output_written(output);
         return 0;
@@ -234,6 +226,4 @@ HLMI_LAUNCH(uc, "stencil_fused8", ctx.stream, (stencil_fused8r<C, I, O, RW>), gr
     return 0;
 }
 
-extern "C" int stencil_chain_argv(void **a) { return stencil_chain((halide_buffer_t *)a[0], (halide_buffer_t *)a[1]); }
-extern "C" const halide_filter_metadata_t *stencil_chain_metadata(void) { return &sc_md; }
-extern "C" int stencil_chain_auto_schedule(halide_buffer_t *input, halide_buffer_t *output) { return stencil_chain(input, output); }
+HLMI_ENTRY_AUTO(stencil_chain, sc_table.md)

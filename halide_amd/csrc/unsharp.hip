@@ -189,21 +189,15 @@ __global__ __launch_bounds__(256) void unsharp_tile2(const float *__restrict__ i
     }
 }
 
-const int64_t e0 = 0, ew = 1536, eh = 2560, ec = 3;
-const int64_t *const est[6] = {&e0, &ew, &e0, &eh, &e0, &ec};
-const halide_type_t ty_f32 = {(decltype(halide_type_t::code))2, 32, 0};
 // estimates: generator :54-61
-const halide_filter_argument_t us_args[2] = {
-    {"input", halide_argument_kind_input_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-    {"output", halide_argument_kind_output_buffer, 3, ty_f32, nullptr, nullptr, nullptr, nullptr, est},
-};
-const halide_filter_metadata_t us_md = {1, 2, us_args, kTargetString, "unsharp"};
+const ArgTable us_table("unsharp", {in_buf("input", T_F32, 3, {0, 1536, 0, 2560, 0, 3}), out_buf("output", T_F32, 3, {0, 1536, 0, 2560, 0, 3})});
 
 }  // namespace
 
 extern "C" int unsharp(halide_buffer_t *input, halide_buffer_t *output) {
     void *uc = nullptr;
-    BufArg args[2] = {{"input", input, T_F32, 3, false}, {"output", output, T_F32, 3, true}};
+    BufArg args[2];
+    us_table.bufs(args, {input, output});
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
@@ -214,7 +208,7 @@ extern "C" int unsharp(halide_buffer_t *input, halide_buffer_t *output) {
         answer_query(output, mins, ext);
         return 0;
     }
-    if ((r = check_shape(uc, args[0])) || (r = check_shape(uc, args[1]))) return r;
+    if ((r = check_shapes(uc, args, 2))) return r;
     const int ow = output->dim[0].extent, oh = output->dim[1].extent, oc = output->dim[2].extent;
     if ((r = check_covers(uc, args[0], 0, output->dim[0].min, ow)) || (r = check_covers(uc, args[0], 1, output->dim[1].min, oh))) return r;
     // gray reads channels 0, 1, 2 (through repeat_edge: any non-empty channel range is legal); the output's channels are
@@ -227,9 +221,7 @@ extern "C" int unsharp(halide_buffer_t *input, halide_buffer_t *output) {
         return report(uc, halide_error_code_constraint_violated, "Input buffer input must hold channels 0..2 (clamped channel reads are not supported)");
     }
     DeviceCtx ctx;
-    if ((r = acquire_device(uc, &ctx))) return r;
-    if ((r = input_to_device(uc, ctx, args[0]))) return r;
-    if ((r = output_on_device(uc, ctx, args[1]))) return r;
+    if ((r = to_device(uc, &ctx, args, 2))) return r;
     if (ow > 0 && oh > 0 && oc > 0) {
         UGeom g;
         g.ix0 = input->dim[0].min, g.iy0 = input->dim[1].min, g.W = input->dim[0].extent, g.H = input->dim[1].extent;
@@ -256,6 +248,4 @@ extern "C" int unsharp(halide_buffer_t *input, halide_buffer_t *output) {
     return 0;
 }
 
-extern "C" int unsharp_argv(void **a) { return unsharp((halide_buffer_t *)a[0], (halide_buffer_t *)a[1]); }
-extern "C" const halide_filter_metadata_t *unsharp_metadata(void) { return &us_md; }
-extern "C" int unsharp_auto_schedule(halide_buffer_t *input, halide_buffer_t *output) { return unsharp(input, output); }
+HLMI_ENTRY_AUTO(unsharp, us_table.md)
