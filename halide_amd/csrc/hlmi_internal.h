@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <initializer_list>
 #include <mutex>
+#include <optional>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -336,8 +337,10 @@ struct ScopedKernelTimer {
         if (on) timing_end(s);
     }
 };
-// Run-time switches (HLMI_*): one helper so that every switch reads the same way — set and non-zero = on, unset / empty / "0" = off.
+// Run-time switches (HLMI_*): two helpers so that every switch reads the same way.  env_int: unset or empty = nullopt (the caller's
+// default), otherwise atoi of the value.  env_flag: env_int(name).value_or(0) != 0 — set and non-zero = on, unset / empty / "0" = off.
 // Read at every call (a getenv, ~100 ns): the parity tests flip switches inside one process to reach the alternative paths.
+HLMI_LOCAL std::optional<int> env_int(const char *name);   // hidden: the library's exported symbols stay as they were
 bool env_flag(const char *name);
 // launch + error check; kernel errors surface as -23 (device_run_failed)
 int launch_failed(void *uc, const char *kernel);

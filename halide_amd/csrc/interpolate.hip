@@ -330,8 +330,127 @@ __global__ __launch_bounds__(256) void ip_final(InGeom g, Lvl d1, Lvl d2, Lvl up
 const ArgTable ip_table("interpolate", {in_buf("input", T_F32, 3, {0, 1536, 0, 2560, 0, 4}), out_buf("output", T_F32, 3, {0, 1536, 0, 2560, 0, 3})});
 
 struct Box {
-    int x0, x1, y0, y1;
+    int x0, x1, y0, y1;   // inclusive
+    int w() const { return x1 - x0 + 1; }
+    int h() const { return y1 - y0 + 1; }
 };
+
+// ---- the plan of one call: boxes, workspace layout and the chain, made by ip_plan() before anything is enqueued.  It holds no
+// pointer (IpBuffers does); it lives on interpolate()'s stack and the stages read it by reference.
+struct IpPlan {
+    int cw, ch;                                 // the coordinate clamp in front of level 4 (:40-49)
+    Box I[IL], D[IL];                           // interpolated[l] / downsampled[l] (header of this file)
+    size_t off_d[IL], off_i[IL], ws_float4;     // workspace layout in float4: downsampled 1 .. 9, interpolated 3 .. 8
+    // chain shape
+    //   T                 levels >= T go through ip_tail (IL: no tail)
+    //   down_to, up_from  ip_down:l runs for l = 2 .. down_to, ip_up:l for l = up_from .. 3 (fused: neither)
+    //   fused             levels 3, 4, 5 in one launch per direction (ip_down_multi / ip_up_multi)
+    int T, down_to, up_from;
+    bool fused;
+    // launch geometry
+    int ntx5, nty5, ntx3, nty3;                 // tiles of downsampled[5] (ip_down_multi) and of interpolated[3] (ip_up_multi)
+};
+
+// the resolved pointers of one call: the input and where the plan's layout landed in the stream's arena, in the form the kernels take
+struct IpBuffers {
+    InGeom g;
+    TailArgs lv;   // ds[0], ip[0 .. 2]: not stored; ip[9] = ds[9]; with cw, ch and T it is ip_tail's argument
+};
+
+int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Do the windows of every ip_down_multi tile fit the kernel's LDS arrays and lie inside the stored boxes?  They do for any image:
+// the check guards the constants (DM5, DM4W, DM3W), not the input.
+bool ip_windows_fit(const Box *D, int cw, int ch) {
+    auto owned = [](int llo, int lhi, int sh, int tlo, int thi, int a, int b, int &lo, int &hi) {
+        lo = a <= tlo ? llo : (llo > a * (1 << sh) ? llo : a * (1 << sh));
+        hi = b >= thi ? lhi : (lhi < (b + 1) * (1 << sh) - 1 ? lhi : (b + 1) * (1 << sh) - 1);
+    };
+    for (int axis = 0; axis < 2; axis++) {
+        const int b5lo = axis ? D[5].y0 : D[5].x0, b5hi = axis ? D[5].y1 : D[5].x1, b4lo = axis ? D[4].y0 : D[4].x0,
+                  b4hi = axis ? D[4].y1 : D[4].x1, b3lo = axis ? D[3].y0 : D[3].x0, b3hi = axis ? D[3].y1 : D[3].x1;
+        const int c = axis ? ch : cw;
+        for (int a = b5lo; a <= b5hi; a += DM5) {
+            const int b = min(a + DM5 - 1, b5hi);
+            int o4l, o4h, o3l, o3h;
+            owned(b4lo, b4hi, 1, b5lo, b5hi, a, b, o4l, o4h);
+            owned(b3lo, b3hi, 2, b5lo, b5hi, a, b, o3l, o3h);
+            const int w4l = min(2 * a - 1, o4l), w4h = max(2 * b + 1, o4h);
+            const int w3l = min(clampi(2 * w4l - 1, 0, c), o3l), w3h = max(clampi(2 * w4h + 1, 0, c), o3h);
+            if (w4h - w4l + 1 > DM4W || w3h - w3l + 1 > DM3W || w4l < b4lo || w4h > b4hi || w3l < b3lo || w3h > b3hi) return false;
+        }
+    }
+    return true;
+}
+
+// No HIP call, no lock, no allocation: a function of the input's extents and the two run-time switches — environment variables, read
+// by interpolate() on every call, since the parity tests flip them between calls of one process (env_int / env_flag, hlmi_internal.h).
+// Every alternative is bit-identical.
+//   HLMI_IP_   default  selects                                                                     flipped by (tests/test_interpolate.py)
+//   TAIL_FROM  6        the first level ip_tail takes (3 .. 8; any other value: no tail, a launch   test_hip_staged_and_other_tails_match_oracle
+//                       per level up to 9); the measurements are in the header of this file
+//   UNFUSED    0        1: levels 3 to 5 as ip_down:l / ip_up:l launches instead of                 test_hip_staged_and_other_tails_match_oracle
+//                       ip_down_multi:3 / ip_up_multi:3 (which also need TAIL_FROM = 6)
+// The chain of every setting: tests/test_launch_plans.py.
+void ip_plan(IpPlan &pl, int W, int H, int tail_from, bool unfused) {
+    Box *I = pl.I, *D = pl.D;
+    I[0] = {0, W - 1, 0, H - 1};
+    for (int l = 1; l < IL; l++) I[l] = {0, floor_div(I[l - 1].x1 + 1, 2), 0, floor_div(I[l - 1].y1 + 1, 2)};
+    D[IL - 1] = I[IL - 1];
+    const int cw = pl.cw = W / 8, ch = pl.ch = H / 8;
+    for (int l = IL - 2; l >= 0; l--) {
+        Box n = {2 * D[l + 1].x0 - 1, 2 * D[l + 1].x1 + 1, 2 * D[l + 1].y0 - 1, 2 * D[l + 1].y1 + 1};
+        if (l + 1 == 4) n = {clampi(n.x0, 0, cw), clampi(n.x1, 0, cw), clampi(n.y0, 0, ch), clampi(n.y1, 0, ch)};
+        D[l] = {min(n.x0, I[l].x0), max(n.x1, I[l].x1), min(n.y0, I[l].y0), max(n.y1, I[l].y1)};
+    }
+    size_t &total = pl.ws_float4 = 0;
+    auto area = [](const Box &b) { return ((size_t)b.w() * b.h() + 15) & ~(size_t)15; };
+    for (int l = 1; l < IL; l++) pl.off_d[l] = total, total += area(D[l]);
+    for (int l = 3; l < IL - 1; l++) pl.off_i[l] = total, total += area(I[l]);   // interpolated[2] and [1] live in ip_final's LDS
+    // levels >= T go through ip_tail (default 6: 25 x 41 pixels and below)
+    pl.T = tail_from < 3 || tail_from > IL - 2 ? IL : tail_from;   // (interpolated[2] and [1] are not stored: no tail from below level 3)
+    // levels 3, 4, 5 in one launch per direction (ip_down_multi / ip_up_multi) when the tail starts at 6 and every tile's windows fit
+    pl.fused = pl.T == 6 && !unfused && ip_windows_fit(D, cw, ch);
+    pl.down_to = pl.fused ? 2 : min(pl.T, IL) - 1;
+    pl.up_from = pl.fused ? 2 : (pl.T < IL ? pl.T - 1 : IL - 2);   // (levels 2 and 1 are made inside ip_final)
+    pl.ntx5 = (D[5].w() + DM5 - 1) / DM5, pl.nty5 = (D[5].h() + DM5 - 1) / DM5;
+    pl.ntx3 = (I[3].w() + UM3 - 1) / UM3, pl.nty3 = (I[3].h() + UM3 - 1) / UM3;
+}
+
+// ---- the two stages of the chain, in launch order.  Each takes the plan, the resolved pointers and the stream; a non-zero return
+// is the error code of the call.
+
+// stage 1, down: downsampled[1 .. T-1] (ip_down:1, ip_down:l, ip_down_multi:3), then the tail — downsampled[T .. 9] and
+// interpolated[8 .. T] by one workgroup
+int ip_stage_down(void *uc, const IpPlan &pl, const IpBuffers &b, hipStream_t st) {
+    const Lvl *ds = b.lv.ds;
+    HLMI_LAUNCH(uc, "ip_down:1", st, ip_down0_tile, dim3((ds[1].w + I0W - 1) / I0W, (ds[1].h + I0H - 1) / I0H), dim3(256), 0, b.g, ds[1]);
+    char nm[32];
+    for (int l = 2; l <= pl.down_to; l++) {
+        snprintf(nm, sizeof nm, "ip_down:%d", l);
+        HLMI_LAUNCH(uc, nm, st, (l == 4 ? ip_down<false, true> : ip_down<false, false>), dim3((ds[l].w + 255) / 256, ds[l].h), dim3(256), 0, b.g, ds[l - 1], ds[l], pl.cw, pl.ch);
+    }
+    if (pl.fused) HLMI_LAUNCH(uc, "ip_down_multi:3", st, ip_down_multi, dim3(pl.ntx5 * pl.nty5), dim3(256), 0, ds[2], ds[3], ds[4], ds[5], pl.cw, pl.ch, pl.ntx5);
+    snprintf(nm, sizeof nm, "ip_tail:%d", pl.T);
+    if (pl.T < IL) HLMI_LAUNCH(uc, nm, st, ip_tail, dim3(1), dim3(1024), 0, b.lv);
+    return 0;
+}
+
+// stage 2, up: interpolated[T-1 .. 3] (ip_up:l, ip_up_multi:3), then interpolated[2], [1] and [0] tile by tile, normalised into the
+// output (ip_final)
+int ip_stage_up(void *uc, const IpPlan &pl, const IpBuffers &b, halide_buffer_t *output, hipStream_t st) {
+    const Lvl *ds = b.lv.ds, *ip = b.lv.ip;
+    for (int l = pl.up_from; l >= 3; l--) {
+        char nm[32];
+        snprintf(nm, sizeof nm, "ip_up:%d", l);
+        HLMI_LAUNCH(uc, nm, st, ip_up, dim3((ip[l].w + 255) / 256, ip[l].h), dim3(256), 0, ds[l], ip[l + 1], ip[l]);
+    }
+    if (pl.fused) HLMI_LAUNCH(uc, "ip_up_multi:3", st, ip_up_multi, dim3(pl.ntx3 * pl.nty3), dim3(256), 0, ds[3], ds[4], ds[5], ip[6], ip[3], pl.ntx3);
+    timing_note_bytes(28.0 * b.g.W * b.g.H);
+    HLMI_LAUNCH(uc, "ip_final", st, ip_final, dim3((b.g.W + F0W - 1) / F0W, (b.g.H + F0H - 1) / F0H), dim3(256), 0, b.g, ds[1], ds[2], ip[3], dev_ptr<float>(output),
+                (long)output->dim[1].stride, (long)output->dim[2].stride);
+    return 0;
+}
 
 }  // namespace
 
@@ -342,13 +461,12 @@ extern "C" int interpolate(halide_buffer_t *input, halide_buffer_t *output) {
     int r = check_not_null(uc, args, 2);
     if (r) return r;
     if ((r = check_type_and_dims(uc, args, 2))) return r;
-    auto real = [](halide_buffer_t *b) { return !(b->host == nullptr && b->device == 0); };
     if (any_bounds_query(args, 2)) {
         // output = input's [0,W) x [0,H) with 3 channels (:83-87); input has channels [0,4) (:23)
         // (a real input pins the box; else the output's shape — real, or given by the caller of an all-null query — else a shaped
         // input, else the estimates)
-        halide_buffer_t *k = real(input) ? input : buffer_known(output) ? output : input;
-        const bool any = real(input) || buffer_known(output) || buffer_has_shape(input);
+        halide_buffer_t *k = buffer_is_real(input) ? input : buffer_known(output) ? output : input;
+        const bool any = buffer_is_real(input) || buffer_known(output) || buffer_has_shape(input);
         const int w = any ? k->dim[0].extent : 1536, h = any ? k->dim[1].extent : 2560;
         int z[3] = {0, 0, 0}, ei[3] = {w, h, 4}, eo[3] = {w, h, 3};
         answer_query(input, z, ei);
@@ -367,102 +485,26 @@ extern "C" int interpolate(halide_buffer_t *input, halide_buffer_t *output) {
     }
     DeviceCtx ctx;
     if ((r = to_device(uc, &ctx, args, 2))) return r;
-    if (W > 0 && H > 0) {
-        Box I[IL], D[IL];
-        I[0] = {0, W - 1, 0, H - 1};
-        for (int l = 1; l < IL; l++) I[l] = {0, floor_div(I[l - 1].x1 + 1, 2), 0, floor_div(I[l - 1].y1 + 1, 2)};
-        D[IL - 1] = I[IL - 1];
-        const int cw = W / 8, ch = H / 8;
-        auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
-        for (int l = IL - 2; l >= 0; l--) {
-            Box n = {2 * D[l + 1].x0 - 1, 2 * D[l + 1].x1 + 1, 2 * D[l + 1].y0 - 1, 2 * D[l + 1].y1 + 1};
-            if (l + 1 == 4) n = {clampi(n.x0, 0, cw), clampi(n.x1, 0, cw), clampi(n.y0, 0, ch), clampi(n.y1, 0, ch)};
-            D[l] = {n.x0 < I[l].x0 ? n.x0 : I[l].x0, n.x1 > I[l].x1 ? n.x1 : I[l].x1, n.y0 < I[l].y0 ? n.y0 : I[l].y0,
-                    n.y1 > I[l].y1 ? n.y1 : I[l].y1};
-        }
-        size_t off_d[IL], off_i[IL], total = 0;
-        auto area = [](const Box &b) { return ((size_t)(b.x1 - b.x0 + 1) * (b.y1 - b.y0 + 1) + 15) & ~(size_t)15; };
-        for (int l = 1; l < IL; l++) off_d[l] = total, total += area(D[l]);
-        for (int l = 3; l < IL - 1; l++) off_i[l] = total, total += area(I[l]);   // interpolated[2] and [1] live in ip_final's LDS
-        void *ws = nullptr;
-        if ((r = get_workspace(uc, ctx, total * sizeof(float4), &ws))) return r;
-        float4 *base = (float4 *)ws;
-        auto lvl = [&](float4 *p, const Box &b) { return Lvl{p, b.x0, b.y0, b.x1 - b.x0 + 1, b.y1 - b.y0 + 1}; };
-        Lvl ds[IL] = {}, ip[IL] = {};
-        for (int l = 1; l < IL; l++) ds[l] = lvl(base + off_d[l], D[l]);
-        for (int l = 3; l < IL - 1; l++) ip[l] = lvl(base + off_i[l], I[l]);
-        ip[IL - 1] = ds[IL - 1];   // interpolated[9] = downsampled[9], and D_9 == I_9
-        InGeom g{dev_ptr<float>(input), input->dim[1].stride, input->dim[2].stride, W, H};
-        hipStream_t st = ctx.stream;
-        char nm[32];
-        // levels >= T go through ip_tail (default 6: 25 x 41 pixels and below)
-        const char *te = getenv("HLMI_IP_TAIL_FROM");
-        int T = te ? atoi(te) : 6;
-        if (T < 3 || T > IL - 2) T = IL;   // (interpolated[2] and [1] are not stored: the tail cannot start below level 3)
-        // levels 3, 4, 5 in one launch per direction (ip_down_multi / ip_up_multi) when the tail starts at 6 and every tile's
-        // windows fit the kernels' LDS arrays (they do for any image: the check guards the constants, not the input)
-        bool fused = T == 6 && !env_flag("HLMI_IP_UNFUSED");
-        const int ntx5 = (ds[5].w + DM5 - 1) / DM5, nty5 = (ds[5].h + DM5 - 1) / DM5;
-        if (fused) {
-            auto owned = [](int llo, int lhi, int sh, int tlo, int thi, int a, int b, int &lo, int &hi) {
-                lo = a <= tlo ? llo : (llo > a * (1 << sh) ? llo : a * (1 << sh));
-                hi = b >= thi ? lhi : (lhi < (b + 1) * (1 << sh) - 1 ? lhi : (b + 1) * (1 << sh) - 1);
-            };
-            auto mn = [](int a, int b) { return a < b ? a : b; };
-            auto mx = [](int a, int b) { return a > b ? a : b; };
-            for (int axis = 0; axis < 2 && fused; axis++) {
-                const int b5lo = axis ? D[5].y0 : D[5].x0, b5hi = axis ? D[5].y1 : D[5].x1, b4lo = axis ? D[4].y0 : D[4].x0,
-                          b4hi = axis ? D[4].y1 : D[4].x1, b3lo = axis ? D[3].y0 : D[3].x0, b3hi = axis ? D[3].y1 : D[3].x1;
-                const int c = axis ? ch : cw;
-                for (int a = b5lo; a <= b5hi; a += DM5) {
-                    const int b = mn(a + DM5 - 1, b5hi);
-                    int o4l, o4h, o3l, o3h;
-                    owned(b4lo, b4hi, 1, b5lo, b5hi, a, b, o4l, o4h);
-                    owned(b3lo, b3hi, 2, b5lo, b5hi, a, b, o3l, o3h);
-                    const int w4l = mn(2 * a - 1, o4l), w4h = mx(2 * b + 1, o4h);
-                    const int w3l = mn(clampi(2 * w4l - 1, 0, c), o3l), w3h = mx(clampi(2 * w4h + 1, 0, c), o3h);
-                    if (w4h - w4l + 1 > DM4W || w3h - w3l + 1 > DM3W || w4l < b4lo || w4h > b4hi || w3l < b3lo || w3h > b3hi) fused = false;
-                }
-            }
-        }
-        for (int l = 1; l < IL && l < T; l++) {
-            if (fused && l >= 3) {
-                if (l == 3) {
-                    HLMI_LAUNCH(uc, "ip_down_multi:3", st, ip_down_multi, dim3(ntx5 * nty5), dim3(256), 0, ds[2], ds[3], ds[4], ds[5], cw, ch, ntx5);
-                }
-                continue;
-            }
-            dim3 grid((ds[l].w + 255) / 256, ds[l].h), block(256);
-            snprintf(nm, sizeof nm, "ip_down:%d", l);
-            if (l == 1) {
-                HLMI_LAUNCH(uc, nm, st, ip_down0_tile, dim3((ds[1].w + I0W - 1) / I0W, (ds[1].h + I0H - 1) / I0H), dim3(256), 0, g, ds[1]);
-            }
-            else if (l == 4) HLMI_LAUNCH(uc, nm, st, (ip_down<false, true>), grid, block, 0, g, ds[l - 1], ds[l], cw, ch);
-            else HLMI_LAUNCH(uc, nm, st, (ip_down<false, false>), grid, block, 0, g, ds[l - 1], ds[l], cw, ch);
-        }
-        if (T < IL) {
-            TailArgs ta;
-            for (int l = 0; l < IL; l++) ta.ds[l] = ds[l], ta.ip[l] = ip[l];
-            ta.cw = cw, ta.ch = ch, ta.from = T;
-            snprintf(nm, sizeof nm, "ip_tail:%d", T);
-            HLMI_LAUNCH(uc, nm, st, ip_tail, dim3(1), dim3(1024), 0, ta);
-        }
-        for (int l = (T < IL ? T - 1 : IL - 2); l >= 3; l--) {   // (levels 2 and 1 are made inside ip_final)
-            if (fused && l >= 3) {
-                if (l == 3) {
-                    const int ntx3 = (ip[3].w + UM3 - 1) / UM3, nty3 = (ip[3].h + UM3 - 1) / UM3;
-                    HLMI_LAUNCH(uc, "ip_up_multi:3", st, ip_up_multi, dim3(ntx3 * nty3), dim3(256), 0, ds[3], ds[4], ds[5], ip[6], ip[3], ntx3);
-                }
-                continue;
-            }
-            dim3 grid((ip[l].w + 255) / 256, ip[l].h), block(256);
-            snprintf(nm, sizeof nm, "ip_up:%d", l);
-            HLMI_LAUNCH(uc, nm, st, ip_up, grid, block, 0, ds[l], ip[l + 1], ip[l]);
-        }
-        timing_note_bytes(28.0 * W * H);
-        HLMI_LAUNCH(uc, "ip_final", st, ip_final, dim3((W + F0W - 1) / F0W, (H + F0H - 1) / F0H), dim3(256), 0, g, ds[1], ds[2], ip[3], dev_ptr<float>(output),
-                    (long)output->dim[1].stride, (long)output->dim[2].stride);
+    if (W == 0 || H == 0) {
+        mark_output_written(output);
+        return 0;
     }
+
+    IpPlan pl = {};
+    ip_plan(pl, W, H, env_int("HLMI_IP_TAIL_FROM").value_or(6), env_flag("HLMI_IP_UNFUSED"));
+
+    void *ws = nullptr;
+    if ((r = get_workspace(uc, ctx, pl.ws_float4 * sizeof(float4), &ws))) return r;
+    float4 *base = (float4 *)ws;
+    IpBuffers b = {};
+    auto lvl = [](float4 *p, const Box &bx) { return Lvl{p, bx.x0, bx.y0, bx.w(), bx.h()}; };
+    for (int l = 1; l < IL; l++) b.lv.ds[l] = lvl(base + pl.off_d[l], pl.D[l]);
+    for (int l = 3; l < IL - 1; l++) b.lv.ip[l] = lvl(base + pl.off_i[l], pl.I[l]);
+    b.lv.ip[IL - 1] = b.lv.ds[IL - 1];   // interpolated[9] = downsampled[9], and D_9 == I_9
+    b.lv.cw = pl.cw, b.lv.ch = pl.ch, b.lv.from = pl.T;
+    b.g = InGeom{dev_ptr<float>(input), input->dim[1].stride, input->dim[2].stride, W, H};
+
+    if ((r = ip_stage_down(uc, pl, b, ctx.stream)) || (r = ip_stage_up(uc, pl, b, output, ctx.stream))) return r;
     mark_output_written(output);
     return 0;
 }

@@ -26,7 +26,6 @@
 #include "hlmi_internal.h"
 
 #include <atomic>
-#include <stdlib.h>
 
 using namespace hlmi;
 
@@ -889,6 +888,215 @@ const ArgTable lb_table("lens_blur", {
     out_buf("final", T_F32, 3, {0, 192, 0, 320, 0, 3}),
 });
 
+// ---- run-time switches: environment variables, read into an LbSwitches by lens_blur() once per call — on every call, since the parity tests flip
+// them between calls of one process (env_flag / env_int, hlmi_internal.h).  All default to the fast path; every alternative is
+// bit-identical.
+//   HLMI_LB_    default                     selects                                                     flipped by (tests/test_lens_blur.py)
+//   UNFUSED     0                           1: one stage per launch — lb_cost, lb_down:1, lb_depth,     test_hip_front_ends_agree_with_the_oracle
+//                                           lb_wcy — instead of lb_cost_down[2] and lb_depth_rc (A/B)
+//   NDY         the fewest row-steps over   rows of push[1] per lb_cost_down[2] workgroup               test_hip_front_ends_agree_with_the_oracle
+//               all rounds (lb_plan)        (clamped to 1 .. 1024)
+//   ROWS2       1 up to 32 slices, else 0   non-zero: lb_cost_down2 (two source rows per step, 512      test_hip_front_ends_agree_with_the_oracle
+//                                           threads); 0: lb_cost_down (A/B)
+//   NO_A32      0                           1: never the *32 kernels (32-bit plane offsets) (A/B)       test_hip_pyramid_launches_above_the_tail_match_the_oracle
+//   WCY_LAUNCH  0                           1: lb_wcy as a launch of its own + lb_final<false>          test_hip_64_bit_pyramid_kernels_and_the_separate_maximum_…
+// The chain every setting gives: tests/test_launch_plans.py.
+struct LbSwitches {
+    bool unfused, no_a32, wcy_launch;
+    std::optional<int> ndy, rows2;
+};
+
+// the largest bokeh radius (generator :14-19)
+int lb_radius(int slices, int focus_depth, float scale) { return (int)((float)max(slices - focus_depth, focus_depth) * scale); }
+
+// ---- the plan of one call: every decision the launches need — boxes, workspace layout, which kernels run and how they are
+// launched — made by lb_plan() before anything is enqueued.  It holds no pointer (LbBuffers does); it lives on lens_blur()'s
+// stack and the stages read it by reference.
+struct LbPlan {
+    LBGeom g;
+    Box D, P[LV], PB[LV], E;   // oracle/lens_blur_oracle.c; E = PB[0]
+    unsigned zc;               // planes: cost x confidence per slice + the confidence
+    size_t off_push[LV], off_pull[LV], off_depth, off_br, off_wcy, ws_floats;   // workspace layout in floats; regions are multiples of 64
+    // chain shape
+    //   fused             lb_cost_down[2] + lb_depth_rc: push[0] is never stored (else lb_cost, lb_down:1, lb_depth)
+    //   rows2             (fused) lb_cost_down2, else lb_cost_down
+    //   s64, full         the cost stack's compile-time bound is 64 (else 32); slices == the bound: no guards
+    //   a32               the *32 kernels (32-bit plane offsets from 24-bit multiplies) take the boxes that are small enough for them:
+    //   down_small[i]       lb_down:i is lb_down32
+    //   pull_multi_small    lb_pull_multi:1 is lb_pull_multi32
+    //   tail, tail_lds    levels tail .. LV-1 go down and up in one launch, a workgroup per plane (LV: none); all of them fit lb_tail_lds
+    //   pull_multi        levels 3, 2, 1 in one launch (pull[3] and pull[2] then exist only in LDS)
+    //   wcy_launch        lb_wcy + lb_final<false>, else lb_final<true> makes the column maxima in LDS
+    bool fused, rows2, s64, full, a32, down_small[LV], pull_multi_small, tail_lds, pull_multi, wcy_launch;
+    // launch geometry of lb_cost_down[2]: column strips, columns per strip, rows of push[1] per workgroup, grid, and the dynamic LDS
+    // of one source row in bytes (lb_cost_down2 holds two)
+    int tail, strips, ndx, ndy;
+    dim3 cd_grid;
+    size_t cd_lds1;
+};
+
+// the resolved pointers of one call: the frames and where the plan's layout landed in the stream's arena
+struct LbBuffers {
+    const uint8_t *left, *right;
+    float *push[LV], *pull[LV], *br, *wcy;   // push[0]: unfused only; pull[0]: never
+    uint32_t *depth;
+};
+
+// No HIP call, no lock, no allocation: a function of the checked arguments, the switches, the random tag and the CU count the stream
+// is sized for.
+void lb_plan(LbPlan &pl, const halide_buffer_t *left_im, const halide_buffer_t *right_im, int slices, int focus_depth, float blur_radius_scale,
+             int aperture_samples, const halide_buffer_t *final_, const LbSwitches &sw, int stream_cus, int rand_tag) {
+    LBGeom &g = pl.g;
+    g.lx0 = left_im->dim[0].min, g.lx1 = g.lx0 + left_im->dim[0].extent - 1, g.ly0 = left_im->dim[1].min, g.ly1 = g.ly0 + left_im->dim[1].extent - 1;
+    g.rx0 = right_im->dim[0].min, g.rx1 = g.rx0 + right_im->dim[0].extent - 1, g.ry0 = right_im->dim[1].min, g.ry1 = g.ry0 + right_im->dim[1].extent - 1;
+    g.l_sy = left_im->dim[1].stride, g.l_sc = left_im->dim[2].stride, g.r_sy = right_im->dim[1].stride, g.r_sc = right_im->dim[2].stride;
+    for (int c = 0; c < 3; c++) {
+        auto cl = [](const halide_buffer_t *b, int c) { const int lo = b->dim[2].min, hi = lo + b->dim[2].extent - 1; return (c < lo ? lo : (c > hi ? hi : c)) - lo; };
+        g.l_c[c] = (long)cl(left_im, c) * g.l_sc, g.r_c[c] = (long)cl(right_im, c) * g.r_sc;
+    }
+    g.slices = slices, g.focus = focus_depth, g.samples = aperture_samples, g.scale = blur_radius_scale, g.fslices = (float)slices;
+    g.R = lb_radius(slices, focus_depth, blur_radius_scale), g.tag = rand_tag;
+    pl.zc = (unsigned)slices + 1u, pl.s64 = slices > 32, pl.full = slices == 32 || slices == 64;
+
+    // ---- boxes (oracle/lens_blur_oracle.c); the pyramids' clamp extents come from left_im's extents (:57-61)
+    Box &D = pl.D, *P = pl.P, *PB = pl.PB;
+    P[0] = D = {final_->dim[0].min - g.R, final_->dim[1].min - g.R, final_->dim[0].extent + 2 * g.R, final_->dim[1].extent + 2 * g.R};
+    for (int i = 1; i < LV; i++) {
+        const int x0 = floor_div(P[i - 1].x0, 2) - 1, x1 = floor_div(P[i - 1].x0 + P[i - 1].w - 1, 2) + 1;
+        const int y0 = floor_div(P[i - 1].y0, 2) - 1, y1 = floor_div(P[i - 1].y0 + P[i - 1].h - 1, 2) + 1;
+        P[i] = {x0, y0, x1 - x0 + 1, y1 - y0 + 1};
+    }
+    for (int i = 1; i < LV; i++) PB[i] = {0, 0, max(left_im->dim[0].extent >> i, 1), max(left_im->dim[1].extent >> i, 1)};   // halved i times
+    const int ex0 = min(D.x0, -1), ey0 = min(D.y0, -1), ex1 = max(D.x0 + D.w - 1, 2 * PB[1].w), ey1 = max(D.y0 + D.h - 1, 2 * PB[1].h);
+    pl.E = PB[0] = {ex0, ey0, ex1 - ex0 + 1, ey1 - ey0 + 1};
+
+    // ---- workspace
+    // fused front end (lb_cost_down, lb_depth_rc): push[0] is never stored.  HLMI_LB_UNFUSED=1: one stage per launch (A/B)
+    pl.fused = (size_t)(slices + 1) * PB[1].w * PB[1].h < ((size_t)1 << 31) && !sw.unfused;
+    auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    size_t &total = pl.ws_floats = 0;
+    for (int i = 0; i < LV; i++) pl.off_push[i] = total, total += (i == 0 && pl.fused) ? 0 : al((size_t)(slices + 1) * PB[i].w * PB[i].h);
+    for (int i = 1; i < LV; i++) pl.off_pull[i] = total, total += al((size_t)(slices + 1) * P[i].w * P[i].h);
+    pl.off_depth = total, total += al((size_t)D.w * D.h);
+    pl.off_br = total, total += al((size_t)D.w * D.h);
+    pl.off_wcy = total, total += al((size_t)D.w * final_->dim[1].extent);
+
+    // ---- front end
+    if (pl.fused) {
+        const int strips = pl.strips = (PB[1].w + 126) / 127;
+        pl.ndx = (PB[1].w + strips - 1) / strips;
+        // rows of push[1] per workgroup: a workgroup walks 2 ndy + 2 source rows (the 2 are halo), and the chip holds
+        // `cap` workgroups at once (registers: two per CU at 32 slices, one at 64) — the fewest row-steps over all rounds
+        pl.ndy = 8;
+        const long cap = (long)stream_cus * (pl.s64 ? 1 : 2);
+        long best_steps = -1;
+        for (int c = 2; c <= 32; c++) {
+            const long wgs = (long)strips * ((PB[1].h + c - 1) / c), steps = ((wgs + cap - 1) / cap) * (2 * c + 2);
+            if (best_steps < 0 || steps < best_steps) best_steps = steps, pl.ndy = c;
+        }
+        if (sw.ndy) pl.ndy = max(1, min(1024, *sw.ndy));
+        pl.cd_grid = dim3(strips, (PB[1].h + pl.ndy - 1) / pl.ndy);
+        pl.rows2 = sw.rows2 ? *sw.rows2 != 0 : !pl.s64;   // two source rows per step, 512 threads (default up to 32 slices; 0 / 1: A/B)
+        pl.cd_lds1 = (size_t)pl.zc * CD_RP * sizeof(float);
+    }
+
+    // ---- pyramids
+    // the *32 kernels (32-bit plane offsets from 24-bit multiplies) take boxes that are small enough for them; HLMI_LB_NO_A32=1: never (A/B)
+    pl.a32 = !sw.no_a32;
+    auto box_small = [&](const Box &b) { return pl.a32 && b.w < (1 << 23) && b.h < (1 << 23) && (long)b.w * b.h < (1L << 29); };
+    for (int i = 2; i < LV; i++) pl.down_small[i] = box_small(PB[i - 1]) && box_small(PB[i]);
+    // levels below `tail` (at most 128 x 128 elements per plane) go down and up in ONE launch, a workgroup per plane
+    pl.tail = LV;
+    while (pl.tail > 2 && (long)PB[pl.tail - 2].w * PB[pl.tail - 2].h <= 128 * 128 * 4 && (long)P[pl.tail - 1].w * P[pl.tail - 1].h <= 128 * 128) pl.tail--;
+    long need = 0;
+    for (int i = pl.tail; i < LV; i++) need += (long)PB[i].w * PB[i].h + (long)P[i].w * P[i].h;
+    pl.tail_lds = need <= TAIL_LDS;
+    // levels 3, 2, 1 in one launch when all three lie above the tail (pull[3] and pull[2] then exist only in LDS)
+    pl.pull_multi = pl.tail >= 4;
+    // 32-bit plane offsets from 24-bit multiplies (lb_pull_multi32) when every plane involved is small enough for them
+    pl.pull_multi_small = box_small(PB[1]) && box_small(PB[2]) && box_small(PB[3]) && box_small(P[4]) && box_small(P[1]);
+    pl.wcy_launch = !pl.fused || sw.wcy_launch;
+}
+
+// ---- the stages of the chain, in launch order.  Each takes the plan, the resolved pointers and the stream; a non-zero return is
+// the error code of the call.  <SB, FULL> of the cost-stack kernels come from (s64, full) through with_flags().
+
+// stage 1: the cost stack — with level 1 of the push pyramid (lb_cost_down / lb_cost_down2), or level 0 alone (lb_cost)
+int lb_stage_front(void *uc, const LbPlan &pl, const LbBuffers &b, hipStream_t st) {
+    return with_flags([&](auto S64, auto FULL) -> int {
+        constexpr int SB = S64.value ? 64 : 32;
+        if (!pl.fused) {
+            HLMI_LAUNCH(uc, "lb_cost", st, (lb_cost<SB, FULL.value>), dim3((pl.E.w + 255) / 256, pl.E.h), dim3(256), 0, b.left, b.right, pl.g, pl.E, b.push[0]);
+            return 0;
+        }
+        // more than the default 64 KB window of dynamic LDS: lb_cost_down at 64 slices, lb_cost_down2 (twice as much) always
+        const size_t lds = pl.rows2 ? 2 * pl.cd_lds1 : pl.cd_lds1;
+        if (S64.value) {
+            HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down<SB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.cd_lds1));
+            HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down<SB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.cd_lds1));
+        }
+        if (pl.rows2) {
+            HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down2<SB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down2<SB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        const auto kernel = pl.rows2 ? lb_cost_down2<SB, FULL.value> : lb_cost_down<SB, FULL.value>;
+        HLMI_LAUNCH(uc, pl.rows2 ? "lb_cost_down2" : "lb_cost_down", st, kernel, pl.cd_grid, dim3(pl.rows2 ? 512 : 256), lds, b.left, b.right, pl.g, b.push[1], pl.PB[1], pl.ndx, pl.ndy);
+        return 0;
+    }, pl.s64, pl.full);
+}
+
+// stage 2: the push pyramid above the tail (level 1 comes from the fused front end), then levels tail .. LV-1 of both pyramids (lb_tail).
+// lb_down:i makes push[i] from push[i - 1]; level 0 (stored by lb_cost alone) is the one source that is not a clamped box
+int lb_stage_push(void *uc, const LbPlan &pl, const LbBuffers &b, hipStream_t st) {
+    const Box *PB = pl.PB;
+    char nm[24];
+    for (int i = pl.fused ? 2 : 1; i < pl.tail; i++) {
+        snprintf(nm, sizeof nm, "lb_down:%d", i);
+        const auto kernel = i == 1 ? lb_down<false> : pl.down_small[i] ? lb_down32<true> : lb_down<true>;
+        HLMI_LAUNCH(uc, nm, st, kernel, dim3((PB[i].w + DTW - 1) / DTW, (PB[i].h + DTH - 1) / DTH, pl.zc), dim3(256), 0, b.push[i - 1], PB[i - 1], b.push[i], PB[i]);
+    }
+    TailArgs ta;
+    for (int i = 0; i < LV; i++) ta.push[i] = b.push[i], ta.pull[i] = b.pull[i], ta.PB[i] = PB[i], ta.P[i] = pl.P[i];
+    ta.from = pl.tail;
+    snprintf(nm, sizeof nm, "lb_tail:%d", pl.tail);
+    if (pl.tail < LV) HLMI_LAUNCH(uc, nm, st, pl.tail_lds ? lb_tail_lds : lb_tail, dim3(pl.zc), dim3(1024), 0, ta);
+    return 0;
+}
+
+// stage 3: the pull pyramid from below the tail down to level 1.  lb_pull:i makes pull[i] from push[i] and pull[i + 1]; the top level has
+// nothing above it
+int lb_stage_pull(void *uc, const LbPlan &pl, const LbBuffers &b, hipStream_t st) {
+    const Box *P = pl.P, *PB = pl.PB;
+    for (int i = min(LV - 1, pl.tail - 1); i >= (pl.pull_multi ? 4 : 1); i--) {
+        char nm[24];
+        snprintf(nm, sizeof nm, "lb_pull:%d", i);
+        const bool top = i == LV - 1;
+        HLMI_LAUNCH(uc, nm, st, top ? lb_pull<true> : lb_pull<false>, dim3((P[i].w + 63) / 64, (P[i].h + 3) / 4, pl.zc), dim3(256), 0, b.push[i], PB[i],
+                    top ? (const float *)nullptr : b.pull[i + 1], P[top ? i : i + 1], b.pull[i], P[i]);
+    }
+    if (pl.pull_multi)
+        HLMI_LAUNCH(uc, "lb_pull_multi:1", st, pl.pull_multi_small ? lb_pull_multi32 : lb_pull_multi, dim3((P[1].w + PMW - 1) / PMW, (P[1].h + PMH - 1) / PMH, pl.zc), dim3(256), 0,
+                    b.push[1], PB[1], b.push[2], PB[2], b.push[3], PB[3], b.pull[4], P[4], b.pull[1], P[1]);
+    return 0;
+}
+
+// stage 4: depth and bokeh radius on D — from the stored push[0] (lb_depth), or with the cost stack made again (lb_depth_rc) —, then the
+// aperture samples (lb_final); the vertical maximum of the bokeh radius is a launch of its own (lb_wcy) or made inside lb_final
+int lb_stage_final(void *uc, const LbPlan &pl, const LbBuffers &b, const halide_buffer_t *final_, hipStream_t st) {
+    const Box &D = pl.D;
+    const auto depth_rc = [&](auto S64, auto FULL) -> int {
+        HLMI_LAUNCH(uc, "lb_depth_rc", st, (lb_depth_rc<S64.value ? 64 : 32, FULL.value>), dim3((D.w + 63) / 64, (D.h + 3) / 4), dim3(256), 0, b.left, b.right, b.pull[1], pl.P[1], pl.g, D, b.depth, b.br);
+        return 0;
+    };
+    if (!pl.fused) HLMI_LAUNCH(uc, "lb_depth", st, lb_depth, dim3((D.w + 255) / 256, D.h), dim3(256), 0, b.push[0], pl.E, b.pull[1], pl.P[1], b.left, pl.g, D, b.depth, b.br);
+    else if (int r = with_flags(depth_rc, pl.s64, pl.full)) return r;
+    const int ox0 = final_->dim[0].min, oy0 = final_->dim[1].min, ow = final_->dim[0].extent, oh = final_->dim[1].extent;
+    if (pl.wcy_launch) HLMI_LAUNCH(uc, "lb_wcy", st, lb_wcy, dim3((D.w + 255) / 256, oh), dim3(256), 0, b.br, D, pl.g.R, oy0, oh, b.wcy);
+    HLMI_LAUNCH(uc, "lb_final", st, pl.wcy_launch ? lb_final<false> : lb_final<true>, dim3((ow + 255) / 256, oh), dim3(256), 0, pl.g, b.depth, pl.wcy_launch ? b.wcy : b.br, D,
+                ox0, oy0, ow, final_->dim[2].extent, dev_ptr<float>(final_), (long)final_->dim[1].stride, (long)final_->dim[2].stride);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" void hlmi_lens_blur_set_random_tag(int tag) { g_rand_tag.store(tag); }
@@ -897,6 +1105,7 @@ extern "C" int hlmi_lens_blur_get_random_tag(void) { return g_rand_tag.load(); }
 extern "C" int lens_blur(halide_buffer_t *left_im, halide_buffer_t *right_im, int32_t slices, int32_t focus_depth,
                          float blur_radius_scale, int32_t aperture_samples, halide_buffer_t *final_) {
     void *uc = nullptr;
+    const LbSwitches sw = {env_flag("HLMI_LB_UNFUSED"), env_flag("HLMI_LB_NO_A32"), env_flag("HLMI_LB_WCY_LAUNCH"), env_int("HLMI_LB_NDY"), env_int("HLMI_LB_ROWS2")};
     BufArg args[3];
     lb_table.bufs(args, {left_im, right_im, final_});
     int r = check_not_null(uc, args, 3);
@@ -907,9 +1116,7 @@ extern "C" int lens_blur(halide_buffer_t *left_im, halide_buffer_t *right_im, in
     if (any_bounds_query(args, 3)) {
         // every tap of the inputs is clamped (:27-28); propose the output's x / y region and the three channels
         int mins[3] = {final_->dim[0].min, final_->dim[1].min, 0}, ext[3] = {final_->dim[0].extent, final_->dim[1].extent, 3};
-        answer_query(left_im, mins, ext);
-        answer_query(right_im, mins, ext);
-        answer_query(final_, mins, ext);
+        for (halide_buffer_t *b : {left_im, right_im, final_}) answer_query(b, mins, ext);
         return 0;
     }
     if ((r = check_shapes(uc, args, 3))) return r;
@@ -918,199 +1125,40 @@ extern "C" int lens_blur(halide_buffer_t *left_im, halide_buffer_t *right_im, in
         return report(uc, halide_error_code_constraint_violated, "Output buffer final has %d channels, at most 3 are defined", final_->dim[2].extent);
     }
     const int ow = final_->dim[0].extent, oh = final_->dim[1].extent, nc = final_->dim[2].extent;
-    if (ow > 0 && oh > 0 && nc > 0) {
+    const bool empty = ow == 0 || oh == 0 || nc == 0;
+    if (!empty) {
         for (int i = 0; i < 2; i++) {
             const halide_buffer_t *b = args[i].buf;
             if (b->dim[0].extent < 1 || b->dim[1].extent < 1 || b->dim[2].extent < 1) {
                 return report(uc, halide_error_code_access_out_of_bounds, "Input buffer %s is empty but is accessed (clamped)", args[i].name);
             }
         }
+        // lb_final addresses a sample's row of D (the output widened by the radius on either side) with a 24-bit multiply
+        const int R = lb_radius(slices, focus_depth, blur_radius_scale);
+        if ((long)ow + 2 * R >= (1 << 23)) {
+            return report(uc, halide_error_code_buffer_extents_too_large, "Output buffer final is %d wide: at most %d columns are supported", ow, (1 << 23) - 1 - 2 * R);
+        }
     }
     DeviceCtx ctx;
     if ((r = to_device(uc, &ctx, args, 3))) return r;
-    if (ow == 0 || oh == 0 || nc == 0) {
+    if (empty) {
         mark_output_written(final_);
         return 0;
     }
-    LBGeom g;
-    auto box_of = [](const halide_buffer_t *b, int &x0, int &x1, int &y0, int &y1) {
-        x0 = b->dim[0].min, x1 = x0 + b->dim[0].extent - 1, y0 = b->dim[1].min, y1 = y0 + b->dim[1].extent - 1;
-    };
-    box_of(left_im, g.lx0, g.lx1, g.ly0, g.ly1);
-    box_of(right_im, g.rx0, g.rx1, g.ry0, g.ry1);
-    g.l_sy = left_im->dim[1].stride, g.l_sc = left_im->dim[2].stride, g.r_sy = right_im->dim[1].stride, g.r_sc = right_im->dim[2].stride;
-    for (int c = 0; c < 3; c++) {
-        auto cl = [](const halide_buffer_t *b, int c) { const int lo = b->dim[2].min, hi = lo + b->dim[2].extent - 1; return (c < lo ? lo : (c > hi ? hi : c)) - lo; };
-        g.l_c[c] = (long)cl(left_im, c) * g.l_sc, g.r_c[c] = (long)cl(right_im, c) * g.r_sc;
-    }
-    g.slices = slices, g.focus = focus_depth, g.samples = aperture_samples, g.scale = blur_radius_scale, g.fslices = (float)slices;
-    g.R = (int)((float)(slices - focus_depth > focus_depth ? slices - focus_depth : focus_depth) * blur_radius_scale);
-    g.tag = g_rand_tag.load();
-    const int ox0 = final_->dim[0].min, oy0 = final_->dim[1].min;
 
-    // ---- boxes (oracle/lens_blur_oracle.c); the pyramids' clamp extents come from left_im's extents (:57-61)
-    Box D = {ox0 - g.R, oy0 - g.R, ow + 2 * g.R, oh + 2 * g.R};
-    if (D.w >= (1 << 23)) {   // lb_final addresses a sample's row with a 24-bit multiply
-        return report(uc, halide_error_code_buffer_extents_too_large, "Output buffer final is %d wide: at most %d columns are supported", ow, (1 << 23) - 1 - 2 * g.R);
-    }
-    Box P[LV], PB[LV];
-    P[0] = D;
-    for (int i = 1; i < LV; i++) {
-        const int x0 = floor_div(P[i - 1].x0, 2) - 1, x1 = floor_div(P[i - 1].x0 + P[i - 1].w - 1, 2) + 1;
-        const int y0 = floor_div(P[i - 1].y0, 2) - 1, y1 = floor_div(P[i - 1].y0 + P[i - 1].h - 1, 2) + 1;
-        P[i] = {x0, y0, x1 - x0 + 1, y1 - y0 + 1};
-    }
-    int w = left_im->dim[0].extent, h = left_im->dim[1].extent;
-    for (int i = 1; i < LV; i++) {
-        w /= 2, h /= 2;
-        PB[i] = {0, 0, w > 1 ? w : 1, h > 1 ? h : 1};
-    }
-    {
-        int x0 = min(P[0].x0, -1), y0 = min(P[0].y0, -1);
-        int x1 = max(P[0].x0 + P[0].w - 1, 2 * PB[1].w), y1 = max(P[0].y0 + P[0].h - 1, 2 * PB[1].h);
-        PB[0] = {x0, y0, x1 - x0 + 1, y1 - y0 + 1};
-    }
-    const Box E = PB[0];
-    // ---- workspace
-    auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    size_t off_push[LV], off_pull[LV], total = 0;
-    // fused front end (lb_cost_down, lb_depth_rc): push[0] is never stored.  HLMI_LB_UNFUSED=1: one stage per launch (A/B)
-    bool fused = (size_t)(slices + 1) * PB[1].w * PB[1].h < ((size_t)1 << 31);
-    {
-        const char *e = getenv("HLMI_LB_UNFUSED");
-        if (e && *e && atoi(e) != 0) fused = false;
-    }
-    for (int i = 0; i < LV; i++) off_push[i] = total, total += (i == 0 && fused) ? 0 : al((size_t)(slices + 1) * PB[i].w * PB[i].h);
-    for (int i = 1; i < LV; i++) off_pull[i] = total, total += al((size_t)(slices + 1) * P[i].w * P[i].h);
-    const size_t off_depth = total;
-    total += al((size_t)D.w * D.h);
-    const size_t off_br = total;
-    total += al((size_t)D.w * D.h);
-    const size_t off_wcy = total;
-    total += al((size_t)D.w * oh);
+    LbPlan pl = {};
+    lb_plan(pl, left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final_, sw, stream_cu_count(ctx.device, ctx.stream), g_rand_tag.load());
+
     void *ws = nullptr;
-    if ((r = get_workspace(uc, ctx, total * sizeof(float), &ws))) return r;
+    if ((r = get_workspace(uc, ctx, pl.ws_floats * sizeof(float), &ws))) return r;
     float *wsf = (float *)ws;
-    float *push[LV], *pull[LV];
-    for (int i = 0; i < LV; i++) push[i] = wsf + off_push[i];
-    for (int i = 1; i < LV; i++) pull[i] = wsf + off_pull[i];
-    pull[0] = nullptr;
-    uint32_t *depth = (uint32_t *)(wsf + off_depth);
-    float *br = wsf + off_br, *wcy = wsf + off_wcy;
+    LbBuffers b;
+    b.left = dev_ptr<uint8_t>(left_im), b.right = dev_ptr<uint8_t>(right_im);
+    for (int i = 0; i < LV; i++) b.push[i] = wsf + pl.off_push[i], b.pull[i] = i ? wsf + pl.off_pull[i] : nullptr;
+    b.depth = (uint32_t *)(wsf + pl.off_depth), b.br = wsf + pl.off_br, b.wcy = wsf + pl.off_wcy;
 
-    const uint8_t *dl = dev_ptr<uint8_t>(left_im), *dr = dev_ptr<uint8_t>(right_im);
     hipStream_t st = ctx.stream;
-    const unsigned zc = (unsigned)slices + 1u;   // planes: cost x confidence per slice + the confidence
-    const bool s64 = slices > 32, full = slices == 32 || slices == 64;
-#define LB_DISPATCH(K, ...)                                                             \
-    do {                                                                                \
-        if (!s64 && full) HLMI_LAUNCH(uc, #K, st, (K<32, true>), __VA_ARGS__);          \
-        else if (!s64) HLMI_LAUNCH(uc, #K, st, (K<32, false>), __VA_ARGS__);            \
-        else if (full) HLMI_LAUNCH(uc, #K, st, (K<64, true>), __VA_ARGS__);             \
-        else HLMI_LAUNCH(uc, #K, st, (K<64, false>), __VA_ARGS__);                      \
-    } while (0)
-    if (fused) {
-        const int strips = (PB[1].w + 126) / 127, ndx = (PB[1].w + strips - 1) / strips;
-        // rows of push[1] per workgroup: a workgroup walks 2 ndy + 2 source rows (the 2 are halo), and the chip holds
-        // `cap` workgroups at once (registers: two per CU at 32 slices, one at 64) — the fewest row-steps over all rounds
-        int ndy = 8;
-        {
-            const long cap = (long)stream_cu_count(ctx.device, ctx.stream) * (s64 ? 1 : 2);
-            long best_steps = -1;
-            for (int c = 2; c <= 32; c++) {
-                const long wgs = (long)strips * ((PB[1].h + c - 1) / c), steps = ((wgs + cap - 1) / cap) * (2 * c + 2);
-                if (best_steps < 0 || steps < best_steps) best_steps = steps, ndy = c;
-            }
-            const char *e = getenv("HLMI_LB_NDY");
-            if (e && *e) ndy = max(1, min(1024, atoi(e)));
-        }
-        const size_t lds = (size_t)zc * CD_RP * sizeof(float);
-        const dim3 grid(strips, (PB[1].h + ndy - 1) / ndy);
-        if (s64) {
-            HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        }
-        const char *two = getenv("HLMI_LB_ROWS2");   // two source rows per step, 512 threads (default up to 32 slices; 0 / 1: A/B)
-        if (two && *two ? *two != '0' : !s64) {
-            const size_t lds2 = 2 * lds;
-            if (s64) {
-                HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down2<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-                HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down2<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-            } else {
-                HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down2<32, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-                HLMI_HIP(uc, hipFuncSetAttribute((const void *)lb_cost_down2<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-            }
-            LB_DISPATCH(lb_cost_down2, grid, dim3(512), lds2, dl, dr, g, push[1], PB[1], ndx, ndy);
-        } else {
-            LB_DISPATCH(lb_cost_down, grid, dim3(256), lds, dl, dr, g, push[1], PB[1], ndx, ndy);
-        }
-    } else {
-        LB_DISPATCH(lb_cost, dim3((E.w + 255) / 256, E.h), dim3(256), 0, dl, dr, g, E, push[0]);
-    }
-    // the *32 kernels (32-bit plane offsets from 24-bit multiplies) take boxes that are small enough for them; HLMI_LB_NO_A32=1: never (A/B)
-    const bool a32 = !env_flag("HLMI_LB_NO_A32");
-    auto box_small = [&](const Box &b) { return a32 && b.w < (1 << 23) && b.h < (1 << 23) && (long)b.w * b.h < (1L << 29); };
-    // levels below `tail` (at most 128 x 128 elements per plane) go down and up in ONE launch, a workgroup per plane
-    int tail = LV;
-    for (int i = LV - 1; i >= 2; i--) {
-        if ((long)PB[i - 1].w * PB[i - 1].h <= 128 * 128 * 4 && (long)P[i].w * P[i].h <= 128 * 128) tail = i;
-        else break;
-    }
-    for (int i = fused ? 2 : 1; i < tail; i++) {
-        char nm[24];
-        snprintf(nm, sizeof nm, "lb_down:%d", i);
-        if (i == 1) HLMI_LAUNCH(uc, nm, st, lb_down<false>, dim3((PB[i].w + DTW - 1) / DTW, (PB[i].h + DTH - 1) / DTH, zc), dim3(256), 0, push[0], PB[0], push[i], PB[i]);
-        else if (box_small(PB[i - 1]) && box_small(PB[i]))
-            HLMI_LAUNCH(uc, nm, st, lb_down32<true>, dim3((PB[i].w + DTW - 1) / DTW, (PB[i].h + DTH - 1) / DTH, zc), dim3(256), 0, push[i - 1], PB[i - 1], push[i], PB[i]);
-        else HLMI_LAUNCH(uc, nm, st, lb_down<true>, dim3((PB[i].w + DTW - 1) / DTW, (PB[i].h + DTH - 1) / DTH, zc), dim3(256), 0, push[i - 1], PB[i - 1], push[i], PB[i]);
-    }
-    if (tail < LV) {
-        TailArgs ta;
-        for (int i = 0; i < LV; i++) ta.push[i] = push[i], ta.pull[i] = pull[i], ta.PB[i] = PB[i], ta.P[i] = P[i];
-        ta.from = tail;
-        char nm[24];
-        snprintf(nm, sizeof nm, "lb_tail:%d", tail);
-        long need = 0;
-        for (int i = tail; i < LV; i++) need += (long)PB[i].w * PB[i].h + (long)P[i].w * P[i].h;
-        if (need <= TAIL_LDS) HLMI_LAUNCH(uc, nm, st, lb_tail_lds, dim3(zc), dim3(1024), 0, ta);
-        else HLMI_LAUNCH(uc, nm, st, lb_tail, dim3(zc), dim3(1024), 0, ta);
-    }
-    // levels 3, 2, 1 in one launch when all three lie above the tail (pull[3] and pull[2] then exist only in LDS)
-    const bool pull_multi = tail >= 4;
-    if (pull_multi) {
-        for (int i = min(LV - 1, tail - 1); i >= 4; i--) {
-            char nm[24];
-            snprintf(nm, sizeof nm, "lb_pull:%d", i);
-            if (i == LV - 1) HLMI_LAUNCH(uc, nm, st, lb_pull<true>, dim3((P[i].w + 63) / 64, (P[i].h + 3) / 4, zc), dim3(256), 0, push[i], PB[i], (const float *)nullptr, P[i], pull[i], P[i]);
-            else HLMI_LAUNCH(uc, nm, st, lb_pull<false>, dim3((P[i].w + 63) / 64, (P[i].h + 3) / 4, zc), dim3(256), 0, push[i], PB[i], pull[i + 1], P[i + 1], pull[i], P[i]);
-        }
-        // 32-bit plane offsets from 24-bit multiplies (lb_pull_multi32) when every plane involved is small enough for them
-        bool small = true;
-        for (const Box *b : {&PB[1], &PB[2], &PB[3], &P[4], &P[1]}) small = small && box_small(*b);
-        if (small)
-            HLMI_LAUNCH(uc, "lb_pull_multi:1", st, lb_pull_multi32, dim3((P[1].w + PMW - 1) / PMW, (P[1].h + PMH - 1) / PMH, zc), dim3(256), 0, push[1],
-                        PB[1], push[2], PB[2], push[3], PB[3], pull[4], P[4], pull[1], P[1]);
-        else
-            HLMI_LAUNCH(uc, "lb_pull_multi:1", st, lb_pull_multi, dim3((P[1].w + PMW - 1) / PMW, (P[1].h + PMH - 1) / PMH, zc), dim3(256), 0, push[1], PB[1],
-                        push[2], PB[2], push[3], PB[3], pull[4], P[4], pull[1], P[1]);
-    }
-    for (int i = pull_multi ? 0 : min(LV - 1, tail - 1); i >= 1; i--) {
-        char nm[24];
-        snprintf(nm, sizeof nm, "lb_pull:%d", i);
-        if (i == LV - 1) HLMI_LAUNCH(uc, nm, st, lb_pull<true>, dim3((P[i].w + 63) / 64, (P[i].h + 3) / 4, zc), dim3(256), 0, push[i], PB[i], (const float *)nullptr, P[i], pull[i], P[i]);
-        else HLMI_LAUNCH(uc, nm, st, lb_pull<false>, dim3((P[i].w + 63) / 64, (P[i].h + 3) / 4, zc), dim3(256), 0, push[i], PB[i], pull[i + 1], P[i + 1], pull[i], P[i]);
-    }
-    if (!fused) HLMI_LAUNCH(uc, "lb_depth", st, lb_depth, dim3((D.w + 255) / 256, D.h), dim3(256), 0, push[0], E, pull[1], P[1], dl, g, D, depth, br);
-    else LB_DISPATCH(lb_depth_rc, dim3((D.w + 63) / 64, (D.h + 3) / 4), dim3(256), 0, dl, dr, pull[1], P[1], g, D, depth, br);
-#undef LB_DISPATCH
-    if (!fused || env_flag("HLMI_LB_WCY_LAUNCH")) {
-        HLMI_LAUNCH(uc, "lb_wcy", st, lb_wcy, dim3((D.w + 255) / 256, oh), dim3(256), 0, br, D, g.R, oy0, oh, wcy);
-        HLMI_LAUNCH(uc, "lb_final", st, lb_final<false>, dim3((ow + 255) / 256, oh), dim3(256), 0, g, depth, wcy, D, ox0, oy0, ow, nc,
-                    dev_ptr<float>(final_), (long)final_->dim[1].stride, (long)final_->dim[2].stride);
-    } else {
-        HLMI_LAUNCH(uc, "lb_final", st, lb_final<true>, dim3((ow + 255) / 256, oh), dim3(256), 0, g, depth, br, D, ox0, oy0, ow, nc,
-                    dev_ptr<float>(final_), (long)final_->dim[1].stride, (long)final_->dim[2].stride);
-    }
+    if ((r = lb_stage_front(uc, pl, b, st)) || (r = lb_stage_push(uc, pl, b, st)) || (r = lb_stage_pull(uc, pl, b, st)) || (r = lb_stage_final(uc, pl, b, final_, st))) return r;
     mark_output_written(final_);
     return 0;
 }

@@ -2427,11 +2427,7 @@ struct LlSwitches {
     std::optional<int> fuse_from, upchain_from, ru, units0, no_vec, emit, nt, fuse_up2, d01_exch, d01_pad_lds, no_lut_cache;
 };
 LlSwitches ll_switches() {
-    auto get = [](const char *name) -> std::optional<int> {
-        const char *e = getenv(name);
-        if (e && *e) return atoi(e);
-        return std::nullopt;
-    };
+    const auto get = env_int;
     LlSwitches s;
     s.fuse_from = get("HLMI_LL_FUSE_FROM"), s.upchain_from = get("HLMI_LL_UPCHAIN_FROM");
     s.ru = get("HLMI_LL_RU"), s.units0 = get("HLMI_LL_UNITS0"), s.no_vec = get("HLMI_LL_NO_VEC");

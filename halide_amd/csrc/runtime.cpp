@@ -356,9 +356,7 @@ static int device_count_locked() {
 
 static int pick_device() {
     if (t_gpu_device >= 0) return t_gpu_device;
-    const char *e = getenv("HL_GPU_DEVICE");
-    if (e && *e) return atoi(e);
-    return 0;
+    return env_int("HL_GPU_DEVICE").value_or(0);
 }
 
 int acquire_device(void *uc, DeviceCtx *ctx, bool lock) {
@@ -493,7 +491,7 @@ int stream_cu_count(int device, hipStream_t stream) {
         auto it = g_part_cus.find(stream);
         if (it != g_part_cus.end()) return it->second;
     }
-    static const int share = [] { const char *e = getenv("HLMI_STREAM_SHARE"); return e && atoi(e) > 1 ? atoi(e) : 1; }();   // experiment: caller-made streams take the throughput geometry too
+    static const int share = std::max(1, env_int("HLMI_STREAM_SHARE").value_or(1));   // experiment: caller-made streams take the throughput geometry too
     static std::atomic<int> cached[64];
     int c = cached[device & 63].load();
     if (c <= 0) {
@@ -1135,10 +1133,11 @@ static std::mutex g_timing_mu;
 static std::vector<TimedLaunch> g_launches;
 static thread_local hipEvent_t t_pending_e1;
 
-bool env_flag(const char *name) {
+std::optional<int> env_int(const char *name) {
     const char *e = getenv(name);
-    return e && *e && atoi(e) != 0;
+    return e && *e ? std::optional<int>(atoi(e)) : std::nullopt;
 }
+bool env_flag(const char *name) { return env_int(name).value_or(0) != 0; }
 
 bool timing_enabled() { return g_timing.load(std::memory_order_relaxed) != 0; }
 
@@ -1534,8 +1533,7 @@ void *halide_hip_partition_stream_replica(int part, int nparts, int replica) {
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx.device) != hipSuccess || ncu < nparts) return nullptr;
     std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-    const char *ml = getenv("HLMI_PART_MASK");
-    const int layout = ml && *ml ? atoi(ml) : 3;
+    const int layout = env_int("HLMI_PART_MASK").value_or(3);
     const int nxcc = ncu >= 64 ? ncu / 32 : 1, slots = ncu / nxcc;
     int mine = 0;
     for (int b = 0; b < ncu; b++) {
@@ -1550,8 +1548,8 @@ void *halide_hip_partition_stream_replica(int part, int nparts, int replica) {
         return nullptr;
     }
     streams[key] = s;
-    const char *gc = getenv("HLMI_PART_GEOM_CUS");   // experiment: the CU count the launch geometry is sized for
-    g_part_cus[s] = gc && atoi(gc) > 0 ? atoi(gc) : layout == 3 ? ncu / nparts : mine;
+    const int gc = env_int("HLMI_PART_GEOM_CUS").value_or(0);   // experiment: the CU count the launch geometry is sized for
+    g_part_cus[s] = gc > 0 ? gc : layout == 3 ? ncu / nparts : mine;
     return (void *)s;
 }
 

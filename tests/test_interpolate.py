@@ -99,6 +99,32 @@ def test_hip_matches_oracle_bit_for_bit(hl, oracle, w, h):
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{np.count_nonzero(got.view(np.uint32) != want.view(np.uint32))} of {got.size} differ"
 
 
+@functools.lru_cache(maxsize=None)
+def _case(w, h):
+    """(input, the oracle's output) of one shape, computed once for all switch settings; read-only."""
+    import oracle_lib
+    inp = _img(w, h, seed=w + h)
+    want = oracle_lib.interpolate(inp)
+    inp.setflags(write=False), want.setflags(write=False)
+    return inp, want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h", [(640, 480), (255, 257), (13, 9)])
+@pytest.mark.parametrize("switch,value", [("HLMI_IP_UNFUSED", "1"), ("HLMI_IP_TAIL_FROM", "3"), ("HLMI_IP_TAIL_FROM", "5"),
+                                          ("HLMI_IP_TAIL_FROM", "8"), ("HLMI_IP_TAIL_FROM", "99"), ("HLMI_IP_TAIL_FROM", "")])
+def test_hip_staged_and_other_tails_match_oracle(hl, monkeypatch, switch, value, w, h):
+    """The chains the default never takes.  HLMI_IP_UNFUSED=1: levels 3 to 5 as ip_down:l / ip_up:l launches instead of ip_down_multi /
+    ip_up_multi.  HLMI_IP_TAIL_FROM: the first level ip_tail takes (3: every stored level below 2; 5, 8: a longer / shorter tail, the
+    staged kernels above it; 99, out of range: no tail, a launch per level up to 9; empty: the default 6, as if unset).
+    640 x 480: level 5 is 21 x 16, 3 x 2 tiles of ip_down_multi with ragged last tiles; 255 x 257: odd extents; 13 x 9: levels of one
+    pixel.  Bit for bit, as test_hip_matches_oracle_bit_for_bit."""
+    monkeypatch.setenv(switch, value)
+    inp, want = _case(w, h)
+    got = _run(hl, inp)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{np.count_nonzero(got.view(np.uint32) != want.view(np.uint32))} of {got.size} differ"
+
+
 @pytest.mark.gpu
 def test_hip_pinned_shapes(hl):
     inp = _img(32, 24, seed=1)

@@ -204,6 +204,32 @@ def test_hip_64_bit_pyramid_kernels_and_the_separate_maximum_launch_match_the_or
     assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{np.count_nonzero(got != want)} of {got.size} differ"
 
 
+@functools.lru_cache(maxsize=None)
+def _large_pair():
+    """(left, right, the oracle's output) of the one shape whose pyramids have levels above the tail, computed once; read-only."""
+    import oracle_lib
+    left, right = _pair(1100, 960, seed=5, shift=1)
+    want = oracle_lib.lens_blur(left, right, 3, 1, 1.0, 2)
+    for a in (left, right, want):
+        a.setflags(write=False)
+    return left, right, want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("switch", [None, "HLMI_LB_NO_A32", "HLMI_LB_UNFUSED"])
+def test_hip_pyramid_launches_above_the_tail_match_the_oracle(hl, monkeypatch, switch):
+    """1100 x 960 is the smallest kind of shape at which the one-launch tail starts at level 4 (level 2 of the push pyramid, 275 x 240,
+    has more than 128 x 128 x 4 elements): lb_down:2, lb_down:3 and lb_pull_multi:1 run, as at the benchmark's size — lb_down32 and
+    lb_pull_multi32 by default, lb_down<true> and lb_pull_multi under HLMI_LB_NO_A32=1, lb_down:1 (lb_down<false>) and lb_depth under
+    HLMI_LB_UNFUSED=1.  Three slices and two samples keep the oracle short.  (lb_pull:i above a tail needs level 4 above 128 x 128 x 4
+    elements, a 16-megapixel input: no test runs it.)"""
+    if switch:
+        monkeypatch.setenv(switch, "1")
+    left, right, want = _large_pair()
+    got = _run(hl, left, right, 3, 1, 1.0, 2)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), f"{np.count_nonzero(got != want)} of {got.size} differ"
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("unfused", [False, True])
 @pytest.mark.parametrize("w,h,slices,samples", [(530, 70, 32, 8), (300, 41, 33, 5), (258, 36, 64, 4), (515, 19, 31, 3)])
