@@ -380,6 +380,40 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
                  {"alg_bytes": nbytes, "kernels_ms": kernels(call, o), "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, o)},
                   "fused_not_slower": bool(t <= tg)})
 
+    # ---- gaussian_blur: the reference's own invocation (apps/gaussian_blur/Makefile: sigma 10 on the app image) at this project's usual
+    #      size, f32 1536x2560: the direct blur at trunc 3, 4, 5 and three resampled variants at trunc 5.  Bounds: direct, 2 (2 R + 1) fused
+    #      operations per pixel at the f32 vector peak (its 16 B/px of HBM traffic with the f32 intermediate is reported beside it); the
+    #      variants, the compulsory 8 B/px.  Each line also times the same call with its blur passes on the general path
+    #      (hlmi_gaussian_blur_general).  `--only gaussian_blur` selects all of them, an entry point's name that one.
+    if not only or any(n.startswith("gaussian_blur") for n in only):
+        W, H, sigma = 1536, 2560, 10.0
+        img = rng.random((H, W), dtype=np.float32)
+        a, o = hl.Buffer(img), hl.Buffer(hl.aligned_array((H, W)))
+        cases = [("gaussian_blur_direct", t) for t in (3, 4, 5)] + [(hl.gaussian_blur_variant(*v), 5) for v in ((3, 2, 8), (2, 1, 2), (4, 3, 16))]
+        for name, trunc in cases:
+            if only and "gaussian_blur" not in only and name not in only:
+                continue
+            fn = hl._fn[name]
+            call = lambda: hl._check(fn(a.ptr, sigma, trunc, o.ptr))
+            general = lambda: hl.debug_gaussian_blur_general(name, a, sigma, trunc, o)
+            iters = 50
+            t = timed(call, o, iters)
+            clock = last_clock[0]
+            tg = timed(general, o, iters)
+            last_clock[0] = clock
+            extra = {"kernels_ms": kernels(call, o), "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, o)},
+                     "tiled_over_general": round(t / tg, 4)}
+            if name == "gaussian_blur_direct":
+                radius = int(np.ceil(np.float32(trunc) * np.float32(sigma)))
+                flops = 2.0 * 2 * (2 * radius + 1) * W * H
+                emit(name, f"apps/gaussian_blur direct sigma={sigma:g} trunc={trunc} (radius {radius}), f32 1536x2560", t, W * H, "valu",
+                     flops / t / 1e12, VALU_F32_PEAK_TF, "TFLOP/s",
+                     {"alg_flops": flops, "alg_bytes": 16 * W * H, "hbm_gbs": round(16.0 * W * H / t / 1e9, 1),
+                      "hbm_frac": round(16.0 * W * H / t / 1e9 / HBM_PEAK_GBS, 4), **extra})
+            else:
+                emit(name, f"apps/gaussian_blur {name[14:]} sigma={sigma:g} trunc={trunc}, f32 1536x2560", t, W * H, "hbm",
+                     8.0 * W * H / t / 1e9, HBM_PEAK_GBS, "GB/s", {"alg_bytes": 8 * W * H, **extra})
+
     # ---- lens_blur u8 stereo pair 768x1280 (the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
     if not only or "lens_blur" in only:
         W, H = 768, 1280

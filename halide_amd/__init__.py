@@ -432,7 +432,8 @@ _RESIZE_TYPES = {"float32": "float32", "uint8": "uint8", "uint16": "uint16"}
 _fn = {name: _bind(name) for name in
        ["local_laplacian", "bilateral_grid", "halide_blur", "nl_means", "stencil_chain", "conv_layer", "conv_layer_bf16",
         "depthwise_separable_conv", "unsharp", "max_filter", "hist", "harris", "interpolate", "iir_blur", "lens_blur", "bgu",
-        "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]}
+        "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
+       + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -580,6 +581,50 @@ def debug_resize_general(variant: str, input, scale_factor, output) -> int:
     fn.restype = C.c_int
     fn.argtypes = [C.c_char_p, _BP, C.c_float, _BP]
     return _check(fn(variant.encode(), _as_ptr(input), float(scale_factor), _as_ptr(output)))
+
+
+def gaussian_blur_variant(upsample_order=3, downsample_order=2, factor=8) -> str:
+    """The AOT variant `gaussian_blur` calls: gaussian_blur_<upsample_order>_<downsample_order>_<factor>, one of the 36 the
+    reference's build generates (apps/gaussian_blur/Makefile)."""
+    if upsample_order not in (2, 3, 4) or downsample_order not in (1, 2, 3) or factor not in (2, 4, 8, 16):
+        raise ValueError(f"no gaussian_blur variant with upsample_order {upsample_order!r}, downsample_order {downsample_order!r}, "
+                         f"factor {factor!r}: orders 2..4 and 1..3, factors 2, 4, 8, 16")
+    return f"gaussian_blur_{int(upsample_order)}_{int(downsample_order)}_{int(factor)}"
+
+
+def gaussian_blur_direct(input, sigma, trunc, output) -> int:
+    """apps/gaussian_blur: f32 [W,H] -> f32, the separable blur of the edge-clamped input truncated at `trunc` sigmas; any
+    output region."""
+    return _check(_fn["gaussian_blur_direct"](_as_ptr(input), float(sigma), int(trunc), _as_ptr(output)))
+
+
+def gaussian_blur(input, sigma, trunc, output, upsample_order=3, downsample_order=2, factor=8) -> int:
+    """apps/gaussian_blur: reduce by `factor` (box spline of downsample_order), blur at low resolution, expand (box spline of
+    upsample_order).  The output's mins are 0, its row stride a multiple of 16 and its host pointer 64-byte aligned:
+    `aligned_array` makes one."""
+    fn = _fn[gaussian_blur_variant(upsample_order, downsample_order, factor)]
+    return _check(fn(_as_ptr(input), float(sigma), int(trunc), _as_ptr(output)))
+
+
+def debug_gaussian_blur_general(variant: str, input, sigma, trunc, output) -> int:
+    """Test and measurement hook: the named blur with its blur passes on the general path, whatever the sizes."""
+    fn = lib.hlmi_gaussian_blur_general
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, _BP, C.c_float, C.c_int32, _BP]
+    return _check(fn(variant.encode(), _as_ptr(input), float(sigma), int(trunc), _as_ptr(output)))
+
+
+def aligned_array(shape, dtype=np.float32, alignment=64, row_multiple=16) -> np.ndarray:
+    """A zeroed C-order array of `shape` whose data pointer is a multiple of `alignment` bytes and whose row stride (the last
+    axis but one) is a multiple of `row_multiple` elements: a view into a larger allocation, which `Buffer` wraps as it is.
+    numpy's own allocations promise neither."""
+    shape = tuple(int(n) for n in shape)
+    dtype = np.dtype(dtype)
+    row = -(-shape[-1] // row_multiple) * row_multiple
+    padded = shape[:-1] + (row,)
+    raw = np.zeros(int(np.prod(padded)) * dtype.itemsize + alignment, np.uint8)
+    off = -raw.ctypes.data % alignment
+    return raw[off:off + int(np.prod(padded)) * dtype.itemsize].view(dtype).reshape(padded)[..., :shape[-1]]
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

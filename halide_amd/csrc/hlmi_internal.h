@@ -160,8 +160,9 @@ int argv_call(int (*fn)(P...), void **a) { return argv_call(fn, a, std::index_se
 //   5. per buffer, per dimension: required region, then extent >= 0      (asserts_required, :414-418, :466-470) -4 / -28
 //   6. per buffer, per dimension: |extent * stride| and the running product of extents <= 2^31 - 1
 //                                                                        (dims_no_overflow_asserts, :436-462) -5 / -6
-//   7. host pointers                                                     (asserts_host_non_null, :648-655)    -34
-// The pipelines call the check_* helpers below in whatever order is convenient for them; failures of phases 4-6 are
+//   7. host pointer alignment (set_host_alignment)                       (asserts_host_alignment, :688-692)   -24
+//   8. host pointers                                                     (asserts_host_non_null, :648-655)    -34
+// The pipelines call the check_* helpers below in whatever order is convenient for them; failures of phases 4-7 are
 // not reported on the spot but RECORDED with their (phase, buffer rank, dimension, kind) key, and the one the
 // reference would have hit first is reported by checks_done() — which acquire_device() calls, so no kernel is ever
 // enqueued with unchecked arguments.  tests/test_entry_protocol.py pins the codes and the order.
@@ -189,6 +190,9 @@ int check_covers(void *uc, const BufArg &a, int d, int req_min, int req_extent);
 // step 4, a pinned constraint "<buffer>.<field>.<dim> == expect" (halide_error_constraint_violated,
 // src/runtime/errors.cpp:104); `what` must start with the buffer's name.  Always returns 0 (recorded).
 int check_equal(void *uc, const char *what, int val, const char *expect_what, int expect);
+// step 7: the buffer's host pointer is a multiple of `alignment` bytes (halide_error_unaligned_host_ptr, src/runtime/errors.cpp:187);
+// a null host pointer passes (0 % alignment == 0) and is step 8's business.  Always returns 0 (recorded).
+HLMI_LOCAL int check_host_aligned(void *uc, const BufArg &a, int alignment);
 // report the recorded failure the reference would have hit first (0 if none) and forget the rest
 int checks_done(void *uc);
 // bounds-query answer: rewrite dim[] to a dense planar shape (stride[0]=1) — only if `buf` is itself
@@ -377,6 +381,11 @@ int conv_check_args(void *uc, BufArg *args, int *CI, int *CO, int *W, int *H, in
 // resize.hip: the named resize variant ("resize_cubic_uint8_down", ...) on its general two-launch path whatever the sizes, for the
 // tests (fused == general bit for bit) and for bench_apps.py (fused is not slower).  Per call: no mode is kept anywhere.
 extern "C" int hlmi_resize_general(const char *variant, halide_buffer_t *input, float scale_factor, halide_buffer_t *output);
+
+// gaussian_blur.hip: the named blur ("gaussian_blur_direct", "gaussian_blur_3_2_8", ...) with its blur passes on the path that
+// has no size conditions (every tap read from global memory with its clamp), for the tests (tiled == general bit for bit) and for
+// bench_apps.py.  Per call: no mode is kept anywhere.
+extern "C" int hlmi_gaussian_blur_general(const char *variant, halide_buffer_t *input, float sigma, int32_t trunc, halide_buffer_t *output);
 
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;

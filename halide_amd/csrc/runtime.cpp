@@ -286,6 +286,15 @@ int check_equal(void *uc, const char *what, int val, const char *expect_what, in
     return 0;
 }
 
+int check_host_aligned(void *uc, const BufArg &a, int alignment) {
+    (void)uc;
+    if ((uintptr_t)a.buf->host % (uintptr_t)alignment != 0) {
+        record(7, rank_of(a.name, strlen(a.name)), 0, 0, halide_error_code_unaligned_host_ptr,
+               "The host pointer of %s is not aligned to a %d bytes boundary.", a.name, alignment);
+    }
+    return 0;
+}
+
 void answer_query(halide_buffer_t *buf, const int *mins, const int *extents) {
     if (!(buf->host == nullptr && buf->device == 0)) return;
     int stride = 1;

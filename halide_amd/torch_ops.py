@@ -217,6 +217,32 @@ def resize(input: torch.Tensor, scale_factor: float, interpolation: str = "cubic
     return out
 
 
+def _gaussian_blur_out(input):
+    # rows padded to a multiple of 16 elements (the resampled variants pin output.stride.1 to one); the result is the view of
+    # the image's own columns
+    h, w = input.shape
+    return input.new_empty((h, -(-w // 16) * 16))[:, :w]
+
+
+@torch.library.custom_op("hlmi::gaussian_blur", mutates_args=())
+def gaussian_blur(input: torch.Tensor, sigma: float, trunc: int = 5, upsample_order: int = 0, downsample_order: int = 0,
+                  factor: int = 0) -> torch.Tensor:
+    """apps/gaussian_blur: (H, W) float32 -> (H, W) float32 blurred with `sigma`, truncated at `trunc` sigmas.  All three of
+    upsample_order, downsample_order and factor 0: the direct blur; otherwise the variant gaussian_blur_<U>_<D>_<F>."""
+    if input.dim() != 2 or input.dtype != torch.float32:
+        raise TypeError("gaussian_blur takes an (H, W) float32 tensor")
+    direct = upsample_order == 0 and downsample_order == 0 and factor == 0
+    if not direct:
+        hl.gaussian_blur_variant(upsample_order, downsample_order, factor)   # ValueError outside the 36
+    out = _gaussian_blur_out(input)
+    with _Wrapped(input, out) as (a, o):
+        if direct:
+            hl.gaussian_blur_direct(a, sigma, trunc, o)
+        else:
+            hl.gaussian_blur(a, sigma, trunc, o, upsample_order, downsample_order, factor)
+    return out
+
+
 @torch.library.custom_op("hlmi::lens_blur", mutates_args=())
 def lens_blur(left_im: torch.Tensor, right_im: torch.Tensor, slices: int, focus_depth: int, blur_radius_scale: float,
               aperture_samples: int) -> torch.Tensor:
@@ -275,6 +301,11 @@ def _(input, alpha):
 @resize.register_fake
 def _(input, scale_factor, interpolation="cubic", upsample=None):
     return input.new_empty(_resize_shape(input, scale_factor))
+
+
+@gaussian_blur.register_fake
+def _(input, sigma, trunc=5, upsample_order=0, downsample_order=0, factor=0):
+    return _gaussian_blur_out(input)
 
 
 @lens_blur.register_fake

@@ -121,6 +121,7 @@ enum hlmi_error_code {
     halide_error_code_unimplemented = -20,
     halide_error_code_internal_error = -22,
     halide_error_code_device_run_failed = -23,
+    halide_error_code_unaligned_host_ptr = -24,
     halide_error_code_requirement_failed = -27,
     halide_error_code_buffer_extents_negative = -28,
     halide_error_code_gpu_device_error = -29,

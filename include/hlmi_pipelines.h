@@ -17,7 +17,8 @@
  *   4. per buffer: element type mismatch -> -3, then wrong dimensionality -> -43
  *   5. per buffer and dimension: dim[0].stride != 1 or another pinned stride / min / extent -> -8
  *   6. per buffer and dimension: region required > region supplied -> -4, then a negative extent -> -28
- *   7. per buffer and dimension: |extent * stride| > 2^31-1 -> -5, product of extents > 2^31-1 -> -6
+ *   7. per buffer and dimension: |extent * stride| > 2^31-1 -> -5, product of extents > 2^31-1 -> -6; then, where a pipeline sets a
+ *      host alignment (the resampled gaussian_blur variants), a host pointer off that grid -> -24
  *   8. with the device: both dirty bits -> -37; device handle without interface -> -19 (and vice versa -36); a
  *      device allocation of another API -> -42; a host-dirty input without host pointer -> -34.  (-44,
  *      device_dirty_with_no_device_support, is what a HOST-only target reports; a GPU target copies instead.)
@@ -208,6 +209,91 @@ HLMI_DECLARE_AUX(resize_lanczos_uint16_up)
 int resize_lanczos_uint16_down(struct halide_buffer_t *input, float scale_factor, struct halide_buffer_t *output);
 HLMI_DECLARE_AUX(resize_lanczos_uint16_down)
 
+/* apps/gaussian_blur/gaussian_blur_generator.cpp:68-100, :104-349 — a Gaussian blur of a chosen sigma, truncated at `trunc` sigmas
+ * (radius = (int)ceil(trunc * sigma)): f32 [x, y] in and out.  gaussian_blur_direct is the separable blur itself over the
+ * edge-clamped input: any output region, any input min; a bounds query leaves both buffers as passed.  The 36 variants
+ * gaussian_blur_<U>_<D>_<F> (upsample_order U in 2..4, downsample_order D in 1..3, factor F in 2, 4, 8, 16) reduce the input by F
+ * with an order-D box-spline prefilter, blur at low resolution with a sigma corrected for the two splines, and expand by F with
+ * an order-U box spline.  Particular to the variants (:344-347): output.min.0 == 0, output.min.1 == 0 and
+ * output.stride.1 % 16 == 0 or -8; an output HOST pointer that is not 64-byte aligned -> -24 (unaligned_host_ptr; a null one
+ * passes); a queried output gets mins 0; input mins are free.  Particular to all 37: !(sigma > 0 and finite) or trunc < 0
+ * returns -9 naming the argument (the algorithm yields NaN or an empty sum there; the generator declares no range, so the
+ * metadata has none).  A radius beyond the image is legal; one whose tables the scratch arena cannot hold returns -11. */
+int gaussian_blur_direct(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_direct)
+int gaussian_blur_2_1_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_1_2)
+int gaussian_blur_2_1_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_1_4)
+int gaussian_blur_2_1_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_1_8)
+int gaussian_blur_2_1_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_1_16)
+int gaussian_blur_2_2_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_2_2)
+int gaussian_blur_2_2_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_2_4)
+int gaussian_blur_2_2_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_2_8)
+int gaussian_blur_2_2_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_2_16)
+int gaussian_blur_2_3_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_3_2)
+int gaussian_blur_2_3_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_3_4)
+int gaussian_blur_2_3_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_3_8)
+int gaussian_blur_2_3_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_2_3_16)
+int gaussian_blur_3_1_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_1_2)
+int gaussian_blur_3_1_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_1_4)
+int gaussian_blur_3_1_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_1_8)
+int gaussian_blur_3_1_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_1_16)
+int gaussian_blur_3_2_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_2_2)
+int gaussian_blur_3_2_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_2_4)
+int gaussian_blur_3_2_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_2_8)
+int gaussian_blur_3_2_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_2_16)
+int gaussian_blur_3_3_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_3_2)
+int gaussian_blur_3_3_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_3_4)
+int gaussian_blur_3_3_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_3_8)
+int gaussian_blur_3_3_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_3_3_16)
+int gaussian_blur_4_1_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_1_2)
+int gaussian_blur_4_1_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_1_4)
+int gaussian_blur_4_1_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_1_8)
+int gaussian_blur_4_1_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_1_16)
+int gaussian_blur_4_2_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_2_2)
+int gaussian_blur_4_2_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_2_4)
+int gaussian_blur_4_2_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_2_8)
+int gaussian_blur_4_2_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_2_16)
+int gaussian_blur_4_3_2(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_3_2)
+int gaussian_blur_4_3_4(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_3_4)
+int gaussian_blur_4_3_8(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_3_8)
+int gaussian_blur_4_3_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian_blur_4_3_16)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,
@@ -240,6 +326,7 @@ int lens_blur_auto_schedule(struct halide_buffer_t *left_im, struct halide_buffe
                             struct halide_buffer_t *final);
 int bgu_auto_schedule(float r_sigma, int32_t s_sigma, struct halide_buffer_t *splat_loc, struct halide_buffer_t *values,
                       struct halide_buffer_t *slice_loc, struct halide_buffer_t *output);
+int gaussian_blur_direct_auto_schedule(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
 int camera_pipe_auto_schedule(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                               struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,
                               float sharpen_strength, int32_t blackLevel, int32_t whiteLevel,

@@ -302,8 +302,63 @@ def fuzz_resize(rng):
     return desc, r == 0 and same(o.numpy(), want)
 
 
+_gaussian_blur_checker = []
+
+
+def gaussian_blur_checker():
+    """tests/cpp/gaussian_blur_check.c as a shared object (oracle/ has no gaussian_blur; the test suite builds the same file the same way)"""
+    if not _gaussian_blur_checker:
+        import ctypes
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="gaussian_blur_check"), "libgaussian_blur_check.so")
+        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", so,
+                        os.path.join(ROOT, "tests", "cpp", "gaussian_blur_check.c"), "-lm"], check=True)
+        lib = ctypes.CDLL(so)
+        lib.gc_set_canon(hl.canon_fma())
+        I, F, P = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+        lib.gc_direct.argtypes = [P, I, I, I, I, F, I, P, I, I, I, I]
+        lib.gc_resampled.argtypes = [I, I, I, P, I, I, I, I, F, I, P, I, I]
+        _gaussian_blur_checker.append(lib)
+    return _gaussian_blur_checker[0]
+
+
+def fuzz_gaussian_blur(rng):
+    """gaussian_blur: the direct blur (any output region) or a random one of the 36 variants, random sigma in [0.3, 12], trunc in 0..5,
+    sizes and input origins, on either path, against tests/cpp/gaussian_blur_check.c"""
+    w, h = rdim(rng, 1, 300), rdim(rng, 1, 200)
+    sigma = float(f32(np.exp(rng.uniform(np.log(0.3), np.log(12.0)))))
+    trunc = int(rng.integers(0, 6))
+    inp = rng.random((h, w), dtype=f32)
+    in_min = [int(v) for v in rng.integers(-40, 41, 2)] if rng.random() < 0.5 else [0, 0]
+    general = bool(rng.integers(0, 2))
+    a = hl.Buffer(inp, mins=in_min)
+    if rng.random() < 0.4:
+        name = "gaussian_blur_direct"
+        ow, oh = rdim(rng, 1, 300), rdim(rng, 1, 200)
+        out_min = [in_min[0] + int(rng.integers(-60, w + 60)), in_min[1] + int(rng.integers(-60, h + 60))] if rng.random() < 0.5 else list(in_min)
+        o = hl.Buffer(np.zeros((oh, ow), f32), mins=out_min)
+        want = np.zeros((oh, ow), f32)
+        r = gaussian_blur_checker().gc_direct(inp.ctypes.data, in_min[0], in_min[1], w, h, sigma, trunc, want.ctypes.data, out_min[0], out_min[1], ow, oh)
+    else:
+        u, d, f = int(rng.integers(2, 5)), int(rng.integers(1, 4)), int(rng.choice([2, 4, 8, 16]))
+        name = hl.gaussian_blur_variant(u, d, f)
+        ow, oh = (w, h) if rng.random() < 0.7 else (rdim(rng, 1, 300), rdim(rng, 1, 200))
+        out_min = [0, 0]
+        o = hl.Buffer(hl.aligned_array((oh, ow)))
+        want = np.zeros((oh, ow), f32)
+        r = gaussian_blur_checker().gc_resampled(u, d, f, inp.ctypes.data, in_min[0], in_min[1], w, h, sigma, trunc, want.ctypes.data, ow, oh)
+    if general:
+        hl.debug_gaussian_blur_general(name, a, sigma, trunc, o)
+    else:
+        hl._check(hl._fn[name](a.ptr, sigma, trunc, o.ptr))
+    desc = f"{name}{' general' if general else ''} sigma {sigma!r} trunc {trunc} in {w}x{h} min {in_min} out {ow}x{oh} min {out_min}"
+    return desc, r == 0 and same(np.ascontiguousarray(o.numpy()), want)
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # its checker is not oracle/'s
+CASES["gaussian_blur"] = fuzz_gaussian_blur
 
 
 def stress(args, only):
