@@ -414,6 +414,42 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
                 emit(name, f"apps/gaussian_blur {name[14:]} sigma={sigma:g} trunc={trunc}, f32 1536x2560", t, W * H, "hbm",
                      8.0 * W * H / t / 1e9, HBM_PEAK_GBS, "GB/s", {"alg_bytes": 8 * W * H, **extra})
 
+    # ---- linear_blur / simple_blur: f32 1536x2560x4, the generator's estimate (apps/linear_blur/linear_blur_generator.cpp:20-21).  Roofline:
+    #      the compulsory 8 B per value.  Each line also times the same call as the unfused composition (hlmi_linear_blur_general: three
+    #      launches and three times the bytes for linear_blur, one launch with nine global taps for simple_blur): the one-launch path must
+    #      not be slower.  linear_blur is bound by VALU issue, not by bytes: its line adds the VALU instructions lb_fused issues per output
+    #      value, counted in its disassembly (scripts/asm_hist.sh halide_amd/csrc/linear_blur.hip lb_fusedILb1; per workgroup of 4 waves
+    #      and 2048 outputs: 4 x 23 set-up + 34 staged rows x 55 + 2 edge columns x 80 + 4 x (76 + 7 x 65) output rows = 4246 wave
+    #      instructions for 32 wave-rows of outputs), and the time that count takes at 2 cycles per wave64 instruction on each of
+    #      256 x 4 SIMDs at 2.4 GHz.  The count is STATIC: taken once from the code object that hipcc 7.2.26015 (AMD clang 22.0.0git, roc-7.2.0)
+    #      makes of linear_blur.hip as it stood when this block was added (688 VALU instructions in lb_fused<true>, 21 VGPRs); the line
+    #      names that source in `valu_count_source`.  Count again after a change to the kernel or the compiler.
+    if not only or "linear_blur" in only or "simple_blur" in only:
+        W, H, NC = 1536, 2560, 4
+        LB_TILE, LB_FUSED_VALU_PER_WORKGROUP = (64, 32), 4246   # linear_blur.hip: TW x TH, and the count above
+        a, o = hl.Buffer(rng.random((NC, H, W), dtype=np.float32)), hl.Buffer(np.zeros((NC, H, W), np.float32))
+        a.copy_to_device()
+        for name in ("linear_blur", "simple_blur"):
+            if only and name not in only:
+                continue
+            call = (lambda: hl.linear_blur(a, o)) if name == "linear_blur" else (lambda: hl.simple_blur(a, W, H, o))
+            general = lambda: hl.debug_linear_blur_general(name, a, W, H, o)
+            iters = 50
+            t = timed(call, o, iters)
+            clock = last_clock[0]
+            tg = timed(general, o, iters)
+            last_clock[0] = clock
+            nbytes = 8 * W * H * NC
+            extra = {"alg_bytes": nbytes, "kernels_ms": kernels(call, o), "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, o)},
+                     "fused_not_slower": bool(t <= tg)}
+            if name == "linear_blur":
+                valu = LB_FUSED_VALU_PER_WORKGROUP / (LB_TILE[0] * LB_TILE[1] / 64.0)
+                issue_s = W * H * NC / 64.0 * valu * 2.0 / (256 * 4 * 2.4e9)
+                extra.update({"valu_per_output": round(valu, 1), "valu_issue_bound_ms": round(issue_s * 1e3, 4), "valu_issue_frac": round(issue_s / t, 4),
+                              "conversions_per_output": round((LB_TILE[0] + 2) * (LB_TILE[1] + 2) / float(LB_TILE[0] * LB_TILE[1]), 4),
+                              "valu_count_source": "static count in the disassembly of lb_fused<true>, hipcc 7.2.26015, 64 x 32 tile; not re-derived by this run"})
+            emit(name, f"apps/linear_blur {name}, f32 {W}x{H}x{NC}", t, W * H, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
+
     # ---- lens_blur u8 stereo pair 768x1280 (the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
     if not only or "lens_blur" in only:
         W, H = 768, 1280

@@ -433,7 +433,8 @@ _fn = {name: _bind(name) for name in
        ["local_laplacian", "bilateral_grid", "halide_blur", "nl_means", "stencil_chain", "conv_layer", "conv_layer_bf16",
         "depthwise_separable_conv", "unsharp", "max_filter", "hist", "harris", "interpolate", "iir_blur", "lens_blur", "bgu",
         "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
-       + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]}
+       + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
+       + ["linear_blur", "simple_blur"]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -625,6 +626,27 @@ def aligned_array(shape, dtype=np.float32, alignment=64, row_multiple=16) -> np.
     raw = np.zeros(int(np.prod(padded)) * dtype.itemsize + alignment, np.uint8)
     off = -raw.ctypes.data % alignment
     return raw[off:off + int(np.prod(padded)) * dtype.itemsize].view(dtype).reshape(padded)[..., :shape[-1]]
+
+
+def linear_blur(input, output) -> int:
+    """apps/linear_blur: f32 [W,H,C] sRGB -> f32, the 3x3 box blur over x .. x + 2, y .. y + 2 in linear light; the clamp is to the
+    input's extents; any output region."""
+    return _check(_fn["linear_blur"](_as_ptr(input), _as_ptr(output)))
+
+
+def simple_blur(input, width, height, output) -> int:
+    """apps/linear_blur's simple_blur: f32 [W,H,C] -> f32, the same blur on the values as they are, the input clamped to
+    [0, width) x [0, height); any output region."""
+    return _check(_fn["simple_blur"](_as_ptr(input), int(width), int(height), _as_ptr(output)))
+
+
+def debug_linear_blur_general(name: str, input, width, height, output) -> int:
+    """Test and measurement hook: "linear_blur" or "simple_blur" as the unfused composition (three launches / one), whatever the
+    sizes; linear_blur does not read width and height."""
+    fn = lib.hlmi_linear_blur_general
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, _BP, C.c_int32, C.c_int32, _BP]
+    return _check(fn(name.encode(), _as_ptr(input), int(width), int(height), _as_ptr(output)))
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

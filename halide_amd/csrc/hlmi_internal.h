@@ -387,6 +387,12 @@ extern "C" int hlmi_resize_general(const char *variant, halide_buffer_t *input, 
 // bench_apps.py.  Per call: no mode is kept anywhere.
 extern "C" int hlmi_gaussian_blur_general(const char *variant, halide_buffer_t *input, float sigma, int32_t trunc, halide_buffer_t *output);
 
+// linear_blur.hip: "linear_blur" or "simple_blur" as the unfused composition (to_linear over the required region into the scratch
+// arena, one thread per output with nine clamped taps from global memory, to_srgb in place: three launches, one for simple_blur),
+// for the tests (fused == general bit for bit) and for bench_apps.py.  linear_blur does not read width and height.  Per call: no
+// mode is kept anywhere.
+extern "C" int hlmi_linear_blur_general(const char *name, halide_buffer_t *input, int32_t width, int32_t height, halide_buffer_t *output);
+
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;
     return (r != 0 && r < 0) ? q - 1 : q;

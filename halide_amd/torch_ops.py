@@ -243,6 +243,33 @@ def gaussian_blur(input: torch.Tensor, sigma: float, trunc: int = 5, upsample_or
     return out
 
 
+def _blur3_check(name, input):
+    if input.dim() != 3 or input.dtype != torch.float32:
+        raise TypeError(f"{name} takes a (C, H, W) float32 tensor")
+
+
+@torch.library.custom_op("hlmi::linear_blur", mutates_args=())
+def linear_blur(input: torch.Tensor) -> torch.Tensor:
+    """apps/linear_blur: (C, H, W) float32 sRGB -> (C, H, W) float32, the 3x3 box blur over x .. x + 2, y .. y + 2 of the
+    edge-clamped image, taken in linear light."""
+    _blur3_check("linear_blur", input)
+    out = torch.empty(tuple(input.shape), dtype=torch.float32, device=input.device)
+    with _Wrapped(input, out) as (a, o):
+        hl.linear_blur(a, o)
+    return out
+
+
+@torch.library.custom_op("hlmi::simple_blur", mutates_args=())
+def simple_blur(input: torch.Tensor) -> torch.Tensor:
+    """apps/linear_blur's simple_blur: (C, H, W) float32 -> (C, H, W) float32, the same blur on the values as they are; width and
+    height are the image's (apps/linear_blur/run_linear_blur.cpp:33)."""
+    _blur3_check("simple_blur", input)
+    out = torch.empty(tuple(input.shape), dtype=torch.float32, device=input.device)
+    with _Wrapped(input, out) as (a, o):
+        hl.simple_blur(a, input.shape[2], input.shape[1], o)
+    return out
+
+
 @torch.library.custom_op("hlmi::lens_blur", mutates_args=())
 def lens_blur(left_im: torch.Tensor, right_im: torch.Tensor, slices: int, focus_depth: int, blur_radius_scale: float,
               aperture_samples: int) -> torch.Tensor:
@@ -306,6 +333,16 @@ def _(input, scale_factor, interpolation="cubic", upsample=None):
 @gaussian_blur.register_fake
 def _(input, sigma, trunc=5, upsample_order=0, downsample_order=0, factor=0):
     return _gaussian_blur_out(input)
+
+
+@linear_blur.register_fake
+def _(input):
+    return input.new_empty(tuple(input.shape))
+
+
+@simple_blur.register_fake
+def _(input):
+    return input.new_empty(tuple(input.shape))
 
 
 @lens_blur.register_fake

@@ -294,6 +294,22 @@ HLMI_DECLARE_AUX(gaussian_blur_4_3_8)
 int gaussian_blur_4_3_16(struct halide_buffer_t *input, float sigma, int32_t trunc, struct halide_buffer_t *output);
 HLMI_DECLARE_AUX(gaussian_blur_4_3_16)
 
+/* apps/linear_blur — the 3x3 box blur, plain and in linear light: f32 [x, y, c] in and out.
+ * simple_blur (simple_blur_generator.cpp:5-22, built with input.type=float32 input.dim=3 output.dim=3): with in(x, y, c) =
+ * input(max(min(x, width - 1), 0), max(min(y, height - 1), 0), c), blur_x = (in(x) + in(x + 1) + in(x + 2)) / 3 and output =
+ * (blur_x(y) + blur_x(y + 1) + blur_x(y + 2)) / 3: the window is x .. x + 2, y .. y + 2, not centred; width and height are the
+ * scalar arguments and need not be the buffer's extents (<= 0 reads column / row 0 everywhere).
+ * linear_blur (linear_blur_generator.cpp:8-27): srgb_to_linear, that blur with width and height the input's EXTENTS (the clamp is
+ * to [0, extent - 1] in absolute coordinates, whatever the input's mins), linear_to_srgb.
+ * Any output region, channel range and mins, padded row and plane strides.  The input must cover columns cx(ox) .. cx(ox + ow + 1),
+ * rows cy(oy) .. cy(oy + oh + 1) and the output's channels, or -4.  Bounds query: the output stays as passed; simple_blur's input
+ * gets exactly that box, linear_blur's keeps x and y as passed and gets the output's channels.  Neither has an _auto_schedule
+ * twin: the reference builds none. */
+int linear_blur(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(linear_blur)
+int simple_blur(struct halide_buffer_t *input, int32_t width, int32_t height, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(simple_blur)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,

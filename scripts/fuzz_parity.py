@@ -356,9 +356,92 @@ def fuzz_gaussian_blur(rng):
     return desc, r == 0 and same(np.ascontiguousarray(o.numpy()), want)
 
 
+_linear_blur_checker = []
+
+
+def linear_blur_checker():
+    """tests/cpp/linear_blur_check.c as a shared object (oracle/ has no linear_blur; the test suite builds the same file the same way)"""
+    if not _linear_blur_checker:
+        import ctypes
+        import subprocess
+        import tempfile
+        so = os.path.join(tempfile.mkdtemp(prefix="linear_blur_check"), "liblinear_blur_check.so")
+        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", so,
+                        os.path.join(ROOT, "tests", "cpp", "linear_blur_check.c"), "-lm"], check=True)
+        lib = ctypes.CDLL(so)
+        lib.lc_set_canon(hl.canon_fma())
+        I, P = ctypes.c_int, ctypes.c_void_p
+        lib.lc_blur.argtypes = [I, P, I, I, I, I, I, I, I, P, I, I, I, I]
+        _linear_blur_checker.append(lib)
+    return _linear_blur_checker[0]
+
+
+def _strided(rng, shape):
+    """a zeroed (C, H, W) array, dense or inside a larger allocation with padded rows and planes"""
+    c, h, w = shape
+    if rng.random() < 0.5:
+        return np.zeros(shape, f32)
+    py, px = int(rng.integers(0, 4)), int(rng.integers(0, 9))
+    return np.zeros((c, h + py, w + px), f32)[:, :h, px // 2:px // 2 + w]
+
+
+def fuzz_linear_blur(rng):
+    """linear_blur or simple_blur on a random output region, channel range, mins and strides, on either path, against
+    tests/cpp/linear_blur_check.c.  simple_blur: random width and height around the region, the input placed over the box they
+    require, now and then one cell short of it; linear_blur: a random region around an input with mins that are 0 or not.  Where
+    the checker finds the input short (-4) the entry point must say the same."""
+    linear = bool(rng.integers(0, 2))
+    general = bool(rng.integers(0, 2))
+    on, oc = int(rng.integers(1, 5)), int(rng.integers(-2, 3))
+    ow, oh = rdim(rng, 1, 200), rdim(rng, 1, 120)
+    clamp = lambda v, n: max(min(v, n - 1), 0)
+    if linear:
+        w, h = rdim(rng, 1, 200), rdim(rng, 1, 120)
+        width, height = w, h
+        ix0, iy0 = (0, 0) if rng.random() < 0.6 else (int(rng.integers(-4, 12)), int(rng.integers(-4, 12)))
+        ox, oy = int(rng.integers(min(ix0, 0) - 30, w + 30)), int(rng.integers(min(iy0, 0) - 30, h + 30))
+        if ix0 > 0 and rng.random() < 0.8:   # mostly regions such an input covers
+            ox, oy = max(ox, ix0), max(oy, iy0)
+        if ix0 < 0 and rng.random() < 0.8:
+            ow, oh = max(1, min(ow, ix0 + w - 2 - ox)), max(1, min(oh, iy0 + h - 2 - oy))
+    else:
+        ox, oy = int(rng.integers(-60, 200)), int(rng.integers(-60, 120))
+        width = int(rng.integers(-3, max(ox + ow, 0) + 40)) if rng.random() < 0.8 else 1
+        height = int(rng.integers(-3, max(oy + oh, 0) + 40)) if rng.random() < 0.8 else 1
+        bx0, bx1, by0, by1 = clamp(ox, width), clamp(ox + ow + 1, width), clamp(oy, height), clamp(oy + oh + 1, height)
+        m = [int(v) for v in rng.integers(0, 4, 4)]
+        if rng.random() < 0.1:
+            m[int(rng.integers(0, 4))] = -1
+        ix0, iy0, w, h = bx0 - m[0], by0 - m[1], bx1 - bx0 + 1 + m[0] + m[2], by1 - by0 + 1 + m[1] + m[3]
+        if w < 1 or h < 1:
+            ix0, iy0, w, h = bx0, by0, max(w, 1), max(h, 1)
+    c_lo, c_hi = int(rng.integers(0, 3)), int(rng.integers(0, 3))   # input channels beside the output's
+    vals = rng.random((on + c_lo + c_hi, h, w), dtype=f32) * f32(1.2) - f32(0.05)
+    src = _strided(rng, vals.shape)
+    src[...] = vals
+    a = hl.Buffer(src, mins=(ix0, iy0, oc - c_lo))
+    o = hl.Buffer(_strided(rng, (on, oh, ow)), mins=(ox, oy, oc))
+    mine = np.ascontiguousarray(vals[c_lo:c_lo + on])
+    want = np.zeros((on, oh, ow), f32)
+    rc = linear_blur_checker().lc_blur(int(linear), mine.ctypes.data, ix0, iy0, w, h, on, width, height, want.ctypes.data, ox, oy, ow, oh)
+    name = "linear_blur" if linear else "simple_blur"
+    fn = hl.lib.hlmi_linear_blur_general
+    fn.restype, fn.argtypes = hl.C.c_int, [hl.C.c_char_p, hl._BP, hl.C.c_int32, hl.C.c_int32, hl._BP]
+    if general:
+        r = fn(name.encode(), a.ptr, width, height, o.ptr)
+    elif linear:
+        r = hl._fn[name](a.ptr, o.ptr)
+    else:
+        r = hl._fn[name](a.ptr, width, height, o.ptr)
+    desc = (f"{name}{' general' if general else ''} in {w}x{h}x{vals.shape[0]} min {(ix0, iy0, oc - c_lo)} strides {[a.dim(i).stride for i in range(3)]} "
+            f"width {width} height {height} out {ow}x{oh}x{on} min {(ox, oy, oc)} strides {[o.dim(i).stride for i in range(3)]} -> {r} (checker {rc})")
+    return desc, r == rc and (rc != 0 or same(np.ascontiguousarray(o.numpy()), want))
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # its checker is not oracle/'s
 CASES["gaussian_blur"] = fuzz_gaussian_blur
+CASES["linear_blur"] = fuzz_linear_blur   # both entry points
 
 
 def stress(args, only):
