@@ -5,7 +5,7 @@
 
 Not part of the pytest suite (the suite pins fixed cases); this is the tool that looks for cases the suite does not have.
 Prints one line per pipeline (cases run, failures) and the parameters of every failure.  Uses oracle/ as the checker
-only (tests/oracle_lib.py)."""
+only (tests/oracle_lib.py) and, for the pipelines oracle/ does not restate, the plain-C checkers (tests/checker_lib.py)."""
 import argparse
 import os
 import sys
@@ -20,6 +20,14 @@ import halide_amd as hl  # noqa: E402
 import oracle_lib as oracle  # noqa: E402
 
 oracle.set_canon(hl.canon_fma())   # the oracle evaluates the canonical form the loaded library was built for
+
+
+def checkers():
+    """tests/checker_lib.py in the same form.  Loaded (and its object built) by the three cases that use it, not at import: the
+    other pipelines' cases need oracle/ only.  Every thread sets the same value, so the call is safe from any of them."""
+    import checker_lib
+    checker_lib.set_canon(hl.canon_fma())
+    return checker_lib
 
 f32 = np.float32
 
@@ -249,33 +257,14 @@ def case_conv_layer_bf16(rng):
     return f"n={n} {ww}x{hh} ci={ci} co={co}", bool((err <= 2e-6 * mag.astype(np.float64) + 1e-6).all())
 
 
-_resize_checker = []
-
-
-def resize_checker():
-    """tests/cpp/resize_check.c as a shared object (oracle/ has no resize; the test suite builds the same file the same way)"""
-    if not _resize_checker:
-        import ctypes
-        import subprocess
-        import tempfile
-        so = os.path.join(tempfile.mkdtemp(prefix="resize_check"), "libresize_check.so")
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "cpp", "resize_check.c"), "-lm"],
-                       check=True)
-        lib = ctypes.CDLL(so)
-        lib.rc_set_canon(hl.canon_fma())
-        lib.rc_resize.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float] + [ctypes.c_void_p] * 6
-        _resize_checker.append(lib)
-    return _resize_checker[0]
-
-
 def fuzz_resize(rng):
     """resize: random type, kernel, direction, factor in [0.05, 8], sizes, origins and crops, against tests/cpp/resize_check.c"""
-    import ctypes
-    kernel = str(rng.choice(hl.RESIZE_KERNELS))
-    tname = str(rng.choice(["float32", "uint8", "uint16"]))
+    checker = checkers()
+    kernel = str(rng.choice(checker.RESIZE_KERNELS))
+    tname = str(rng.choice(list(checker.RESIZE_TYPE_INDEX)))
     up = bool(rng.integers(0, 2))
     scale = float(f32(np.exp(rng.uniform(np.log(0.05), np.log(8.0)))))
-    taps = {"box": 1, "linear": 2, "cubic": 4, "lanczos": 6}[kernel]
+    taps = checker.RESIZE_TAPS[kernel]
     need = taps if up else int(np.ceil(f32(taps) * (f32(1) / f32(scale))))
     w, h, c = max(rdim(rng, 1, 700), need), max(rdim(rng, 1, 500), need), int(rng.integers(1, 5))
     dt = np.dtype(tname)
@@ -295,37 +284,16 @@ def fuzz_resize(rng):
     a, o = hl.Buffer(inp, mins=in_min), hl.Buffer(np.zeros((oc, oh, ow), dt), mins=out_min)
     hl.resize(a, scale, o, kernel, upsample=up)
     want = np.zeros((oc, oh, ow), dt)
-    i3 = lambda v: (ctypes.c_int * 3)(*[int(x) for x in v])
-    r = resize_checker().rc_resize(hl.RESIZE_KERNELS.index(kernel), ["float32", "uint8", "uint16"].index(tname), int(up), scale, inp.ctypes.data,
-                                   i3(in_min), i3((w, h, c)), want.ctypes.data, i3(out_min), i3((ow, oh, oc)))
+    r = checker.lib().rc_resize(checker.RESIZE_KERNELS.index(kernel), checker.RESIZE_TYPE_INDEX[tname], int(up), scale, inp.ctypes.data,
+                                checker.i3(in_min), checker.i3((w, h, c)), want.ctypes.data, checker.i3(out_min), checker.i3((ow, oh, oc)))
     desc = f"{kernel} {tname} {'up' if up else 'down'} x{scale!r} in {w}x{h}x{c} min {in_min} out {ow}x{oh}x{oc} min {out_min}"
     return desc, r == 0 and same(o.numpy(), want)
-
-
-_gaussian_blur_checker = []
-
-
-def gaussian_blur_checker():
-    """tests/cpp/gaussian_blur_check.c as a shared object (oracle/ has no gaussian_blur; the test suite builds the same file the same way)"""
-    if not _gaussian_blur_checker:
-        import ctypes
-        import subprocess
-        import tempfile
-        so = os.path.join(tempfile.mkdtemp(prefix="gaussian_blur_check"), "libgaussian_blur_check.so")
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", so,
-                        os.path.join(ROOT, "tests", "cpp", "gaussian_blur_check.c"), "-lm"], check=True)
-        lib = ctypes.CDLL(so)
-        lib.gc_set_canon(hl.canon_fma())
-        I, F, P = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
-        lib.gc_direct.argtypes = [P, I, I, I, I, F, I, P, I, I, I, I]
-        lib.gc_resampled.argtypes = [I, I, I, P, I, I, I, I, F, I, P, I, I]
-        _gaussian_blur_checker.append(lib)
-    return _gaussian_blur_checker[0]
 
 
 def fuzz_gaussian_blur(rng):
     """gaussian_blur: the direct blur (any output region) or a random one of the 36 variants, random sigma in [0.3, 12], trunc in 0..5,
     sizes and input origins, on either path, against tests/cpp/gaussian_blur_check.c"""
+    check = checkers().lib()
     w, h = rdim(rng, 1, 300), rdim(rng, 1, 200)
     sigma = float(f32(np.exp(rng.uniform(np.log(0.3), np.log(12.0)))))
     trunc = int(rng.integers(0, 6))
@@ -339,7 +307,7 @@ def fuzz_gaussian_blur(rng):
         out_min = [in_min[0] + int(rng.integers(-60, w + 60)), in_min[1] + int(rng.integers(-60, h + 60))] if rng.random() < 0.5 else list(in_min)
         o = hl.Buffer(np.zeros((oh, ow), f32), mins=out_min)
         want = np.zeros((oh, ow), f32)
-        r = gaussian_blur_checker().gc_direct(inp.ctypes.data, in_min[0], in_min[1], w, h, sigma, trunc, want.ctypes.data, out_min[0], out_min[1], ow, oh)
+        r = check.gc_direct(inp.ctypes.data, in_min[0], in_min[1], w, h, sigma, trunc, want.ctypes.data, out_min[0], out_min[1], ow, oh)
     else:
         u, d, f = int(rng.integers(2, 5)), int(rng.integers(1, 4)), int(rng.choice([2, 4, 8, 16]))
         name = hl.gaussian_blur_variant(u, d, f)
@@ -347,33 +315,13 @@ def fuzz_gaussian_blur(rng):
         out_min = [0, 0]
         o = hl.Buffer(hl.aligned_array((oh, ow)))
         want = np.zeros((oh, ow), f32)
-        r = gaussian_blur_checker().gc_resampled(u, d, f, inp.ctypes.data, in_min[0], in_min[1], w, h, sigma, trunc, want.ctypes.data, ow, oh)
+        r = check.gc_resampled(u, d, f, inp.ctypes.data, in_min[0], in_min[1], w, h, sigma, trunc, want.ctypes.data, ow, oh)
     if general:
         hl.debug_gaussian_blur_general(name, a, sigma, trunc, o)
     else:
         hl._check(hl._fn[name](a.ptr, sigma, trunc, o.ptr))
     desc = f"{name}{' general' if general else ''} sigma {sigma!r} trunc {trunc} in {w}x{h} min {in_min} out {ow}x{oh} min {out_min}"
     return desc, r == 0 and same(np.ascontiguousarray(o.numpy()), want)
-
-
-_linear_blur_checker = []
-
-
-def linear_blur_checker():
-    """tests/cpp/linear_blur_check.c as a shared object (oracle/ has no linear_blur; the test suite builds the same file the same way)"""
-    if not _linear_blur_checker:
-        import ctypes
-        import subprocess
-        import tempfile
-        so = os.path.join(tempfile.mkdtemp(prefix="linear_blur_check"), "liblinear_blur_check.so")
-        subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", so,
-                        os.path.join(ROOT, "tests", "cpp", "linear_blur_check.c"), "-lm"], check=True)
-        lib = ctypes.CDLL(so)
-        lib.lc_set_canon(hl.canon_fma())
-        I, P = ctypes.c_int, ctypes.c_void_p
-        lib.lc_blur.argtypes = [I, P, I, I, I, I, I, I, I, P, I, I, I, I]
-        _linear_blur_checker.append(lib)
-    return _linear_blur_checker[0]
 
 
 def _strided(rng, shape):
@@ -423,7 +371,7 @@ def fuzz_linear_blur(rng):
     o = hl.Buffer(_strided(rng, (on, oh, ow)), mins=(ox, oy, oc))
     mine = np.ascontiguousarray(vals[c_lo:c_lo + on])
     want = np.zeros((on, oh, ow), f32)
-    rc = linear_blur_checker().lc_blur(int(linear), mine.ctypes.data, ix0, iy0, w, h, on, width, height, want.ctypes.data, ox, oy, ow, oh)
+    rc = checkers().lib().lc_blur(int(linear), mine.ctypes.data, ix0, iy0, w, h, on, width, height, want.ctypes.data, ox, oy, ow, oh)
     name = "linear_blur" if linear else "simple_blur"
     fn = hl.lib.hlmi_linear_blur_general
     fn.restype, fn.argtypes = hl.C.c_int, [hl.C.c_char_p, hl._BP, hl.C.c_int32, hl.C.c_int32, hl._BP]
@@ -439,7 +387,7 @@ def fuzz_linear_blur(rng):
 
 
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
-CASES["resize"] = fuzz_resize   # its checker is not oracle/'s
+CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
 CASES["linear_blur"] = fuzz_linear_blur   # both entry points
 

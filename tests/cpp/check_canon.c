@@ -1,0 +1,7 @@
+/* check_canon.c — the one canonical-form switch of the plain-C checkers (resize_check.c, gaussian_blur_check.c,
+ * linear_blur_check.c), which tests/checker_lib.py links into one shared object.  o_canon_fma is the form that
+ * oracle/oracle_common.h's helpers read; the object is linked with -Wl,-Bsymbolic, so it is this definition and not
+ * liboracle.so's that the checkers see when both are loaded. */
+int o_canon_fma = 1;
+void ck_set_canon(int fma) { o_canon_fma = fma != 0; }
+int ck_get_canon(void) { return o_canon_fma; }

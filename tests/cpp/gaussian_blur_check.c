@@ -1,7 +1,7 @@
 /* gaussian_blur_check.c — the checker of the gaussian_blur pipelines: the arithmetic of
- * apps/gaussian_blur/gaussian_blur_generator.cpp restated in plain C, one rounding per operator (compile with -O2
- * -ffp-contract=off -Ioracle), every fused operation written out.  tests/test_gaussian_blur.py builds it as a shared object
- * and drives it through ctypes.  Written from the generator's text:
+ * apps/gaussian_blur/gaussian_blur_generator.cpp restated in plain C, one rounding per operator (no contraction by the
+ * compiler), every fused operation written out.  tests/checker_lib.py holds the build line: it links this file, with the other
+ * *_check.c files, into one shared object and drives it through ctypes.  Written from the generator's text:
  *
  *   :18-63    direct_gaussian_blur: the kernel table, its sum, the normalised table, the two passes
  *   :68-100   gaussian_blur_direct: repeat_edge of the input in front of it
@@ -9,8 +9,8 @@
  *   :160-214  the resampled blur: down_y in phases, down_x, sigma_lo, the second row clamp, the small blur, the two expansions
  *
  * Two canonical float forms, those of oracle/oracle_common.h, whose o_mad / o_mad2 / o_mulsub and o_halide_exp are used as they
- * are (the device's halide_exp is held to that one bit for bit by tests/test_device_math.py): gc_set_canon(0) rounds every
- * operator on its own, gc_set_canon(1) contracts a multiply with one use that feeds an add or a subtract.
+ * are (the device's halide_exp is held to that one bit for bit by tests/test_device_math.py): ck_set_canon(0) (check_canon.c)
+ * rounds every operator on its own, ck_set_canon(1) contracts a multiply with one use that feeds an add or a subtract.
  *
  * Zero folding.  The expansions are written `e = 0.f; e += t_0; e += t_1; ...` on Exprs (:197-200, :207-210), and Halide's
  * simplifier folds `0.f + t_0` to `t_0`; this checker follows it: e = t_0 + t_1 + ... with no leading zero, so a result of -0
@@ -24,10 +24,6 @@
 #include <string.h>
 
 #include "oracle_common.h"
-
-int o_canon_fma = 1;   /* the form oracle_common.h's helpers read; this object is linked against nothing else */
-void gc_set_canon(int fma) { o_canon_fma = fma != 0; }
-int gc_get_canon(void) { return o_canon_fma; }
 
 static int gc_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 static int gc_div_up(int a, int b) { return o_fdiv(a + b - 1, b); }

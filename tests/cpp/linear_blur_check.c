@@ -1,6 +1,7 @@
 /* linear_blur_check.c — the checker of simple_blur and linear_blur: the arithmetic of apps/linear_blur restated in plain C, one
- * rounding per operator (compile with -O2 -ffp-contract=off -Ioracle), the one fused operation written out.
- * tests/test_linear_blur.py builds it as a shared object and drives it through ctypes.  Written from the generators' text:
+ * rounding per operator (no contraction by the compiler), the one fused operation written out.  tests/checker_lib.py holds the
+ * build line: it links this file, with the other *_check.c files, into one shared object and drives it through ctypes.  Written
+ * from the generators' text:
  *
  *   simple_blur_generator.cpp:5-22       in = repeat_edge(input, {{0, width}, {0, height}}); blur_x = (in(x) + in(x + 1) + in(x + 2)) / 3;
  *                                        output = (blur_x(y) + blur_x(y + 1) + blur_x(y + 2)) / 3.  The channel is not clamped.
@@ -9,18 +10,15 @@
  *   linear_blur_generator.cpp:8-27       to_srgb(simple_blur(to_linear(input), input.width(), input.height()))
  *
  * x / c is x * fold(1 / c) (src/Simplify_Div.cpp:204); 1 + .055f, 1 / 2.4f and the reciprocals are folded in f32.  Two canonical
- * float forms, those of oracle/oracle_common.h, whose o_halide_pow and o_mulsub are used as they are: the only multiply that feeds
- * an add or a subtract is the last step of to_srgb, one fma in form 1 and two roundings in form 0.  blur_x is a Func of its own
- * (a stored value), so its multiply by a third does not contract into the sum that reads it. */
+ * float forms, those of oracle/oracle_common.h (ck_set_canon in check_canon.c selects one), whose o_halide_pow and o_mulsub are
+ * used as they are: the only multiply that feeds an add or a subtract is the last step of to_srgb, one fma in form 1 and two
+ * roundings in form 0.  blur_x is a Func of its own (a stored value), so its multiply by a third does not contract into the sum
+ * that reads it. */
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "oracle_common.h"
-
-int o_canon_fma = 1;   /* the form oracle_common.h's helpers read; this object is linked against nothing else */
-void lc_set_canon(int fma) { o_canon_fma = fma != 0; }
-int lc_get_canon(void) { return o_canon_fma; }
 
 static const float lc_third = 1.0f / 3.0f;
 

@@ -1,15 +1,18 @@
 /* resize_check.c — the checker of the resize pipelines: the arithmetic of apps/resize/resize_generator.cpp restated in
- * plain C, one rounding per operator (compile with -O2 -ffp-contract=off), every fused operation written out.
- * tests/test_resize.py builds it as a shared object and drives it through ctypes.  Written from the generator's text:
+ * plain C, one rounding per operator (no contraction by the compiler), every fused operation written out.
+ * tests/checker_lib.py holds the build line: it links this file, with the other *_check.c files, into one shared object
+ * and drives it through ctypes.
+ * Written from the generator's text:
  *
  *   :12-46   the four kernels (box, linear, cubic, lanczos)
  *   :85-147  inverse factor, kernel scaling, radius, taps, source coordinates, begin, weights, the two sums, the cast
  *
- * Two canonical float forms, as in oracle/oracle_common.h: rc_set_canon(0) rounds every operator on its own,
- * rc_set_canon(1) contracts a multiply with one use that feeds an add or a subtract (fmaf below).  The `begin`
- * expression sits under strict_float in the generator and is never contracted.  sin() is rc_halide_sin, the routine the
- * device uses (hlmi_device_math.h: dev::halide_sin), the same in both forms: the reference's CPU targets call libm there,
- * one opaque function, and no device routine can be bit-equal to it.
+ * Two canonical float forms, those of oracle/oracle_common.h, whose o_mad and o_mulsub are used as they are:
+ * ck_set_canon(0) (check_canon.c) rounds every operator on its own, ck_set_canon(1) contracts a multiply with one use
+ * that feeds an add or a subtract.  The `begin` expression sits under strict_float in the generator and is never
+ * contracted.  sin() is rc_halide_sin, the routine the device uses (hlmi_device_math.h: dev::halide_sin), the same in
+ * both forms: the reference's CPU targets call libm there, one opaque function, and no device routine can be bit-equal
+ * to it.
  */
 #include <math.h>
 #include <stddef.h>
@@ -17,13 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-static int rc_canon = 1;
-void rc_set_canon(int fma) { rc_canon = fma != 0; }
-int rc_get_canon(void) { return rc_canon; }
-
-/* fadd(fmul(a, b), c) and fsub(fmul(a, b), c) */
-static float rc_mad(float a, float b, float c) { return rc_canon ? fmaf(a, b, c) : a * b + c; }
-static float rc_mulsub(float a, float b, float c) { return rc_canon ? fmaf(a, b, -c) : a * b - c; }
+#include "oracle_common.h"
 
 /* ------------------------------------------------------------------------------------------------ sin
  * Specified for |x| <= 3 pi (1 + eps) only (the lanczos window cuts at |x| = 3 before the multiplication by pi).
@@ -105,8 +102,8 @@ static float rc_kernel(int kind, float x) {
         case RC_CUBIC: {
             const float xx2 = xx * xx, xx3 = xx2 * xx;
             /* a = -0.5: (a + 2) xx3 - (a + 3) xx2 + 1  and  a xx3 - 5a xx2 + 8a xx - 4a, constants folded in C++ */
-            const float inner = rc_mulsub(1.5f, xx3, 2.5f * xx2) + 1.0f;
-            const float outer = rc_mad(-4.0f, xx, rc_mulsub(-0.5f, xx3, -2.5f * xx2)) - -2.0f;
+            const float inner = o_mulsub(1.5f, xx3, 2.5f * xx2) + 1.0f;
+            const float outer = o_mad(-4.0f, xx, o_mulsub(-0.5f, xx3, -2.5f * xx2)) - -2.0f;
             return xx < 1.0f ? inner : (xx < 2.0f ? outer : 0.0f);
         }
         default: {
@@ -148,7 +145,7 @@ int rc_tables(int kind, int up, float scale, int out_min, int n, int in_min, int
         b = b < hi ? b : hi;
         b = b > in_min ? b : in_min;
         begin[i] = b;
-        const float src = rc_mulsub(xf, inv, 0.5f);
+        const float src = o_mulsub(xf, inv, 0.5f);
         float sum = 0.0f;
         for (int k = 0; k < taps; k++) {
             float arg = (float)(k + b) - src;
@@ -204,26 +201,26 @@ int rc_resize(int kind, int type, int up, float scale, const void *in, const int
             for (int y = 0; y < H; y++)
                 for (int x = 0; x < ow; x++) {
                     float s = 0.0f;
-                    for (int k = 0; k < taps; k++) s = rc_mad(wx[(size_t)k * ow + x], rc_load(in, type, plane + (size_t)y * W + (bx[x] + k - in_min[0])), s);
+                    for (int k = 0; k < taps; k++) s = o_mad(wx[(size_t)k * ow + x], rc_load(in, type, plane + (size_t)y * W + (bx[x] + k - in_min[0])), s);
                     mid[(size_t)y * ow + x] = s;
                 }
             for (int y = 0; y < oh; y++)
                 for (int x = 0; x < ow; x++) {
                     float s = 0.0f;
-                    for (int k = 0; k < taps; k++) s = rc_mad(wy[(size_t)k * oh + y], mid[(size_t)(by[y] + k - in_min[1]) * ow + x], s);
+                    for (int k = 0; k < taps; k++) s = o_mad(wy[(size_t)k * oh + y], mid[(size_t)(by[y] + k - in_min[1]) * ow + x], s);
                     rc_store(out, type, ((size_t)c * oh + y) * ow + x, s);
                 }
         } else {
             for (int y = 0; y < oh; y++)
                 for (int x = 0; x < W; x++) {
                     float s = 0.0f;
-                    for (int k = 0; k < taps; k++) s = rc_mad(wy[(size_t)k * oh + y], rc_load(in, type, plane + (size_t)(by[y] + k - in_min[1]) * W + x), s);
+                    for (int k = 0; k < taps; k++) s = o_mad(wy[(size_t)k * oh + y], rc_load(in, type, plane + (size_t)(by[y] + k - in_min[1]) * W + x), s);
                     mid[(size_t)y * W + x] = s;
                 }
             for (int y = 0; y < oh; y++)
                 for (int x = 0; x < ow; x++) {
                     float s = 0.0f;
-                    for (int k = 0; k < taps; k++) s = rc_mad(wx[(size_t)k * ow + x], mid[(size_t)y * W + (bx[x] + k - in_min[0])], s);
+                    for (int k = 0; k < taps; k++) s = o_mad(wx[(size_t)k * ow + x], mid[(size_t)y * W + (bx[x] + k - in_min[0])], s);
                     rc_store(out, type, ((size_t)c * oh + y) * ow + x, s);
                 }
         }

@@ -2,13 +2,12 @@
 (shape, origin, parameter) cases — not a time budget, so the cases are the same on every box — GPU result vs the oracle, bit
 for bit (conv_layer_bf16: its tolerance).  The full sweeps (minutes, 10^5 cases, 8 host threads) stay a script:
 profiles/r02c_fuzz_parity.txt."""
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from parity_helpers import ROOT, load_fuzz_parity
 
 # cases per pipeline: sized so that the whole slice takes a few seconds of GPU + oracle time
 N_CASES = {"local_laplacian": 6, "bilateral_grid": 6, "nl_means": 4, "stencil_chain": 6, "halide_blur": 8, "unsharp": 6,
@@ -18,10 +17,7 @@ N_CASES = {"local_laplacian": 6, "bilateral_grid": 6, "nl_means": 4, "stencil_ch
 
 @pytest.fixture(scope="module")
 def fuzz():
-    spec = importlib.util.spec_from_file_location("fuzz_parity", os.path.join(ROOT, "scripts", "fuzz_parity.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)     # imports halide_amd (the product) and oracle_lib (the checker)
-    return mod
+    return load_fuzz_parity()
 
 
 def test_slice_covers_every_fuzzed_pipeline():

@@ -1,7 +1,7 @@
 """gaussian_blur: the direct separable blur and its 36 resampled variants gaussian_blur_<U>_<D>_<F> (apps/gaussian_blur).
 
 The checker is tests/cpp/gaussian_blur_check.c, a plain C restatement of apps/gaussian_blur/gaussian_blur_generator.cpp:18-63,
-:117-150, :160-214 in both canonical float forms, compiled here with `gcc -O2 -ffp-contract=off` and driven through ctypes; it
+:117-150, :160-214 in both canonical float forms, built and driven through ctypes by tests/checker_lib.py; it
 takes halide_exp from oracle/oracle_common.h.  The CPU tests hold the checker to an independent numpy float64 evaluation
 (per-axis matrices: the pipelines are separable, out = M_y img M_x^T) and to properties that follow from the generator's text;
 the GPU tests hold the library to the checker bit for bit.  Like every float pipeline here, gaussian_blur is pinned to this
@@ -13,7 +13,9 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import checker_lib
+from parity_helpers import ROOT, RUNGEN, call_argv, call_direct, launches, load_fuzz_parity, noise, same_bits as _same
+
 ORDERS_UP, ORDERS_DOWN, FACTORS = (2, 3, 4), (1, 2, 3), (2, 4, 8, 16)
 UDF = [(u, d, f) for u in ORDERS_UP for d in ORDERS_DOWN for f in FACTORS]
 VARIANTS = [f"gaussian_blur_{u}_{d}_{f}" for u, d, f in UDF]
@@ -22,75 +24,29 @@ FOUR = [(3, 2, 8), (4, 3, 16), (2, 3, 16), (2, 1, 2)]
 
 
 # ---------------------------------------------------------------------------------------------------- the checker
-class Checker:
-    def __init__(self, path):
-        self.lib = L = C.CDLL(path)
-        I, F, P = C.c_int, C.c_float, C.c_void_p
-        L.gc_radius.argtypes = [F, I]
-        L.gc_kernel_table.argtypes = [F, I, P, P]
-        L.gc_resampling_kernel.argtypes = [I, I, P]
-        L.gc_variance.restype = F
-        L.gc_variance.argtypes = [I, I]
-        L.gc_sigma_lo.restype = F
-        L.gc_sigma_lo.argtypes = [I, I, I, F]
-        L.gc_direct.argtypes = [P, I, I, I, I, F, I, P, I, I, I, I]
-        L.gc_resampled.argtypes = [I, I, I, P, I, I, I, I, F, I, P, I, I]
-
-    def set_canon(self, fma):
-        self.lib.gc_set_canon(int(fma))
-
-    def radius(self, sigma, trunc):
-        return int(self.lib.gc_radius(sigma, trunc))
-
-    def kernel_table(self, sigma, radius):
-        kn, s = np.zeros(2 * radius + 1, np.float32), np.zeros(1, np.float32)
-        self.lib.gc_kernel_table(sigma, radius, kn.ctypes.data, s.ctypes.data)
-        return kn, s[0]
-
-    def resampling_kernel(self, order, factor):
-        k = np.zeros(order * factor, np.float32)
-        self.lib.gc_resampling_kernel(order, factor, k.ctypes.data)
-        return k
-
-    def sigma_lo(self, u, d, f, sigma):
-        return float(self.lib.gc_sigma_lo(u, d, f, sigma))
-
-    def direct(self, img, sigma, trunc, out_shape=None, out_min=None, in_min=(0, 0)):
-        """img: (H, W); out_shape: (H', W'), default the image's own region"""
-        img = np.ascontiguousarray(img, np.float32)
-        out_shape = img.shape if out_shape is None else out_shape
-        out_min = in_min if out_min is None else out_min
-        out = np.zeros(out_shape, np.float32)
-        r = self.lib.gc_direct(img.ctypes.data, in_min[0], in_min[1], img.shape[1], img.shape[0], sigma, trunc, out.ctypes.data, out_min[0], out_min[1],
-                               out.shape[1], out.shape[0])
-        assert r == 0, r
-        return out
-
-    def resampled(self, udf, img, sigma, trunc, out_shape=None, in_min=(0, 0)):
-        img = np.ascontiguousarray(img, np.float32)
-        out = np.zeros(img.shape if out_shape is None else out_shape, np.float32)
-        r = self.lib.gc_resampled(*udf, img.ctypes.data, in_min[0], in_min[1], img.shape[1], img.shape[0], sigma, trunc, out.ctypes.data, out.shape[1],
-                                  out.shape[0])
-        assert r == 0, r
-        return out
-
-
 @pytest.fixture(scope="session")
-def gc(tmp_path_factory):
-    so = tmp_path_factory.mktemp("gaussian_blur_check") / "libgaussian_blur_check.so"
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", str(so),
-                    os.path.join(ROOT, "tests", "cpp", "gaussian_blur_check.c"), "-lm"], check=True)
-    return Checker(str(so))
+def gc():
+    return checker_lib.gaussian_blur
 
 
 @pytest.fixture(params=[0, 1], ids=["canon0", "canon1"])
-def each_canon_gc(request, gc):
-    gc.set_canon(request.param)
-    yield request.param
+def each_canon_gc(request):
+    with checker_lib.canon(request.param):
+        yield request.param
 
 
-def noise(shape, seed):
-    return np.random.default_rng(seed).random(shape, dtype=np.float32)
+@pytest.fixture
+def canon0_gc():
+    """for the tests whose tolerance was measured in canonical form 0"""
+    with checker_lib.canon(0):
+        yield
+
+
+@pytest.fixture
+def canon_gc(hl, gc):
+    """the checker in the form the loaded library was built for"""
+    with checker_lib.canon(hl.canon_fma()):
+        yield gc
 
 
 # ---------------------------------------------------------------------------------------------------- float64 evaluation
@@ -228,25 +184,7 @@ def test_aligned_array(hl):
 
 
 # ---------------------------------------------------------------------------------------------------- CPU: the entry protocol
-def _ptr(b):
-    return None if b is None else b.ptr
-
-
-def _call_direct(hl, name, inp, sigma, trunc, out):
-    return hl._fn[name](_ptr(inp), C.c_float(sigma), C.c_int32(trunc), _ptr(out))
-
-
-def _call_argv(hl, name, inp, sigma, trunc, out):
-    fn = getattr(hl.lib, name + "_argv")
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(C.c_void_p)]
-    s, t = C.c_float(sigma), C.c_int32(trunc)
-    argv = (C.c_void_p * 4)(None if inp is None else C.cast(inp.ptr, C.c_void_p), C.cast(C.pointer(s), C.c_void_p), C.cast(C.pointer(t), C.c_void_p),
-                            None if out is None else C.cast(out.ptr, C.c_void_p))
-    return fn(argv)
-
-
-@pytest.mark.parametrize("how", [_call_direct, _call_argv], ids=["direct_call", "argv"])
+@pytest.mark.parametrize("how", [call_direct, call_argv], ids=["direct_call", "argv"])
 @pytest.mark.parametrize("name", ["gaussian_blur_direct", "gaussian_blur_3_2_8", "gaussian_blur_2_3_16"])
 def test_entry_protocol(hl, name, how):
     resampled = name != "gaussian_blur_direct"
@@ -289,7 +227,7 @@ def test_entry_protocol(hl, name, how):
         assert free() == -29 and call(mk(), mk()) == -29
 
 
-@pytest.mark.parametrize("how", [_call_direct, _call_argv], ids=["direct_call", "argv"])
+@pytest.mark.parametrize("how", [call_direct, call_argv], ids=["direct_call", "argv"])
 def test_bounds_queries(hl, how):
     dims = lambda b: [(b.raw.dim[i].min, b.raw.dim[i].extent) for i in range(2)]
     real = lambda: hl.Buffer(hl.aligned_array((48, 64)), mins=(2, 3))
@@ -327,7 +265,7 @@ def test_without_a_gpu_the_python_calls_refuse_to_run(hl):
 # ---------------------------------------------------------------------------------------------------- CPU: tables
 @pytest.mark.parametrize("factor", FACTORS)
 @pytest.mark.parametrize("order", [1, 2, 3, 4])
-def test_resampling_tables_are_exact_and_sum_to_one(gc, order, factor):
+def test_resampling_tables_are_exact_and_sum_to_one(gc, canon_gc, order, factor):
     k = gc.resampling_kernel(order, factor)
     want = _spline64(order, factor)
     assert np.array_equal(k.astype(np.float64), want)                     # f32 and f64 evaluations agree exactly
@@ -382,16 +320,14 @@ def truth64(cpu_image):
 
 
 @pytest.mark.parametrize("sigma,trunc", DIRECT_CASES)
-def test_checker_direct_against_float64(gc, cpu_image, sigma, trunc):
-    gc.set_canon(0)
+def test_checker_direct_against_float64(gc, canon0_gc, cpu_image, sigma, trunc):
     d = float(np.max(np.abs(gc.direct(cpu_image, sigma, trunc).astype(np.float64) - ref64_direct(gc, cpu_image, sigma, trunc))))
     print(f"direct sigma {sigma} trunc {trunc}: largest |checker - float64| = {d:.3g}")
     assert d <= F32_VS_FLOAT64
 
 
 @pytest.mark.parametrize("udf,sigma", RESAMPLED_CASES, ids=lambda v: "_".join(map(str, v)) if isinstance(v, tuple) else str(v))
-def test_checker_resampled_against_float64(gc, cpu_image, udf, sigma):
-    gc.set_canon(0)
+def test_checker_resampled_against_float64(gc, canon0_gc, cpu_image, udf, sigma):
     d = float(np.max(np.abs(gc.resampled(udf, cpu_image, sigma, 5).astype(np.float64) - ref64_resampled(gc, udf, cpu_image, sigma, 5))))
     print(f"{udf} sigma {sigma}: largest |checker - float64| = {d:.3g}")
     assert d <= F32_VS_FLOAT64
@@ -428,9 +364,8 @@ def test_radius_zero_is_a_bit_exact_copy(gc, each_canon_gc):
 
 
 @pytest.mark.parametrize("udf", UDF, ids=lambda v: "_".join(map(str, v)))
-def test_a_constant_image_stays_constant(gc, udf):
+def test_a_constant_image_stays_constant(gc, canon0_gc, udf):
     """follows from |checker - float64| <= the tolerance: every row of every float64 matrix sums to 1"""
-    gc.set_canon(0)
     img = np.full((45, 70), 0.7, np.float32)
     for sigma in (10.0, 4.0):
         assert np.max(np.abs(gc.resampled(udf, img, sigma, 5).astype(np.float64) - float(np.float32(0.7)))) <= F32_VS_FLOAT64, sigma
@@ -486,18 +421,6 @@ def _gpu_resampled(hl, udf, img, sigma, trunc, out_shape=None, in_min=(0, 0), ge
     return np.ascontiguousarray(o.numpy())
 
 
-def _same(got, want, what):
-    assert got.shape == want.shape, what
-    bad = got.view(np.uint32) != want.view(np.uint32)
-    assert not bad.any(), f"{what}: {np.count_nonzero(bad)} of {got.size} differ, first at {tuple(np.argwhere(bad)[0])}"
-
-
-@pytest.fixture
-def canon_gc(hl, gc):
-    gc.set_canon(hl.canon_fma())
-    return gc
-
-
 @pytest.fixture(params=["by_size", "general", "tile16", "tile4"])
 def general(request, monkeypatch):
     """Every path a blur pass can take (halide_amd/csrc/gaussian_blur.hip, run_blur): chosen by size, the general kernels through the
@@ -505,8 +428,6 @@ def general(request, monkeypatch):
     if request.param.startswith("tile"):
         monkeypatch.setenv("HLMI_GB_TILE", request.param[4:])
     return request.param == "general"
-
-
 
 
 @pytest.mark.gpu
@@ -563,14 +484,7 @@ def test_resampled_sizes_sigmas_and_mins(hl, canon_gc, on_stream, udf, general):
 
 
 def _launches(hl, fn):
-    hl.kernel_timing(True)
-    hl.kernel_timing_reset()
-    try:
-        fn()
-        return {e["name"] for e in hl.kernel_timing_report()}
-    finally:
-        hl.kernel_timing(False)
-        hl.kernel_timing_reset()
+    return set(launches(hl, fn))   # which kernels, however often
 
 
 TILED, GENERAL = {"gb_tables", "gb_blur_y", "gb_blur_x"}, {"gb_tables", "gb_blur_y_general", "gb_blur_x_general"}
@@ -621,7 +535,7 @@ def test_direct_radius_past_the_staged_span(hl, canon_gc, monkeypatch):
 def test_argv_equals_the_direct_call(hl, name):
     img = noise((45, 70), 6)
     outs = []
-    for how in (_call_direct, _call_argv):
+    for how in (call_direct, call_argv):
         a, o = hl.Buffer(img.copy()), hl.Buffer(hl.aligned_array((45, 70)))
         assert how(hl, name, a, 3.0, 4, o) == 0
         outs.append(np.ascontiguousarray(o.numpy()))
@@ -661,9 +575,6 @@ def test_torch_op_equals_the_checker(hl, canon_gc):
 
 
 # ---------------------------------------------------------------------------------------------------- the RunGen-compatible runner
-RUNGEN = os.path.join(ROOT, "halide_amd", "bin", "hlmi_rungen")
-
-
 def test_runner_describes_a_variant_by_name():
     out = subprocess.run([RUNGEN, "--name=gaussian_blur_3_2_8", "--describe"], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stdout + out.stderr
@@ -675,10 +586,7 @@ def test_runner_describes_a_variant_by_name():
 @pytest.mark.gpu
 def test_seeded_fuzz_slice_of_gaussian_blur():
     """scripts/fuzz_parity.py's gaussian_blur case, a fixed number of cases from a fixed seed"""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("fuzz_parity", os.path.join(ROOT, "scripts", "fuzz_parity.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_fuzz_parity()
     rng = np.random.default_rng(20261017)
     for i in range(40):
         desc, ok = mod.CASES["gaussian_blur"](rng)

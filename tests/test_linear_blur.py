@@ -2,7 +2,7 @@
 
 The checker is tests/cpp/linear_blur_check.c, a plain C restatement of apps/linear_blur/simple_blur_generator.cpp:5-22,
 srgb_to_linear_generator.cpp:14-16, linear_to_srgb_generator.cpp:14-16 and linear_blur_generator.cpp:8-27 in both canonical float
-forms, compiled here with `gcc -O2 -ffp-contract=off` and driven through ctypes; it takes halide_pow and the mul+sub pair from
+forms, built and driven through ctypes by tests/checker_lib.py; it takes halide_pow and the mul+sub pair from
 oracle/oracle_common.h.  The CPU tests hold the checker to a numpy float64 evaluation and to properties that follow from the
 generators' text, and the entry points to their contract; the GPU tests hold the library to the checker bit for bit.  Like every
 float pipeline here, the two are pinned to this repository's restatement only: no output of a real Halide build is involved."""
@@ -13,68 +13,32 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import checker_lib
+from parity_helpers import ROOT, RUNGEN, call_argv, call_direct, load_fuzz_parity, noise
+from parity_helpers import gpu_present as _gpu_present, launches as _launches, same_bits as _same
+
 NAMES = ["linear_blur", "simple_blur"]
 f32 = np.float32
 T_LINEAR, T_SRGB = f32(0.04045), f32(0.0031308)   # the thresholds of the two conversions
 
 
 # ---------------------------------------------------------------------------------------------------- the checker
-class Checker:
-    def __init__(self, path):
-        self.lib = L = C.CDLL(path)
-        I, P = C.c_int, C.c_void_p
-        L.lc_blur.argtypes = [I, P, I, I, I, I, I, I, I, P, I, I, I, I]
-        for fn in (L.lc_to_linear, L.lc_to_srgb):
-            fn.restype, fn.argtypes = C.c_float, [C.c_float]
-
-    def set_canon(self, fma):
-        self.lib.lc_set_canon(int(fma))
-
-    def to_linear(self, s):
-        return f32(self.lib.lc_to_linear(float(s)))
-
-    def to_srgb(self, l):
-        return f32(self.lib.lc_to_srgb(float(l)))
-
-    def blur(self, name, img, width=None, height=None, out_shape=None, out_min=None, in_min=(0, 0, 0), expect=0):
-        """img: (C, H, W) at mins in_min = (x, y, c); out_shape: (C', H', W') at out_min, default the image's own region.  width and
-        height (simple_blur): default the image's."""
-        img = np.asarray(img, f32)
-        out_shape = img.shape if out_shape is None else out_shape
-        out_min = in_min if out_min is None else out_min
-        c0 = out_min[2] - in_min[2]
-        assert 0 <= c0 and c0 + out_shape[0] <= img.shape[0]
-        mine = np.ascontiguousarray(img[c0:c0 + out_shape[0]])
-        out = np.zeros(out_shape, f32)
-        r = self.lib.lc_blur(int(name == "linear_blur"), mine.ctypes.data, in_min[0], in_min[1], img.shape[2], img.shape[1], out_shape[0],
-                             img.shape[2] if width is None else width, img.shape[1] if height is None else height, out.ctypes.data,
-                             out_min[0], out_min[1], out_shape[2], out_shape[1])
-        assert r == expect, r
-        return out
-
-
 @pytest.fixture(scope="session")
-def lc(tmp_path_factory):
-    so = tmp_path_factory.mktemp("linear_blur_check") / "liblinear_blur_check.so"
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", str(so),
-                    os.path.join(ROOT, "tests", "cpp", "linear_blur_check.c"), "-lm"], check=True)
-    return Checker(str(so))
+def lc():
+    return checker_lib.linear_blur
 
 
 @pytest.fixture(params=[0, 1], ids=["canon0", "canon1"])
-def each_canon_lc(request, lc):
-    lc.set_canon(request.param)
-    yield request.param
+def each_canon_lc(request):
+    with checker_lib.canon(request.param):
+        yield request.param
 
 
-def noise(shape, seed):
-    return np.random.default_rng(seed).random(shape, dtype=f32)
-
-
-def _gpu_present():
-    import torch
-    return torch.cuda.is_available()
+@pytest.fixture
+def canon_lc(hl, lc):
+    """the checker in the form the loaded library was built for"""
+    with checker_lib.canon(hl.canon_fma()):
+        yield lc
 
 
 # ---------------------------------------------------------------------------------------------------- CPU: the library's surface
@@ -123,9 +87,6 @@ def test_the_aot_headers_compile_as_c(tmp_path):
         subprocess.run(["gcc", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(one), "-o", str(tmp_path / (name + ".o"))], check=True)
 
 
-RUNGEN = os.path.join(ROOT, "halide_amd", "bin", "hlmi_rungen")
-
-
 def test_runner_describes_both_by_name():
     out = subprocess.run([RUNGEN, "--name=linear_blur", "--describe"], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stdout + out.stderr
@@ -137,28 +98,12 @@ def test_runner_describes_both_by_name():
 
 
 # ---------------------------------------------------------------------------------------------------- CPU: the entry protocol
-def _ptr(b):
-    return None if b is None else b.ptr
+def _args(name, inp, width, height, out):
+    """the entry point's own arguments: linear_blur takes no width and no height"""
+    return (inp, out) if name == "linear_blur" else (inp, width, height, out)
 
 
-def _call_direct(hl, name, inp, width, height, out):
-    if name == "linear_blur":
-        return hl._fn[name](_ptr(inp), _ptr(out))
-    return hl._fn[name](_ptr(inp), C.c_int32(width), C.c_int32(height), _ptr(out))
-
-
-def _call_argv(hl, name, inp, width, height, out):
-    fn = getattr(hl.lib, name + "_argv")
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(C.c_void_p)]
-    vp = lambda b: None if b is None else C.cast(b.ptr, C.c_void_p)
-    if name == "linear_blur":
-        return fn((C.c_void_p * 2)(vp(inp), vp(out)))
-    w, h = C.c_int32(width), C.c_int32(height)
-    return fn((C.c_void_p * 4)(vp(inp), C.cast(C.pointer(w), C.c_void_p), C.cast(C.pointer(h), C.c_void_p), vp(out)))
-
-
-HOW = pytest.mark.parametrize("how", [_call_direct, _call_argv], ids=["direct_call", "argv"])
+HOW = pytest.mark.parametrize("how", [call_direct, call_argv], ids=["direct_call", "argv"])
 
 
 @HOW
@@ -167,7 +112,7 @@ def test_entry_protocol(hl, name, how):
     ok = 0 if _gpu_present() else -29   # with everything in order only the device can be missing
     mk = lambda shape=(3, 32, 40), dtype=f32, mins=None: hl.Buffer(np.zeros(shape, dtype), mins=mins)
     strided = lambda mins=None: hl.Buffer(np.zeros((3, 32, 80), f32)[:, :, ::2], mins=mins)   # stride.0 == 2
-    call = lambda i, o, w=40, h=32: how(hl, name, i, w, h, o)
+    call = lambda i, o, w=40, h=32: how(hl, name, *_args(name, i, w, h, o))
     assert call(None, mk()) == -12 and call(mk(), None) == -12
     assert call(mk(dtype=np.uint16), mk()) == -3 and call(mk(), mk(dtype=np.uint16)) == -3
     assert call(mk((32, 40)), mk()) == -43 and call(mk(), mk((32, 40))) == -43
@@ -195,7 +140,7 @@ def test_linear_blur_clamps_to_the_extents_whatever_the_mins(hl, how):
     ok = 0 if _gpu_present() else -29
     inp = lambda mins: hl.Buffer(np.zeros((3, 32, 40), f32), mins=mins)
     out = lambda shape, mins: hl.Buffer(np.zeros(shape, f32), mins=mins)
-    call = lambda i, o: how(hl, "linear_blur", i, 0, 0, o)
+    call = lambda i, o: how(hl, "linear_blur", i, o)
     assert call(inp((5, 0, 0)), out((3, 32, 40), (0, 0, 0))) == -4 and "dimension 0" in hl.last_error() and "before" in hl.last_error()
     assert call(inp((5, 0, 0)), out((3, 32, 40), (4, 0, 0))) == -4
     assert call(inp((5, 0, 0)), out((3, 32, 40), (5, 0, 0))) == ok     # columns 5 .. 39 (clamped at extent - 1 = 39)
@@ -257,16 +202,16 @@ def test_bounds_queries(hl, how):
     assert dims(q) == [(5, 40), (6, 30), (1, 2)] and dims(qi) == [(5, 42), (6, 32), (1, 2)]
     # linear_blur: its box depends on the input's own extents, so x and y stay as passed and the channels are the output's
     qi = query((2, 3, 0), (64, 48, 5))
-    assert how(hl, "linear_blur", qi, 0, 0, real((3, 30, 40), (-5, 100, 1))) == 0
+    assert how(hl, "linear_blur", qi, real((3, 30, 40), (-5, 100, 1))) == 0
     assert dims(qi) == [(2, 64), (3, 48), (1, 3)]
     q, a = query((5, 6, 1), (40, 30, 2)), real()
-    assert how(hl, "linear_blur", a, 0, 0, q) == 0
+    assert how(hl, "linear_blur", a, q) == 0
     assert dims(q) == [(5, 40), (6, 30), (1, 2)] and dims(a) == [(2, 64), (3, 48), (0, 3)]
     q, qi = query((5, 6, 1), (40, 30, 2), np.uint16), query((0, 0, 0), (64, 48, 3))
-    assert how(hl, "linear_blur", qi, 0, 0, q) == 0
+    assert how(hl, "linear_blur", qi, q) == 0
     assert dims(q) == [(5, 40), (6, 30), (1, 2)] and dims(qi) == [(0, 64), (0, 48), (1, 2)] and (q.raw.type.code, q.raw.type.bits) == (2, 32)
     # a query with the wrong dimensionality stays an error
-    assert how(hl, "linear_blur", hl.Buffer.bounds_query(f32, 2, mins=(0, 0), extents=(4, 4)), 0, 0, real()) == -43
+    assert how(hl, "linear_blur", hl.Buffer.bounds_query(f32, 2, mins=(0, 0), extents=(4, 4)), real()) == -43
 
 
 def test_without_a_gpu_the_python_calls_refuse_to_run(hl):
@@ -407,18 +352,6 @@ def _gpu(hl, name, img, width=None, height=None, out_shape=None, out_min=None, i
     return np.ascontiguousarray(o.numpy())
 
 
-def _same(got, want, what):
-    assert got.shape == want.shape, what
-    bad = got.view(np.uint32) != want.view(np.uint32)
-    assert not bad.any(), f"{what}: {np.count_nonzero(bad)} of {got.size} differ, first at {tuple(np.argwhere(bad)[0])}"
-
-
-@pytest.fixture
-def canon_lc(hl, lc):
-    lc.set_canon(hl.canon_fma())
-    return lc
-
-
 @pytest.fixture(params=["by_size", "general"])
 def general(request):
     """Both implementations (halide_amd/csrc/linear_blur.hip): the one launch every shape takes, and the unfused composition through
@@ -489,17 +422,6 @@ def test_special_values(hl, canon_lc, on_stream, name, general):
     assert np.array_equal(got.view(np.uint32)[~np.isnan(want)], want.view(np.uint32)[~np.isnan(want)])
 
 
-def _launches(hl, fn):
-    hl.kernel_timing(True)
-    hl.kernel_timing_reset()
-    try:
-        fn()
-        return sorted(e["name"] for e in hl.kernel_timing_report())
-    finally:
-        hl.kernel_timing(False)
-        hl.kernel_timing_reset()
-
-
 @pytest.mark.gpu
 def test_the_paths_launch_what_they_say(hl):
     for shape in ((3, 97, 131), (1, 1, 1)):   # one launch for every shape
@@ -524,9 +446,9 @@ def test_fused_equals_general(hl, on_stream, name, shape):
 def test_argv_equals_the_direct_call(hl, on_stream, name):
     img = noise((3, 45, 70), 6)
     outs = []
-    for how in (_call_direct, _call_argv):
+    for how in (call_direct, call_argv):
         a, o = hl.Buffer(img.copy()), hl.Buffer(np.zeros((3, 45, 70), f32))
-        assert how(hl, name, a, 61, 33, o) == 0   # a width and a height that are not the buffer's, and not each other's
+        assert how(hl, name, *_args(name, a, 61, 33, o)) == 0   # a width and a height that are not the buffer's, and not each other's
         outs.append(np.ascontiguousarray(o.numpy()))
     assert outs[0].tobytes() == outs[1].tobytes() and outs[0].any()
 
@@ -564,10 +486,7 @@ def test_torch_ops_equal_the_checker(hl, canon_lc):
 @pytest.mark.gpu
 def test_seeded_fuzz_slice_of_linear_blur(on_stream):
     """scripts/fuzz_parity.py's linear_blur case (both entry points), a fixed number of cases from a fixed seed"""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("fuzz_parity", os.path.join(ROOT, "scripts", "fuzz_parity.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_fuzz_parity()
     rng = np.random.default_rng(20261018)
     for i in range(40):
         desc, ok = mod.CASES["linear_blur"](rng)

@@ -1,7 +1,7 @@
 """resize: box / linear / cubic / lanczos resampling for f32, u8 and u16, 24 AOT variants (apps/resize).
 
 The checker is tests/cpp/resize_check.c, a plain C restatement of apps/resize/resize_generator.cpp:12-46, :85-147 in both
-canonical float forms, compiled here with `gcc -O2 -ffp-contract=off` and driven through ctypes.  The CPU tests hold the
+canonical float forms, built and driven through ctypes by tests/checker_lib.py.  The CPU tests hold the
 checker to an independent numpy float64 evaluation and to properties that follow from the generator's text; the GPU tests
 hold the library to the checker bit for bit.  Like every float pipeline here, resize is pinned to this repository's
 restatement only: no output of a real Halide build is involved."""
@@ -12,70 +12,40 @@ import subprocess
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ("box", "linear", "cubic", "lanczos")
-TAPS = {"box": 1, "linear": 2, "cubic": 4, "lanczos": 6}
+import checker_lib
+from checker_lib import RESIZE_KERNELS as KERNELS, RESIZE_TAPS as TAPS, resize_out_size as out_size
+from parity_helpers import ROOT, RUNGEN, call_argv, launches, load_fuzz_parity, same_bits as _same
+
 TYPES = {"float32": np.float32, "uint8": np.uint8, "uint16": np.uint16}
-TYPE_INDEX = {"float32": 0, "uint8": 1, "uint16": 2}
 DOWN_FACTORS = (0.125, 0.23, 0.37, 0.5, 0.9, 1.0)
 UP_FACTORS = (0.6, 1.0, 1.7, 2.0, 3.3, 4.0)
 VARIANTS = [f"resize_{k}_{t}_{d}" for k in KERNELS for t in TYPES for d in ("up", "down")]
 
 
 # ---------------------------------------------------------------------------------------------------- the checker
-class Checker:
-    def __init__(self, path):
-        self.lib = L = C.CDLL(path)
-        L.rc_halide_sin.restype = C.c_float
-        L.rc_halide_sin.argtypes = [C.c_float]
-        L.rc_sin_array.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-        L.rc_sin_sweep.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_float)]
-        L.rc_tables.argtypes = [C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rc_resize.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rc_taps_f.restype = C.c_float
-        L.rc_taps_f.argtypes = [C.c_int, C.c_int, C.c_float]
-
-    def set_canon(self, fma):
-        self.lib.rc_set_canon(int(fma))
-
-    def sin(self, x):
-        x = np.ascontiguousarray(x, np.float32)
-        out = np.empty_like(x)
-        self.lib.rc_sin_array(x.ctypes.data, out.ctypes.data, x.size)
-        return out
-
-    def tables(self, kernel, up, scale, out_min, n, in_min, in_extent):
-        taps = int(self.lib.rc_taps_f(KERNELS.index(kernel), int(up), scale))
-        begin, w, sums = np.zeros(n, np.int32), np.zeros((taps, n), np.float32), np.zeros(n, np.float32)
-        r = self.lib.rc_tables(KERNELS.index(kernel), int(up), scale, out_min, n, in_min, in_extent, begin.ctypes.data, w.ctypes.data, sums.ctypes.data)
-        assert r == taps, r
-        return begin, w, sums
-
-    def resize(self, kernel, img, scale, up, out_shape=None, out_min=(0, 0, 0), in_min=(0, 0, 0)):
-        """img: (C, H, W); out_shape: (C', H', W'), default the driver's int(W * scale), int(H * scale)"""
-        img = np.ascontiguousarray(img)
-        tname = img.dtype.name
-        if out_shape is None:
-            out_shape = (img.shape[0],) + out_size(img.shape[2], img.shape[1], scale)[::-1]
-        out = np.zeros(out_shape, img.dtype)
-        i3 = lambda v: (C.c_int * 3)(*[int(a) for a in v])
-        r = self.lib.rc_resize(KERNELS.index(kernel), TYPE_INDEX[tname], int(up), scale, img.ctypes.data, i3(in_min), i3(img.shape[::-1]),
-                               out.ctypes.data, i3(out_min), i3(out.shape[::-1]))
-        assert r == 0, r
-        return out
-
-
 @pytest.fixture(scope="session")
-def rc(tmp_path_factory):
-    so = tmp_path_factory.mktemp("resize_check") / "libresize_check.so"
-    subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", str(so), os.path.join(ROOT, "tests", "cpp", "resize_check.c"), "-lm"],
-                   check=True)
-    return Checker(str(so))
+def rc():
+    return checker_lib.resize
 
 
-def out_size(w, h, scale):
-    """apps/resize/resize.cpp:77-78: int out_width = in.width() * scale_factor (int * float, truncated)"""
-    return int(np.float32(w) * np.float32(scale)), int(np.float32(h) * np.float32(scale))
+@pytest.fixture(params=[0, 1], ids=["canon0", "canon1"])
+def each_canon_rc(request):
+    with checker_lib.canon(request.param):
+        yield request.param
+
+
+@pytest.fixture
+def canon0_rc():
+    """for the tests whose tolerance was measured in canonical form 0"""
+    with checker_lib.canon(0):
+        yield
+
+
+@pytest.fixture
+def canon_rc(hl, rc):
+    """the checker in the form the loaded library was built for"""
+    with checker_lib.canon(hl.canon_fma()):
+        yield rc
 
 
 def image(tname, shape, seed):
@@ -198,16 +168,6 @@ def test_python_picks_the_variant_from_type_name_and_direction(hl):
         hl.resize_variant(hl.Buffer(np.zeros((3, 8, 8), np.int32)), 0.5)
 
 
-def _argv_call(hl, name, inp, scale, out):
-    fn = getattr(hl.lib, name + "_argv")
-    fn.restype = C.c_int
-    fn.argtypes = [C.POINTER(C.c_void_p)]
-    s = C.c_float(scale)
-    argv = (C.c_void_p * 3)(None if inp is None else C.cast(inp.ptr, C.c_void_p), C.cast(C.pointer(s), C.c_void_p),
-                            None if out is None else C.cast(out.ptr, C.c_void_p))
-    return fn(argv)
-
-
 @pytest.mark.parametrize("name", ["resize_lanczos_float32_down", "resize_cubic_uint8_down", "resize_linear_uint16_up"])
 def test_entry_protocol_through_argv(hl, name):
     _, kernel, tname, d = name.split("_")
@@ -216,7 +176,7 @@ def test_entry_protocol_through_argv(hl, name):
     scale = 0.5 if d == "down" else 2.0
     mk = lambda shape, dtype=dt: hl.Buffer(np.zeros(shape, dtype))
     good_in, good_out = (3, 32, 32), ((3, 16, 16) if d == "down" else (3, 64, 64))
-    call = lambda i, o, s=scale: _argv_call(hl, name, i, s, o)
+    call = lambda i, o, s=scale: call_argv(hl, name, i, s, o)
     assert call(None, mk(good_out)) == -12 and call(mk(good_in), None) == -12
     assert call(mk(good_in, other), mk(good_out)) == -3 and call(mk(good_in), mk(good_out, other)) == -3
     assert call(mk(good_in[1:]), mk(good_out)) == -43 and call(mk(good_in), mk(good_out[1:])) == -43
@@ -249,29 +209,29 @@ def test_entry_protocol_through_argv(hl, name):
 def test_the_issues_own_example_of_too_many_taps(hl):
     """8-pixel-wide input, lanczos _down, factor 0.5: 12 taps"""
     a, o = hl.Buffer(np.zeros((3, 32, 8), np.float32)), hl.Buffer(np.zeros((3, 16, 4), np.float32))
-    assert _argv_call(hl, "resize_lanczos_float32_down", a, 0.5, o) == -4
+    assert call_argv(hl, "resize_lanczos_float32_down", a, 0.5, o) == -4
     assert "12-tap" in hl.last_error()
 
 
 def test_bounds_queries(hl):
     q = hl.Buffer.bounds_query(np.uint8, 3, mins=(5, 6, 1), extents=(40, 30, 2))
     a = hl.Buffer(np.zeros((3, 64, 64), np.uint8))
-    assert _argv_call(hl, "resize_cubic_uint8_down", a, 0.5, q) == 0
+    assert call_argv(hl, "resize_cubic_uint8_down", a, 0.5, q) == 0
     assert [(q.raw.dim[i].min, q.raw.dim[i].extent) for i in range(3)] == [(5, 40), (6, 30), (1, 2)]
     assert (q.raw.type.code, q.raw.type.bits) == (1, 8)
     qi = hl.Buffer.bounds_query(np.uint8, 3, mins=(2, 3, 0), extents=(64, 48, 0))
     o = hl.Buffer(np.zeros((2, 30, 40), np.uint8), mins=(5, 6, 1))
-    assert _argv_call(hl, "resize_cubic_uint8_down", qi, 0.5, o) == 0
+    assert call_argv(hl, "resize_cubic_uint8_down", qi, 0.5, o) == 0
     assert [(qi.raw.dim[i].min, qi.raw.dim[i].extent) for i in range(3)] == [(2, 64), (3, 48), (1, 2)]
 
 
 # ---------------------------------------------------------------------------------------------------- CPU: halide_sin
-def test_halide_sin_is_no_worse_than_glibc_plus_one_ulp(rc):
+def test_halide_sin_is_no_worse_than_glibc_plus_one_ulp(canon_rc):
     """Every float of both signs in [2^-12, 9.5] against (float)sin((double)x): the yardstick is glibc's sinf measured the same
     way, the margin one ulp for not having its table-driven reduction.  Measured: halide_sin 0.783 ulp, glibc 0.561 ulp."""
     lo, hi = int(np.float32(2.0 ** -12).view(np.uint32)), int(np.float32(9.5).view(np.uint32))
     ulp, where = (C.c_double * 2)(), (C.c_float * 2)()
-    rc.lib.rc_sin_sweep(lo, hi, ulp, where)
+    canon_rc.lib.rc_sin_sweep(lo, hi, ulp, where)
     print(f"halide_sin: {ulp[0]:.4f} ulp at {where[0]!r}; glibc sinf: {ulp[1]:.4f} ulp at {where[1]!r}")
     assert ulp[1] < 1.0, "the yardstick itself is off"
     assert ulp[0] <= ulp[1] + 1.0
@@ -279,10 +239,10 @@ def test_halide_sin_is_no_worse_than_glibc_plus_one_ulp(rc):
 
 def test_halide_sin_is_the_same_in_both_canonical_forms(rc):
     x = np.linspace(-9.5, 9.5, 200001).astype(np.float32)
-    rc.set_canon(0)
-    a = rc.sin(x)
-    rc.set_canon(1)
-    b = rc.sin(x)
+    with checker_lib.canon(0):
+        a = rc.sin(x)
+    with checker_lib.canon(1):
+        b = rc.sin(x)
     assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
     assert rc.sin(np.zeros(1, np.float32))[0] == 0.0
 
@@ -290,8 +250,7 @@ def test_halide_sin_is_the_same_in_both_canonical_forms(rc):
 # ---------------------------------------------------------------------------------------------------- CPU: checker vs float64
 @pytest.mark.parametrize("kernel", ["linear", "cubic", "lanczos"])
 @pytest.mark.parametrize("tname", list(TYPES))
-def test_checker_against_float64(rc, kernel, tname):
-    rc.set_canon(0)
+def test_checker_against_float64(rc, canon0_rc, kernel, tname):
     img = image(tname, (3, 97, 131), 131 + 97)
     worst = 0.0
     for up, factors in ((False, DOWN_FACTORS), (True, UP_FACTORS)):
@@ -328,12 +287,6 @@ def test_box_down_by_one_nth_has_n_equal_weights_per_axis(rc, each_canon_rc, n):
         assert np.array_equal(begin, np.arange(extent // n) * n)
 
 
-@pytest.fixture(params=[0, 1], ids=["canon0", "canon1"])
-def each_canon_rc(request, rc):
-    rc.set_canon(request.param)
-    yield request.param
-
-
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("up", [True, False], ids=["up", "down"])
 def test_factor_one_returns_an_integer_image(rc, each_canon_rc, kernel, up):
@@ -349,9 +302,8 @@ def test_factor_one_returns_an_integer_image(rc, each_canon_rc, kernel, up):
 
 
 @pytest.mark.parametrize("kernel", KERNELS)
-def test_a_constant_image_stays_constant_within_one_lsb(rc, kernel):
+def test_a_constant_image_stays_constant_within_one_lsb(rc, canon0_rc, kernel):
     """follows from |checker - float64| <= 1: the float64 evaluation of a constant image is that constant"""
-    rc.set_canon(0)
     for tname, value in (("uint8", 200), ("uint16", 51234)):
         img = np.full((2, 97, 131), value, TYPES[tname])
         for up, factors in ((False, DOWN_FACTORS), (True, UP_FACTORS)):
@@ -379,31 +331,7 @@ def _gpu(hl, kernel, img, scale, up, out_shape=None, out_min=(0, 0, 0), in_min=(
     return o.numpy()
 
 
-def _same(got, want, what):
-    assert got.shape == want.shape, what
-    bits = {4: np.uint32, 2: np.uint16, 1: np.uint8}[got.itemsize]
-    assert np.array_equal(got.view(bits), want.view(bits)), f"{what}: {np.count_nonzero(got != want)} of {got.size} differ"
-
-
-def _launches(hl, fn):
-    """names of the kernels one call launches"""
-    hl.kernel_timing(True)
-    hl.kernel_timing_reset()
-    try:
-        fn()
-        return {e["name"] for e in hl.kernel_timing_report()}
-    finally:
-        hl.kernel_timing(False)
-        hl.kernel_timing_reset()
-
-
 FUSED, GENERAL = {"rs_tables", "rs_fused"}, {"rs_tables", "rs_pass_x", "rs_pass_y"}
-
-
-@pytest.fixture
-def canon_rc(hl, rc):
-    rc.set_canon(hl.canon_fma())
-    return rc
 
 
 @pytest.mark.gpu
@@ -452,9 +380,9 @@ def test_each_path_runs_and_matches_the_checker(hl, canon_rc, kernel, tname, up,
     img = image(tname, shape, shape[1])
     want = canon_rc.resize(kernel, img, scale, up)
     got = {}
-    assert _launches(hl, lambda: got.update(a=_gpu(hl, kernel, img, scale, up))) == path
+    assert set(launches(hl, lambda: got.update(a=_gpu(hl, kernel, img, scale, up)))) == path
     _same(got["a"], want, "by size")
-    assert _launches(hl, lambda: got.update(b=_gpu(hl, kernel, img, scale, up, general=True))) == GENERAL
+    assert set(launches(hl, lambda: got.update(b=_gpu(hl, kernel, img, scale, up, general=True)))) == GENERAL
     _same(got["b"], want, "general path")
 
 
@@ -504,7 +432,7 @@ def test_crops_and_mins(hl, canon_rc, on_stream, kernel, tname, up, scale, gener
 
 
 @pytest.mark.gpu
-def test_device_halide_sin_is_the_checkers_bit_for_bit(hl, rc):
+def test_device_halide_sin_is_the_checkers_bit_for_bit(hl, canon_rc):
     """every float of both signs in [2^-12, 9.5], the range halide_sin is specified and measured on"""
     f = hl.lib.hlmi_debug_math
     f.restype = C.c_int
@@ -516,7 +444,7 @@ def test_device_halide_sin_is_the_checkers_bit_for_bit(hl, rc):
             x = (np.arange(start, min(start + step, hi + 1), dtype=np.uint32) | np.uint32(sign)).view(np.float32)
             got = np.empty_like(x)
             assert f(5, x.ctypes.data, None, None, got.ctypes.data, x.size) == 0
-            want = rc.sin(x)
+            want = canon_rc.sin(x)
             bad = np.flatnonzero(got.view(np.uint32) != want.view(np.uint32))
             assert bad.size == 0, f"{bad.size} differ, first at x = {x[bad[0]]!r}: {got[bad[0]]!r} vs {want[bad[0]]!r}"
 
@@ -564,9 +492,6 @@ def test_torch_op_equals_the_c_entry(hl, canon_rc, tname):
 
 
 # ---------------------------------------------------------------------------------------------------- the RunGen-compatible runner
-RUNGEN = os.path.join(ROOT, "halide_amd", "bin", "hlmi_rungen")
-
-
 def test_runner_describes_a_variant_by_name():
     out = subprocess.run([RUNGEN, "--name=resize_cubic_uint8_down", "--describe"], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0, out.stdout + out.stderr
@@ -577,10 +502,8 @@ def test_runner_describes_a_variant_by_name():
 @pytest.mark.gpu
 def test_runner_resizes_a_ppm(tmp_path, rc):
     """hlmi_rungen finds pipelines by name and needs no entry of its own: PPM in, PPM out, the checker's pixels"""
-    import ctypes
-    lib = ctypes.CDLL(os.environ.get("HLMI_LIB") or os.path.join(ROOT, "halide_amd", "lib", "libhlmi.so"))   # the library the runner loads
-    lib.hlmi_canon_fma.restype = ctypes.c_int
-    rc.set_canon(lib.hlmi_canon_fma())
+    lib = C.CDLL(os.environ.get("HLMI_LIB") or os.path.join(ROOT, "halide_amd", "lib", "libhlmi.so"))   # the library the runner loads
+    lib.hlmi_canon_fma.restype = C.c_int
     rgb = np.random.default_rng(8).integers(0, 256, (24, 40, 3), dtype=np.uint8)
     with open(tmp_path / "in.ppm", "wb") as f:
         f.write(b"P6\n40 24\n255\n" + rgb.tobytes())
@@ -590,7 +513,8 @@ def test_runner_resizes_a_ppm(tmp_path, rc):
     raw = open(tmp_path / "out.ppm", "rb").read()
     assert raw.split()[:4] == [b"P6", b"20", b"12", b"255"]
     got = np.frombuffer(raw[-20 * 12 * 3:], np.uint8).reshape(12, 20, 3).transpose(2, 0, 1)
-    want = rc.resize("cubic", np.ascontiguousarray(rgb.transpose(2, 0, 1)), 0.5, False)
+    with checker_lib.canon(lib.hlmi_canon_fma()):
+        want = rc.resize("cubic", np.ascontiguousarray(rgb.transpose(2, 0, 1)), 0.5, False)
     assert np.array_equal(got, want)
 
 
@@ -599,10 +523,7 @@ def test_runner_resizes_a_ppm(tmp_path, rc):
 def test_seeded_fuzz_slice_of_resize():
     """scripts/fuzz_parity.py's resize case (random type, kernel, direction, factor in [0.05, 8], sizes, origins, crops), a fixed
     number of cases from a fixed seed"""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("fuzz_parity", os.path.join(ROOT, "scripts", "fuzz_parity.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = load_fuzz_parity()
     rng = np.random.default_rng(20261016)
     for i in range(40):
         desc, ok = mod.CASES["resize"](rng)
