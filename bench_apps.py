@@ -450,6 +450,34 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
                               "valu_count_source": "static count in the disassembly of lb_fused<true>, hipcc 7.2.26015, 64 x 32 tile; not re-derived by this run"})
             emit(name, f"apps/linear_blur {name}, f32 {W}x{H}x{NC}", t, W * H, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
 
+    # ---- wavelet: haar_x, inverse_haar_x, daubechies_x, inverse_daubechies_x on f32 1536x2560, the size of apps/images/gray.png that the
+    #      reference's test feeds apps/wavelet/wavelet.cpp, and on 7680x4320, whose bytes do not fit the on-die caches.  The transform is
+    #      (W / 2, H, 2), as the driver allocates it.  Roofline: the compulsory 8 B per sample, which is what a device copy moves, so the
+    #      yardstick is membench's copy rate of the same run.  Each line also times the same call with one thread per output and
+    #      per-tap clamped scalar loads (hlmi_wavelet_general): the default path must not be slower.
+    if not only or "wavelet" in only or only & {"haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"}:
+        for W, H in ((1536, 2560), (7680, 4320)):
+            img, tr = hl.Buffer(rng.random((H, W), dtype=np.float32)), hl.Buffer(rng.random((2, H, W // 2), dtype=np.float32))
+            img_out, tr_out = hl.Buffer(np.zeros((H, W), np.float32)), hl.Buffer(np.zeros((2, H, W // 2), np.float32))
+            img.copy_to_device()
+            tr.copy_to_device()
+            for name in ("haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"):
+                if only and "wavelet" not in only and name not in only:
+                    continue
+                a, o = (tr, img_out) if name.startswith("inverse_") else (img, tr_out)
+                fn = getattr(hl, name)
+                call = lambda: fn(a, o)
+                general = lambda: hl.debug_wavelet_general(name, a, o)
+                iters = 50 if W == 1536 else 20
+                t = timed(call, o, iters)
+                clock = last_clock[0]
+                tg = timed(general, o, iters)
+                last_clock[0] = clock
+                nbytes = 8 * W * H
+                emit(name, f"apps/wavelet {name}, f32 {W}x{H}", t, W * H, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s",
+                     {"alg_bytes": nbytes, "kernels_ms": kernels(call, o), "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, o)},
+                      "fused_not_slower": bool(t <= tg)})
+
     # ---- lens_blur u8 stereo pair 768x1280 (the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
     if not only or "lens_blur" in only:
         W, H = 768, 1280

@@ -434,7 +434,7 @@ _fn = {name: _bind(name) for name in
         "depthwise_separable_conv", "unsharp", "max_filter", "hist", "harris", "interpolate", "iir_blur", "lens_blur", "bgu",
         "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
-       + ["linear_blur", "simple_blur"]}
+       + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -647,6 +647,34 @@ def debug_linear_blur_general(name: str, input, width, height, output) -> int:
     fn.restype = C.c_int
     fn.argtypes = [C.c_char_p, _BP, C.c_int32, C.c_int32, _BP]
     return _check(fn(name.encode(), _as_ptr(input), int(width), int(height), _as_ptr(output)))
+
+
+def haar_x(input, output) -> int:
+    """apps/wavelet: f32 [W,H] -> f32 [W/2,H,c]; plane 0 the pair means, any other plane the half differences; any output region."""
+    return _check(_fn["haar_x"](_as_ptr(input), _as_ptr(output)))
+
+
+def inverse_haar_x(input, output) -> int:
+    """apps/wavelet: f32 [W2,H,2] -> f32 [2*W2,H], the inverse of haar_x; reads clamp into the input's own box."""
+    return _check(_fn["inverse_haar_x"](_as_ptr(input), _as_ptr(output)))
+
+
+def daubechies_x(input, output) -> int:
+    """apps/wavelet: f32 [W,H] -> f32 [W/2,H,c], the D4 low-pass (plane 0) and high-pass over samples 2x - 1 .. 2x + 2."""
+    return _check(_fn["daubechies_x"](_as_ptr(input), _as_ptr(output)))
+
+
+def inverse_daubechies_x(input, output) -> int:
+    """apps/wavelet: f32 [W2,H,2] -> f32 [2*W2,H] from pairs x/2 and x/2 + 1; reconstructs daubechies_x's input one sample on."""
+    return _check(_fn["inverse_daubechies_x"](_as_ptr(input), _as_ptr(output)))
+
+
+def debug_wavelet_general(name: str, input, output) -> int:
+    """Test and measurement hook: the named wavelet entry point with one thread per output and clamped scalar taps."""
+    fn = lib.hlmi_wavelet_general
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, _BP, _BP]
+    return _check(fn(name.encode(), _as_ptr(input), _as_ptr(output)))
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

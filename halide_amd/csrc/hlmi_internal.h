@@ -393,6 +393,11 @@ extern "C" int hlmi_gaussian_blur_general(const char *variant, halide_buffer_t *
 // mode is kept anywhere.
 extern "C" int hlmi_linear_blur_general(const char *name, halide_buffer_t *input, int32_t width, int32_t height, halide_buffer_t *output);
 
+// wavelet.hip: "haar_x", "inverse_haar_x", "daubechies_x" or "inverse_daubechies_x" with one thread per output and every tap a
+// clamped scalar load from global memory, for the tests (default == general bit for bit) and for bench_apps.py.  Per call: no mode
+// is kept anywhere.
+extern "C" int hlmi_wavelet_general(const char *name, halide_buffer_t *in, halide_buffer_t *out);
+
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;
     return (r != 0 && r < 0) ? q - 1 : q;

@@ -270,6 +270,49 @@ def simple_blur(input: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _wavelet_forward(name, fn, input):
+    if input.dim() != 2 or input.dtype != torch.float32:
+        raise TypeError(f"{name} takes an (H, W) float32 tensor")
+    out = torch.empty((2, input.shape[0], input.shape[1] // 2), dtype=torch.float32, device=input.device)
+    with _Wrapped(input, out) as (a, o):
+        fn(a, o)
+    return out
+
+
+def _wavelet_inverse(name, fn, input):
+    if input.dim() != 3 or input.shape[0] != 2 or input.dtype != torch.float32:
+        raise TypeError(f"{name} takes a (2, H, W2) float32 tensor")
+    out = torch.empty((input.shape[1], 2 * input.shape[2]), dtype=torch.float32, device=input.device)
+    with _Wrapped(input, out) as (a, o):
+        fn(a, o)
+    return out
+
+
+@torch.library.custom_op("hlmi::haar_x", mutates_args=())
+def haar_x(input: torch.Tensor) -> torch.Tensor:
+    """apps/wavelet: (H, W) float32 -> (2, H, W // 2) float32, the pair means and half differences, the output the driver allocates
+    (apps/wavelet/wavelet.cpp:61)."""
+    return _wavelet_forward("haar_x", hl.haar_x, input)
+
+
+@torch.library.custom_op("hlmi::daubechies_x", mutates_args=())
+def daubechies_x(input: torch.Tensor) -> torch.Tensor:
+    """apps/wavelet: (H, W) float32 -> (2, H, W // 2) float32, the D4 low-pass and high-pass of the edge-clamped rows."""
+    return _wavelet_forward("daubechies_x", hl.daubechies_x, input)
+
+
+@torch.library.custom_op("hlmi::inverse_haar_x", mutates_args=())
+def inverse_haar_x(input: torch.Tensor) -> torch.Tensor:
+    """apps/wavelet: (2, H, W2) float32 -> (H, 2 * W2) float32, the inverse of haar_x."""
+    return _wavelet_inverse("inverse_haar_x", hl.inverse_haar_x, input)
+
+
+@torch.library.custom_op("hlmi::inverse_daubechies_x", mutates_args=())
+def inverse_daubechies_x(input: torch.Tensor) -> torch.Tensor:
+    """apps/wavelet: (2, H, W2) float32 -> (H, 2 * W2) float32, the D4 synthesis from pairs x / 2 and x / 2 + 1 (clamped)."""
+    return _wavelet_inverse("inverse_daubechies_x", hl.inverse_daubechies_x, input)
+
+
 @torch.library.custom_op("hlmi::lens_blur", mutates_args=())
 def lens_blur(left_im: torch.Tensor, right_im: torch.Tensor, slices: int, focus_depth: int, blur_radius_scale: float,
               aperture_samples: int) -> torch.Tensor:
@@ -343,6 +386,26 @@ def _(input):
 @simple_blur.register_fake
 def _(input):
     return input.new_empty(tuple(input.shape))
+
+
+@haar_x.register_fake
+def _(input):
+    return input.new_empty((2, input.shape[0], input.shape[1] // 2))
+
+
+@daubechies_x.register_fake
+def _(input):
+    return input.new_empty((2, input.shape[0], input.shape[1] // 2))
+
+
+@inverse_haar_x.register_fake
+def _(input):
+    return input.new_empty((input.shape[1], 2 * input.shape[2]))
+
+
+@inverse_daubechies_x.register_fake
+def _(input):
+    return input.new_empty((input.shape[1], 2 * input.shape[2]))
 
 
 @lens_blur.register_fake

@@ -310,6 +310,36 @@ HLMI_DECLARE_AUX(linear_blur)
 int simple_blur(struct halide_buffer_t *input, int32_t width, int32_t height, struct halide_buffer_t *output);
 HLMI_DECLARE_AUX(simple_blur)
 
+/* apps/wavelet — the one-level horizontal Haar and Daubechies-4 transforms and their inverses, all f32.  The forwards take in[x, y]
+ * and give out[x, y, c]; the inverses take in[x, y, c] and give out[x, y]; x is scaled by two between the two sides.  `in` below is
+ * repeat_edge of the input over the input buffer's own min and extent in EVERY dimension (for the inverses the channel too), and
+ * D0 .. D3 are the four float literals of daubechies_constants.h:4-7, the D4 taps (1 +- sqrt 3) / (4 sqrt 2) and
+ * (3 +- sqrt 3) / (4 sqrt 2), D3 < 0.
+ * haar_x (haar_x_generator.cpp:15-21): c == 0: (in(2x, y) + in(2x + 1, y)) * 0.5f; any other c: (in(2x, y) - in(2x + 1, y)) * 0.5f
+ * (mux: every index other than 0 selects the last value; / 2 is * 0.5f, src/Simplify_Div.cpp:204).
+ * inverse_haar_x (inverse_haar_x_generator.cpp:15-20): x % 2 == 0: in(x/2, y, 0) + in(x/2, y, 1); otherwise in(x/2, y, 0) - in(x/2, y, 1).
+ * daubechies_x (daubechies_x_generator.cpp:15-20), a .. d = in(2x - 1), in(2x), in(2x + 1), in(2x + 2): c == 0:
+ * ((D0*a + D1*b) + D2*c) + D3*d; any other c: ((D3*a - D2*b) + D1*c) - D0*d.
+ * inverse_daubechies_x (inverse_daubechies_x_generator.cpp:15-20), p, q, r, s = in(x/2, ., 0), in(x/2, ., 1), in(x/2 + 1, ., 0),
+ * in(x/2 + 1, ., 1): even x: ((D2*p + D1*q) + D0*r) + D3*s; odd x: ((D3*p - D0*q) + D1*r) - D2*s.
+ * x/2 and x%2 are Halide's (floor, Euclidean): output mins may be negative; 2x +- k and x/2 + 1 are formed in 64 bits before the clamp.
+ * Float forms as in oracle/oracle_common.h: one rounding per operator in the order written, or, contracted, the sum of four
+ * products mad(D3,d, mad(D2,c, mad2(D0,a, D1,b))) and the alternating one msub(mad(D1,c, mulsub(D3,a, D2*b)), D0, d) (the inverse
+ * alike with its constants); Haar has no multiply that feeds an add.
+ * Any output region, mins, channel range (extent 1, 3, min -1, ...) and padded strides; the reference's unroll(c, 2) / unroll(x, 2)
+ * would refuse extents below 2, here the algorithm's value is computed for every extent.  Every read is clamped into the input's own
+ * box, so the input only fails to cover where it has an empty dimension and the output is not empty (-4); nothing is read where
+ * the output is empty.  Bounds query: both buffers stay as passed, return 0.  More workgroups than one launch holds: -6.  No
+ * estimates and no _auto_schedule twins: the reference has none. */
+int haar_x(struct halide_buffer_t *in, struct halide_buffer_t *out);
+HLMI_DECLARE_AUX(haar_x)
+int inverse_haar_x(struct halide_buffer_t *in, struct halide_buffer_t *out);
+HLMI_DECLARE_AUX(inverse_haar_x)
+int daubechies_x(struct halide_buffer_t *in, struct halide_buffer_t *out);
+HLMI_DECLARE_AUX(daubechies_x)
+int inverse_daubechies_x(struct halide_buffer_t *in, struct halide_buffer_t *out);
+HLMI_DECLARE_AUX(inverse_daubechies_x)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,

@@ -386,10 +386,63 @@ def fuzz_linear_blur(rng):
     return desc, r == rc and (rc != 0 or same(np.ascontiguousarray(o.numpy()), want))
 
 
+def _strided_rows(rng, shape):
+    """a zeroed (H, W) or (C, H, W) array, dense or inside a larger allocation: padded rows (an odd row stride among them), padded
+    planes and a first element that is not the allocation's"""
+    lead, (h, w) = tuple(shape[:-2]), shape[-2:]
+    if rng.random() < 0.4:
+        return np.zeros(shape, f32)
+    py, px, x0 = int(rng.integers(0, 3)), int(rng.integers(0, 8)), int(rng.integers(0, 4))
+    return np.zeros(lead + (h + py, w + px + x0), f32)[..., :h, x0:x0 + w]
+
+
+def fuzz_wavelet(rng):
+    """One of haar_x, inverse_haar_x, daubechies_x and inverse_daubechies_x on a random output region (mins negative, odd, past the
+    input on either side), channel range, input mins and strides, on either path, against tests/cpp/wavelet_check.c
+    (tests/wavelet_checker.py).  Widths reach several 128-pair waves, so that the wide and the per-tap paths both run."""
+    import wavelet_checker as wc
+    wc.set_canon(hl.canon_fma())
+    name = wc.NAMES[int(rng.integers(0, 4))]
+    general = bool(rng.integers(0, 2))
+    w, h = rdim(rng, 1, 700), rdim(rng, 1, 24)
+    ix0, iy0 = (0, 0) if rng.random() < 0.5 else (int(rng.integers(-9, 10)), int(rng.integers(-5, 6)))
+    oh, oy = rdim(rng, 1, 24), iy0 + int(rng.integers(-4, h + 4))
+    if wc.is_inverse(name):
+        ic0 = int(rng.choice([0, 0, 0, 1, -1, -2, 2]))
+        nc = int(rng.integers(1, 4))
+        vals = rng.random((nc, h, w), dtype=f32) * f32(2) - f32(1)
+        in_min = (ix0, iy0, ic0)
+        ow = rdim(rng, 1, 1400)
+        ox = int(rng.integers(2 * ix0 - 40, 2 * (ix0 + w) + 40)) if rng.random() < 0.6 else 2 * ix0
+        out_shape, out_min = (oh, ow), (ox, oy)
+    else:
+        vals = rng.random((h, w), dtype=f32) * f32(2) - f32(1)
+        in_min = (ix0, iy0)
+        ow = rdim(rng, 1, 400)
+        ox = int(rng.integers((ix0 - 40) // 2, (ix0 + w + 40) // 2)) if rng.random() < 0.6 else ix0 // 2
+        oc, on = [(0, 2), (0, 2), (1, 1), (0, 1), (-1, 3), (0, 3), (5, 1)][int(rng.integers(0, 7))]
+        out_shape, out_min = (on, oh, ow), (ox, oy, oc)
+    src = _strided_rows(rng, vals.shape)
+    src[...] = vals
+    a, o = hl.Buffer(src, mins=in_min), hl.Buffer(_strided_rows(rng, out_shape), mins=out_min)
+    want = wc.run(name, vals, out_shape=out_shape, out_min=out_min, in_min=in_min)
+    if general:
+        fn = hl.lib.hlmi_wavelet_general
+        fn.restype, fn.argtypes = hl.C.c_int, [hl.C.c_char_p, hl._BP, hl._BP]
+        r = fn(name.encode(), a.ptr, o.ptr)
+    else:
+        r = hl._fn[name](a.ptr, o.ptr)
+    nd = len(in_min)
+    desc = (f"{name}{' general' if general else ''} in {vals.shape[::-1]} min {in_min} strides {[a.dim(i).stride for i in range(nd)]} "
+            f"out {out_shape[::-1]} min {out_min} strides {[o.dim(i).stride for i in range(len(out_min))]} -> {r}")
+    return desc, r == 0 and same(np.ascontiguousarray(o.numpy()), want)
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
 CASES["linear_blur"] = fuzz_linear_blur   # both entry points
+CASES["wavelet"] = fuzz_wavelet   # all four entry points; its checker has a module of its own (tests/wavelet_checker.py)
 
 
 def stress(args, only):
