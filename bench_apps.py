@@ -146,8 +146,10 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
                            "frac": round(achieved / peak, 4)}, "clock_state": last_clock[0], **extra})
 
     # ---- the practical HBM ceiling: copy / read / write kernels over 1 GiB buffers (4x the MALL)
+    copy_gbs = [None]   # this run's device copy rate, for the blocks that state their rate as a fraction of it
     if not only or "membench" in only:
         m = hl.membench(1 << 30, 10)
+        copy_gbs[0] = m["copy_gbs"]
         sink({"pipeline": "membench", "workload": "grid-stride float4 kernels over 1 GiB buffers, HIP events over 10 launches",
               "copy_gbs": round(m["copy_gbs"], 1), "read_gbs": round(m["read_gbs"], 1),
               "write_gbs": round(m["write_gbs"], 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -477,6 +479,40 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
                 emit(name, f"apps/wavelet {name}, f32 {W}x{H}", t, W * H, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s",
                      {"alg_bytes": nbytes, "kernels_ms": kernels(call, o), "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, o)},
                       "fused_not_slower": bool(t <= tg)})
+
+    # ---- compositing: six u8 RGBA layers and five op codes at 1536x2560 (the generator's estimate and the size of the image the
+    #      reference's test feeds apps/compositing/process.cpp) and at 7680x4320, with the driver's blobs and op codes {4, 3, 2, 1, 0}
+    #      (process.cpp:33-51) over a noise input.  Compulsory traffic: 24 B/px read, 4 B/px written; the yardstick is membench's copy
+    #      rate of the same run over those 28 B/px (`of_copy_rate`, absent when membench is not part of the run).  Whether bytes or
+    #      integer VALU issue bounds it is what the line is there to show.  It also times the same call with one thread per pixel and
+    #      byte loads (hlmi_compositing_general): the default path must not be slower.
+    if not only or "compositing" in only:
+        for W, H in ((1536, 2560), (7680, 4320)):
+            xs, ys = np.arange(W)[None, :], np.arange(H)[:, None]
+            layers = [hl.Buffer(rng.integers(0, 256, (4, H, W), dtype=np.uint8))]
+            for i in range(5):
+                cx, cy = int(np.cos(i * 2 * np.pi / 5) * 300 + W // 2), int(np.sin(i * 2 * np.pi / 5) * 300 + H // 2)
+                blob = np.empty((4, H, W), np.uint8)
+                g = ((255 // 3) * i) & 255   # stored into a uint8 by the driver: 340 wraps to 84
+                blob[0], blob[1], blob[2] = 255, g, 255 - g
+                blob[3] = np.minimum(255, np.minimum(np.maximum(0, 500 - np.abs(xs - cx)), np.maximum(0, 500 - np.abs(ys - cy))))
+                layers.append(hl.Buffer(blob))
+            ops, o = hl.Buffer(np.array([4, 3, 2, 1, 0], np.int32)), hl.Buffer(np.zeros((4, H, W), np.uint8))
+            for b in layers + [ops]:
+                b.copy_to_device()
+            call = lambda: hl.compositing(layers, ops, o)
+            general = lambda: hl.debug_compositing_general(layers, ops, o)
+            iters = 50 if W == 1536 else 10
+            t = timed(call, o, iters)
+            clock = last_clock[0]
+            tg = timed(general, o, iters)
+            last_clock[0] = clock
+            nbytes = 28 * W * H
+            extra = {"alg_bytes": nbytes, "kernels_ms": kernels(call, o),
+                     "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, o)}, "fused_not_slower": bool(t <= tg)}
+            if copy_gbs[0]:
+                extra["of_copy_rate"] = round(nbytes / t / 1e9 / copy_gbs[0], 4)
+            emit("compositing", f"apps/compositing, six u8 RGBA layers {W}x{H}, ops 4 3 2 1 0", t, W * H, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
 
     # ---- lens_blur u8 stereo pair 768x1280 (the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
     if not only or "lens_blur" in only:

@@ -434,7 +434,7 @@ _fn = {name: _bind(name) for name in
         "depthwise_separable_conv", "unsharp", "max_filter", "hist", "harris", "interpolate", "iir_blur", "lens_blur", "bgu",
         "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
-       + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"]}
+       + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -675,6 +675,24 @@ def debug_wavelet_general(name: str, input, output) -> int:
     fn.restype = C.c_int
     fn.argtypes = [C.c_char_p, _BP, _BP]
     return _check(fn(name.encode(), _as_ptr(input), _as_ptr(output)))
+
+
+def compositing(layers, ops, output) -> int:
+    """apps/compositing: six u8 [W,H,4] layers blended by five int32 op codes (0 over, 1 atop, 2 xor, 3 in, 4 out, anything else
+    skips the layer) into u8 [W,H,4]; the generator's integer form (include/hlmi_pipelines.h)."""
+    if len(layers) != 6:
+        raise ValueError(f"compositing takes six layers, not {len(layers)}")
+    return _check(_fn["compositing"](*[_as_ptr(l) for l in layers], _as_ptr(ops), _as_ptr(output)))
+
+
+def debug_compositing_general(layers, ops, output) -> int:
+    """Test and measurement hook: compositing with one thread per pixel and byte loads."""
+    if len(layers) != 6:
+        raise ValueError(f"compositing takes six layers, not {len(layers)}")
+    fn = lib.hlmi_compositing_general
+    fn.restype = C.c_int
+    fn.argtypes = [_BP] * 8
+    return _check(fn(*[_as_ptr(l) for l in layers], _as_ptr(ops), _as_ptr(output)))
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

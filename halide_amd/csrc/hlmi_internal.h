@@ -398,6 +398,15 @@ extern "C" int hlmi_linear_blur_general(const char *name, halide_buffer_t *input
 // is kept anywhere.
 extern "C" int hlmi_wavelet_general(const char *name, halide_buffer_t *in, halide_buffer_t *out);
 
+// compositing.hip: the same call with one thread per pixel and byte loads, written from the operator table of hlmi_pipelines.h, for
+// the tests (default == general bit for bit) and for bench_apps.py.  Per call: no mode is kept anywhere.
+extern "C" int hlmi_compositing_general(halide_buffer_t *layer_rgba_0, halide_buffer_t *layer_rgba_1, halide_buffer_t *layer_rgba_2,
+                                        halide_buffer_t *layer_rgba_3, halide_buffer_t *layer_rgba_4, halide_buffer_t *layer_rgba_5,
+                                        halide_buffer_t *ops, halide_buffer_t *output);
+// compositing.hip, test hook: fn 0 = the device's normalise quotient of (numerator a[i], alpha b[i]) before the saturation, fn 1 =
+// the device's scale16(a[i], b[i]); host pointers to n elements.  Returns 0, < 0 = HIP error.
+extern "C" int hlmi_debug_compositing(int fn, const uint16_t *a, const uint8_t *b, uint16_t *out, size_t n);
+
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;
     return (r != 0 && r < 0) ? q - 1 : q;

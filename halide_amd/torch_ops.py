@@ -313,6 +313,20 @@ def inverse_daubechies_x(input: torch.Tensor) -> torch.Tensor:
     return _wavelet_inverse("inverse_daubechies_x", hl.inverse_daubechies_x, input)
 
 
+@torch.library.custom_op("hlmi::compositing", mutates_args=())
+def compositing(layers: list[torch.Tensor], ops: torch.Tensor) -> torch.Tensor:
+    """apps/compositing: six (4, H, W) uint8 layers and five int32 op codes (0 over, 1 atop, 2 xor, 3 in, 4 out; any other code skips
+    its layer) -> (4, H, W) uint8, the generator's integer form.  The op codes are read on the device."""
+    if len(layers) != 6 or any(t.dim() != 3 or t.shape != layers[0].shape or t.shape[0] != 4 or t.dtype != torch.uint8 for t in layers):
+        raise TypeError("compositing takes six (4, H, W) uint8 tensors of one shape")
+    if ops.dim() != 1 or ops.shape[0] != 5 or ops.dtype != torch.int32:
+        raise TypeError("compositing takes five int32 op codes")
+    out = torch.empty_like(layers[0])
+    with _Wrapped(*layers, ops, out) as bufs:
+        hl.compositing(bufs[:6], bufs[6], bufs[7])
+    return out
+
+
 @torch.library.custom_op("hlmi::lens_blur", mutates_args=())
 def lens_blur(left_im: torch.Tensor, right_im: torch.Tensor, slices: int, focus_depth: int, blur_radius_scale: float,
               aperture_samples: int) -> torch.Tensor:
@@ -406,6 +420,11 @@ def _(input):
 @inverse_daubechies_x.register_fake
 def _(input):
     return input.new_empty((input.shape[1], 2 * input.shape[2]))
+
+
+@compositing.register_fake
+def _(layers, ops):
+    return layers[0].new_empty(tuple(layers[0].shape))
 
 
 @lens_blur.register_fake

@@ -340,6 +340,38 @@ HLMI_DECLARE_AUX(daubechies_x)
 int inverse_daubechies_x(struct halide_buffer_t *in, struct halide_buffer_t *out);
 HLMI_DECLARE_AUX(inverse_daubechies_x)
 
+/* apps/compositing/compositing_generator.cpp:17-23,25-154 — Porter-Duff blending of six u8 RGBA layers [W,H,4] by five run-time
+ * op codes (int32 [5]) into u8 [W,H,4]: a small interpreter.  THE CONTRACT IS THE GENERATOR'S INTEGER FORM (the branch a target
+ * without a GPU feature takes, and what the reference's own test runs): the float form normalises by 255.0f / alpha, which at
+ * alpha 0 is 0 * inf = NaN through a saturating_cast whose result for NaN is the target's business, and the driver reaches alpha 0
+ * (`out` first, apps/compositing/process.cpp:35); it is not built.  No float operation: both library builds give the same bytes.
+ * Per pixel, every type as written, additions wrapping in their type:
+ *   state C[0..2] uint16, A uint8;  layer 0: C[i] = u16(v_i) * u16(a), A = a;  layers k = 1 .. 5 premultiplied alike into Bc[i], B3,
+ *   then operator ops(k - 1), all four results formed from the OLD state (a tuple assignment).  ~e = 255 - e.
+ *   scale16(a: u16, s: u8): c = u32(a) * u32(s); c += (c + 128) >> 8; c = (c + 128) >> 8; u16(c).   scale8(a: u8, s: u8): the same
+ *   two steps on c = u16(a) * u16(s), u8(c).  The generator's comment "equivalent to c = (c + 127) / 255" (:64) holds for scale8
+ *   only: for scale16 the two-shift form first departs at c = 65663 and is one lower on 4 096 162 of the 16 646 656 pairs
+ *   a <= 65025, s <= 255.  The contract is the two-shift form.
+ *     code  name   C[i]                                         A
+ *     0     over   Bc[i] + scale16(C[i], ~B3)                   B3 + scale8(A, ~B3)
+ *     1     atop   scale16(Bc[i], A) + scale16(C[i], ~B3)       A
+ *     2     xor    scale16(Bc[i], ~A) + scale16(C[i], ~B3)      scale8(B3, ~A) + scale8(A, ~B3)
+ *     3     in     scale16(C[i], B3)                            scale8(A, B3)
+ *     4     out    scale16(C[i], ~B3)                           scale8(A, ~B3)
+ *   Any other op code (negative, 5 or more) leaves the state unchanged: the RDom's where() matches no operator (:146-147).
+ *   out[i] = sat_u8(A == 0 ? 0 : u16(C[i] + A / 2) / A), i < 3 (fast_integer_divide: the exact floor quotient, the numerator for a
+ *   denominator of 1, 0 for a zero denominator, src/FastIntegerDivide.cpp:302-307); out[3] = A.  The saturation is real: after
+ *   `over` a colour can exceed 255 * A by up to 127.
+ * Entry contract: null (-12), type (-3), dimensionality (-43); the output's channels are min 0, extent 4 (-8: bound(c, 0, 4), all
+ * four are produced together); then a bounds query answers every layer with the output's x, y box and channels [0, 4) and ops with
+ * [0, 5), and leaves the output as passed; then sizes and coverage: nothing is clamped, each layer covers the output's x, y region
+ * and channels [0, 4), ops covers [0, 5) (-4).  Every buffer has its own mins and strides; one buffer may be several layers.  ops
+ * is read on the device.  Nothing is read or launched where the output's x or y extent is 0.  No _auto_schedule twin. */
+int compositing(struct halide_buffer_t *layer_rgba_0, struct halide_buffer_t *layer_rgba_1, struct halide_buffer_t *layer_rgba_2,
+                struct halide_buffer_t *layer_rgba_3, struct halide_buffer_t *layer_rgba_4, struct halide_buffer_t *layer_rgba_5,
+                struct halide_buffer_t *ops, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(compositing)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,

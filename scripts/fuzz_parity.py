@@ -438,11 +438,62 @@ def fuzz_wavelet(rng):
     return desc, r == 0 and same(np.ascontiguousarray(o.numpy()), want)
 
 
+def _u8_view(rng, shape):
+    """a zeroed uint8 (C, H, W) view inside one allocation: dense, or with longer rows, planes further apart (channel strides that
+    are no multiple of 4 among them) and a first element that is not the allocation's"""
+    c, h, w = shape
+    if rng.random() < 0.35:
+        return np.zeros(shape, np.uint8)
+    rs = w + int(rng.integers(0, 10))
+    cs = rs * h + int(rng.integers(0, 10))
+    x0 = int(rng.integers(0, 9))
+    return np.lib.stride_tricks.as_strided(np.zeros(x0 + c * cs + 8, np.uint8)[x0:], shape, (cs, rs, 1))
+
+
+def fuzz_compositing(rng):
+    """compositing on a random output box (a non-zero min among them), every layer larger than it or exactly it with mins, extents and
+    strides of its own (sometimes one buffer for several layers), random op codes with out-of-range ones, on either path, against
+    tests/cpp/compositing_check.c (tests/compositing_checker.py).  Widths reach several 512-pixel waves, so that the 8-byte and the
+    per-byte paths both run."""
+    import compositing_checker as cc
+    general = bool(rng.integers(0, 2))
+    w, h = rdim(rng, 1, 1300), rdim(rng, 1, 12)
+    ox, oy = (0, 0) if rng.random() < 0.4 else (int(rng.integers(-20, 21)), int(rng.integers(-9, 10)))
+    bufs, crops = [], []
+    for k in range(6):
+        if k and rng.random() < 0.15:   # the same buffer again
+            j = int(rng.integers(0, k))
+            bufs.append(bufs[j]), crops.append(crops[j])
+            continue
+        lx, ly, lc = (int(v) for v in rng.integers(0, 9, 3)) if rng.random() < 0.6 else (0, 0, 0)   # what the layer holds before the box
+        shape = (4 + lc + int(rng.integers(0, 2)), h + ly + int(rng.integers(0, 3)), w + lx + int(rng.integers(0, 9)))
+        a = _u8_view(rng, shape)
+        a[...] = rng.integers(0, 256, shape, dtype=np.uint8)
+        if rng.random() < 0.5:   # alphas 0, 1 and 255 often
+            pick = rng.integers(0, 6, shape[1:])
+            a[lc + 3] = np.where(pick == 0, 0, np.where(pick == 1, 255, np.where(pick == 2, 1, a[lc + 3])))
+        bufs.append(hl.Buffer(a, mins=(ox - lx, oy - ly, -lc)))
+        crops.append(a[lc:lc + 4, ly:ly + h, lx:lx + w].copy())
+    codes = rng.integers(-1, 6, 5).astype(np.int32)
+    if rng.random() < 0.2:
+        codes[int(rng.integers(0, 5))] = int(rng.choice([-2 ** 31, 2 ** 31 - 1, 255, 256, -128, 1 << 16]))
+    pre = int(rng.integers(0, 4))
+    opsa = np.concatenate([rng.integers(-9, 9, pre), codes, rng.integers(-9, 9, int(rng.integers(0, 3)))]).astype(np.int32)
+    ops = hl.Buffer(opsa, mins=(-pre,))
+    o = hl.Buffer(_u8_view(rng, (4, h, w)), mins=(ox, oy, 0))
+    want = cc.run(crops, codes)
+    (hl.debug_compositing_general if general else hl.compositing)(bufs, ops, o)
+    desc = (f"compositing{' general' if general else ''} {w}x{h} at ({ox}, {oy}) ops {codes.tolist()} layer mins {[b.mins for b in bufs]} "
+            f"strides {[[b.dim(i).stride for i in (1, 2)] for b in bufs]} out strides {[o.dim(i).stride for i in (1, 2)]}")
+    return desc, same(np.ascontiguousarray(o.numpy()), want)
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
 CASES["linear_blur"] = fuzz_linear_blur   # both entry points
 CASES["wavelet"] = fuzz_wavelet   # all four entry points; its checker has a module of its own (tests/wavelet_checker.py)
+CASES["compositing"] = fuzz_compositing   # integer throughout: its checker (tests/compositing_checker.py) has no canonical form
 
 
 def stress(args, only):
