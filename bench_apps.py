@@ -514,6 +514,37 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
                 extra["of_copy_rate"] = round(nbytes / t / 1e9 / copy_gbs[0], 4)
             emit("compositing", f"apps/compositing, six u8 RGBA layers {W}x{H}, ops 4 3 2 1 0", t, W * H, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
 
+    # ---- hexagon_benchmarks: the six u8 stencils at 1024x1024 (the size apps/hexagon_benchmarks/process.cpp runs them at) and at
+    #      7680x4320, noise under the driver's mask (process.h).  Compulsory traffic: 1 B/px read, 1 B/px written; the yardstick is
+    #      membench's copy rate of the same run over those 2 B/px (`of_copy_rate`, absent when membench is not part of the run),
+    #      which at such a rate is some 3 Tpx/s: whether bytes or packed 16-bit VALU issue bounds a filter is what the lines are there
+    #      to show.  Each also times the same call with one thread per pixel and clamped byte taps (hlmi_hexagon_benchmarks_general):
+    #      the default path must not be slower.
+    if not only or "hexagon_benchmarks" in only:
+        for W, H in ((1024, 1024), (7680, 4320)):
+            a, o = hl.Buffer(rng.integers(0, 256, (H, W), dtype=np.uint8)), hl.Buffer(np.zeros((H, W), np.uint8))
+            mask = hl.Buffer(np.array([[1, -4, 7], [2, -5, 8], [3, -6, 9]], np.int8))
+            a.copy_to_device()
+            for name in hl.HEXAGON_BENCHMARKS:
+                m = mask if name.startswith("conv3x3") else None
+                call = (lambda f=getattr(hl, name), m=m: f(a, m, o)) if m is not None else (lambda f=getattr(hl, name): f(a, o))
+                general = lambda name=name, m=m: hl.debug_hexagon_benchmarks_general(name, a, m, o)
+                iters = 200 if W == 1024 else 20
+                t = timed(call, o, iters)
+                clock = last_clock[0]
+                tg = timed(general, o, iters)
+                last_clock[0] = clock
+                nbytes = 2 * W * H
+                k, kg = kernels(call, o), kernels(general, o)
+                extra = {"alg_bytes": nbytes, "kernels_ms": k, "gpx_per_s": round(W * H / t / 1e9, 2),
+                         "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kg}, "fused_not_slower": bool(t <= tg),
+                         "kernel_not_slower": bool(sum(k.values()) <= sum(kg.values()))}
+                if copy_gbs[0]:
+                    extra["of_copy_rate"] = round(nbytes / t / 1e9 / copy_gbs[0], 4)
+                    extra["kernel_of_copy_rate"] = round(nbytes / (sum(k.values()) * 1e-3) / 1e9 / copy_gbs[0], 4)
+                emit(name, f"apps/hexagon_benchmarks {name}, u8 {W}x{H}, noise" + (", the driver's mask" if m is not None else ""), t, W * H, "hbm",
+                     nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
+
     # ---- lens_blur u8 stereo pair 768x1280 (the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
     if not only or "lens_blur" in only:
         W, H = 768, 1280

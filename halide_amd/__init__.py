@@ -434,7 +434,8 @@ _fn = {name: _bind(name) for name in
         "depthwise_separable_conv", "unsharp", "max_filter", "hist", "harris", "interpolate", "iir_blur", "lens_blur", "bgu",
         "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
-       + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]}
+       + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]
+       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -693,6 +694,51 @@ def debug_compositing_general(layers, ops, output) -> int:
     fn.restype = C.c_int
     fn.argtypes = [_BP] * 8
     return _check(fn(*[_as_ptr(l) for l in layers], _as_ptr(ops), _as_ptr(output)))
+
+
+HEXAGON_BENCHMARKS = ("conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel")
+
+
+def conv3x3a16(input, mask, output) -> int:
+    """apps/hexagon_benchmarks: u8 [W,H] under an int8 3x3 mask, the sum wrapped to int16, u8(clamp(sum >> 4, 0, 255)); the input is
+    edge-clamped to its own box (include/hlmi_pipelines.h)."""
+    return _check(_fn["conv3x3a16"](_as_ptr(input), _as_ptr(mask), _as_ptr(output)))
+
+
+def conv3x3a32(input, mask, output) -> int:
+    """apps/hexagon_benchmarks: conv3x3a16 with the sum in int32."""
+    return _check(_fn["conv3x3a32"](_as_ptr(input), _as_ptr(mask), _as_ptr(output)))
+
+
+def dilate3x3(input, output) -> int:
+    """apps/hexagon_benchmarks: u8 [W,H] -> u8, the maximum of the 3x3 window of the edge-clamped input."""
+    return _check(_fn["dilate3x3"](_as_ptr(input), _as_ptr(output)))
+
+
+def median3x3(input, output) -> int:
+    """apps/hexagon_benchmarks: u8 [W,H] -> u8, the median of the 3x3 window of the edge-clamped input."""
+    return _check(_fn["median3x3"](_as_ptr(input), _as_ptr(output)))
+
+
+def gaussian5x5(input, output) -> int:
+    """apps/hexagon_benchmarks: u8 [W,H] -> u8, the (1, 4, 6, 4, 1) x (1, 4, 6, 4, 1) window of the edge-clamped input over 256,
+    truncated."""
+    return _check(_fn["gaussian5x5"](_as_ptr(input), _as_ptr(output)))
+
+
+def sobel(input, output) -> int:
+    """apps/hexagon_benchmarks: u8 [W,H] -> u8, min(|gx| + |gy|, 255) of the edge-clamped input, no square root; the output region
+    may lie anywhere."""
+    return _check(_fn["sobel"](_as_ptr(input), _as_ptr(output)))
+
+
+def debug_hexagon_benchmarks_general(name: str, input, mask, output) -> int:
+    """Test and measurement hook: the named hexagon_benchmarks entry point with one thread per output pixel and clamped taps from
+    global memory; `mask` is None for the four filters that take none."""
+    fn = lib.hlmi_hexagon_benchmarks_general
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, _BP, _BP, _BP]
+    return _check(fn(name.encode(), _as_ptr(input), _as_ptr(mask), _as_ptr(output)))
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

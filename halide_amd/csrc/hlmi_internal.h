@@ -35,7 +35,7 @@ int hip_failed(void *uc, hipError_t e, const char *what);  // -> halide_error_co
 // ---------------------------------------------------------------------------------------------
 // ABI helpers
 constexpr uint32_t type_abi(int code, int bits) { return (uint32_t)code | ((uint32_t)bits << 8); }
-constexpr uint32_t T_U8 = type_abi(1, 8), T_U16 = type_abi(1, 16), T_I16 = type_abi(0, 16),
+constexpr uint32_t T_U8 = type_abi(1, 8), T_I8 = type_abi(0, 8), T_U16 = type_abi(1, 16), T_I16 = type_abi(0, 16),
                    T_I32 = type_abi(0, 32), T_F32 = type_abi(2, 32);
 inline uint32_t buf_type_abi(const halide_buffer_t *b) {
     uint32_t v;
@@ -406,6 +406,12 @@ extern "C" int hlmi_compositing_general(halide_buffer_t *layer_rgba_0, halide_bu
 // compositing.hip, test hook: fn 0 = the device's normalise quotient of (numerator a[i], alpha b[i]) before the saturation, fn 1 =
 // the device's scale16(a[i], b[i]); host pointers to n elements.  Returns 0, < 0 = HIP error.
 extern "C" int hlmi_debug_compositing(int fn, const uint16_t *a, const uint8_t *b, uint16_t *out, size_t n);
+
+// hexagon_benchmarks.hip: "conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5" or "sobel" with one thread per output
+// pixel and its 9 (25) clamped taps read from global memory, the arithmetic in the contract's own types, for the tests (default ==
+// general bit for bit) and for bench_apps.py.  `mask` is read by the two conv3x3 filters only and may be null for the others.  Per
+// call: no mode is kept anywhere.
+extern "C" int hlmi_hexagon_benchmarks_general(const char *name, halide_buffer_t *input, halide_buffer_t *mask, halide_buffer_t *output);
 
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;

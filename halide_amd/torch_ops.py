@@ -327,6 +327,67 @@ def compositing(layers: list[torch.Tensor], ops: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _plane_check(name, input):
+    if input.dim() != 2 or input.dtype != torch.uint8:
+        raise TypeError(f"{name} takes an (H, W) uint8 tensor")
+
+
+def _plane_op(name, input):
+    _plane_check(name, input)
+    out = torch.empty_like(input, memory_format=torch.contiguous_format)
+    with _Wrapped(input, out) as (a, o):
+        getattr(hl, name)(a, o)
+    return out
+
+
+def _conv3x3(name, input, mask):
+    _plane_check(name, input)
+    if mask.dim() != 2 or tuple(mask.shape) != (3, 3) or mask.dtype != torch.int8:
+        raise TypeError(f"{name} takes a (3, 3) int8 mask")
+    out = torch.empty_like(input, memory_format=torch.contiguous_format)
+    with _Wrapped(input, out) as (a, o):
+        # the entry point reads the nine values on the host: hand them over there
+        getattr(hl, name)(a, hl.Buffer(mask.cpu().contiguous().numpy()), o)
+    return out
+
+
+@torch.library.custom_op("hlmi::conv3x3a16", mutates_args=())
+def conv3x3a16(input: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """apps/hexagon_benchmarks: (H, W) uint8 under a (3, 3) int8 mask (mask[i][j] multiplies in(x + j - 1, y + i - 1)), the sum wrapped
+    to int16 -> (H, W) uint8."""
+    return _conv3x3("conv3x3a16", input, mask)
+
+
+@torch.library.custom_op("hlmi::conv3x3a32", mutates_args=())
+def conv3x3a32(input: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """apps/hexagon_benchmarks: conv3x3a16 with the sum in int32."""
+    return _conv3x3("conv3x3a32", input, mask)
+
+
+@torch.library.custom_op("hlmi::dilate3x3", mutates_args=())
+def dilate3x3(input: torch.Tensor) -> torch.Tensor:
+    """apps/hexagon_benchmarks: (H, W) uint8 -> (H, W) uint8, the 3x3 maximum of the edge-clamped image."""
+    return _plane_op("dilate3x3", input)
+
+
+@torch.library.custom_op("hlmi::median3x3", mutates_args=())
+def median3x3(input: torch.Tensor) -> torch.Tensor:
+    """apps/hexagon_benchmarks: (H, W) uint8 -> (H, W) uint8, the 3x3 median of the edge-clamped image."""
+    return _plane_op("median3x3", input)
+
+
+@torch.library.custom_op("hlmi::gaussian5x5", mutates_args=())
+def gaussian5x5(input: torch.Tensor) -> torch.Tensor:
+    """apps/hexagon_benchmarks: (H, W) uint8 -> (H, W) uint8, the 5x5 binomial window over 256, truncated."""
+    return _plane_op("gaussian5x5", input)
+
+
+@torch.library.custom_op("hlmi::sobel", mutates_args=())
+def sobel(input: torch.Tensor) -> torch.Tensor:
+    """apps/hexagon_benchmarks: (H, W) uint8 -> (H, W) uint8, min(|gx| + |gy|, 255), no square root."""
+    return _plane_op("sobel", input)
+
+
 @torch.library.custom_op("hlmi::lens_blur", mutates_args=())
 def lens_blur(left_im: torch.Tensor, right_im: torch.Tensor, slices: int, focus_depth: int, blur_radius_scale: float,
               aperture_samples: int) -> torch.Tensor:
@@ -425,6 +486,20 @@ def _(input):
 @compositing.register_fake
 def _(layers, ops):
     return layers[0].new_empty(tuple(layers[0].shape))
+
+
+@conv3x3a16.register_fake
+@conv3x3a32.register_fake
+def _(input, mask):
+    return input.new_empty(tuple(input.shape))
+
+
+@dilate3x3.register_fake
+@median3x3.register_fake
+@gaussian5x5.register_fake
+@sobel.register_fake
+def _(input):
+    return input.new_empty(tuple(input.shape))
 
 
 @lens_blur.register_fake

@@ -372,6 +372,43 @@ int compositing(struct halide_buffer_t *layer_rgba_0, struct halide_buffer_t *la
                 struct halide_buffer_t *ops, struct halide_buffer_t *output);
 HLMI_DECLARE_AUX(compositing)
 
+/* apps/hexagon_benchmarks — six single-plane u8 stencils (conv3x3_generator.cpp with accumulator_type=int16 / int32,
+ * dilate3x3_generator.cpp, median3x3_generator.cpp, gaussian5x5_generator.cpp, sobel_generator.cpp), signatures as the reference's
+ * Makefile generates them.  input and output: uint8, 2-D; mask: int8, 2-D.  INTEGER ARITHMETIC ONLY: both library builds give the
+ * same bytes.  in(x, y) is the input read at x clamped to [min0, min0 + extent0 - 1] and y clamped likewise: repeat_edge of the
+ * INPUT's own box, not of the output's.
+ *   dilate3x3    the maximum of the nine in(x + j, y + i), i, j in -1 .. 1.
+ *   median3x3    the generator's network: max, min and mid of each column of three, mid(a, b, c) = max(min(max(a, b), c), min(a, b));
+ *                the output is the mid of min(the three max_y), max(the three min_y) and mid(the three mid_y): the median of the nine.
+ *   sobel        in uint16: ax(x, y) = in(x-1, y) + 2 in(x, y) + in(x+1, y), ay(x, y) = in(x, y-1) + 2 in(x, y) + in(x, y+1);
+ *                out = min(|ax(x, y-1) - ax(x, y+1)| + |ay(x-1, y) - ay(x+1, y)|, 255).  Each term is at most 1020; no square root.
+ *   gaussian5x5  weights (1, 4, 6, 4, 1) down the column, then along the row, in int16; out = u8(cols >> 8).  cols reaches 65280 and
+ *                wraps in int16; the arithmetic shift and the narrowing cast undo the wrap: floor(true sum / 256) for every input.
+ *                The shift truncates (no rounding), nothing is clamped; a constant image v gives v.
+ *   conv3x3a32   S = sum over i, j in -1 .. 1 of in(x + j, y + i) * mask(j + 1, i + 1) in int32; out = u8(clamp(S >> 4, 0, 255)),
+ *                an arithmetic shift.
+ *   conv3x3a16   the same with S wrapped to int16 before the shift: two's complement modulo 2^16, neither saturated nor undefined
+ *                (each product fits int16).  An all-255 image under an all-16 mask: S = 36720 wraps to -28816, >> 4 is -1801: 0,
+ *                where conv3x3a32 writes 255.
+ * Entry contract: null (-12), type (-3), dimensionality (-43); input.min.0 == 0 and input.min.1 == 0 on all six, output.min.0 == 0
+ * and output.min.1 == 0 on all but sobel (-8), which takes an output region at any origin; then a bounds query answers mask with
+ * [0, 3) x [0, 3) and leaves input and output as passed (the clamp's bound is the input's own box); then sizes (-8, -5, -6) and
+ * coverage (-4): mask covers [0, 3) x [0, 3), its mins and strides otherwise free, and the input holds the clamped samples the
+ * region reads, which only an empty input fails.  The output's extents are independent of the input's.  The mask's nine values are
+ * read on the host at the call.  Nothing is launched for an empty output.  No _auto_schedule twins. */
+int conv3x3a16(struct halide_buffer_t *input, struct halide_buffer_t *mask, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(conv3x3a16)
+int conv3x3a32(struct halide_buffer_t *input, struct halide_buffer_t *mask, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(conv3x3a32)
+int dilate3x3(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(dilate3x3)
+int median3x3(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(median3x3)
+int gaussian5x5(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(gaussian5x5)
+int sobel(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(sobel)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,

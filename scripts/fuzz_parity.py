@@ -488,12 +488,68 @@ def fuzz_compositing(rng):
     return desc, same(np.ascontiguousarray(o.numpy()), want)
 
 
+def _u8_plane(rng, h, w):
+    """(row stride, byte offset of the first element) of a uint8 (H, W) plane: dense and on the 8-byte grid, or with longer rows
+    (multiples of 8 and not) and a first element 0 .. 8 bytes into its allocation"""
+    if rng.random() < 0.35:
+        return w, 0
+    return w + int(rng.choice([0, 8, 16, 1, 3, 5, 11])), int(rng.integers(0, 9))
+
+
+def fuzz_hexagon_benchmarks(rng):
+    """one of the six filters of apps/hexagon_benchmarks on a random input and an output of its own size (smaller, equal, larger; for
+    sobel at any origin, negative and past the input included), random row strides and pointer offsets for both, for the conv3x3
+    pair a random mask (with +-127 and -128) inside a mask buffer with mins, extents and a row stride of its own, on either path,
+    against tests/cpp/hexagon_benchmarks_check.c (tests/hexagon_benchmarks_checker.py).  Widths reach several 496-pixel waves, so
+    that the 8-byte and the per-byte paths both run."""
+    import hexagon_benchmarks_checker as hb
+    name = hb.NAMES[int(rng.integers(0, len(hb.NAMES)))]
+    general = bool(rng.integers(0, 2))
+    iw, ih = rdim(rng, 1, 1100), rdim(rng, 1, 40)
+    if rng.random() < 0.5:   # sizes on the 8-byte grid: the 8-byte path
+        iw = max(8, iw // 8 * 8)
+    r = rng.random()
+    ow, oh = (iw, ih) if r < 0.5 else (rdim(rng, 1, 1100), rdim(rng, 1, 40))
+    if r < 0.7 and iw % 8 == 0:
+        ow = max(8, ow // 8 * 8)
+    ox, oy = 0, 0
+    if name == "sobel" and rng.random() < 0.6:
+        ox, oy = int(rng.choice([-16, -8, 8, 24, -3, 5, iw, iw + 8, -ow - 8])), int(rng.integers(-12, ih + 6))
+    data = rng.integers(0, 256, (ih, iw), dtype=np.uint8) if rng.random() < 0.7 else rng.choice(np.array([0, 1, 127, 128, 254, 255], np.uint8), (ih, iw))
+    a, o = hb.DevPlane(hl, ih, iw, *_u8_plane(rng, ih, iw), fill=data), hb.DevPlane(hl, oh, ow, *_u8_plane(rng, oh, ow), mins=(ox, oy))
+    mask = mb = None
+    if name in hb.MASKED:
+        pick = rng.random()
+        mask = (rng.integers(-128, 128, (3, 3)) if pick < 0.5 else rng.choice(np.array([-128, -127, 127, 16, 0, 1, -1]), (3, 3))).astype(np.int8)
+        if pick > 0.9:
+            mask = hb.DRIVER_MASK.copy()
+        mx, my, ex, ey = int(rng.integers(0, 3)), int(rng.integers(0, 3)), int(rng.integers(0, 3)), int(rng.integers(0, 3))
+        rs = 3 + mx + ex + int(rng.integers(0, 6))
+        box = np.lib.stride_tricks.as_strided(rng.integers(-128, 128, (3 + my + ey) * rs + 8).astype(np.int8), (3 + my + ey, 3 + mx + ex), (rs, 1))
+        box[my:my + 3, mx:mx + 3] = mask
+        mb = hl.Buffer(box, mins=(-mx, -my))
+    want = hb.run(name, data, mask, (ox, oy, ow, oh))
+    try:
+        if general:
+            hl.debug_hexagon_benchmarks_general(name, a.buf, mb, o.buf)
+        else:
+            getattr(hl, name)(*([a.buf, mb, o.buf] if mb is not None else [a.buf, o.buf]))
+        got = o.result()
+    finally:
+        a.free(), o.free()
+    desc = (f"{name}{' general' if general else ''} input {iw}x{ih} stride {a.buf.dim(1).stride} at byte {a.host.ctypes.data - a.flat.ctypes.data}, "
+            f"output {ow}x{oh} at ({ox}, {oy}) stride {o.buf.dim(1).stride} at byte {o.host.ctypes.data - o.flat.ctypes.data}"
+            + (f", mask {mask.tolist()} mins {mb.mins} stride {mb.dim(1).stride}" if mb else ""))
+    return desc, same(got, want)
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
 CASES["linear_blur"] = fuzz_linear_blur   # both entry points
 CASES["wavelet"] = fuzz_wavelet   # all four entry points; its checker has a module of its own (tests/wavelet_checker.py)
 CASES["compositing"] = fuzz_compositing   # integer throughout: its checker (tests/compositing_checker.py) has no canonical form
+CASES["hexagon_benchmarks"] = fuzz_hexagon_benchmarks   # all six entry points; integer throughout (tests/hexagon_benchmarks_checker.py)
 
 
 def stress(args, only):

@@ -1,0 +1,114 @@
+"""ctypes bindings to tests/cpp/hexagon_benchmarks_check.c, the plain-C checker of the six filters of apps/hexagon_benchmarks — TEST
+INFRASTRUCTURE ONLY, the sibling of compositing_checker.py.
+
+The checker is one file of integer arithmetic: it needs neither check_canon.c nor a canonical-form switch.  It is built into a
+shared object of its own, once per process, in a temporary directory; tests/test_hexagon_benchmarks.py and scripts/fuzz_parity.py
+both come here.  Imports neither the product nor torch."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import subprocess
+import tempfile
+import threading
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCES = ("hexagon_benchmarks_check.c",)
+NAMES = ("conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel")
+MASKED = ("conv3x3a16", "conv3x3a32")
+HALO = {n: (2 if n == "gaussian5x5" else 1) for n in NAMES}
+DRIVER_MASK = np.array([[1, -4, 7], [2, -5, 8], [3, -6, 9]], np.int8)   # [i][j] = mask(j, i), as process.h fills it
+
+_lock = threading.Lock()
+_lib = []
+
+
+def lib():
+    """The loaded shared object (the raw ctypes library), built on the first call."""
+    with _lock:
+        if not _lib:
+            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_hexagon_benchmarks_checker"), "libhexagonbenchmarkscheck.so")
+            subprocess.run(["gcc", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so] + [os.path.join(ROOT, "tests", "cpp", s) for s in SOURCES], check=True)
+            L = C.CDLL(so)
+            P, I, G = C.c_void_p, C.c_int, C.c_long
+            for n in NAMES:
+                for f in (getattr(L, "hb_" + n), getattr(L, "hb_" + n + "_verify")):
+                    f.restype = None
+                    f.argtypes = [P, I, I, G] + ([P] if n in MASKED else []) + [P, I, I, I, I]
+            L.hb_conv3x3_sum.restype, L.hb_conv3x3_sum.argtypes = None, [P, I, I, G, P, P, I, I, I, I]
+            _lib.append(L)
+    return _lib[0]
+
+
+def _plane(image):
+    image = np.asarray(image)
+    assert image.ndim == 2 and image.dtype == np.uint8 and image.strides[1] == 1 and image.shape[0] > 0 and image.shape[1] > 0
+    return image, image.strides[0] if image.shape[0] > 1 else image.shape[1]
+
+
+def _mask(name, mask):
+    if name not in MASKED:
+        assert mask is None
+        return []
+    m = np.ascontiguousarray(mask, np.int8)
+    assert m.shape == (3, 3)
+    return [m]
+
+
+def run(name, image, mask=None, region=None, verify=False):
+    """The filter `name` of the (H, W) uint8 `image` (sample (0, 0) its first element) over the output region (ox, oy, ow, oh), by
+    default the image's own box; mask: (3, 3) int8, [i][j] = mask(j, i), for the two conv3x3 filters.  verify: the restatement of
+    process.h's verifier instead of the generator's.  Returns (oh, ow) uint8."""
+    image, stride = _plane(image)
+    ox, oy, ow, oh = region if region is not None else (0, 0, image.shape[1], image.shape[0])
+    out = np.zeros((oh, ow), np.uint8)
+    m = _mask(name, mask)
+    f = getattr(lib(), "hb_" + name + ("_verify" if verify else ""))
+    f(image.ctypes.data, image.shape[1], image.shape[0], stride, *[a.ctypes.data for a in m], out.ctypes.data, ox, oy, ow, oh)
+    return out
+
+
+def conv_sum(image, mask, region=None):
+    """the int32 sum of the 3x3 window before the shift, (oh, ow) int32"""
+    image, stride = _plane(image)
+    ox, oy, ow, oh = region if region is not None else (0, 0, image.shape[1], image.shape[0])
+    out = np.zeros((oh, ow), np.int32)
+    m = np.ascontiguousarray(mask, np.int8)
+    lib().hb_conv3x3_sum(image.ctypes.data, image.shape[1], image.shape[0], stride, m.ctypes.data, out.ctypes.data, ox, oy, ow, oh)
+    return out
+
+
+class DevPlane:
+    """An (H, W) uint8 plane inside a flat device allocation of its own, wrapped as a device-only buffer: the row stride and the
+    byte offset of the first element from the allocation's start (which is 256-byte aligned) are the caller's.  `hl` is the product
+    module; the allocation is made with the HIP runtime directly, as a caller with device memory of its own would."""
+
+    def __init__(self, hl, h, w, row_stride=None, offset=0, mins=None, fill=None):
+        rs = w if row_stride is None else row_stride
+        assert rs >= w
+        self.hl, self.hip = hl, hl.hip_runtime()
+        self.flat = np.zeros(offset + h * rs + 8, np.uint8)
+        self.host = np.lib.stride_tricks.as_strided(self.flat[offset:], (h, w), (rs, 1))
+        if fill is not None:
+            self.host[...] = fill
+        self.p = C.c_void_p()
+        assert self.hip.hipMalloc(C.byref(self.p), C.c_size_t(self.flat.nbytes)) == 0
+        assert self.hip.hipMemcpy(self.p, C.c_void_p(self.flat.ctypes.data), C.c_size_t(self.flat.nbytes), 1) == 0   # host to device
+        self.buf = hl.Buffer.wrap_device(self.p.value + offset, np.uint8, (w, h), (1, rs), mins)
+
+    def result(self):
+        """the plane as the device holds it now, contiguous; everything outside it must be as it was"""
+        self.buf.device_sync()
+        back = np.empty_like(self.flat)
+        assert self.hip.hipMemcpy(C.c_void_p(back.ctypes.data), self.p, C.c_size_t(back.nbytes), 2) == 0   # device to host
+        view = np.lib.stride_tricks.as_strided(back[self.host.ctypes.data - self.flat.ctypes.data:], self.host.shape, self.host.strides)
+        got = view.copy()   # (ascontiguousarray would alias a dense plane)
+        view[...] = self.host
+        assert np.array_equal(back, self.flat), "bytes outside the plane were written"
+        return got
+
+    def free(self):
+        self.buf.device_detach()
+        assert self.hip.hipFree(self.p) == 0
