@@ -14,6 +14,8 @@ import threading
 
 import numpy as np
 
+from parity_helpers import DevArray
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = ("hexagon_benchmarks_check.c",)
 NAMES = ("conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel")
@@ -80,35 +82,11 @@ def conv_sum(image, mask, region=None):
     return out
 
 
-class DevPlane:
+class DevPlane(DevArray):
     """An (H, W) uint8 plane inside a flat device allocation of its own, wrapped as a device-only buffer: the row stride and the
     byte offset of the first element from the allocation's start (which is 256-byte aligned) are the caller's.  `hl` is the product
-    module; the allocation is made with the HIP runtime directly, as a caller with device memory of its own would."""
+    module.  parity_helpers.DevArray for one uint8 plane: `result()` returns the plane as the device holds it and asserts that
+    every byte outside it (a sentinel) is as it was."""
 
     def __init__(self, hl, h, w, row_stride=None, offset=0, mins=None, fill=None):
-        rs = w if row_stride is None else row_stride
-        assert rs >= w
-        self.hl, self.hip = hl, hl.hip_runtime()
-        self.flat = np.zeros(offset + h * rs + 8, np.uint8)
-        self.host = np.lib.stride_tricks.as_strided(self.flat[offset:], (h, w), (rs, 1))
-        if fill is not None:
-            self.host[...] = fill
-        self.p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.p), C.c_size_t(self.flat.nbytes)) == 0
-        assert self.hip.hipMemcpy(self.p, C.c_void_p(self.flat.ctypes.data), C.c_size_t(self.flat.nbytes), 1) == 0   # host to device
-        self.buf = hl.Buffer.wrap_device(self.p.value + offset, np.uint8, (w, h), (1, rs), mins)
-
-    def result(self):
-        """the plane as the device holds it now, contiguous; everything outside it must be as it was"""
-        self.buf.device_sync()
-        back = np.empty_like(self.flat)
-        assert self.hip.hipMemcpy(C.c_void_p(back.ctypes.data), self.p, C.c_size_t(back.nbytes), 2) == 0   # device to host
-        view = np.lib.stride_tricks.as_strided(back[self.host.ctypes.data - self.flat.ctypes.data:], self.host.shape, self.host.strides)
-        got = view.copy()   # (ascontiguousarray would alias a dense plane)
-        view[...] = self.host
-        assert np.array_equal(back, self.flat), "bytes outside the plane were written"
-        return got
-
-    def free(self):
-        self.buf.device_detach()
-        assert self.hip.hipFree(self.p) == 0
+        super().__init__(hl, (h, w), np.uint8, row_stride, offset=offset, mins=mins, fill=fill)
