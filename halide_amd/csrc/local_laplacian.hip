@@ -22,6 +22,7 @@
 //   ll_remap_lut    remap LUT (generator :23-25); cached per (device, levels, alpha)
 //   ll_down01e      levels 0 -> 1 -> 2 of all K+1 planes in ONE walk; emits outLPyramid[0] (one plane) and three planes of level 1
 //                   instead of the K+1-plane level-1 pyramid (round 4's dataflow; ll_down01f = round 3's, which stores them all)
+//                   (on a frame queue, <.., EM1>: ONE plane of level 1, outLPyramid[1]; ll_up0h<.., EM1> adds it to its level-2 tile)
 //   ll_down_strip2  levels 3 and 4 from level 2 in one launch (round 5; ll_down_strip = one level per launch, other chains)
 //   ll_down_multi   levels 5..7 from level 4 in one launch;  ll_up_multi: outGPyramid[3] from levels 3..7 in one launch
 //   ll_up0h         outGPyramid[2] and outGPyramid[1] (LDS tiles) -> outGPyramid[0] = upsample + outLPyramid[0] -> recolour -> u16 store
@@ -815,6 +816,31 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01f(D01Args p, Geometry 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// upsample(f)(X,Y) (:276-282) of a stored level plane `f` (origin lox/loy, row stride ws)
+// The four taps of the bilinear footprint and the lerps on them are separate steps so that a caller can REQUEST the taps of many
+// values before it combines the first (ll_up_multi); up_at = both steps, the same operations in the same order.
+struct UpTaps {
+    float aa, ab, ba, bb;    // f(ya, xa), f(ya, xb), f(yb, xa), f(yb, xb)
+};
+__device__ __forceinline__ UpTaps up_taps(const float *__restrict__ f, int lox, int loy, int ws, int X, int Y) {
+    const int xa = dev::fdiv2(X + 1) - lox, xb = dev::fdiv2(X - 1) - lox;
+    const int ya = dev::fdiv2(Y + 1) - loy, yb = dev::fdiv2(Y - 1) - loy;
+    UpTaps t;
+    t.aa = f[(size_t)ya * ws + xa], t.ab = f[(size_t)ya * ws + xb];
+    t.ba = f[(size_t)yb * ws + xa], t.bb = f[(size_t)yb * ws + xb];
+    return t;
+}
+__device__ __forceinline__ float up_from(const UpTaps &t, int X, int Y) {
+    const float wx = (float)(dev::fmod2(X) * 2 + 1) * 0.25f, wy = (float)(dev::fmod2(Y) * 2 + 1) * 0.25f;
+    const float ua = dev::lerpf(t.aa, t.ab, wx);
+    const float ub = dev::lerpf(t.ba, t.bb, wx);
+    return dev::lerpf(ua, ub, wy);
+}
+__device__ __forceinline__ float up_at(const float *__restrict__ f, int lox, int loy, int ws, int X, int Y) {
+    return up_from(up_taps(f, lox, loy, ws, X, Y), X, Y);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // ll_down01e: ll_down01f re-cut so that the (K + 1)-plane level-1 pyramid never leaves the chip (round 4).
 //
 // outLPyramid[0](x, y) (:63-72) — ONE value per pixel — is a pure function of gray(x, y), of gPyramid[0](x, y, li / li + 1)
@@ -842,7 +868,30 @@ struct D01EArgs {
     // xcd_block() hands an XCD holds horizontal AND vertical neighbours: a strip's 512-byte row pieces start 16 bytes before a
     // 128-byte line, which its left neighbour reads too — from the same L2 then (68.8 -> 58.8 MB fetched per 4K frame)
     unsigned nsx_magic;        // floor(2^32 / nsx) + 1, 0 when nsx == 1
+    // EM1: outLPyramid[1] goes to plane 0 of level 1 (d.g1) instead of the three planes; level-2 rows above `last2` do not exist
+    int last2;                 // loy2 + h2 - 1
 };
+// EM1 (HLMI_LL_EMIT1): the wave also holds what outLPyramid[1] (:63-72) reads — (ga, gb, inG) of its level-1 rows and, once level-2
+// row U is complete (step T = 2U + 2), level-2 rows U - 1 and U of the planes 0 .. K-1: fdiv2(Y - 1) = U - 1 for both level-1 rows
+// Y = 2U - 1 and Y = 2U.  So it stores ONE level-1 plane, outLPyramid[1], instead of three, and ll_up0h<.., EM1> neither reads the
+// other two nor gathers level-2 taps.  The arithmetic is ll_up0h's phase 1 (up_from on the four taps of planes li and li + 1, two
+// subtractions, dev::mad2): bit-identical.
+//   * The level-2 rows live in a wave-private two-row ring in LDS ([plane][row parity][64 lanes] floats, 4 KB per wave; the plane
+//     index is data), the (ga, gb, inG) pairs of the up to four level-1 rows that wait for their level-2 row in registers —
+//     the instance is launch-bound to ONE wave per SIMD, which is what a frame queue runs anyway (ll_plan).
+//   * Columns: a pixel's taps are the level-2 values of lanes L - 1, L (ODD1) or L - 1, L, L + 1 (!ODD1), and level 2 is valid in
+//     S2max lanes only, so the strips of an EM1 launch advance by one (two) lanes less (ll_plan: S2) and lanes 1 .. S2
+//     (2 .. S2 + 1) emit.
+//   * Rows: a unit owning level-2 rows [A, B] emits level-1 rows 2A + 1 .. 2B from its own rows.  The pair (2B + 1, 2B + 2) needs
+//     level-2 row B + 1: a wave that walks its own halo (self_halo) walks two more level-1 rows for it; inside a workgroup (EXCH)
+//     the upper wave emits the pair after its walk from the first two level-1 rows (pub_next) and the first level-2 row (pub2) the
+//     wave below published — a second workgroup barrier, after the fourth step.  Rows 2 loy2 - 1, 2 loy2 and those above
+//     2 last2 lie outside R_1.
+constexpr int D01_RING = KCH * 2 * 64;   // floats of one wave's level-2 ring
+constexpr int D01_PUB2 = KCH * 64;       // floats of the level-2 row a wave publishes
+// The rows of pub2 are part of the size with or without EXCH: lanes 0 and 63 do not emit, but they read their (discarded) taps like
+// every lane — one float before the lane's ring and one past it, i.e. in a neighbouring wave's ring or, after the last ring, in pub2.
+constexpr size_t d01_em1_lds_bytes() { return sizeof(float) * ((D0_THREADS / 64) * D01_RING + (D0_THREADS / 64 - 1) * D01_PUB2); }
 // Packed arithmetic: at two waves per SIMD this kernel is bound by how often ONE wave can issue (a wave issues an
 // independent VALU instruction every ~2.1 ns whatever it is, scripts/ubench/valu_pk.hip: v_pk_add / mul / fma_f32 2.4 ns for
 // two results against 2.1 ns for one), so every pointwise pass runs on column PAIRS held as <2 x float>: pair A = the
@@ -856,8 +905,8 @@ __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementw
 __device__ __forceinline__ f2 mad_2(f2 a, f2 b, f2 c) { return dev::CANON_FMA ? fma2(a, b, c) : a * b + c; }
 __device__ __forceinline__ f2 mad2_2(f2 a, f2 b, f2 c, f2 d) { return dev::CANON_FMA ? fma2(a, b, c * d) : a * b + c * d; }
 
-template<bool ODD0, bool ODD1, bool B1, bool EXCH, bool NT>
-__global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometry gm, Levels lev) {
+template<bool ODD0, bool ODD1, bool B1, bool EXCH, bool NT, bool EM1>
+__global__ __launch_bounds__(D0_THREADS, EM1 ? 1 : 2) void ll_down01e(D01EArgs pe, Geometry gm, Levels lev) {
     const D01Args &p = pe.d;
     LL_RESIDENCY(0);
     extern __shared__ float slut[];
@@ -878,6 +927,7 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
         A = GA + wave * n, B = min(A + n - 1, GB);
         if (A > GB) {          // no rows left for this wave: it only keeps the barrier count
             __syncthreads();
+            if (EM1) __syncthreads();
             return;
         }
         self_halo = !(wave < 3 && A + n <= GB);
@@ -898,8 +948,10 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
 #pragma unroll
     for (int i = 0; i < 4; i++) xo[i] = qs.oq + qs.sel[i];
     const bool edge_wave = __any(!qs.plain);
+    // EM1: a wave that walks its own halo walks two level-1 rows further, to level-2 row B + 1 (outLPyramid[1] rows 2B + 1, 2B + 2)
+    const bool ext1 = EM1 && self_halo && B < pe.last2;
     // level-1 rows [T0, T1] computed, [Ts0, Ts1] stored (their three planes), steps [2A, 2B + 1] emit outLPyramid[0]
-    const int T0 = 2 * A - 1, T1 = self_halo ? 2 * B + 2 : 2 * B;
+    const int T0 = 2 * A - 1, T1 = self_halo ? (ext1 ? 2 * B + 4 : 2 * B + 2) : 2 * B;
     const int Ts0 = max(EXCH ? 2 * A - 1 : 2 * A, p.loy1), Ts1 = min(EXCH ? 2 * B : 2 * B + 1, p.loy1 + p.h1 - 1);
     const int off1 = P - p.so1;
     const bool st1_ok = lane < p.S2 && off1 >= 0 && off1 < p.w1;
@@ -913,6 +965,12 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
     f2 *st2 = reinterpret_cast<f2 *>(slut + ((2 * gm.half + 2) & ~1)) + wave * D01_STATE + lane;
     f2 *pub_all = reinterpret_cast<f2 *>(slut + ((2 * gm.half + 2) & ~1)) + (D0_THREADS / 64) * D01_STATE + lane;
     f2 *pub_mine = pub_all + (wave - 1) * D01_STATE, *pub_next = pub_all + wave * D01_STATE;
+    // EM1: the level-2 rings of the four waves ([plane][row parity][64 lanes]), then the level-2 rows that waves 1 .. 3 publish
+    // ([plane][64 lanes]; lane 63's unused tap of its right neighbour in the last ring lands in the first of them)
+    float *const ring = slut + ((2 * gm.half + 2) & ~1) + 2 * D01_STATE * ((D0_THREADS / 64) + (EXCH ? D0_THREADS / 64 - 1 : 0)) +
+                        wave * D01_RING + lane;
+    float *const pub2_mine = ring + ((D0_THREADS / 64) - wave) * D01_RING + (wave - 1) * D01_PUB2, *const pub2_next = pub2_mine + D01_PUB2;
+    const bool e1_ok = (ODD1 ? (lane >= 1 && lane <= p.S2) : (lane >= 2 && lane <= p.S2 + 1)) && off1 >= 0 && off1 < p.w1;
     const int lbase = gm.half - 256 * (KCH - 1);
     float level[KCH];
 #pragma unroll
@@ -1121,6 +1179,48 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
             else *dst = f4_t{r[0], r[1], r[2], r[3]};
         }
     };
+    // ---- what the collapse of level 1 reads at the lane's two coarse pixels of one level-1 row (:63-72): gPyramid[1](., ., li1),
+    // gPyramid[1](., ., li1 + 1) for li1 of the pixel, and inGPyramid[1].  `row`: the lane's float2 of plane 0 in that row (window
+    // slot or published row: plane stride 256 floats), sK: its float2 of inGPyramid[1]
+    struct L1Row {
+        float2 a, b;
+        f2 k;
+    };
+    auto sel_row = [&](const f2 *row, f2 sK) {
+        const int lx = dev::clampi((int)(sK.x * gm.Km1), 0, KCH - 2), ly = dev::clampi((int)(sK.y * gm.Km1), 0, KCH - 2);
+        const float *fx = reinterpret_cast<const float *>(row) + (lx << 8), *fy = reinterpret_cast<const float *>(row) + (ly << 8) + 1;
+        L1Row r;
+        r.a = make_float2(fx[0], fy[0]), r.b = make_float2(fx[256], fy[256]), r.k = sK;
+        return r;
+    };
+    // EM1: outLPyramid[1] of the lane's two pixels of level-1 row 2U - 1 (YODD) or 2U from level-2 rows U - 1 and U of the ring:
+    // ll_up0h's phase 1 — the pixel's plane pair from the row's L1Row, the four taps of planes li and li + 1 (xb = fdiv2(X - 1) is
+    // the level-2 column of lane L - 1, except at the odd column of an even pair: lane L), up_from, dev::mad2
+    auto em1_pair = [&](const L1Row &r, int U, auto yodd_tag) {
+        constexpr int YP = decltype(yodd_tag)::value ? 1 : 0;
+        const int ob = ((U - 1) & 1) * 64, oa = 64 - ob;
+        auto px = [&](float ga, float gb, float inG, int coff, int xpar) {
+            const float level = inG * gm.Km1;
+            const int li = dev::clampi((int)level, 0, KCH - 2);
+            const float lf = level - (float)li;
+            const float *q = ring + (li << 7) + coff;
+            UpTaps t0, t1;
+            t0.bb = q[ob], t0.ba = q[ob + 1], t0.ab = q[oa], t0.aa = q[oa + 1];
+            t1.bb = q[128 + ob], t1.ba = q[128 + ob + 1], t1.ab = q[128 + oa], t1.aa = q[128 + oa + 1];
+            const float l0 = ga - up_from(t0, xpar, YP), l1 = gb - up_from(t1, xpar, YP);
+            return dev::mad2(1.0f - lf, l0, lf, l1);
+        };
+        return make_float2(px(r.a.x, r.b.x, r.k.x, -1, ODD1 ? 1 : 0), px(r.a.y, r.b.y, r.k.y, ODD1 ? -1 : 0, ODD1 ? 0 : 1));
+    };
+    auto em1_store = [&](int U, float2 vo, float2 ve) {   // level-1 rows 2U - 1 and 2U, into plane 0 of level 1
+        if (e1_ok) {
+            const int y = 2 * U - 1 - p.loy1;
+            float *drow = p.g1 + (long)y * p.ws1 + off1;
+            if (y >= 0 && y < p.h1) *reinterpret_cast<float2 *>(drow) = vo;
+            if (y + 1 >= 0 && y + 1 < p.h1) *reinterpret_cast<float2 *>(drow + p.ws1) = ve;
+        }
+    };
+    L1Row dl_o0 = {}, dl_o1 = {}, dl_e = {};   // EM1 delay line: level-1 rows 2U - 1, 2U + 1 and 2U at the step that completes level-2 row U
 #if HLMI_LL_PROBE
     unsigned long long pr_planes = 0, pr_emit = 0, pr_prep = 0, pr_steps = 0;
     LL_PROBE_T(pe0);
@@ -1157,8 +1257,11 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
         f2 lv[2][4], dy[2][2];
         f2 res[KCH + 1];
         f2 sa, sb;
-        const bool out2 = PH == 1 && T >= 2 * A + 2;   // wave-uniform
+        const bool out2 = PH == 1 && T >= 2 * A + 2 && (!EM1 || T <= 2 * B + 2);   // wave-uniform (EM1: row B + 1 is the next unit's to store)
         float *d2 = p.g2 + (size_t)(((T - 2) >> 1) - p.loy2) * p.ws2 + off2;
+        const int U = (T - 2) >> 1;                            // PH == 1: the level-2 row this step completes
+        float *const ringU = ring + (U & 1) * 64;              // EM1: its ring slot
+        const bool pub2 = EM1 && EXCH && publish && T == 2 * A + 2;   // wave-uniform: the wave's first level-2 row, for the wave above
         LL_PROBE_T(ps0);
         auto level2 = [&](int k) {
             const f2 c = res[k];
@@ -1177,6 +1280,10 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
                 }
                 if (out2 && st2_ok) d2[(size_t)k * p.ps2] = o;
                 st2[(2 * k + 1) * 64] = c;
+                if (EM1 && k < KCH) {
+                    ringU[(2 * k) * 64] = o;
+                    if (pub2) pub2_mine[k * 64] = o;
+                }
             }
         };
         auto state_issue = [&](int k) {
@@ -1205,7 +1312,7 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_sched_barrier(0);
         f2 *const rowT = st2 + (PH == 0 ? 0 : 64), *const rowP = st2 + (PH == 0 ? 64 : 0);   // rows T and T - 1
-        const bool st1_row = T >= Ts0 && T <= Ts1;                                                  // wave-uniform
+        const bool st1_row = !EM1 && T >= Ts0 && T <= Ts1;                                          // wave-uniform
         const bool em_rows = T >= 2 * A && T <= 2 * B + 1;   // wave-uniform
         EmPix eg[4];
         if (em_rows) {
@@ -1260,6 +1367,19 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
             em_wait(fg[2], after1), ee[2] = em_arith(n1, 2, fg[2], row_even);
             em_wait(fg[3], after0), ee[3] = em_arith(n1, 3, fg[3], row_even);
         }
+        // EM1: this row joins the delay line; the step that completed level-2 row U emits outLPyramid[1] rows 2U - 1 and 2U (the
+        // first such step of a unit completes row A - 1, which is not its own: nothing to emit)
+        float2 x1o = make_float2(0.0f, 0.0f), x1e = x1o;
+        const bool em1_rows = EM1 && PH == 1 && U >= A + 1;   // wave-uniform
+        if (EM1) {
+            const L1Row cur = sel_row(rowT, sK);
+            if (PH == 0) {
+                dl_o1 = cur;
+            } else {
+                if (em1_rows) x1o = em1_pair(dl_o0, U, row_odd), x1e = em1_pair(dl_e, U, row_even);
+                dl_o0 = dl_o1, dl_e = cur;
+            }
+        }
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         LL_PROBE_T(ps2);
@@ -1273,6 +1393,7 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
             *reinterpret_cast<float2 *>(drow + p.ps1) = s1;
             *reinterpret_cast<f2 *>(drow + (size_t)KCH * p.ps1) = sK;
         }
+        if (em1_rows) em1_store(U, x1o, x1e);
         if (em_rows) {
             emit_store(2 * T - 1, eo);
             emit_store(2 * T, ee);
@@ -1298,6 +1419,8 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
         step(std::integral_constant<int, 0>{}, T, p0, p1, p2, p3, a, b, a2, b2, first && publish ? pub_mine : nullptr);
         step(std::integral_constant<int, 1>{}, T + 1, p2, p3, p0, p1, a2, b2, a, b, first && publish ? pub_mine + 64 : nullptr);
         if (first) __syncthreads();   // every wave of the workgroup that has rows passes here exactly once
+        // EM1: ... and here, after the step that published the first level-2 row (every wave walks at least four rows)
+        if (EM1 && EXCH && T == T0 + 2) __syncthreads();
     }
 #if HLMI_LL_PROBE
     LL_PROBE_T(pe1);
@@ -1319,6 +1442,24 @@ __global__ __launch_bounds__(D0_THREADS, 2) void ll_down01e(D01EArgs pe, Geometr
                 o = down4_tail(py, r.x, r.y, nx);
             }
             if (st2_ok) d2[(size_t)k * p.ps2] = o;
+            if (EM1 && k < KCH) ring[(2 * k + (B & 1)) * 64] = o;
+        }
+        if (EM1) {
+            // outLPyramid[1] rows 2B - 1, 2B (still in the delay line) from level-2 rows B - 1 and B, then rows 2B + 1, 2B + 2 — the
+            // published level-1 rows — from row B and the published level-2 row B + 1, which takes row B - 1's ring slot
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            const float2 ao = em1_pair(dl_o0, B, row_odd), ae = em1_pair(dl_e, B, row_even);
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int k = 0; k < KCH; k++) ring[(2 * k + ((B + 1) & 1)) * 64] = pub2_next[k * 64];
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+            const L1Row r0 = sel_row(pub_next, pub_next[(2 * KCH) * 64]), r1 = sel_row(pub_next + 64, pub_next[(2 * KCH + 1) * 64]);
+            const float2 bo = em1_pair(r0, B + 1, row_odd), be = em1_pair(r1, B + 1, row_even);
+            em1_store(B, ao, ae);
+            em1_store(B + 1, bo, be);
         }
         // outLPyramid[0] rows 4B + 1, 4B + 2 (the pair the last step brought in: p2 / p3) from level-1 rows 2B (slot 1) and 2B + 1
         // (published)
@@ -1484,29 +1625,7 @@ __global__ __launch_bounds__(256) void ll_down_strip2(Strip2Args p) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// upsample(f)(X,Y) (:276-282) of a stored level plane `f` (origin lox/loy, row stride ws)
-// The four taps of the bilinear footprint and the lerps on them are separate steps so that a caller can REQUEST the taps of many
-// values before it combines the first (ll_up_multi); up_at = both steps, the same operations in the same order.
-struct UpTaps {
-    float aa, ab, ba, bb;    // f(ya, xa), f(ya, xb), f(yb, xa), f(yb, xb)
-};
-__device__ __forceinline__ UpTaps up_taps(const float *__restrict__ f, int lox, int loy, int ws, int X, int Y) {
-    const int xa = dev::fdiv2(X + 1) - lox, xb = dev::fdiv2(X - 1) - lox;
-    const int ya = dev::fdiv2(Y + 1) - loy, yb = dev::fdiv2(Y - 1) - loy;
-    UpTaps t;
-    t.aa = f[(size_t)ya * ws + xa], t.ab = f[(size_t)ya * ws + xb];
-    t.ba = f[(size_t)yb * ws + xa], t.bb = f[(size_t)yb * ws + xb];
-    return t;
-}
-__device__ __forceinline__ float up_from(const UpTaps &t, int X, int Y) {
-    const float wx = (float)(dev::fmod2(X) * 2 + 1) * 0.25f, wy = (float)(dev::fmod2(Y) * 2 + 1) * 0.25f;
-    const float ua = dev::lerpf(t.aa, t.ab, wx);
-    const float ub = dev::lerpf(t.ba, t.bb, wx);
-    return dev::lerpf(ua, ub, wy);
-}
-__device__ __forceinline__ float up_at(const float *__restrict__ f, int lox, int loy, int ws, int X, int Y) {
-    return up_from(up_taps(f, lox, loy, ws, X, Y), X, Y);
-}
+// The up pass (upsample: UpTaps / up_from / up_at, above ll_down01e, which collapses with them too)
 
 // outGPyramid[J-1] = outLPyramid[J-1] (:76, :63-72 with lPyramid[J-1] = gPyramid[J-1], :51); o = element offset
 __device__ __forceinline__ float top_value(const float *__restrict__ g, size_t ps, size_t o, int K, float Km1) {
@@ -1563,6 +1682,14 @@ __device__ __forceinline__ void up_pixel(const UpArgs &a, int x, int y) {   // (
 template<bool SEL = false>
 __global__ __launch_bounds__(256) void ll_up(UpArgs a) {
     up_pixel<SEL>(a, blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y);
+}
+// The same where plane 0 of level j already holds outLPyramid[j] (ll_down01e<.., EM1>; the test hook's collapse of level 1)
+__global__ __launch_bounds__(256) void ll_up_outl(UpArgs a) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= a.rw || y >= a.rh) return;
+    const int X = a.rx0 + x, Y = a.ry0 + y;
+    const size_t o = (size_t)(Y - a.loy) * a.ws + (X - a.lox);
+    a.out[o] = up_at(a.outc, a.clox, a.cloy, a.cws, X, Y) + a.g[o];
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2162,8 +2289,9 @@ struct Up0HArgs {
 };
 constexpr int U0H_PF = 4;      // rows in flight per wave
 constexpr int U0H_T2 = 68;     // row stride of the level-2 tile
-template<bool NT, int CH = 2>  // CH: tile values a thread requests at a time in the two tile phases (1: 102.0, 2: 101.1, 4: 102.4 us per
-                               // frame on one stream — 4 costs occupancy: 124 VGPRs against 66)
+// EM1: plane 0 of level 1 holds outLPyramid[1] (ll_down01e<.., EM1>); phase 1 is one load per tile value (needs fuse2)
+template<bool NT, bool EM1, int CH = 2>  // CH: tile values a thread requests at a time in the two tile phases (1: 102.0, 2: 101.1, 4: 102.4 us per
+                                         // frame on one stream — 4 costs occupancy: 124 VGPRs against 66)
 __global__ __launch_bounds__(256) void ll_up0h(Up0HArgs ph, Geometry gm) {
     const Up0Args &p = ph.u;
     LL_RESIDENCY(1);
@@ -2264,50 +2392,75 @@ __global__ __launch_bounds__(256) void ll_up0h(Up0HArgs ph, Geometry gm) {
         const int n1 = U0_TW * th;
         constexpr uint32_t M1 = (4194304u + U0_TW - 1) / U0_TW;
         const uint32_t row1 = (uint32_t)((cy0 - p.loy1) * p.ws1), row2 = (uint32_t)((c2y0 - p.loy2) * p.ws2);
-        for (int e0 = threadIdx.x; e0 < n1; e0 += 256 * CH) {
-            int cx[CH], cy[CH];
-            uint32_t ti[CH];
-            bool ok[CH];
-            Taps32 t2[CH];
-            float inG[CH], lf[CH], ga[CH], gb[CH];
-            UpTaps o2[CH], t0[CH], t1[CH];
+        if constexpr (EM1) {
+            for (int e0 = threadIdx.x; e0 < n1; e0 += 256 * CH) {
+                // outGPyramid[1] = upsample(outGPyramid[2]) + outLPyramid[1]   (:76-79): the stored value and up_at on the LDS tile
+                int cx[CH], cy[CH];
+                uint32_t ti[CH];
+                bool ok[CH];
+                float outL[CH];
 #pragma unroll
-            for (int i = 0; i < CH; i++) {
-                const int e = e0 + 256 * i;
-                const uint32_t ec = (uint32_t)min(e, n1 - 1), ty = mul24(ec, M1) >> 22, tx = ec - mul24(ty, U0_TW);
-                ok[i] = e < n1 && cx0 + (int)tx <= p.rx1_1, ti[i] = mul24(ty, U0_TS) + tx;
-                cx[i] = min(cx0 + (int)tx, p.rx1_1), cy[i] = cy0 + (int)ty;      // columns right of R_1 are not tile values: their threads re-read its last one
-                const uint32_t ob = (row1 + mul24(ty, (uint32_t)p.ws1) + (uint32_t)(cx[i] - p.lox1)) << 2;
-                // level 1 as ll_down01e stored it: plane 0 / 1 = gPyramid[1](., ., li / li + 1) of the pixel's own li, plane K = inGPyramid[1]
-                inG[i] = ld_su<float>(p.g1, (uint32_t)gm.K * ps1b + ob), ga[i] = ld_su<float>(p.g1, ob), gb[i] = ld_su<float>(p.g1, ps1b + ob);
-                t2[i] = tap_bytes(row2, c2y0, p.lox2, p.ws2, cx[i], cy[i]);
-                if (!ph.fuse2) o2[i] = taps_at(p.out2, 0u, t2[i]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+                for (int i = 0; i < CH; i++) {
+                    const int e = e0 + 256 * i;
+                    const uint32_t ec = (uint32_t)min(e, n1 - 1), ty = mul24(ec, M1) >> 22, tx = ec - mul24(ty, U0_TW);
+                    ok[i] = e < n1 && cx0 + (int)tx <= p.rx1_1, ti[i] = mul24(ty, U0_TS) + tx;
+                    cx[i] = min(cx0 + (int)tx, p.rx1_1), cy[i] = cy0 + (int)ty;
+                    outL[i] = ld_su<float>(p.g1, (row1 + mul24(ty, (uint32_t)p.ws1) + (uint32_t)(cx[i] - p.lox1)) << 2);
+                }
 #pragma unroll
-            for (int i = 0; i < CH; i++) {
-                const float level = inG[i] * gm.Km1;
-                const int li = dev::clampi((int)level, 0, gm.K - 2);
-                lf[i] = level - (float)li;
-                t0[i] = taps_at(p.g2, (uint32_t)li * ps2b, t2[i]);
-                t1[i] = taps_at(p.g2, (uint32_t)(li + 1) * ps2b, t2[i]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < CH; i++) {
-                // outGPyramid[1] = upsample(outGPyramid[2]) + outLPyramid[1]   (:76-79), exactly as ll_up computes it
-                const float l0 = ga[i] - up_from(t0[i], cx[i], cy[i]), l1 = gb[i] - up_from(t1[i], cx[i], cy[i]);
-                const float outL = dev::mad2(1.0f - lf[i], l0, lf[i], l1);
-                float up2;
-                if (ph.fuse2) {   // up_at on the LDS tile: the same taps, weights and lerps
+                for (int i = 0; i < CH; i++) {
                     const float *q = s_out2 + mul24((uint32_t)(dev::fdiv2(cy[i] - 1) - c2y0), U0H_T2) + (uint32_t)(dev::fdiv2(cx[i] - 1) - c2x0);
                     UpTaps t;
                     t.bb = q[0], t.ba = q[1], t.ab = q[U0H_T2], t.aa = q[U0H_T2 + 1];
-                    up2 = up_from(t, cx[i], cy[i]);
-                } else {
-                    up2 = up_from(o2[i], cx[i], cy[i]);
+                    if (ok[i]) s_out1[ti[i]] = up_from(t, cx[i], cy[i]) + outL[i];
                 }
-                if (ok[i]) s_out1[ti[i]] = up2 + outL;
+            }
+        } else {
+            for (int e0 = threadIdx.x; e0 < n1; e0 += 256 * CH) {
+                int cx[CH], cy[CH];
+                uint32_t ti[CH];
+                bool ok[CH];
+                Taps32 t2[CH];
+                float inG[CH], lf[CH], ga[CH], gb[CH];
+                UpTaps o2[CH], t0[CH], t1[CH];
+#pragma unroll
+                for (int i = 0; i < CH; i++) {
+                    const int e = e0 + 256 * i;
+                    const uint32_t ec = (uint32_t)min(e, n1 - 1), ty = mul24(ec, M1) >> 22, tx = ec - mul24(ty, U0_TW);
+                    ok[i] = e < n1 && cx0 + (int)tx <= p.rx1_1, ti[i] = mul24(ty, U0_TS) + tx;
+                    cx[i] = min(cx0 + (int)tx, p.rx1_1), cy[i] = cy0 + (int)ty;      // columns right of R_1 are not tile values: their threads re-read its last one
+                    const uint32_t ob = (row1 + mul24(ty, (uint32_t)p.ws1) + (uint32_t)(cx[i] - p.lox1)) << 2;
+                    // level 1 as ll_down01e stored it: plane 0 / 1 = gPyramid[1](., ., li / li + 1) of the pixel's own li, plane K = inGPyramid[1]
+                    inG[i] = ld_su<float>(p.g1, (uint32_t)gm.K * ps1b + ob), ga[i] = ld_su<float>(p.g1, ob), gb[i] = ld_su<float>(p.g1, ps1b + ob);
+                    t2[i] = tap_bytes(row2, c2y0, p.lox2, p.ws2, cx[i], cy[i]);
+                    if (!ph.fuse2) o2[i] = taps_at(p.out2, 0u, t2[i]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < CH; i++) {
+                    const float level = inG[i] * gm.Km1;
+                    const int li = dev::clampi((int)level, 0, gm.K - 2);
+                    lf[i] = level - (float)li;
+                    t0[i] = taps_at(p.g2, (uint32_t)li * ps2b, t2[i]);
+                    t1[i] = taps_at(p.g2, (uint32_t)(li + 1) * ps2b, t2[i]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < CH; i++) {
+                    // outGPyramid[1] = upsample(outGPyramid[2]) + outLPyramid[1]   (:76-79), exactly as ll_up computes it
+                    const float l0 = ga[i] - up_from(t0[i], cx[i], cy[i]), l1 = gb[i] - up_from(t1[i], cx[i], cy[i]);
+                    const float outL = dev::mad2(1.0f - lf[i], l0, lf[i], l1);
+                    float up2;
+                    if (ph.fuse2) {   // up_at on the LDS tile: the same taps, weights and lerps
+                        const float *q = s_out2 + mul24((uint32_t)(dev::fdiv2(cy[i] - 1) - c2y0), U0H_T2) + (uint32_t)(dev::fdiv2(cx[i] - 1) - c2x0);
+                        UpTaps t;
+                        t.bb = q[0], t.ba = q[1], t.ab = q[U0H_T2], t.aa = q[U0H_T2 + 1];
+                        up2 = up_from(t, cx[i], cy[i]);
+                    } else {
+                        up2 = up_from(o2[i], cx[i], cy[i]);
+                    }
+                    if (ok[i]) s_out1[ti[i]] = up2 + outL;
+                }
             }
         }
     }
@@ -2411,8 +2564,8 @@ const ArgTable ll_table("local_laplacian", {
 //                                                           else none: strips down to level J-1)           test_hip_repeated_calls_follow_new_contents
 //   UPCHAIN_FROM  3 if FUSE_FROM is 4, else 0               first level ll_up_multi collapses (1 .. J-2;   test_hip_pyramid_levels_match_oracle
 //                                                           else FUSE_FROM)
-//   RU            ll_up0h: 32 on a frame queue, else 8;     rows per wave of the level-0 kernel            test_hip_emit_launch_geometries_match_oracle
-//                 fused ll_up0f: 32 / 16; otherwise 8       (clamped to 1 .. 300, dev_clamp_ru)
+//   RU            ll_up0h: 32 (EMIT1: 24) on a frame queue, rows per wave of the level-0 kernel            test_hip_emit_launch_geometries_match_oracle
+//                 else 8; fused ll_up0f: 32 / 16; else 8    (clamped to 1 .. 300, dev_clamp_ru)
 //   UNITS0        ll_down01e on a frame queue: 10 x the     resident-wave target of the level-1 kernel     test_hip_fused_levels_1_and_2_match_oracle,
 //                 stream's CUs; otherwise 8 x the device's                                                 test_hip_emit_launch_geometries_match_oracle
 //   NO_VEC        0                                         1: the scalar frame-access kernels only        none
@@ -2423,8 +2576,11 @@ const ArgTable ll_table("local_laplacian", {
 //   D01_PAD_LDS   ll_down01e on a frame queue: -1 (one      bytes of unused LDS per ll_down01* workgroup   none (scripts/residency_probe.py)
 //                 workgroup per CU); otherwise 0            (< 0: over half a CU's LDS)
 //   NO_LUT_CACHE  0                                         1: the remap table is recomputed in every call none
+//   EMIT1         on a frame queue where d0.lds + 3 x       ll_down01e stores outLPyramid[1] as ONE plane   tests/test_local_laplacian_outl1.py
+//                 up0_lds <= 160 KB (RU, when unset, is     of level 1 instead of three, ll_up0h adds it
+//                 chosen to fit: 24); otherwise off         (1: on any stream, whatever the budget; 0: off)
 struct LlSwitches {
-    std::optional<int> fuse_from, upchain_from, ru, units0, no_vec, emit, nt, fuse_up2, d01_exch, d01_pad_lds, no_lut_cache;
+    std::optional<int> fuse_from, upchain_from, ru, units0, no_vec, emit, nt, fuse_up2, d01_exch, d01_pad_lds, no_lut_cache, emit1;
 };
 LlSwitches ll_switches() {
     const auto get = env_int;
@@ -2433,6 +2589,7 @@ LlSwitches ll_switches() {
     s.ru = get("HLMI_LL_RU"), s.units0 = get("HLMI_LL_UNITS0"), s.no_vec = get("HLMI_LL_NO_VEC");
     s.emit = get("HLMI_LL_EMIT"), s.nt = get("HLMI_LL_NT"), s.fuse_up2 = get("HLMI_LL_FUSE_UP2");
     s.d01_exch = get("HLMI_LL_D01_EXCH"), s.d01_pad_lds = get("HLMI_LL_D01_PAD_LDS"), s.no_lut_cache = get("HLMI_LL_NO_LUT_CACHE");
+    s.emit1 = get("HLMI_LL_EMIT1");
     return s;
 }
 
@@ -2465,7 +2622,8 @@ struct LlPlan {
     bool vec_in;       // 8-byte loads of the input (ll_down0<VEC>; the condition of `d01`)
     bool b1;           // beta == 1
     bool fast, fuse1, fuse2, emit, nt;
-    bool d01;          // levels 1 and 2 in one walk of the input (ll_down01e / ll_down01f), no ll_down_strip:1
+    bool emit1;        // level 1 is stored as ONE plane, outLPyramid[1] (ll_down01e / ll_up0h <.., EM1>), not as three
+    bool d01;         // levels 1 and 2 in one walk of the input (ll_down01e / ll_down01f), no ll_down_strip:1
     bool strip2;       // levels 3 and 4 in one launch (ll_down_strip2), no ll_down_strip:2 / :3
     // launch geometry
     struct { PairGeom pg; bool exch; int nsy, nunits; size_t lds; } d0;   // ll_down0, or (d01: pg, exch) ll_down01e / ll_down01f
@@ -2480,9 +2638,10 @@ struct LlBuffers {
     float *g[J], *outg[J];   // (K+1) planes of level j, outGPyramid[j]; [0] unused
 };
 
-PairGeom pair_geom(const Level &d, const Level &e) {   // d: level j+1, e: level j+2; e.odd == (d.lox & 1)
+// `fewer`: lanes to give up (ll_down01e<.., EM1> needs level 2 in the lanes beside an emitting one)
+PairGeom pair_geom(const Level &d, const Level &e, int fewer = 0) {   // d: level j+1, e: level j+2; e.odd == (d.lox & 1)
     PairGeom g;
-    g.S2 = (d.odd || e.odd) ? 62 : 61;
+    g.S2 = ((d.odd || e.odd) ? 62 : 61) - fewer;
     const int lim = e.odd ? 2 * e.lox - 1 : 2 * e.lox - 2;   // leftmost pair must reach level-(j+2) column so2
     g.Pbase = min(d.lox, lim);                                // same parity as so1 in either case
     const int hi1 = d.lox + d.w - 1, hi2 = e.lox + e.w - 1;
@@ -2598,7 +2757,7 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
     // stream that owns the device (31.7 us at 8 rows per wave against 33.5 / 38.4 at 16 / 32); with four frames in flight 8 / 12 / 16 /
     // 24 / 32 rows measure 107.8 / 110.1 / 111.2 / 112.3 / 112.3 Gpx/s (profiles/r06_frame_queue_geometry.txt), and next to ONE
     // resident ll_down01e workgroup per CU 32 rows beat 24 / 40 / 48 / 64 (profiles/r06_coresidency_ab.txt)
-    const int RU = p.RU = dev_clamp_ru(sw.ru.value_or(emit ? (partitioned ? 32 : 8) : fuse1 ? (partitioned ? 32 : 16) : 8));
+    int RU = dev_clamp_ru(sw.ru.value_or(emit ? (partitioned ? 32 : 8) : fuse1 ? (partitioned ? 32 : 16) : 8));
     // non-temporal frame / outLPyramid[0] accesses: +6-7 % frames per second with four frames in flight, -2-3 % on a stream that owns the device
     pl.nt = sw.nt.value_or(partitioned ? 1 : 0) != 0;
     // ll_up0h also collapses level 2 (into an LDS tile) when level 3 is a stored level of its own: the ll_up:2 launch goes
@@ -2607,6 +2766,39 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
     // tile phases: 104.1 -> 98.7 us per frame, 115 -> 110.6 for one call + sync)
     pl.fuse2 = emit && SU >= 3 && SU < J && sw.fuse_up2.value_or(1);
     pl.up_low = fuse1 ? (pl.fuse2 ? 3 : 2) : 1;
+    // emit1: ll_down01e collapses level 1 as far as outLPyramid[1] itself and stores that ONE plane instead of three; ll_up0h adds
+    // it to the upsampled level-2 tile (so it needs fuse2).  Per 4K frame 16.6 MB less written, as much less read and no level-2 tap
+    // gathers in ll_up0h — for 16 KB of level-2 rings + 6 KB of published rows in ll_down01e's LDS, ~8 % more arithmetic there
+    // and strips one or two lanes narrower.  On a frame queue the sum counts: one ll_down01e workgroup and THREE of ll_up0h share
+    // a CU (losing the third costs 3-9 %), so an unset switch means on only where d0.lds + 3 x up0_lds fits the CU's 160 KB — both
+    // sizes as the CU hands them out, in granules of 1280 bytes (320 dwords: the AMDGPU backend's figure for the parts with 160 KB)
+    // — with the largest RU (rows per ll_up0h wave, a multiple of 4, when the caller set none) at which it does: 24 at 4K
+    // (102 400 + 3 x 19 200 = 160 000 bytes; 28: 167 680).  The stream that owns the device keeps the three planes: it needs two
+    // ll_down01e workgroups per CU.  HLMI_LL_EMIT1 = 1: on for any stream whatever the budget, 0: off.  Measurements:
+    // profiles/NOTES.md, profiles/r16_emit1_speed_ab.txt.
+    constexpr bool kEmit1Default = true;   // an unset switch means "on, on a frame queue, where it fits"
+    constexpr size_t kCuLds = 160 * 1024, kLdsGranule = 1280;   // gfx950
+    constexpr int WPB = D0_THREADS / 64;
+    auto lds_alloc = [](size_t bytes) { return (bytes + kLdsGranule - 1) / kLdsGranule * kLdsGranule; };
+    auto up0h_lds = [](int ru) { return sizeof(float) * ((size_t)U0_TS * (ru + 2) + (size_t)U0H_T2 * (ru / 2 + 4)); };
+    // ll_down01e's LDS: the table, the level-1 -> 2 window state of the four waves and the published rows of three, the EM1 part
+    const size_t d01_lds_exch = sizeof(float) * ((nlut + 1) & ~1) + sizeof(float2) * D01_STATE * (2 * WPB - 1);
+    pl.emit1 = false;
+    {
+        const int e1 = sw.emit1.value_or(-1);
+        if (pl.fuse2 && (e1 > 0 || (e1 < 0 && partitioned && kEmit1Default))) {
+            const size_t d0 = lds_alloc(d01_lds_exch + d01_em1_lds_bytes());
+            auto fits = [&](int ru) { return d0 + 3 * lds_alloc(up0h_lds(ru)) <= kCuLds; };
+            int ru = RU;
+            if (partitioned && !sw.ru) {
+                ru &= ~3;
+                while (ru > 8 && !fits(ru)) ru -= 4;
+            }
+            pl.emit1 = e1 > 0 || fits(ru);
+            if (pl.emit1) RU = ru;
+        }
+    }
+    p.RU = RU;
     // levels 3 and 4 from level 2 in one launch (ll_down_strip2) when the chain would otherwise run ll_down_strip:2 and :3
     // (one stream: 111.6 -> 105.1 us per frame back to back, 123 -> 116.6 for one call + sync; four frame queues 75-77 -> 72-76)
     pl.strip2 = d01 && S == 4;
@@ -2617,7 +2809,6 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
     pl.ws_floats = ws_floats;
 
     // ---- launch geometry
-    constexpr int WPB = D0_THREADS / 64;
     if (!d01) {
         const Level &d = lv[1];
         // two waves per SIMD with (almost) equal row counts: the kernel is VALU-bound, so balance is what counts
@@ -2627,7 +2818,7 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
         pl.d0.lds = (lut_lds ? sizeof(float) * ((nlut + 1) & ~1) : 0) + sizeof(float2) * D0_THREADS * (KCH + 1);
     } else {
         const Level &e = lv[2];
-        const PairGeom pg = pl.d0.pg = pair_geom(lv[1], e);
+        const PairGeom pg = pl.d0.pg = pair_geom(lv[1], e, pl.emit1 ? (e.odd ? 1 : 2) : 0);
         // ll_down01f: sized for the whole device on every stream (fewer, taller units measured 2-3 % slower: 101.5 vs 98.9 us per
         // frame).  ll_down01e on a frame-queue stream (several frames in flight, the launches of different frames fill the device
         // together): fewer and taller units — fewer seam rows walked twice, less per-workgroup set-up — measure 10 % more frames
@@ -2656,7 +2847,8 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
             pl.d0.nsy = max(1, min(max(target2 / pg.nsx, (e.h + 31) / 32), e.h));
             pl.d0.nunits = pg.nsx * pl.d0.nsy;
         }
-        size_t sh2 = sizeof(float) * ((nlut + 1) & ~1) + sizeof(float2) * D01_STATE * (WPB + (exch ? WPB - 1 : 0));
+        size_t sh2 = sizeof(float) * ((nlut + 1) & ~1) + sizeof(float2) * D01_STATE * (WPB + (exch ? WPB - 1 : 0));   // exch: d01_lds_exch
+        if (pl.emit1) sh2 += d01_em1_lds_bytes();   // over half a CU's LDS by itself when exch: the pad below adds nothing then
         // With frames in flight (a frame-queue stream) ll_down01e asks for so much LDS that only ONE of its workgroups fits a
         // CU (2 x 77 KB would): the other half of the CU's registers and 77 KB of its LDS stay free for the workgroups of the
         // OTHER frames' kernels — ll_up0h above all, which waits for memory while this one computes.  Four frames in flight,
@@ -2787,14 +2979,18 @@ int ll_stage_down0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t s
     dim3 grid((a.nunits + WPB - 1) / WPB);
     if (pl.emit) {
         // input read once; outLPyramid[0] (4 B per output pixel), three level-1 planes and K + 1 level-2 planes written
-        timing_note_bytes(6.0 * iw * (gm.iy1 - gm.iy0 + 1) + 4.0 * iw * f.oh + 4.0 * 3.0 * d.w * d.h + 4.0 * (levels + 1) * e.w * e.h);
+        // (emit1: one level-1 plane, outLPyramid[1])
+        timing_note_bytes(6.0 * iw * (gm.iy1 - gm.iy0 + 1) + 4.0 * iw * f.oh + 4.0 * (pl.emit1 ? 1.0 : 3.0) * d.w * d.h +
+                          4.0 * (levels + 1) * e.w * e.h);
         D01EArgs ae;
         ae.d = a, ae.outl0 = b.outl0, ae.oy0 = f.oy0, ae.oh = f.oh;
         ae.nsx_magic = a.nsx == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)a.nsx + 1ull);
-        return with_flags([&](auto O0, auto O1, auto B, auto EX, auto NT) -> int {
-            HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0.value, O1.value, B.value, EX.value, NT.value>), grid, block, pl.d0.lds, ae, gm, lev);
+        ae.last2 = e.loy + e.h - 1;
+        return with_flags([&](auto O0, auto O1, auto B, auto EX, auto NT, auto E1) -> int {
+            HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0.value, O1.value, B.value, EX.value, NT.value, E1.value>), grid, block, pl.d0.lds, ae,
+                        gm, lev);
             return 0;
-        }, d.odd, e.odd, pl.b1, pl.d0.exch, pl.nt);
+        }, d.odd, e.odd, pl.b1, pl.d0.exch, pl.nt, pl.emit1);
     }
     timing_note_bytes(d0_bytes + 4.0 * (levels + 1) * e.w * e.h);
     return with_flags([&](auto O0, auto O1, auto B, auto EX) -> int {
@@ -2906,15 +3102,16 @@ int ll_stage_up0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st)
     if (pl.emit) {
         // input read + output written (u16 x 3 channels), outLPyramid[0] read, three planes of level 1, per level-2 pixel two
         // planes of g_2 + outG_2
-        timing_note_bytes(2.0 * (3 + nc) * ow * oh + 4.0 * ow * oh + 4.0 * 3.0 * n1 + 4.0 * 3.0 * n2);
+        // (emit1: one plane of level 1, outLPyramid[1])
+        timing_note_bytes(2.0 * (3 + nc) * ow * oh + 4.0 * ow * oh + 4.0 * (pl.emit1 ? 1.0 : 3.0) * n1 + 4.0 * 3.0 * n2);
         Up0HArgs ph;
         ph.u = p, ph.outl0 = b.outl0, ph.l0_ws = gm.ix1 - gm.ix0 + 1;
         ph.fuse2 = pl.fuse2 ? 1 : 0;
         ph.g3 = b.g[3], ph.out3 = b.outg[3], ph.lox3 = lv[3].lox, ph.loy3 = lv[3].loy, ph.ws3 = lv[3].ws, ph.ps3 = lv[3].ps;
-        return with_flags([&](auto NT) -> int {
-            HLMI_LAUNCH(uc, "ll_up0", st, ll_up0h<NT.value>, grid, block, pl.up0_lds, ph, gm);
+        return with_flags([&](auto NT, auto E1) -> int {
+            HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0h<NT.value, E1.value>), grid, block, pl.up0_lds, ph, gm);
             return 0;
-        }, pl.nt);
+        }, pl.nt, pl.emit1);
     }
     // input read + output written (u16 x nc channels), 2 selected planes of g_1 read; unfused: + outG_1 read;
     // fused: + inG_1 and, per level-2 pixel, 2 planes of g_2 + outG_2
@@ -3094,7 +3291,13 @@ extern "C" int hlmi_debug_local_laplacian_outg(int level, float *dst, int cap_fl
     if (level == 1 && c.out1_pending) {
         // the fused ll_up0f / ll_up0h kept outGPyramid[1] in LDS: produce the plane now with the stand-alone kernel (its inputs are
         // still in the arena) so that the tests can compare every level
-        if (!collapse(1, c.pl.emit)) return -1;   // emit: level 1 holds its three planes only (ll_down01e)
+        if (c.pl.emit1) {   // level 1 holds outLPyramid[1] only: outGPyramid[2] upsampled plus the stored plane
+            const UpArgs ua = up_args(c.pl, c.b, 1);
+            hipLaunchKernelGGL(ll_up_outl, dim3((ua.rw + 255) / 256, ua.rh), dim3(256), 0, c.stream, ua);
+            if (hipGetLastError() != hipSuccess) return -1;
+        } else if (!collapse(1, c.pl.emit)) {   // emit: level 1 holds its three planes only (ll_down01e)
+            return -1;
+        }
         c.out1_pending = false;
     }
     if (hipStreamSynchronize(c.stream) != hipSuccess) return -1;
