@@ -545,6 +545,51 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
                 emit(name, f"apps/hexagon_benchmarks {name}, u8 {W}x{H}, noise" + (", the driver's mask" if m is not None else ""), t, W * H, "hbm",
                      nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
 
+    # ---- mat_mul: the f32 product at 1024^2 (the size apps/cuda_mat_mul builds and its runner times beside cuBLAS) and, in the same
+    #      line under "size_4096", at 4096^2.  2 n^3 flops against the f32 matrix-core peak.  Beside each: the same call with one
+    #      thread per output (hlmi_mat_mul_general), which the default path must beat or the plan may not choose it, and torch.mm on
+    #      the same operands in the same run, the runner's vendor-BLAS column: recorded, not thresholded.  torch.mm is not bound to the
+    #      chain order, so its bits may differ from mat_mul's.
+    if not only or "mat_mul" in only:
+        import torch   # this block only: the runner's BLAS column
+        fields = {}
+        for n in (1024, 4096):
+            A, B = (rng.random((n, n), dtype=np.float32) * 2 - 1 for _ in range(2))
+            a, b, o = hl.Buffer(A), hl.Buffer(B), hl.Buffer(np.zeros((n, n), np.float32))
+            a.copy_to_device(), b.copy_to_device()
+            call = (lambda: hl.mat_mul(a, b, o)) if n == 1024 else (lambda n=n: hl.mat_mul_sized(n, a, b, o))
+            general = lambda n=n: hl.debug_mat_mul_general(n, a, b, o)
+            iters = 200 if n == 1024 else 10
+            t = timed(call, o, iters)
+            clock = last_clock[0]
+            tg = timed(general, o, max(2, iters // 10))
+            ta, tb_ = torch.from_numpy(A).cuda(), torch.from_numpy(B).cuda()
+            tm = 1e30
+            torch.mm(tb_, ta)
+            torch.cuda.synchronize()
+            for _ in range(args.samples):
+                t0 = time.perf_counter()
+                for _ in range(iters):
+                    torch.mm(tb_, ta)   # B @ A, as mat_mul
+                torch.cuda.synchronize()
+                tm = min(tm, (time.perf_counter() - t0) / iters)
+            del ta, tb_
+            last_clock[0] = clock
+            flops = 2.0 * n ** 3
+            k, kg = kernels(call, o), kernels(general, o)
+            fields[n] = {"ms_per_call": round(t * 1e3, 4), "tflops": round(flops / t / 1e12, 2), "mfma_frac": round(flops / t / 1e12 / MFMA_F32_PEAK_TF, 4),
+                         "alg_flops": flops, "alg_bytes": 12.0 * n * n, "kernels_ms": k,
+                         "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kg}, "fast_path_faster": bool(t < tg),
+                         "kernel_faster": bool(sum(k.values()) < sum(kg.values())),
+                         "torch_mm_ms": round(tm * 1e3, 4), "torch_mm_tflops": round(flops / tm / 1e12, 2),
+                         "torch_mm_note": "torch.mm(B, A) on the same f32 operands; not bound to the chain order, its bits may differ"}
+            if n == 1024:
+                t1024 = t
+        extra = {k_: v for k_, v in fields[1024].items() if k_ not in ("ms_per_call",)}
+        extra["size_4096"] = fields[4096]
+        emit("mat_mul", "apps/cuda_mat_mul, f32 1024x1024 = B @ A as a k-ordered fmaf chain, noise in [-1, 1)", t1024, 1024 * 1024, "mfma",
+             2.0 * 1024 ** 3 / t1024 / 1e12, MFMA_F32_PEAK_TF, "TFLOP/s", extra)
+
     # ---- lens_blur u8 stereo pair 768x1280 (the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
     if not only or "lens_blur" in only:
         W, H = 768, 1280

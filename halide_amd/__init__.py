@@ -435,7 +435,7 @@ _fn = {name: _bind(name) for name in
         "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
        + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]
-       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"]}
+       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -739,6 +739,30 @@ def debug_hexagon_benchmarks_general(name: str, input, mask, output) -> int:
     fn.restype = C.c_int
     fn.argtypes = [C.c_char_p, _BP, _BP, _BP]
     return _check(fn(name.encode(), _as_ptr(input), _as_ptr(mask), _as_ptr(output)))
+
+
+def mat_mul(A, B, out) -> int:
+    """apps/cuda_mat_mul at the size the reference builds (1024): f32 [1024, 1024] x 2 -> f32, out(x, y) the k-ordered fmaf chain over
+    r of A(x, r) * B(r, y) from +0.  Dimension 0 is innermost: with row-major arrays out = B @ A, not A @ B."""
+    return _check(_fn["mat_mul"](_as_ptr(A), _as_ptr(B), _as_ptr(out)))
+
+
+def _mat_mul_hook(symbol):
+    fn = getattr(lib, symbol)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int32, _BP, _BP, _BP]
+    return fn
+
+
+def mat_mul_sized(size, A, B, out) -> int:
+    """mat_mul as the generator instantiated at another size, 1 .. 8192: the same shim, plan and rules, every buffer
+    [0, size) x [0, size) (csrc/hlmi_internal.h)."""
+    return _check(_mat_mul_hook("hlmi_mat_mul_sized")(int(size), _as_ptr(A), _as_ptr(B), _as_ptr(out)))
+
+
+def debug_mat_mul_general(size, A, B, out) -> int:
+    """Test and measurement hook: mat_mul_sized with one thread per output running a plain fmaf loop."""
+    return _check(_mat_mul_hook("hlmi_mat_mul_general")(int(size), _as_ptr(A), _as_ptr(B), _as_ptr(out)))
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

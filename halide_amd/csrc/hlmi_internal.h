@@ -413,6 +413,13 @@ extern "C" int hlmi_debug_compositing(int fn, const uint16_t *a, const uint8_t *
 // call: no mode is kept anywhere.
 extern "C" int hlmi_hexagon_benchmarks_general(const char *name, halide_buffer_t *input, halide_buffer_t *mask, halide_buffer_t *output);
 
+// mat_mul.hip: the generator instantiated at another `size` (1 .. 8192; mat_mul is hlmi_mat_mul_sized(1024, ...)): the same shim,
+// plan and rules, every buffer [0, size) x [0, size).  -8 for a size outside the range.
+extern "C" int hlmi_mat_mul_sized(int32_t size, halide_buffer_t *A, halide_buffer_t *B, halide_buffer_t *out);
+// mat_mul.hip: the same call with one thread per output running a plain fmaf loop, for the tests (default == general bit for bit)
+// and for bench_apps.py.  Per call: no mode is kept anywhere.
+extern "C" int hlmi_mat_mul_general(int32_t size, halide_buffer_t *A, halide_buffer_t *B, halide_buffer_t *out);
+
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;
     return (r != 0 && r < 0) ? q - 1 : q;

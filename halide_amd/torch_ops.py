@@ -351,6 +351,25 @@ def _conv3x3(name, input, mask):
     return out
 
 
+@torch.library.custom_op("hlmi::mat_mul", mutates_args=())
+def mat_mul(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """apps/cuda_mat_mul at any size 1 .. 8192: two (n, n) float32 tensors -> (n, n) float32, out[y][x] the k-ordered fmaf chain over
+    r of A[r][x] * B[y][r] from +0.  Mathematically this is B @ A, NOT A @ B: tensor axes are the Halide dimensions reversed, and the
+    generator writes out(x, y) += A(x, r) * B(r, y)."""
+    for t in (A, B):
+        if t.dim() != 2 or t.shape[0] != t.shape[1] or t.dtype != torch.float32:
+            raise TypeError("mat_mul takes two square float32 tensors")
+    if A.shape != B.shape:
+        raise TypeError("mat_mul takes two tensors of one size")
+    n = A.shape[0]
+    if not 1 <= n <= 8192:
+        raise TypeError("mat_mul takes sizes 1 .. 8192")
+    out = torch.empty((n, n), dtype=torch.float32, device=A.device)
+    with _Wrapped(A, B, out) as (a, b, o):
+        hl.mat_mul_sized(n, a, b, o)
+    return out
+
+
 @torch.library.custom_op("hlmi::conv3x3a16", mutates_args=())
 def conv3x3a16(input: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """apps/hexagon_benchmarks: (H, W) uint8 under a (3, 3) int8 mask (mask[i][j] multiplies in(x + j - 1, y + i - 1)), the sum wrapped
@@ -486,6 +505,11 @@ def _(input):
 @compositing.register_fake
 def _(layers, ops):
     return layers[0].new_empty(tuple(layers[0].shape))
+
+
+@mat_mul.register_fake
+def _(A, B):
+    return A.new_empty(tuple(A.shape))
 
 
 @conv3x3a16.register_fake

@@ -409,6 +409,18 @@ HLMI_DECLARE_AUX(gaussian5x5)
 int sobel(struct halide_buffer_t *input, struct halide_buffer_t *output);
 HLMI_DECLARE_AUX(sobel)
 
+/* apps/cuda_mat_mul/mat_mul_generator.cpp:15-32,74 — the square f32 matrix product, built with size = 1024 as the reference builds it:
+ *   out(x, y) = acc_size,  acc_0 = +0.0f,  acc_{r+1} = fmaf(A(x, r), B(r, y), acc_r),  r = 0 .. size - 1
+ * Dimension 0 is innermost, so in memory out[y][x] = sum_r B[y][r] * A[r][x]: with row-major arrays this is B @ A, not A @ B.  The
+ * k-ordered fmaf chain is the contract in BOTH canonical float forms: both library builds give the same bits.  No step is padded (a
+ * chain may end in -0.0f), subnormals are kept, NaN in gives NaN out, Inf and overflow follow fmaf.
+ * A, B and out: float32, 2-D, min 0 and extent 1024 in both dimensions, stride 1 in dimension 0 (-8 otherwise); out may not alias an
+ * input (-8).  A superset of the reference in two respects: the stride of dimension 1 may be any value >= 1024 (the reference pins
+ * stride == size), and any element alignment is accepted (the reference asks for 16-byte host pointers).  A bounds query on any
+ * buffer fills all three with [0, 1024) x [0, 1024), dense.  No _auto_schedule twin: the reference builds none. */
+int mat_mul(struct halide_buffer_t *A, struct halide_buffer_t *B, struct halide_buffer_t *out);
+HLMI_DECLARE_AUX(mat_mul)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,

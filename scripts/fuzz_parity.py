@@ -543,6 +543,44 @@ def fuzz_hexagon_benchmarks(rng):
     return desc, same(got, want)
 
 
+def _f32_square(rng, n):
+    """(row stride in elements, byte offset of the first element) of an (n, n) float32 matrix: dense on 16 bytes, or with longer rows
+    (multiples of 4 elements and not) and a first element 0 .. 3 elements into its allocation"""
+    if rng.random() < 0.35:
+        return n, 0
+    return n + int(rng.choice([0, 4, 8, 1, 3, 5])), 4 * int(rng.integers(0, 4))
+
+
+def fuzz_mat_mul(rng):
+    """mat_mul at a random size 1 .. 200 (hlmi_mat_mul_sized) or on the one-thread-per-output path, A, B and out each with a row stride
+    and a pointer offset of their own, noise in [-1, 1) and in a third of the cases a handful of +-0, subnormals, +-Inf, NaN and
+    magnitudes whose products overflow, against tests/cpp/mat_mul_check.c (tests/mat_mul_checker.py).  Compared bit for bit, NaN for
+    NaN (sign and payload of a produced NaN belong to the processor); the bytes around `out` must come back unchanged."""
+    import mat_mul_checker as mm
+    from parity_helpers import DevArray
+    n = rdim(rng, 1, 200)
+    general = rng.random() < 0.3
+    A, B = (rng.random((n, n), dtype=f32) * 2 - 1 for _ in range(2))
+    special = rng.random() < 0.33
+    if special:
+        pool = np.array([0.0, -0.0, 1e-40, -3e-39, np.inf, -np.inf, np.nan, 3e38, -2e38, 2.0 ** 100, 2.0 ** -100], f32)
+        for m in (A, B):
+            k = int(rng.integers(1, 6))
+            m[rng.integers(0, n, k), rng.integers(0, n, k)] = rng.choice(pool, k)
+    la, lb, lo = (_f32_square(rng, n) for _ in range(3))
+    a, b, o = (DevArray(hl, (n, n), f32, lay[0], offset=lay[1], fill=m) for lay, m in ((la, A), (lb, B), (lo, None)))
+    want = mm.run(A, B)
+    try:
+        (hl.debug_mat_mul_general if general else hl.mat_mul_sized)(n, a.buf, b.buf, o.buf)
+        got = o.result()
+    finally:
+        a.free(), b.free(), o.free()
+    nan = np.isnan(want)
+    ok = got.shape == want.shape and bool(np.isnan(got[nan]).all()) and np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
+    desc = (f"mat_mul{' general' if general else ''} n {n}{' special values' if special else ''}, (row stride, byte offset) A {la} B {lb} out {lo}")
+    return desc, ok
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
@@ -550,6 +588,7 @@ CASES["linear_blur"] = fuzz_linear_blur   # both entry points
 CASES["wavelet"] = fuzz_wavelet   # all four entry points; its checker has a module of its own (tests/wavelet_checker.py)
 CASES["compositing"] = fuzz_compositing   # integer throughout: its checker (tests/compositing_checker.py) has no canonical form
 CASES["hexagon_benchmarks"] = fuzz_hexagon_benchmarks   # all six entry points; integer throughout (tests/hexagon_benchmarks_checker.py)
+CASES["mat_mul"] = fuzz_mat_mul   # sized and general paths; one chain in both canonical forms (tests/mat_mul_checker.py)
 
 
 def stress(args, only):
