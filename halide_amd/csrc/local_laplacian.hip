@@ -25,6 +25,8 @@
 //                   (on a frame queue, <.., EM1>: ONE plane of level 1, outLPyramid[1]; ll_up0h<.., EM1> adds it to its level-2 tile)
 //   ll_down_strip2  levels 3 and 4 from level 2 in one launch (round 5; ll_down_strip = one level per launch, other chains)
 //   ll_down_multi   levels 5..7 from level 4 in one launch;  ll_up_multi: outGPyramid[3] from levels 3..7 in one launch
+//                   (on a frame queue, chain_fit: the FIT instances of these three — at most 56 VGPRs, what a CU has left beside one
+//                   ll_down01e and three ll_up0h workgroups; the same operations with fewer loads in flight)
 //   ll_up0h         outGPyramid[2] and outGPyramid[1] (LDS tiles) -> outGPyramid[0] = upsample + outLPyramid[0] -> recolour -> u16 store
 //                   (HLMI_LL_FUSE_UP2=0: outGPyramid[2] by an ll_up launch of its own)
 // Everything else (other `levels`, odd widths or strides, fewer channels, odd output origins) takes the general kernels:
@@ -115,8 +117,49 @@ struct ResidencyProbe {
     }
 };
 #define LL_RESIDENCY(kind) ResidencyProbe residency_probe_(kind)
+// The three short launches between the two big kernels (chain 0 .. 2 = ll_down_strip2, ll_down_multi, ll_up_multi) do not count
+// themselves in: a workgroup records how many ll_down01e and ll_up0h workgroups its CU held when it started
+// (g_chain_hist[chain][kind][min(resident, 3)]) and, per launch, how long after the first workgroup the last one started
+// (g_chain_span[chain] = launches, sum and maximum in 10 ns ticks).  A launch is told from the same kernel's launches on the other
+// frame queues by `key`, a pointer into the queue's own workspace; launches of one queue follow each other, so a queue's count
+// of started workgroups modulo the grid is the workgroup's rank in its launch.  hlmi_debug_ll_chain_residency reads and clears.
+__device__ unsigned long long g_chain_hist[3][2][4], g_chain_span[3][3], g_chain_first[3][16], g_chain_key[16];
+__device__ unsigned g_chain_count[3][16];
+__device__ __forceinline__ void chain_probe(int chain, const void *key, unsigned nwg) {
+    if (threadIdx.x != 0) return;
+    const unsigned long long t = wall_clock64();
+    unsigned hw, xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+    const int slot = (int)(((xcc & 0xfu) << 8) | ((hw >> 8) & 0xffu));
+    for (int kind = 0; kind < 2; kind++) atomicAdd(&g_chain_hist[chain][kind][min(atomicAdd(&g_res[kind][slot], 0), 3)], 1ull);
+    int q = 0;
+    for (; q < 15; q++) {
+        const unsigned long long was = atomicCAS(&g_chain_key[q], 0ull, (unsigned long long)key);
+        if (was == 0ull || was == (unsigned long long)key) break;
+    }
+    const unsigned rank = atomicAdd(&g_chain_count[chain][q], 1u) % nwg;
+    if (rank == 0) atomicExch(&g_chain_first[chain][q], t);
+    if (rank == nwg - 1) {
+        const unsigned long long first = atomicAdd(&g_chain_first[chain][q], 0ull), span = t > first ? t - first : 0ull;
+        atomicAdd(&g_chain_span[chain][0], 1ull), atomicAdd(&g_chain_span[chain][1], span), atomicMax(&g_chain_span[chain][2], span);
+    }
+}
+#define LL_CHAIN_RESIDENCY(chain, key) chain_probe(chain, key, gridDim.x)
 #else
 #define LL_RESIDENCY(kind)
+#define LL_CHAIN_RESIDENCY(chain, key)
+#endif
+
+// HLMI_LL_CHAIN_PRIO=<0..3> (compile-time, `make VARIANT=_cp3 EXTRA=-DHLMI_LL_CHAIN_PRIO=3`): s_setprio at the top of the three chain
+// kernels, whose waves share their SIMDs with ll_down01e's and ll_up0h's while other frames are in flight.  0: none.
+#ifndef HLMI_LL_CHAIN_PRIO
+#define HLMI_LL_CHAIN_PRIO 0
+#endif
+#if HLMI_LL_CHAIN_PRIO
+#define LL_CHAIN_PRIO() __builtin_amdgcn_s_setprio(HLMI_LL_CHAIN_PRIO)
+#else
+#define LL_CHAIN_PRIO()
 #endif
 
 struct Geometry {
@@ -1563,8 +1606,14 @@ struct Strip2Args {
     size_t ps2;
     int Pbase, S2, nsx, nsy, nunits;   // nunits = planes * nsx * nsy
 };
-template<bool ODD0, bool ODD1>
+// FIT (the plan's chain_fit): the instance that fits the 56 registers per lane a CU has left beside one ll_down01e and three ll_up0h
+// workgroups.  It requests S2_FIT_NSRC of the unit's rows up front and the rest two at a time, into the registers of the two rows a
+// step has just consumed: the same loads and the same operations in the same order on the same values, fewer of them in flight.
+constexpr int S2_FIT_NSRC = 8, S2_FIT_NSRC_ODD = 7;   // (ODD0 instances need three registers more elsewhere)
+template<bool ODD0, bool ODD1, bool FIT = false>
 __global__ __launch_bounds__(256) void ll_down_strip2(Strip2Args p) {
+    LL_CHAIN_PRIO();
+    LL_CHAIN_RESIDENCY(0, p.g1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int unit = xcd_block() * 4 + wave;
     if (unit >= p.nunits) return;
@@ -1582,27 +1631,57 @@ __global__ __launch_bounds__(256) void ll_down_strip2(Strip2Args p) {
     const int off2 = X2 - p.so2;
     const bool st2_ok = (ODD1 ? lane < p.S2 : (lane >= 1 && lane <= p.S2)) && off2 >= 0 && off2 < p.w2;
     const float *sp = p.src + (size_t)plane * p.sps + qs.oq;
-    float4 r[S2_NSRC];                                   // level-j rows 2 T0 - 1 .. 2 T0 + 2 NT (clamped to the level's box)
+    constexpr int NR = !FIT ? S2_NSRC : ODD0 ? S2_FIT_NSRC_ODD : S2_FIT_NSRC;      // rows in flight; row i lives in r[i % NR]
+    float4 r[NR];                                        // level-j rows 2 T0 - 1 .. 2 T0 + 2 NT (clamped to the level's box)
+    const float *const su = p.src + (size_t)plane * p.sps;   // FIT addresses: a wave-uniform row pointer plus the lane's 32-bit byte offset
+    const uint32_t lane_off = 4u * (uint32_t)qs.oq;
+    auto request = [&](int i) {
+        const size_t row = (size_t)dev::clampi(2 * T0 - 1 + i - p.sloy, 0, p.sh - 1) * p.sws;
+        return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(su + row) + lane_off);
+    };
+    auto select = [&](float4 &v) {
+        v = make_float4(pick4(v.x, v.y, v.z, v.w, qs.sel[0]), pick4(v.x, v.y, v.z, v.w, qs.sel[1]),
+                        pick4(v.x, v.y, v.z, v.w, qs.sel[2]), pick4(v.x, v.y, v.z, v.w, qs.sel[3]));
+    };
+    if constexpr (FIT) {
 #pragma unroll
-    for (int i = 0; i < S2_NSRC; i++) r[i] = *reinterpret_cast<const float4 *>(sp + (size_t)dev::clampi(2 * T0 - 1 + i - p.sloy, 0, p.sh - 1) * p.sws);
-    if (edge_wave) {
+        for (int i = 0; i < NR; i++) r[i] = request(i);
+    } else {
 #pragma unroll
-        for (int i = 0; i < S2_NSRC; i++) {
-            const float4 v = r[i];
-            r[i] = make_float4(pick4(v.x, v.y, v.z, v.w, qs.sel[0]), pick4(v.x, v.y, v.z, v.w, qs.sel[1]),
-                               pick4(v.x, v.y, v.z, v.w, qs.sel[2]), pick4(v.x, v.y, v.z, v.w, qs.sel[3]));
+        for (int i = 0; i < S2_NSRC; i++) r[i] = *reinterpret_cast<const float4 *>(sp + (size_t)dev::clampi(2 * T0 - 1 + i - p.sloy, 0, p.sh - 1) * p.sws);
+        if (edge_wave) {
+#pragma unroll
+            for (int i = 0; i < S2_NSRC; i++) {
+                const float4 v = r[i];
+                r[i] = make_float4(pick4(v.x, v.y, v.z, v.w, qs.sel[0]), pick4(v.x, v.y, v.z, v.w, qs.sel[1]),
+                                   pick4(v.x, v.y, v.z, v.w, qs.sel[2]), pick4(v.x, v.y, v.z, v.w, qs.sel[3]));
+            }
         }
     }
     float *d1 = p.g1 + (size_t)plane * p.ps1 + off1, *d2 = p.g2 + (size_t)plane * p.ps2 + off2;
+    float *const u1 = p.g1 + (size_t)plane * p.ps1, *const u2 = p.g2 + (size_t)plane * p.ps2;   // FIT: uniform, + 4 off1 / 4 off2 per lane
     float2 s0 = make_float2(0.0f, 0.0f), s1 = s0, pc = s0;   // raw level-(j+1) rows T - 2 / T - 1 of the window; a + 3 (b + c)
 #pragma unroll
     for (int t = 0; t < S2_NT; t++) {
         const int T = T0 + t;
-        const float4 a = r[2 * t], b = r[2 * t + 1], c = r[2 * t + 2], d = r[2 * t + 3];
+        if (FIT && edge_wave) {  // the rows this step is the first to read
+#pragma unroll
+            for (int i = (t == 0 ? 0 : 2 * t + 2); i < 2 * t + 4; i++) select(r[i % NR]);
+        }
+        const float4 a = r[(2 * t) % NR], b = r[(2 * t + 1) % NR], c = r[(2 * t + 2) % NR], d = r[(2 * t + 3) % NR];
         const float dy[4] = {down4_raw(a.x, b.x, c.x, d.x), down4_raw(a.y, b.y, c.y, d.y), down4_raw(a.z, b.z, c.z, d.z),
                              down4_raw(a.w, b.w, c.w, d.w)};
+        if (FIT && 2 * t + NR < S2_NSRC) {   // rows 2 t and 2 t + 1 are done with
+            __builtin_amdgcn_sched_barrier(0);
+            r[(2 * t) % NR] = request(2 * t + NR);
+            if (2 * t + 1 + NR < S2_NSRC) r[(2 * t + 1) % NR] = request(2 * t + 1 + NR);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         const float2 res = hpair<ODD0>(dy);
-        if (T >= Ts0 && T <= Ts1 && st1_ok) *reinterpret_cast<float2 *>(d1 + (size_t)(T - p.loy1) * p.ws1) = res;
+        if (T >= Ts0 && T <= Ts1 && st1_ok) {
+            if constexpr (FIT) *reinterpret_cast<float2 *>(reinterpret_cast<char *>(u1 + (size_t)(T - p.loy1) * p.ws1) + 4u * (uint32_t)off1) = res;
+            else *reinterpret_cast<float2 *>(d1 + (size_t)(T - p.loy1) * p.ws1) = res;
+        }
         if ((t & 1) == 0) {      // third row of a level-(j+2) window (the first step's window is incomplete: its result is dropped)
             pc.x = dev::mad(3.0f, s1.x + res.x, s0.x);
             pc.y = dev::mad(3.0f, s1.y + res.y, s0.y);
@@ -1618,7 +1697,10 @@ __global__ __launch_bounds__(256) void ll_down_strip2(Strip2Args p) {
                 o = down4_tail(py, rx, ry, nx);
             }
             const int Y = (T - 2) >> 1;
-            if (T >= 2 * A + 2 && Y <= B && st2_ok) d2[(size_t)(Y - p.loy2) * p.ws2] = o;
+            if (T >= 2 * A + 2 && Y <= B && st2_ok) {
+                if constexpr (FIT) *reinterpret_cast<float *>(reinterpret_cast<char *>(u2 + (size_t)(Y - p.loy2) * p.ws2) + 4u * (uint32_t)off2) = o;
+                else d2[(size_t)(Y - p.loy2) * p.ws2] = o;
+            }
             s1 = res;
         }
     }
@@ -1722,6 +1804,11 @@ __host__ __device__ constexpr int dm_win(int depth_below) {  // window edge `dep
     for (int i = 0; i < depth_below; i++) w = 2 * w + 2;
     return w;
 }
+__host__ __device__ constexpr size_t dm_lds_bytes(int depth) {   // LDS of ll_down_multi<depth>: the windows the next level reads
+    size_t n = 0;
+    for (int below = 1; below < depth; below++) n += (size_t)dm_win(below) * dm_win(below);
+    return sizeof(float) * n;
+}
 struct Range2 { int x0, x1, y0, y1; };  // inclusive, absolute
 __device__ __forceinline__ Range2 clamp_to_box(const DevLevel &L, int x0, int x1, int y0, int y1) {
     Range2 r;
@@ -1729,7 +1816,7 @@ __device__ __forceinline__ Range2 clamp_to_box(const DevLevel &L, int x0, int x1
     r.y0 = dev::clampi(y0, L.loy, L.loy + L.h - 1), r.y1 = dev::clampi(y1, L.loy, L.loy + L.h - 1);
     return r;
 }
-template<int DEPTH>
+template<int DEPTH, bool FIT = false>   // FIT: 32-bit byte offsets from the plane's (workgroup-uniform) pointer, not a 64-bit address per tap
 __device__ __forceinline__ void down_multi_tile(const CoarseArgs &a, int ntx, int nty, int b) {   // b = tile x + ntx (tile y + nty plane)
     constexpr int W1 = dm_win(DEPTH - 1), W2 = DEPTH >= 2 ? dm_win(DEPTH - 2) : 1, W3 = DEPTH >= 3 ? dm_win(DEPTH - 3) : 1,
                   W4 = DEPTH >= 4 ? dm_win(DEPTH - 4) : 1;
@@ -1777,8 +1864,13 @@ __device__ __forceinline__ void down_multi_tile(const CoarseArgs &a, int ntx, in
                     for (int k = 0; k < 4; k++) {
                         const int qx = dev::clampi(2 * X[u] - 1 + i, Sx.lox, Sx.lox + Sx.w - 1);
                         const int qy = dev::clampi(2 * Y[u] - 1 + k, Sx.loy, Sx.loy + Sx.h - 1);
-                        r[u][i][k] = (d == 1) ? src_g[(size_t)(qy - Sx.loy) * Sx.ws + (qx - Sx.lox)]
-                                              : src_t[(qy - pw.y0) * pnx + (qx - pw.x0)];
+                        if (FIT && d == 1) {
+                            r[u][i][k] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(src_g) +
+                                                                          4u * (uint32_t)((qy - Sx.loy) * Sx.ws + (qx - Sx.lox)));
+                        } else {
+                            r[u][i][k] = (d == 1) ? src_g[(size_t)(qy - Sx.loy) * Sx.ws + (qx - Sx.lox)]
+                                                  : src_t[(qy - pw.y0) * pnx + (qx - pw.x0)];
+                        }
                     }
                 }
             }
@@ -1801,7 +1893,15 @@ __device__ __forceinline__ void down_multi_tile(const CoarseArgs &a, int ntx, in
 }
 template<int DEPTH>
 __global__ __launch_bounds__(256) void ll_down_multi(CoarseArgs a, int ntx, int nty) {
+    LL_CHAIN_PRIO();
+    LL_CHAIN_RESIDENCY(1, a.lv[1].g);
     down_multi_tile<DEPTH>(a, ntx, nty, (int)blockIdx.x);
+}
+template<int DEPTH>
+__global__ __launch_bounds__(256) void ll_down_multi_fit(CoarseArgs a, int ntx, int nty) {
+    LL_CHAIN_PRIO();
+    LL_CHAIN_RESIDENCY(1, a.lv[1].g);
+    down_multi_tile<DEPTH, true>(a, ntx, nty, (int)blockIdx.x);
 }
 
 // ---- ll_up_multi<TOP>: outGPyramid[S] on R_S from gPyramid / inGPyramid of levels S .. S+TOP (= J-1).
@@ -1820,9 +1920,10 @@ __host__ __device__ constexpr int um_off(int d) {  // offset of level S+d's regi
     for (int i = 0; i < d; i++) o += um_win(i) * um_win(i);
     return o;
 }
+__host__ __device__ constexpr size_t um_lds_bytes(int top) { return sizeof(float) * um_off(top + 1); }   // LDS of ll_up_multi<top>
 // up_multi_tile handles ONE element per thread and level (act[d] = tid < n): every region of a tile must fit 256 threads
 static_assert(UM_T * UM_T <= 256 && um_win(1) * um_win(1) <= 256, "ll_up_multi: a level's region of a tile exceeds the workgroup");
-template<int TOP>
+template<int TOP, bool FIT = false>
 __device__ __forceinline__ void up_multi_tile(const CoarseArgs &a, int ntx, int b) {
     __shared__ float tl[um_off(TOP + 1)];
     const int tx = b % ntx, ty = b / ntx;
@@ -1842,54 +1943,90 @@ __device__ __forceinline__ void up_multi_tile(const CoarseArgs &a, int ntx, int 
     //    gathers — two dependent round trips.  Round 5: THREE passes over all levels — request every inGPyramid value, then every
     //    gather, then combine — so that the tile pays the two round trips once, not once per level (the per-level loops this
     //    replaces ran them level after level: ten dependent trips).  outl_value's / top_value's operations in their order.
-    int eX[TOP + 1], eY[TOP + 1];
-    bool act[TOP + 1];
-    size_t eo[TOP + 1];
-    float lvl[TOP + 1];
-#pragma unroll
-    for (int d = 0; d <= TOP; d++) {
-        const DevLevel &L = a.lv[d];
-        const Range2 r = reg[d];
-        const int nx = r.x1 - r.x0 + 1, n = nx * (r.y1 - r.y0 + 1);
-        act[d] = (int)threadIdx.x < n;
-        const int e = act[d] ? (int)threadIdx.x : 0, yy = e / nx;   // idle threads re-read element 0 and store nothing
-        eX[d] = r.x0 + (e - yy * nx), eY[d] = r.y0 + yy;
-        eo[d] = (size_t)(eY[d] - L.loy) * L.ws + (eX[d] - L.lox);
-        lvl[d] = L.g[(size_t)a.K * L.ps + eo[d]];
-    }
-    __builtin_amdgcn_sched_barrier(0);   // (left alone the scheduler starts a level's gathers as soon as its first load is back)
-    float lf[TOP + 1], g0[TOP + 1], g1[TOP + 1];
-    int lis[TOP + 1];
-    UpTaps t0[TOP + 1], t1[TOP + 1];
-    auto planes_of = [&](int d) {
-        const float level = lvl[d] * a.Km1;
-        lis[d] = dev::clampi((int)level, 0, a.K - 2);
-        lf[d] = level - (float)lis[d];
+    //    FIT (the plan's chain_fit): the levels in two groups, the three passes per group — half the taps held at once.
+    //    Its loads take a 32-bit byte offset from the level's (uniform) pointer instead of a 64-bit address each.
+    auto at = [](const float *g, size_t o) -> float {
+        if constexpr (FIT) return *reinterpret_cast<const float *>(reinterpret_cast<const char *>(g) + 4u * (uint32_t)o);
+        else return g[o];
     };
+    auto levels_lo_hi = [&](auto lo_c, auto hi_c) {
+        constexpr int LO = decltype(lo_c)::value, HI = decltype(hi_c)::value, N = HI - LO + 1;
+        int eX[N], eY[N];
+        bool act[N];
+        size_t eo[N];
+        float lvl[N];
 #pragma unroll
-    for (int d = 0; d <= TOP; d++) {
-        const DevLevel &L = a.lv[d];
-        planes_of(d);
-        const int li = lis[d];
-        g0[d] = L.g[(size_t)li * L.ps + eo[d]], g1[d] = L.g[(size_t)(li + 1) * L.ps + eo[d]];
-        if (d < TOP) {
-            const DevLevel &C = a.lv[d + 1];
-            t0[d] = up_taps(C.g + (size_t)li * C.ps, C.lox, C.loy, C.ws, eX[d], eY[d]);
-            t1[d] = up_taps(C.g + (size_t)(li + 1) * C.ps, C.lox, C.loy, C.ws, eX[d], eY[d]);
+        for (int d = LO; d <= HI; d++) {
+            const int i = d - LO;
+            const DevLevel &L = a.lv[d];
+            const Range2 r = reg[d];
+            const int nx = r.x1 - r.x0 + 1, n = nx * (r.y1 - r.y0 + 1);
+            act[i] = (int)threadIdx.x < n;
+            const int e = act[i] ? (int)threadIdx.x : 0, yy = e / nx;   // idle threads re-read element 0 and store nothing
+            eX[i] = r.x0 + (e - yy * nx), eY[i] = r.y0 + yy;
+            eo[i] = (size_t)(eY[i] - L.loy) * L.ws + (eX[i] - L.lox);
+            lvl[i] = at(L.g, (size_t)a.K * L.ps + eo[i]);
         }
-    }
-    __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);   // (left alone the scheduler starts a level's gathers as soon as its first load is back)
+        float lf[N], g0[N], g1[N];
+        int lis[N];
+        UpTaps t0[N], t1[N];
+        auto planes_of = [&](int i) {
+            const float level = lvl[i] * a.Km1;
+            lis[i] = dev::clampi((int)level, 0, a.K - 2);
+            lf[i] = level - (float)lis[i];
+        };
 #pragma unroll
-    for (int d = 0; d <= TOP; d++) {
-        float v;
-        if (d == TOP) {
-            v = dev::mad2(1.0f - lf[d], g0[d], lf[d], g1[d]);
-        } else {
-            const float l0 = g0[d] - up_from(t0[d], eX[d], eY[d]);
-            const float l1 = g1[d] - up_from(t1[d], eX[d], eY[d]);
-            v = dev::mad2(1.0f - lf[d], l0, lf[d], l1);
+        for (int d = LO; d <= HI; d++) {
+            const int i = d - LO;
+            const DevLevel &L = a.lv[d];
+            planes_of(i);
+            const int li = lis[i];
+            g0[i] = at(L.g, (size_t)li * L.ps + eo[i]), g1[i] = at(L.g, (size_t)(li + 1) * L.ps + eo[i]);
+            if (d < TOP) {
+                const DevLevel &C = a.lv[d + 1];
+                if constexpr (FIT) {
+                    const int xa = dev::fdiv2(eX[i] + 1) - C.lox, xb = dev::fdiv2(eX[i] - 1) - C.lox;   // up_taps
+                    const int ya = dev::fdiv2(eY[i] + 1) - C.loy, yb = dev::fdiv2(eY[i] - 1) - C.loy;
+                    const size_t p0 = (size_t)li * C.ps, p1 = (size_t)(li + 1) * C.ps;
+                    t0[i].aa = at(C.g, p0 + ya * C.ws + xa), t0[i].ab = at(C.g, p0 + ya * C.ws + xb);
+                    t0[i].ba = at(C.g, p0 + yb * C.ws + xa), t0[i].bb = at(C.g, p0 + yb * C.ws + xb);
+                    t1[i].aa = at(C.g, p1 + ya * C.ws + xa), t1[i].ab = at(C.g, p1 + ya * C.ws + xb);
+                    t1[i].ba = at(C.g, p1 + yb * C.ws + xa), t1[i].bb = at(C.g, p1 + yb * C.ws + xb);
+                } else {
+                    t0[i] = up_taps(C.g + (size_t)li * C.ps, C.lox, C.loy, C.ws, eX[i], eY[i]);
+                    t1[i] = up_taps(C.g + (size_t)(li + 1) * C.ps, C.lox, C.loy, C.ws, eX[i], eY[i]);
+                }
+            }
         }
-        if (act[d]) (tl + um_off(d))[(eY[d] - reg[d].y0) * um_win(d) + (eX[d] - reg[d].x0)] = v;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int d = LO; d <= HI; d++) {
+            const int i = d - LO;
+            float v;
+            if (d == TOP) {
+                v = dev::mad2(1.0f - lf[i], g0[i], lf[i], g1[i]);
+            } else {
+                const float l0 = g0[i] - up_from(t0[i], eX[i], eY[i]);
+                const float l1 = g1[i] - up_from(t1[i], eX[i], eY[i]);
+                v = dev::mad2(1.0f - lf[i], l0, lf[i], l1);
+            }
+            if (act[i]) (tl + um_off(d))[(eY[i] - reg[d].y0) * um_win(d) + (eX[i] - reg[d].x0)] = v;
+        }
+    };
+    if constexpr (FIT && TOP >= 5) {   // (instances only HLMI_LL_UPCHAIN_FROM reaches: three groups)
+        levels_lo_hi(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        levels_lo_hi(std::integral_constant<int, 2>{}, std::integral_constant<int, 3>{});
+        __builtin_amdgcn_sched_barrier(0);
+        levels_lo_hi(std::integral_constant<int, 4>{}, std::integral_constant<int, TOP>{});
+    } else if constexpr (FIT) {
+        constexpr int GS = (TOP + 1) / 2;
+        levels_lo_hi(std::integral_constant<int, 0>{}, std::integral_constant<int, GS - 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        levels_lo_hi(std::integral_constant<int, GS>{}, std::integral_constant<int, TOP>{});
+    } else {
+        levels_lo_hi(std::integral_constant<int, 0>{}, std::integral_constant<int, TOP>{});
     }
     __syncthreads();
     // 2. collapse: level S+d from level S+d+1 (both in LDS), operation order of up_at
@@ -1920,7 +2057,15 @@ __device__ __forceinline__ void up_multi_tile(const CoarseArgs &a, int ntx, int 
 }
 template<int TOP>
 __global__ __launch_bounds__(256) void ll_up_multi(CoarseArgs a, int ntx) {
+    LL_CHAIN_PRIO();
+    LL_CHAIN_RESIDENCY(2, a.lv[0].out);
     up_multi_tile<TOP>(a, ntx, (int)blockIdx.x);
+}
+template<int TOP>
+__global__ __launch_bounds__(256) void ll_up_multi_fit(CoarseArgs a, int ntx) {
+    LL_CHAIN_PRIO();
+    LL_CHAIN_RESIDENCY(2, a.lv[0].out);
+    up_multi_tile<TOP, true>(a, ntx, (int)blockIdx.x);
 }
 
 // Measured and not kept (round 6, git a068ebd, profiles/r06_ll_mid_ab.txt, profiles/NOTES.md): ll_down_multi and ll_up_multi as ONE
@@ -2579,8 +2724,14 @@ const ArgTable ll_table("local_laplacian", {
 //   EMIT1         on a frame queue where d0.lds + 3 x       ll_down01e stores outLPyramid[1] as ONE plane   tests/test_local_laplacian_outl1.py
 //                 up0_lds <= 160 KB (RU, when unset, is     of level 1 instead of three, ll_up0h adds it
 //                 chosen to fit: 24); otherwise off         (1: on any stream, whatever the budget; 0: off)
+//   CHAIN_FIT     on where EMIT1 is on and the CU has the   ll_down_strip2 / ll_down_multi / ll_up_multi     tests/test_local_laplacian_chain.py
+//                 LDS left (see ll_plan); otherwise off     instances of at most 56 VGPRs, which fit beside
+//                                                           one ll_down01e and three ll_up0h workgroups
+//                                                           (1: on any stream, whatever the budget; 0: off)
+// Compile-time (csrc/Makefile EXTRA): HLMI_LL_CHAIN_PRIO (0) — s_setprio at the top of the three chain kernels; the whole GPU suite
+// runs on such a build through HLMI_LIB.
 struct LlSwitches {
-    std::optional<int> fuse_from, upchain_from, ru, units0, no_vec, emit, nt, fuse_up2, d01_exch, d01_pad_lds, no_lut_cache, emit1;
+    std::optional<int> fuse_from, upchain_from, ru, units0, no_vec, emit, nt, fuse_up2, d01_exch, d01_pad_lds, no_lut_cache, emit1, chain_fit;
 };
 LlSwitches ll_switches() {
     const auto get = env_int;
@@ -2589,7 +2740,7 @@ LlSwitches ll_switches() {
     s.ru = get("HLMI_LL_RU"), s.units0 = get("HLMI_LL_UNITS0"), s.no_vec = get("HLMI_LL_NO_VEC");
     s.emit = get("HLMI_LL_EMIT"), s.nt = get("HLMI_LL_NT"), s.fuse_up2 = get("HLMI_LL_FUSE_UP2");
     s.d01_exch = get("HLMI_LL_D01_EXCH"), s.d01_pad_lds = get("HLMI_LL_D01_PAD_LDS"), s.no_lut_cache = get("HLMI_LL_NO_LUT_CACHE");
-    s.emit1 = get("HLMI_LL_EMIT1");
+    s.emit1 = get("HLMI_LL_EMIT1"), s.chain_fit = get("HLMI_LL_CHAIN_FIT");
     return s;
 }
 
@@ -2625,6 +2776,7 @@ struct LlPlan {
     bool emit1;        // level 1 is stored as ONE plane, outLPyramid[1] (ll_down01e / ll_up0h <.., EM1>), not as three
     bool d01;         // levels 1 and 2 in one walk of the input (ll_down01e / ll_down01f), no ll_down_strip:1
     bool strip2;       // levels 3 and 4 in one launch (ll_down_strip2), no ll_down_strip:2 / :3
+    bool chain_fit;    // ll_down_strip2, ll_down_multi and ll_up_multi run their <= 56-VGPR instances
     // launch geometry
     struct { PairGeom pg; bool exch; int nsy, nunits; size_t lds; } d0;   // ll_down0, or (d01: pg, exch) ll_down01e / ll_down01f
     struct { PairGeom pg; int nsy, nunits; } s2;                          // ll_down_strip2 (strip2)
@@ -2872,6 +3024,20 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
     pl.up0_lds = emit   ? sizeof(float) * ((size_t)U0_TS * (RU + 2) + (size_t)U0H_T2 * (RU / 2 + 4))
                  : fast ? lut_sh + (fuse1 ? ((lut_lds && (nlut & 1)) ? 4 : 0) + sizeof(float) * U0_TS * (RU + 2) : 0)
                         : lut_sh;
+    // chain_fit: with frames in flight the three short launches between the two big kernels find their CUs full — one ll_down01e
+    // workgroup (312 VGPRs allocated) and three of ll_up0h (3 x 48) leave 512 - 456 = 56 registers per lane, and of the LDS what
+    // d0.lds + 3 x up0_lds leave of 160 KB (3 840 bytes at 4K) — and wait for an ll_up0h workgroup or two to leave first.  Their
+    // FIT instances keep within 56 VGPRs (no AGPRs, no scratch: `make resources` prints every instance's) by having less in
+    // flight at once; the plan picks them where the LDS of ll_down_multi and ll_up_multi fits that rest too.  An unset switch
+    // means on where emit1 is on (a frame queue): the stream that owns the device has no such neighbours and keeps the instances
+    // that request everything at once.  HLMI_LL_CHAIN_FIT = 1: on for any stream whatever the budget, 0: off.  (The instances
+    // address a level's planes by 32-bit byte offsets: never on where the K + 1 planes of a level could exceed them.)
+    {
+        const int cf = (double)(levels + 1) * (4.0 * (double)lv[1].ps) < 4.0e9 ? sw.chain_fit.value_or(-1) : 0;
+        const size_t taken = lds_alloc(pl.d0.lds) + 3 * lds_alloc(pl.up0_lds);
+        const size_t need = max(S < J - 1 ? lds_alloc(dm_lds_bytes(J - 1 - S)) : (size_t)0, SU < J - 1 ? lds_alloc(um_lds_bytes(J - 1 - SU)) : (size_t)0);
+        pl.chain_fit = cf > 0 || (cf < 0 && pl.emit1 && partitioned && taken + need <= kCuLds);
+    }
 }
 
 // last call's plan and pointers, for hlmi_debug_local_laplacian_outg (tests only)
@@ -3012,10 +3178,10 @@ int ll_stage_down_rest(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream
         a.S2 = pl.s2.pg.S2, a.Pbase = pl.s2.pg.Pbase, a.nsx = pl.s2.pg.nsx, a.nsy = pl.s2.nsy, a.nunits = pl.s2.nunits;
         timing_note_bytes(4.0 * (levels + 1) * ((double)sl.w * sl.h + (double)d.w * d.h + (double)e.w * e.h));
         dim3 grid((a.nunits + 3) / 4), block(256);
-        if (int r = with_flags([&](auto O0, auto O1) -> int {
-                HLMI_LAUNCH(uc, "ll_down_strip2:2", st, (ll_down_strip2<O0.value, O1.value>), grid, block, 0, a);
+        if (int r = with_flags([&](auto O0, auto O1, auto F) -> int {
+                HLMI_LAUNCH(uc, "ll_down_strip2:2", st, (ll_down_strip2<O0.value, O1.value, F.value>), grid, block, 0, a);
                 return 0;
-            }, d.odd, e.odd)) return r;
+            }, d.odd, e.odd, pl.chain_fit)) return r;
     }
     for (int j = 1; j + 1 < J; j++) {
         if (pl.strip2 && (j == 2 || j == 3)) continue;
@@ -3028,10 +3194,12 @@ int ll_stage_down_rest(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream
             char nm[32];
             snprintf(nm, sizeof nm, "ll_down_multi:%d", S);
             timing_note_bytes(4.0 * ((double)(levels + 1) * lv[S].w * lv[S].h + (double)total));
-            if (J - 1 - S == 4) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<4>), grid, block, 0, ca, ntx, nty);
-            else if (J - 1 - S == 3) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<3>), grid, block, 0, ca, ntx, nty);
-            else if (J - 1 - S == 2) HLMI_LAUNCH(uc, nm, st, (ll_down_multi<2>), grid, block, 0, ca, ntx, nty);
-            else HLMI_LAUNCH(uc, nm, st, (ll_down_multi<1>), grid, block, 0, ca, ntx, nty);
+            switch ((J - 1 - S) * 2 + (pl.chain_fit ? 1 : 0)) {
+#define LL_DM(D) case 2 * D: HLMI_LAUNCH(uc, nm, st, (ll_down_multi<D>), grid, block, 0, ca, ntx, nty); break; \
+                 case 2 * D + 1: HLMI_LAUNCH(uc, nm, st, (ll_down_multi_fit<D>), grid, block, 0, ca, ntx, nty); break;
+                LL_DM(1) LL_DM(2) LL_DM(3) LL_DM(4)
+#undef LL_DM
+            }
             break;
         }
         if (j == 1 && pl.d01) continue;   // level 2 came out of ll_down01e / ll_down01f
@@ -3063,8 +3231,9 @@ int ll_stage_up_coarse(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream
             const double px = (double)cu.lv[0].rw * cu.lv[0].rh;
             timing_note_bytes(4.0 * 4.0 * px * (SU + 1 < J ? 4.0 / 3.0 : 1.0));
         }
-        switch (J - 1 - SU) {
-#define LL_UM(T) case T: HLMI_LAUNCH(uc, nm, st, (ll_up_multi<T>), grid, block, 0, cu, ntx); break;
+        switch ((J - 1 - SU) * 2 + (pl.chain_fit ? 1 : 0)) {
+#define LL_UM(T) case 2 * T: HLMI_LAUNCH(uc, nm, st, (ll_up_multi<T>), grid, block, 0, cu, ntx); break; \
+                 case 2 * T + 1: HLMI_LAUNCH(uc, nm, st, (ll_up_multi_fit<T>), grid, block, 0, cu, ntx); break;
             LL_UM(1) LL_UM(2) LL_UM(3) LL_UM(4) LL_UM(5) LL_UM(6)
 #undef LL_UM
         }
@@ -3226,6 +3395,24 @@ extern "C" int hlmi_debug_ll_residency(unsigned long long *out16) {
     return 1;
 #else
     (void)out16;
+    return 0;
+#endif
+}
+
+// Residency builds: the chain kernels' counters — out33[8 chain + 4 kind + n] = workgroups of chain kernel `chain` (0 .. 2 =
+// ll_down_strip2, ll_down_multi, ll_up_multi) that started beside min(n, 3) resident workgroups of `kind` (0 = ll_down01e, 1 =
+// ll_up0h); out33[24 + 3 chain ..] = its launches, the sum and the maximum of (last workgroup's start - first's) in 10 ns ticks.
+extern "C" int hlmi_debug_ll_chain_residency(unsigned long long *out33) {
+#if HLMI_LL_RESIDENCY
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out33, HIP_SYMBOL(g_chain_hist), sizeof(unsigned long long) * 24) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out33 + 24, HIP_SYMBOL(g_chain_span), sizeof(unsigned long long) * 9) != hipSuccess) return -1;
+    unsigned long long zero[24] = {};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_chain_hist), zero, sizeof(unsigned long long) * 24) != hipSuccess) return -1;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_chain_span), zero, sizeof(unsigned long long) * 9) != hipSuccess) return -1;
+    return 1;
+#else
+    (void)out33;
     return 0;
 #endif
 }
