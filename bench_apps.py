@@ -590,7 +590,99 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
         emit("mat_mul", "apps/cuda_mat_mul, f32 1024x1024 = B @ A as a k-ordered fmaf chain, noise in [-1, 1)", t1024, 1024 * 1024, "mfma",
              2.0 * 1024 ** 3 / t1024 / 1e12, MFMA_F32_PEAK_TF, "TFLOP/s", extra)
 
-    # ---- lens_blur u8 stereo pair 768x1280 (the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
+    # ---- linear_algebra: apps/linear_algebra's f32 BLAS subset.  "sgemm": the four variants at 768^3 and 1024^3, notrans at 4096^3 and
+    #      one rectangular notrans case, each beside its one-thread-per-output path (which the plan's choice must beat) and beside
+    #      hl.mat_mul_sized / torch.addmm on the same operands in the same run (recorded, not thresholded; neither is bound to the
+    #      contract's order).  "linear_algebra": sgemv (both) at 768, 4096 and 8192 and the vector routines and sger at 2^20 and 2^24
+    #      (sger: 1024^2 and 4096^2), time and fraction of the HBM roofline on moved bytes, beside the general path; for sdot, sasum and
+    #      sgemv_notrans the contract's chain length is in the line ("chain_steps"): time / steps is the latency per dependent step.
+    if not only or "sgemm" in only or "linear_algebra" in only:
+        import torch
+        F = np.float32
+        mk = lambda *s: (rng.random(s, dtype=F) * 2 - 1).astype(F)
+
+        def dev(m):
+            b = hl.Buffer(m)
+            b.copy_to_device()
+            return b
+
+    if not only or "sgemm" in only:
+        cases = [(ta, tb, n, n, n) for n in (768, 1024) for ta in (0, 1) for tb in (0, 1)] + [(0, 0, 4096, 4096, 4096), (0, 0, 4096, 512, 1024)]
+        for ta, tb, M, N, K in cases:
+            name = hl.sgemm_name(ta, tb)
+            A, B, Cm = dev(mk(K, M)), dev(mk(N, K)), dev(mk(N, M))
+            o = hl.Buffer(np.zeros((N, M), F))
+            big = M * N * K >= 2 ** 34
+            iters = 10 if big else 100
+            t = timed(lambda: hl.sgemm(ta, tb, 0.75, A, B, -1.5, Cm, o), o, iters)
+            clock = last_clock[0]
+            tg = timed(lambda: hl.debug_sgemm_general(ta, tb, 0.75, A, B, -1.5, Cm, o), o, max(2, iters // 10))
+            extra = {"general_ms_per_call": round(tg * 1e3, 4), "default_over_general": round(t / tg, 4), "canon_fma": hl.canon_fma()}
+            if M == N == K and not ta and not tb:
+                tm = timed(lambda: hl.mat_mul_sized(M, A, B, o), o, iters)
+                extra["mat_mul_ms_per_call"] = round(tm * 1e3, 4)
+                extra["c_read_ms_at_copy_rate"] = round(4.0 * M * N / ((copy_gbs[0] or HBM_PEAK_GBS) * 1e9) * 1e3, 4)
+            tA, tB, tC = (torch.from_numpy(x.array).cuda() for x in (A, B, Cm))
+            opA, opB = (tA if ta else tA.T), (tB if tb else tB.T)   # (M, K) and (K, N) in torch's terms
+            torch.addmm(tC.T, opA, opB, beta=-1.5, alpha=0.75)
+            torch.cuda.synchronize()
+            tt = 1e30
+            for _ in range(args.samples):
+                t0 = time.perf_counter()
+                for _ in range(iters):
+                    torch.addmm(tC.T, opA, opB, beta=-1.5, alpha=0.75)
+                torch.cuda.synchronize()
+                tt = min(tt, (time.perf_counter() - t0) / iters)
+            del tA, tB, tC, opA, opB
+            extra["torch_addmm_ms_per_call"] = round(tt * 1e3, 4)
+            last_clock[0] = clock
+            emit(f"sgemm_{name[13:]}_{M}x{N}x{K}", f"apps/linear_algebra {name}, M {M} N {N} K {K}, noise in [-1, 1), a 0.75 b -1.5", t, M * N, "mfma",
+                 2.0 * M * N * K / t / 1e12, MFMA_F32_PEAK_TF, "TFLOP/s", extra)
+            for x in (A, B, Cm, o):
+                x.device_free()
+
+    if not only or "linear_algebra" in only:
+        def line(label, what, call, general, sync, nbytes, outputs, iters, more=None):
+            t = timed(call, sync, iters)
+            clock = last_clock[0]
+            tg = timed(general, sync, max(1, iters // 10))
+            last_clock[0] = clock
+            extra = {"general_ms_per_call": round(tg * 1e3, 4), "default_over_general": round(t / tg, 4), "moved_bytes": nbytes, **(more or {})}
+            if "chain_steps" in extra:
+                extra["ns_per_chain_step"] = round(t * 1e9 / extra["chain_steps"], 3)
+            emit(label, what, t, outputs, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
+
+        G = hl.debug_linear_algebra_general
+        for n in (768, 4096, 8192):
+            A, x, y, o = dev(mk(n, n)), dev(mk(n)), dev(mk(n)), hl.Buffer(np.zeros(n, F))
+            nbytes = 4.0 * (n * n + 3 * n)
+            line(f"sgemv_notrans_{n}", f"apps/linear_algebra halide_sgemv_notrans, {n}x{n}", lambda: hl.sgemv(False, 0.75, A, x, -1.5, y, o),
+                 lambda: G("halide_sgemv_notrans", 0.75, A, x, -1.5, y, o), o, nbytes, n, 50, {"chain_steps": n})
+            line(f"sgemv_trans_{n}", f"apps/linear_algebra halide_sgemv_trans, {n}x{n}", lambda: hl.sgemv(True, 0.75, A, x, -1.5, y, o),
+                 lambda: G("halide_sgemv_trans", 0.75, A, x, -1.5, y, o), o, nbytes, n, 50, {"chain_steps": n // 8 + 8})
+            for b_ in (A, x, y, o):
+                b_.device_free()
+        for lg in (20, 24):
+            n = 1 << lg
+            x, y, o, s = dev(mk(n)), dev(mk(n)), hl.Buffer(np.zeros(n, F)), hl.Buffer(np.zeros((), F))
+            line(f"scopy_2^{lg}", f"apps/linear_algebra halide_scopy_impl, n 2^{lg}", lambda: hl.scopy(x, o), lambda: G("halide_scopy_impl", 0.0, x, None, o), o, 8.0 * n, n, 50)
+            line(f"sscal_2^{lg}", f"apps/linear_algebra halide_sscal_impl, n 2^{lg}", lambda: hl.sscal(0.75, x, o), lambda: G("halide_sscal_impl", 0.75, x, None, o), o,
+                 8.0 * n, n, 50)
+            line(f"saxpy_2^{lg}", f"apps/linear_algebra halide_saxpy_impl, n 2^{lg}", lambda: hl.saxpy(0.75, x, y, o), lambda: G("halide_saxpy_impl", 0.75, x, y, o), o,
+                 12.0 * n, n, 50)
+            slow = 2 if lg == 24 else 10
+            line(f"sdot_2^{lg}", f"apps/linear_algebra halide_sdot, n 2^{lg}: one wave, 8 chains", lambda: hl.sdot(x, y, s), lambda: G("halide_sdot", x, y, s), s, 8.0 * n, 1,
+                 slow, {"chain_steps": n // 8})
+            line(f"sasum_2^{lg}", f"apps/linear_algebra halide_sasum, n 2^{lg}: one wave, 8 chains", lambda: hl.sasum(x, s), lambda: G("halide_sasum", x, s), s, 4.0 * n, 1,
+                 slow, {"chain_steps": n // 8})
+            m = 1 << (lg // 2)
+            xm, ym, R = dev(mk(m)), dev(mk(m)), dev(mk(m, m))
+            line(f"sger_{m}x{m}", f"apps/linear_algebra halide_sger_impl, {m}x{m} in place", lambda: hl.sger(2.0 ** -20, xm, ym, R),
+                 lambda: G("halide_sger_impl", 2.0 ** -20, xm, ym, R), R, 8.0 * m * m + 8.0 * m, m * m, 50)
+            for b_ in (x, y, o, s, xm, ym, R):
+                b_.device_free()
+
+    # ---- lens_blur u8 stereo pair 768x1280(the size of apps/images/rgb.png the reference's Makefile feeds process.cpp), 32 slices, 32 samples
     if not only or "lens_blur" in only:
         W, H = 768, 1280
         left = rng.integers(0, 256, (3, H, W), dtype=np.uint8)

@@ -435,7 +435,10 @@ _fn = {name: _bind(name) for name in
         "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
        + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]
-       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"]}
+       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"]
+       + ["halide_scopy_impl", "halide_sscal_impl", "halide_saxpy_impl", "halide_sdot", "halide_sasum", "halide_sgemv_notrans",
+          "halide_sgemv_trans", "halide_sger_impl", "halide_sgemm_notrans", "halide_sgemm_transA", "halide_sgemm_transB",
+          "halide_sgemm_transAB"]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -763,6 +766,94 @@ def mat_mul_sized(size, A, B, out) -> int:
 def debug_mat_mul_general(size, A, B, out) -> int:
     """Test and measurement hook: mat_mul_sized with one thread per output running a plain fmaf loop."""
     return _check(_mat_mul_hook("hlmi_mat_mul_general")(int(size), _as_ptr(A), _as_ptr(B), _as_ptr(out)))
+
+
+# apps/linear_algebra: the f32 BLAS subset (include/hlmi_pipelines.h, include/hlmi_blas.h).  Vectors are 1-D buffers; a matrix with
+# Halide extents (w, h) is column-major, i.e. a numpy array of shape (h, w).  Where `result` / `output` is left out the call is the
+# wrapper's of hlmi_blas.h: in place on y (x for sscal, C for sgemm).
+LINEAR_ALGEBRA = ("halide_scopy_impl", "halide_sscal_impl", "halide_saxpy_impl", "halide_sdot", "halide_sasum", "halide_sgemv_notrans",
+                  "halide_sgemv_trans", "halide_sger_impl", "halide_sgemm_notrans", "halide_sgemm_transA", "halide_sgemm_transB",
+                  "halide_sgemm_transAB")
+
+
+def scopy(x, result) -> int:
+    """result(i) = x(i)"""
+    return _check(_fn["halide_scopy_impl"](0.0, _as_ptr(x), None, _as_ptr(result)))
+
+
+def sscal(a, x, result=None) -> int:
+    """result(i) = a * x(i); in place on x by default"""
+    return _check(_fn["halide_sscal_impl"](float(a), _as_ptr(x), None, _as_ptr(x if result is None else result)))
+
+
+def saxpy(a, x, y, result=None) -> int:
+    """result(i) = a * x(i) + y(i); in place on y by default"""
+    return _check(_fn["halide_saxpy_impl"](float(a), _as_ptr(x), _as_ptr(y), _as_ptr(y if result is None else result)))
+
+
+def sdot(x, y, result) -> int:
+    """result() = the V = 8 lane-chain dot product of the contract; result is a 0-dimensional buffer"""
+    return _check(_fn["halide_sdot"](_as_ptr(x), _as_ptr(y), _as_ptr(result)))
+
+
+def sasum(x, result) -> int:
+    """result() = the sum of |x(i)| in the contract's order"""
+    return _check(_fn["halide_sasum"](_as_ptr(x), _as_ptr(result)))
+
+
+def sgemv(trans, a, A, x, b, y, output=None) -> int:
+    """output = a op(A) x + b y for A of extents (M, N): notrans x[N], y[M]; trans x[M], y[N]; in place on y by default"""
+    name = "halide_sgemv_trans" if trans else "halide_sgemv_notrans"
+    return _check(_fn[name](float(a), _as_ptr(A), _as_ptr(x), float(b), _as_ptr(y), _as_ptr(y if output is None else output)))
+
+
+def sger(a, x, y, result) -> int:
+    """result(i, j) += (a * y(j)) * x(i), in place"""
+    return _check(_fn["halide_sger_impl"](float(a), _as_ptr(x), _as_ptr(y), _as_ptr(result)))
+
+
+def sgemm_name(transA, transB) -> str:
+    return "halide_sgemm_" + ("transAB" if transA and transB else "transA" if transA else "transB" if transB else "notrans")
+
+
+def sgemm(transA, transB, a, A, B, b, C, result=None) -> int:
+    """result = a op(A) op(B) + b C, k upward; a transposed operand must be square; in place on C by default"""
+    return _check(_fn[sgemm_name(transA, transB)](float(a), _as_ptr(A), _as_ptr(B), float(b), _as_ptr(C), _as_ptr(C if result is None else result)))
+
+
+def _linear_algebra_hook():
+    fn = lib.hlmi_linear_algebra_general
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, C.c_float, C.c_float, _BP, _BP, _BP, _BP]
+    return fn
+
+
+def debug_linear_algebra_general(name: str, *args) -> int:
+    """Test and measurement hook: the entry point `name` of LINEAR_ALGEBRA, with the arguments of its C signature in order, with one
+    thread per output running the chain as written."""
+    if name not in LINEAR_ALGEBRA:
+        raise ValueError(f"no linear_algebra entry point named {name}")
+    md = metadata(name)
+    if len(args) != md.num_arguments:
+        raise TypeError(f"{name} takes {md.num_arguments} arguments, not {len(args)}")
+    scalars = [float(v) for v, i in zip(args, range(md.num_arguments)) if md.arguments[i].kind == 0]
+    bufs = [_as_ptr(v) for v, i in zip(args, range(md.num_arguments)) if md.arguments[i].kind != 0]
+    if name in ("halide_scopy_impl", "halide_sscal_impl", "halide_saxpy_impl", "halide_sger_impl"):
+        a, b = scalars[0], 0.0
+    elif name in ("halide_sdot", "halide_sasum"):
+        a, b = 0.0, 0.0
+    else:
+        a, b = scalars
+    bufs += [None] * (4 - len(bufs))
+    return _check(_linear_algebra_hook()(name.encode(), a, b, *bufs))
+
+
+def debug_sgemm_general(transA, transB, a, A, B, b, C, result=None) -> int:
+    return debug_linear_algebra_general(sgemm_name(transA, transB), a, A, B, b, C, C if result is None else result)
+
+
+def debug_sgemv_general(trans, a, A, x, b, y, output=None) -> int:
+    return debug_linear_algebra_general("halide_sgemv_trans" if trans else "halide_sgemv_notrans", a, A, x, b, y, y if output is None else output)
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

@@ -420,6 +420,12 @@ extern "C" int hlmi_mat_mul_sized(int32_t size, halide_buffer_t *A, halide_buffe
 // and for bench_apps.py.  Per call: no mode is kept anywhere.
 extern "C" int hlmi_mat_mul_general(int32_t size, halide_buffer_t *A, halide_buffer_t *B, halide_buffer_t *out);
 
+// linear_algebra.hip: the named entry point ("halide_sdot", "halide_sgemm_transA", ...) with one thread per output running the chain
+// as written, for the tests (default == general bit for bit) and for bench_apps.py.  p0 .. p3: the entry point's buffers in its own
+// order, the unused trailing ones null; a and b are read where the entry point has them.  Per call: no mode is kept anywhere.
+extern "C" int hlmi_linear_algebra_general(const char *name, float a, float b, halide_buffer_t *p0, halide_buffer_t *p1, halide_buffer_t *p2,
+                                           halide_buffer_t *p3);
+
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;
     return (r != 0 && r < 0) ? q - 1 : q;

@@ -370,6 +370,88 @@ def mat_mul(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---- apps/linear_algebra (include/hlmi_blas.h): functional forms, each returns a new tensor and leaves its arguments as they are.
+# A matrix with Halide extents (w, h) — column-major in BLAS terms — is a tensor of shape (h, w).
+def _la_check(what, *pairs):
+    """pairs: (tensor, number of dimensions)"""
+    for t, nd in pairs:
+        if t.dim() != nd or t.dtype != torch.float32:
+            raise TypeError(f"{what} takes float32 tensors of {', '.join(str(n) for _, n in pairs)} dimensions")
+
+
+@torch.library.custom_op("hlmi::saxpy", mutates_args=())
+def saxpy(a: float, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """a * x + y over two float32 vectors of one length"""
+    _la_check("saxpy", (x, 1), (y, 1))
+    if x.shape != y.shape:
+        raise TypeError("saxpy takes two vectors of one length")
+    out = torch.empty_like(y, memory_format=torch.contiguous_format)
+    with _Wrapped(x, y, out) as (bx, by, bo):
+        hl.saxpy(a, bx, by, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::sdot", mutates_args=())
+def sdot(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """the dot product in the contract's order (eight lane chains, their sum, the tail): a 0-dimensional tensor"""
+    _la_check("sdot", (x, 1), (y, 1))
+    if x.shape != y.shape:
+        raise TypeError("sdot takes two vectors of one length")
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    with _Wrapped(x, y, out) as (bx, by, bo):
+        hl.sdot(bx, by, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::sasum", mutates_args=())
+def sasum(x: torch.Tensor) -> torch.Tensor:
+    """the sum of |x| in the contract's order: a 0-dimensional tensor"""
+    _la_check("sasum", (x, 1))
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    with _Wrapped(x, out) as (bx, bo):
+        hl.sasum(bx, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::sgemv", mutates_args=())
+def sgemv(trans: bool, a: float, A: torch.Tensor, x: torch.Tensor, b: float, y: torch.Tensor) -> torch.Tensor:
+    """a op(A) x + b y for A of shape (h, w): notrans x[h], y[w]; trans x[w], y[h]"""
+    _la_check("sgemv", (A, 2), (x, 1), (y, 1))
+    h, w = A.shape
+    if (x.shape[0], y.shape[0]) != ((w, h) if trans else (h, w)):
+        raise TypeError("sgemv: the vectors do not fit the matrix")
+    out = torch.empty_like(y, memory_format=torch.contiguous_format)
+    with _Wrapped(A, x, y, out) as (bA, bx, by, bo):
+        hl.sgemv(trans, a, bA, bx, b, by, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::sger", mutates_args=())
+def sger(a: float, x: torch.Tensor, y: torch.Tensor, A: torch.Tensor) -> torch.Tensor:
+    """A + a x y' for x[m], y[n] and A of shape (n, m)"""
+    _la_check("sger", (x, 1), (y, 1), (A, 2))
+    if tuple(A.shape) != (y.shape[0], x.shape[0]):
+        raise TypeError("sger: the vectors do not fit the matrix")
+    out = A.clone(memory_format=torch.contiguous_format)
+    with _Wrapped(x, y, out) as (bx, by, bo):
+        hl.sger(a, bx, by, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::sgemm", mutates_args=())
+def sgemm(transA: bool, transB: bool, a: float, A: torch.Tensor, B: torch.Tensor, b: float, C: torch.Tensor) -> torch.Tensor:
+    """a op(A) op(B) + b C with k upward; A of shape (K, M) as stored, B (N, K), C (N, M); a transposed operand must be square"""
+    _la_check("sgemm", (A, 2), (B, 2), (C, 2))
+    K, M = A.shape
+    N = B.shape[0]
+    if B.shape[1] != K or tuple(C.shape) != (N, M) or (transA and M != K) or (transB and N != K):
+        raise TypeError("sgemm: the shapes do not fit (A (K, M), B (N, K), C (N, M); a transposed operand is square)")
+    out = torch.empty((N, M), dtype=torch.float32, device=C.device)
+    with _Wrapped(A, B, C, out) as (bA, bB, bC, bo):
+        hl.sgemm(transA, transB, a, bA, bB, b, bC, bo)
+    return out
+
+
 @torch.library.custom_op("hlmi::conv3x3a16", mutates_args=())
 def conv3x3a16(input: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """apps/hexagon_benchmarks: (H, W) uint8 under a (3, 3) int8 mask (mask[i][j] multiplies in(x + j - 1, y + i - 1)), the sum wrapped
@@ -510,6 +592,36 @@ def _(layers, ops):
 @mat_mul.register_fake
 def _(A, B):
     return A.new_empty(tuple(A.shape))
+
+
+@saxpy.register_fake
+def _(a, x, y):
+    return y.new_empty(tuple(y.shape))
+
+
+@sdot.register_fake
+def _(x, y):
+    return x.new_empty(())
+
+
+@sasum.register_fake
+def _(x):
+    return x.new_empty(())
+
+
+@sgemv.register_fake
+def _(trans, a, A, x, b, y):
+    return y.new_empty(tuple(y.shape))
+
+
+@sger.register_fake
+def _(a, x, y, A):
+    return A.new_empty(tuple(A.shape))
+
+
+@sgemm.register_fake
+def _(transA, transB, a, A, B, b, C):
+    return C.new_empty(tuple(C.shape))
 
 
 @conv3x3a16.register_fake

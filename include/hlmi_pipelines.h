@@ -421,6 +421,60 @@ HLMI_DECLARE_AUX(sobel)
 int mat_mul(struct halide_buffer_t *A, struct halide_buffer_t *B, struct halide_buffer_t *out);
 HLMI_DECLARE_AUX(mat_mul)
 
+/* apps/linear_algebra/src/blas_l{1,2,3}_generators.cpp, the twelve f32 objects of src/CMakeLists.txt — the pipelines behind
+ * halide_blas.h (here: hlmi_blas.h, which adds the wrappers and the hblas_s* calls).  All buffers float32; dimension 0 is innermost
+ * with stride 1 and min 0 (-8 otherwise); matrices are column-major, the stride of dimension 1 any value >= extent 0.  V = 8, the
+ * natural_vector_size(float) of the reference's x86-64 AVX2 build.  mad(a, b, c) = a * b + c and mad2(a, b, c, d) = a * b + c * d are
+ * fused (the first product) in the default build and round every operator with HLMI_CANON_FMA=0; `*` is a rounded multiply.
+ *   halide_scopy_impl     result(i) = x(i); a and y unused, y may be null
+ *   halide_sscal_impl     result(i) = a * x(i); y unused and may be null; result may be x itself
+ *   halide_saxpy_impl     result(i) = mad(a, x(i), y(i)); result may be y itself
+ *   halide_sdot           lane_i = +0, k upward over n / V: lane_i = mad(x(kV + i), y(kV + i), lane_i); s = +0, s = s + lane_i for
+ *                         i = 0 .. V - 1; t = +0, upward over the tail: t = mad(x, y, t); result() = s + t (0-dimensional)
+ *   halide_sasum          the same with lane_i + |x| and t + |x|
+ *   halide_sgemv_notrans  A[M x N], x[N], y[M]: acc = b * y(i), k upward: acc = mad(a * A(i, k), x(k), acc); output(i) = acc
+ *   halide_sgemv_trans    A[M x N], x[M], y[N]: per output i the V lane chains lane_j = mad(A(kV + j, i), x(kV + j), lane_j), s = +0,
+ *                         s = s + lane_j, the tail upward s = mad(A(t, i), x(t), s); output(i) = mad2(b, y(i), a, s)
+ *   halide_sger_impl      x[M], y[N]: result(i, j) = mad(a * y(j), x(i), result(i, j)), in place
+ *   halide_sgemm_*        ab = +0, k upward: ab = mad(opA(i, k), opB(k, j), ab); result(i, j) = mad2(a, ab, b, C(i, j)); b * C is always
+ *                         evaluated (b = 0 does not hide a NaN in C).  The sizes come from the stored matrices — M = A.extent.0,
+ *                         K = A.extent.1 = B.extent.0, N = B.extent.1, C and result M x N — so notrans is fully rectangular, transA
+ *                         (opA(i, k) = A(k, i)) needs A square, transB (opB(k, j) = B(j, k)) needs B square, transAB both (-8 otherwise)
+ * The output may be exactly the y / C argument (the same buffer, or the same first element and layout): that is the call every wrapper
+ * makes.  Any other overlap of the output with an input is refused (-8).  Vector lengths 0 .. 2^27, matrix extents 0 .. 8192 (-8
+ * beyond); an empty output launches nothing, sdot and sasum of nothing write +0.  A bounds query fills the query buffers with the
+ * shapes the given ones imply.  No _auto_schedule twins: the reference builds none. */
+int halide_scopy_impl(float a, struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_scopy_impl)
+int halide_sscal_impl(float a, struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_sscal_impl)
+int halide_saxpy_impl(float a, struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_saxpy_impl)
+int halide_sdot(struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_sdot)
+int halide_sasum(struct halide_buffer_t *x, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_sasum)
+int halide_sgemv_notrans(float a, struct halide_buffer_t *A, struct halide_buffer_t *x, float b, struct halide_buffer_t *y,
+                         struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(halide_sgemv_notrans)
+int halide_sgemv_trans(float a, struct halide_buffer_t *A, struct halide_buffer_t *x, float b, struct halide_buffer_t *y,
+                       struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(halide_sgemv_trans)
+int halide_sger_impl(float a, struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_sger_impl)
+int halide_sgemm_notrans(float a, struct halide_buffer_t *A, struct halide_buffer_t *B, float b, struct halide_buffer_t *C,
+                         struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_sgemm_notrans)
+int halide_sgemm_transA(float a, struct halide_buffer_t *A, struct halide_buffer_t *B, float b, struct halide_buffer_t *C,
+                        struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_sgemm_transA)
+int halide_sgemm_transB(float a, struct halide_buffer_t *A, struct halide_buffer_t *B, float b, struct halide_buffer_t *C,
+                        struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_sgemm_transB)
+int halide_sgemm_transAB(float a, struct halide_buffer_t *A, struct halide_buffer_t *B, float b, struct halide_buffer_t *C,
+                         struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_sgemm_transAB)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,

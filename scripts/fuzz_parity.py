@@ -581,6 +581,97 @@ def fuzz_mat_mul(rng):
     return desc, ok
 
 
+def fuzz_linear_algebra(rng):
+    """One of the twelve f32 pipelines of apps/linear_algebra at random sizes (vectors 0 .. 3000, matrix extents 1 .. 200 within the
+    variant's squareness rule), on the default or the one-thread-per-output path, every buffer in a device allocation with a column
+    stride and a pointer offset of its own, in a third of the cases with the output being the wrapper's y / C input, noise in [-1, 1)
+    with random a and b and in a third of the cases a handful of special values, against tests/cpp/linear_algebra_check.c
+    (tests/linear_algebra_checker.py) in the library's canonical form.  Bit for bit, NaN for NaN; the bytes around every buffer must
+    come back unchanged."""
+    import linear_algebra_checker as la
+    la.set_canon(hl.canon_fma())
+    name = la.NAMES[int(rng.integers(0, len(la.NAMES)))]
+    general = rng.random() < 0.3
+    a, b = (float(f32(rng.random() * 4 - 2)) for _ in range(2))
+    mk = lambda *s: (rng.random(s, dtype=f32) * 2 - 1).astype(f32)
+    gemm = name in la.GEMM_FLAGS
+    if gemm:
+        ta, tb = la.GEMM_FLAGS[name]
+        M, N, K = (rdim(rng, 1, 200) for _ in range(3))
+        K = M if ta else K
+        N = K if tb else N
+        ins = {"A_": mk(K, M), "B_": mk(N, K), "C_": mk(N, M)}
+        order, out, alias_of = ("A_", "B_", "C_", "result"), "result", "C_"
+        want = lambda: la.sgemm(ta, tb, a, ins["A_"], ins["B_"], b, ins["C_"])
+    elif name.startswith("halide_sgemv"):
+        t = name.endswith("_trans")
+        w, h = rdim(rng, 1, 200), rdim(rng, 1, 200)
+        ins = {"A": mk(h, w), "x": mk(w if t else h), "y": mk(h if t else w)}
+        order, out, alias_of = ("A", "x", "y", "output"), "output", "y"
+        want = lambda: la.sgemv(t, a, ins["A"], ins["x"], b, ins["y"])
+    elif name == "halide_sger_impl":
+        w, h = rdim(rng, 1, 200), rdim(rng, 1, 200)
+        ins = {"x": mk(w), "y": mk(h), "result": mk(h, w)}
+        order, out, alias_of = ("x", "y", "result"), "result", None
+        want = lambda: la.sger(a, ins["x"], ins["y"], ins["result"])
+    else:
+        n = int(rng.integers(0, 3001))
+        ins = {"x": mk(n)}
+        if name in ("halide_saxpy_impl", "halide_sdot"):
+            ins["y"] = mk(n)
+        order = ("x", "result") if name == "halide_sasum" else ("x", "y", "result")
+        out, alias_of = "result", {"halide_sscal_impl": "x", "halide_saxpy_impl": "y"}.get(name)
+        want = {"halide_scopy_impl": lambda: la.scopy(ins["x"]), "halide_sscal_impl": lambda: la.sscal(a, ins["x"]),
+                "halide_saxpy_impl": lambda: la.saxpy(a, ins["x"], ins["y"]), "halide_sdot": lambda: la.sdot(ins["x"], ins["y"]),
+                "halide_sasum": lambda: la.sasum(ins["x"])}[name]
+    special = rng.random() < 0.33
+    if special:
+        pool = np.array([0.0, -0.0, 1e-40, -3e-39, np.inf, -np.inf, np.nan, 3e38, -2e38, 2.0 ** 100, 2.0 ** -100], f32)
+        for m in ins.values():
+            if m.size:
+                k = int(rng.integers(1, 4))
+                m.reshape(-1)[rng.integers(0, m.size, k)] = rng.choice(pool, k)
+    expect = want()
+    alias = alias_of is not None and rng.random() < 0.33
+    shapes = {k: v.shape for k, v in ins.items()}
+    shapes.setdefault(out, expect.shape)
+    lays, arrs = {}, {}
+    try:
+        for k in order:
+            if k == "y" and k not in ins:
+                arrs[k] = None
+                continue
+            if k == out and alias:
+                arrs[k] = arrs[alias_of]
+                continue
+            s = shapes[k]
+            lays[k] = ((s[1] + int(rng.choice([0, 4, 1, 3]))) if len(s) == 2 else None, 4 * int(rng.integers(0, 4)))
+            arrs[k] = la.Arr(hl, "dev", s, lays[k][0], lays[k][1], fill=ins.get(k))
+        bufs = [None if arrs[k] is None else arrs[k].buf for k in order]
+        if name in ("halide_sdot", "halide_sasum"):
+            args = bufs
+        elif gemm or name.startswith("halide_sgemv"):
+            args = [a, bufs[0], bufs[1], b, bufs[2], bufs[3]]
+        else:
+            args = [a] + bufs
+        if general:
+            hl.debug_linear_algebra_general(name, *args)
+        else:
+            hl._check(hl._fn[name](*[v.ptr if isinstance(v, hl.Buffer) else v for v in args]))
+        got = np.asarray(arrs[out].result()).reshape(expect.shape)
+        for k, v in arrs.items():
+            if v is not None and v is not arrs[out]:
+                v.result()   # the inputs and the bytes around them are as they were
+    finally:
+        for v in {id(v): v for v in arrs.values() if v is not None}.values():
+            v.free()
+    nan = np.isnan(expect)
+    ok = bool(np.isnan(got[nan]).all()) and np.array_equal(got.view(np.uint32)[~nan], expect.view(np.uint32)[~nan])
+    desc = (f"{name}{' general' if general else ''} shapes {shapes} a {a} b {b}{' special values' if special else ''}{' in place' if alias else ''}, "
+            f"(column stride, byte offset) {lays}")
+    return desc, ok
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
@@ -589,6 +680,7 @@ CASES["wavelet"] = fuzz_wavelet   # all four entry points; its checker has a mod
 CASES["compositing"] = fuzz_compositing   # integer throughout: its checker (tests/compositing_checker.py) has no canonical form
 CASES["hexagon_benchmarks"] = fuzz_hexagon_benchmarks   # all six entry points; integer throughout (tests/hexagon_benchmarks_checker.py)
 CASES["mat_mul"] = fuzz_mat_mul   # sized and general paths; one chain in both canonical forms (tests/mat_mul_checker.py)
+CASES["linear_algebra"] = fuzz_linear_algebra   # all twelve entry points, both paths (tests/linear_algebra_checker.py)
 
 
 def stress(args, only):
