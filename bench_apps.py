@@ -590,6 +590,65 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
         emit("mat_mul", "apps/cuda_mat_mul, f32 1024x1024 = B @ A as a k-ordered fmaf chain, noise in [-1, 1)", t1024, 1024 * 1024, "mfma",
              2.0 * 1024 ** 3 / t1024 / 1e12, MFMA_F32_PEAK_TF, "TFLOP/s", extra)
 
+    # ---- fft: apps/fft's c2c, r2c and c2r at 16^2 (the size the reference builds; launch-bound), 256^2, 1024^2 and 4096^2, device buffers,
+    #      gain 1.  The two line passes move each complex array twice in and twice out: "moved_bytes" is that, its rate stands beside
+    #      membench's copy rate of the same run ("copy_frac"); "launch_bound": moving those bytes at that rate would take under a tenth
+    #      of the call's time.  Beside each: the same call with one thread per line
+    #      (hlmi_fft2d_general), which every launch the plan chooses must beat, and torch.fft.fft2 / rfft2 / irfft2 on the same data in
+    #      the same run: recorded, not thresholded (rocFFT is bound to no operation order, its bits differ).
+    if not only or "fft" in only:
+        import torch   # this block only: the vendor column
+        for n in (16, 256, 1024, 4096):
+            for kind in ("c2c_forward", "r2c", "c2r"):
+                ishape = {"r2c": (n, n, 1), "c2r": (n // 2 + 1, n, 2)}.get(kind, (n, n, 2))
+                oshape = {"r2c": (n // 2 + 1, n, 2), "c2r": (n, n, 1)}.get(kind, (n, n, 2))
+                x = (rng.random(ishape, dtype=np.float32) * 2 - 1).astype(np.float32)
+                a, o = hl.fft_buffer(x), hl.fft_buffer(np.zeros(oshape, np.float32))
+                a.copy_to_device()
+                call = lambda kind=kind, n=n: hl.fft2d(kind, a, o, 1.0, sizes=(n, n))
+                general = lambda kind=kind, n=n: hl.debug_fft2d_general(kind, a, o, 1.0, sizes=(n, n))
+                iters = 200 if n <= 256 else 50 if n == 1024 else 5
+                t = timed(call, o, iters)
+                clock = last_clock[0]
+                tg = timed(general, o, max(1, iters // (10 if n <= 1024 else 5)))
+                tx = torch.from_numpy(x).cuda()
+                if kind == "c2c_forward":
+                    z = torch.view_as_complex(tx)
+                    vendor, vname = (lambda: torch.fft.fft2(z)), "torch.fft.fft2"
+                elif kind == "r2c":
+                    r = tx[..., 0].T.contiguous()   # rfft2 halves its last dimension: hand it dimension 1 there
+                    vendor, vname = (lambda: torch.fft.rfft2(r)), "torch.fft.rfft2"
+                else:
+                    z = torch.view_as_complex(tx).T.contiguous()
+                    vendor, vname = (lambda n=n: torch.fft.irfft2(z, s=(n, n))), "torch.fft.irfft2"
+                vendor()
+                torch.cuda.synchronize()
+                tv = 1e30
+                for _ in range(args.samples):
+                    t0 = time.perf_counter()
+                    for _ in range(iters):
+                        vendor()
+                    torch.cuda.synchronize()
+                    tv = min(tv, (time.perf_counter() - t0) / iters)
+                del tx
+                last_clock[0] = clock
+                k, kg = kernels(call, o), kernels(general, o)
+                a_cols = kind == "r2c" and n >= 16   # pass A of the zipped r2c runs down columns, every other pass A along rows
+                pass_a = sum(v for name, v in k.items() if name.startswith("fft_cols") == a_cols)
+                pass_b = sum(v for name, v in k.items() if name.startswith("fft_cols") != a_cols)
+                if len(k) == 1:   # the whole transform in one launch: it stands against both launches of the general path
+                    faster = bool(sum(k.values()) < sum(kg.values()))
+                else:
+                    faster = bool(pass_a < kg["fft_general_a"] and pass_b < kg["fft_general_b"])
+                moved = 2.0 * 4.0 * (np.prod(ishape) + np.prod(oshape)) if kind == "c2c_forward" else 4.0 * (np.prod(ishape) + np.prod(oshape)) + 2.0 * 8.0 * n * n / 2
+                extra = {"moved_bytes": float(moved), "kernels_ms": k, "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kg},
+                         "fast_path_faster": bool(t < tg), "every_launch_faster": faster,
+                         "launch_bound": bool(moved / 1e9 / (copy_gbs[0] or HBM_PEAK_GBS) < 0.1 * t), "vendor": vname, "vendor_ms": round(tv * 1e3, 4),
+                         "vendor_note": "rocFFT through torch on the same data; bound to no operation order, its bits differ"}
+                if copy_gbs[0]:
+                    extra["copy_frac"] = round(moved / t / 1e9 / copy_gbs[0], 4)
+                emit(f"fft_{kind}_{n}", f"apps/fft {kind}, f32 {n}x{n}, gain 1, noise in [-1, 1)", t, n * n, "hbm", moved / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
+
     # ---- linear_algebra: apps/linear_algebra's f32 BLAS subset.  "sgemm": the four variants at 768^3 and 1024^3, notrans at 4096^3 and
     #      one rectangular notrans case, each beside its one-thread-per-output path (which the plan's choice must beat) and beside
     #      hl.mat_mul_sized / torch.addmm on the same operands in the same run (recorded, not thresholded; neither is bound to the

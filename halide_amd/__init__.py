@@ -436,6 +436,7 @@ _fn = {name: _bind(name) for name in
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
        + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]
        + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"]
+       + ["fft_forward_r2c", "fft_inverse_c2r", "fft_forward_c2c", "fft_inverse_c2c"]
        + ["halide_scopy_impl", "halide_sscal_impl", "halide_saxpy_impl", "halide_sdot", "halide_sasum", "halide_sgemv_notrans",
           "halide_sgemv_trans", "halide_sger_impl", "halide_sgemm_notrans", "halide_sgemm_transA", "halide_sgemm_transB",
           "halide_sgemm_transAB"]}
@@ -766,6 +767,85 @@ def mat_mul_sized(size, A, B, out) -> int:
 def debug_mat_mul_general(size, A, B, out) -> int:
     """Test and measurement hook: mat_mul_sized with one thread per output running a plain fmaf loop."""
     return _check(_mat_mul_hook("hlmi_mat_mul_general")(int(size), _as_ptr(A), _as_ptr(B), _as_ptr(out)))
+
+
+# apps/fft: the four objects the reference builds (16 x 16) and the generator at other sizes and gains (include/hlmi_pipelines.h).  A
+# complex array with Halide extents (N0, rows, 2) is a numpy array of shape (rows, N0, 2), a real one (rows, N0, 1).
+FFT_KINDS = ("c2c_forward", "c2c_inverse", "r2c", "c2r")
+
+
+def fft_forward_r2c(input, output) -> int:
+    """real [16, 16, 1] -> complex [16, 9, 2], gain 1/256"""
+    return _check(_fn["fft_forward_r2c"](_as_ptr(input), _as_ptr(output)))
+
+
+def fft_inverse_c2r(input, output) -> int:
+    """complex [16, >= 9, 2] -> real [16, 16, 1], gain 1"""
+    return _check(_fn["fft_inverse_c2r"](_as_ptr(input), _as_ptr(output)))
+
+
+def fft_forward_c2c(input, output) -> int:
+    """complex [16, 16, 2] -> complex [16, 16, 2], sign -1, gain 1/256"""
+    return _check(_fn["fft_forward_c2c"](_as_ptr(input), _as_ptr(output)))
+
+
+def fft_inverse_c2c(input, output) -> int:
+    """complex [16, 16, 2] -> complex [16, 16, 2], sign +1, gain 1"""
+    return _check(_fn["fft_inverse_c2c"](_as_ptr(input), _as_ptr(output)))
+
+
+def _fft_hook(symbol):
+    fn = getattr(lib, symbol)
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_float, _BP, _BP]
+    return fn
+
+
+def fft_buffer(array) -> "Buffer":
+    """A numpy array of shape (rows, N0, 2) (complex: re, im), (rows, N0, 1) or (rows, N0) (real) as the generator's buffer: dimension
+    0 along N0, dimension 1 the rows, dimension 2 the components with stride 1.  No copy: the rows may be padded."""
+    a = array if array.ndim == 3 else array.reshape(array.shape + (1,)) if array.flags.c_contiguous else array[..., None]
+    b = Buffer(a)
+    d = [(x.min, x.extent, x.stride) for x in (b._dims[1], b._dims[2], b._dims[0])]
+    for i, (mn, ext, st) in enumerate(d):
+        b._dims[i] = halide_dimension_t(mn, ext, 1 if i == 2 and ext == 1 else st, 0)
+    return b
+
+
+def _fft_sizes(kind, input, output):
+    """N0 and N1 from the buffers: N0 is the output's extent 0, N1 the rows of the side that is not halved"""
+    full = output if kind == "c2r" else input
+    return int(output.dim(0).extent), int(full.dim(1).extent)
+
+
+def fft2d(kind, input, output, gain=1.0, sizes=None) -> int:
+    """The transform `kind` (one of FFT_KINDS) with the sizes taken from the buffers (or given as (N0, N1)): each 2 .. 4096 with
+    radix factors 8, 6, 4, 2 only, both even for r2c and c2r."""
+    n0, n1 = _fft_sizes(kind, input, output) if sizes is None else sizes
+    return _check(_fft_hook("hlmi_fft2d")(FFT_KINDS.index(kind), n0, n1, float(gain), _as_ptr(input), _as_ptr(output)))
+
+
+def debug_fft2d_general(kind, input, output, gain=1.0, sizes=None) -> int:
+    """Test and measurement hook: fft2d with one thread per 1-D line, every pass in full through the scratch arena."""
+    n0, n1 = _fft_sizes(kind, input, output) if sizes is None else sizes
+    return _check(_fft_hook("hlmi_fft2d_general")(FFT_KINDS.index(kind), n0, n1, float(gain), _as_ptr(input), _as_ptr(output)))
+
+
+def fft_radix_factor(n):
+    """radix_factor(n) as the library holds it"""
+    R = (C.c_int32 * 16)()
+    lib.hlmi_fft_radix_factor.restype, lib.hlmi_fft_radix_factor.argtypes = C.c_int, [C.c_int32, C.POINTER(C.c_int32)]
+    return list(R[:lib.hlmi_fft_radix_factor(int(n), R)])
+
+
+def fft_size_ok(n) -> bool:
+    lib.hlmi_fft_size_ok.restype, lib.hlmi_fft_size_ok.argtypes = C.c_int, [C.c_int32]
+    return bool(lib.hlmi_fft_size_ok(int(n)))
+
+
+def fft_twiddles_address() -> int:
+    """the address of hlmi_fft_twiddles, the host function behind every twiddle table (tests/fft_checker.py: use_twiddles)"""
+    return C.cast(lib.hlmi_fft_twiddles, C.c_void_p).value
 
 
 # apps/linear_algebra: the f32 BLAS subset (include/hlmi_pipelines.h, include/hlmi_blas.h).  Vectors are 1-D buffers; a matrix with

@@ -426,6 +426,18 @@ extern "C" int hlmi_mat_mul_general(int32_t size, halide_buffer_t *A, halide_buf
 extern "C" int hlmi_linear_algebra_general(const char *name, float a, float b, halide_buffer_t *p0, halide_buffer_t *p1, halide_buffer_t *p2,
                                            halide_buffer_t *p3);
 
+// fft.hip: the fft generator instantiated at other sizes and gains (fft_forward_c2c is hlmi_fft2d(0, 16, 16, 1 / 256, ...)): the same
+// shim, plan and rules.  kind: 0 c2c forward, 1 c2c inverse, 2 r2c, 3 c2r; N0, N1 in 2 .. 4096 with radix factors 8, 6, 4, 2 only, both
+// even for r2c and c2r; -8 for any other size.
+extern "C" int hlmi_fft2d(int32_t kind, int32_t N0, int32_t N1, float gain, halide_buffer_t *input, halide_buffer_t *output);
+// fft.hip: the same call with one thread per 1-D line (per zipped column pair), every pass in full through the scratch arena, for the
+// tests (default == general bit for bit) and for bench_apps.py.  Per call: no mode is kept anywhere.
+extern "C" int hlmi_fft2d_general(int32_t kind, int32_t N0, int32_t N1, float gain, halide_buffer_t *input, halide_buffer_t *output);
+// fft.hip: the host function behind every twiddle table (the checker builds its tables with it too), radix_factor and the size predicate
+extern "C" void hlmi_fft_twiddles(int32_t n, int32_t sign, float gain, float *out);
+extern "C" int hlmi_fft_radix_factor(int32_t N, int32_t *R);
+extern "C" int hlmi_fft_size_ok(int32_t N);
+
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;
     return (r != 0 && r < 0) ? q - 1 : q;

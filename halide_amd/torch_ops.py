@@ -370,6 +370,41 @@ def mat_mul(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     return out
 
 
+@torch.library.custom_op("hlmi::fft2d", mutates_args=())
+def fft2d(input: torch.Tensor, kind: str, gain: float) -> torch.Tensor:
+    """apps/fft at any allowed size: kind "c2c_forward" / "c2c_inverse" take and return a complex array, "r2c" takes a real (N1, N0)
+    tensor and returns the N1/2 + 1 rows of its spectrum, "c2r" takes those rows and returns the real (N1, N0) array.  A complex
+    array is a float32 tensor (rows, N0, 2), the layout of torch.view_as_real and the generator's interleaved one: no copy either way."""
+    if kind not in hl.FFT_KINDS:
+        raise TypeError(f"fft2d: kind must be one of {hl.FFT_KINDS}")
+    real_in = kind == "r2c"
+    if input.dtype != torch.float32 or input.dim() != (2 if real_in else 3) or (not real_in and input.shape[2] != 2):
+        raise TypeError("fft2d takes a float32 tensor (rows, N0) for r2c and (rows, N0, 2) otherwise")
+    if input.stride(-1) != 1 or (not real_in and input.stride(1) != 2):
+        raise RuntimeError("fft2d: the components and dimension 0 must be dense")
+    rows, n0 = input.shape[0], input.shape[1]
+    n1 = 2 * (rows - 1) if kind == "c2r" else rows
+    out_shape = {"r2c": (n1 // 2 + 1, n0, 2), "c2r": (n1, n0)}.get(kind, (n1, n0, 2))
+    out = torch.empty(out_shape, dtype=torch.float32, device=input.device)
+    if not input.is_cuda:
+        raise RuntimeError("hlmi ops need tensors on the GPU (there is no CPU implementation)")
+
+    def wrap(t, comps):
+        return hl.Buffer.wrap_device(t.data_ptr(), np.float32, [n0, t.shape[0], comps], [comps, t.stride(0), 1])
+
+    a, o = wrap(input, 1 if real_in else 2), wrap(out, 1 if kind == "c2r" else 2)
+    s = torch.cuda.current_stream(input.device).cuda_stream
+    hl.set_stream(s if s else 1)
+    hl.set_gpu_device(input.device.index or 0)
+    try:
+        hl.fft2d(kind, a, o, gain, sizes=(n0, n1))
+    finally:
+        hl.set_stream(None)
+        a.device_detach()
+        o.device_detach()
+    return out
+
+
 # ---- apps/linear_algebra (include/hlmi_blas.h): functional forms, each returns a new tensor and leaves its arguments as they are.
 # A matrix with Halide extents (w, h) — column-major in BLAS terms — is a tensor of shape (h, w).
 def _la_check(what, *pairs):
@@ -592,6 +627,13 @@ def _(layers, ops):
 @mat_mul.register_fake
 def _(A, B):
     return A.new_empty(tuple(A.shape))
+
+
+@fft2d.register_fake
+def _(input, kind, gain):
+    rows, n0 = input.shape[0], input.shape[1]
+    n1 = 2 * (rows - 1) if kind == "c2r" else rows
+    return input.new_empty({"r2c": (n1 // 2 + 1, n0, 2), "c2r": (n1, n0)}.get(kind, (n1, n0, 2)))
 
 
 @saxpy.register_fake

@@ -421,6 +421,32 @@ HLMI_DECLARE_AUX(sobel)
 int mat_mul(struct halide_buffer_t *A, struct halide_buffer_t *B, struct halide_buffer_t *out);
 HLMI_DECLARE_AUX(mat_mul)
 
+/* apps/fft/fft_generator.cpp, the four objects of apps/fft/CMakeLists.txt:22-47 — the 2-D f32 Fourier transform of a 16 x 16 image:
+ *   fft_forward_r2c   real [16, 16, 1] -> complex [16, 9, 2],  gain 1/256      fft_inverse_c2r   complex [16, >= 9, 2] -> real [16, 16, 1], gain 1
+ *   fft_forward_c2c   complex [16, 16, 2] -> complex [16, 16, 2], gain 1/256   fft_inverse_c2c   the same, sign +1, gain 1
+ * X(k0, k1) = gain * sum over n0, n1 of x(n0, n1) exp(sign 2 pi j (k0 n0 / N0 + k1 n1 / N1)), sign -1 forward and +1 inverse, evaluated
+ * as the reference's Stockham passes (fft.cpp:295-421): radix_factor's radices (16 = {4, 4}), the codelets dft2 / dft4 / dft6 / dft8
+ * with their literals, dimension 0 first with gain 1, then dimension 1; the gain is folded into the first twiddle table of the pass
+ * that carries it.  Twiddles W(n) = (cosf(a), sinf(a)) * gain with a = ((float)(sign * 2) * (float)M_PI * (float)n) / (float)(R S),
+ * a true f32 division, built on the host.  r2c and c2r pair real columns in groups of V = 8 (natural_vector_size of the reference's
+ * x86-64 AVX2 build, vector_width = 0) and zip the DC and Nyquist rows as the reference writes them (fft.cpp:667-1061), so r2c equals
+ * the first N1/2 + 1 rows of c2c within rounding, not bit for bit.  A complex product is (a.re b.re - a.im b.im, a.re b.im + a.im
+ * b.re) with the first product of each fused in the default build (mulsub, mad2) and every operator rounded with HLMI_CANON_FMA=0;
+ * `* j` swaps and negates once, `* sign` negates or does nothing, conj negates the imaginary part, 0.5f * is a rounded multiply.
+ * Subnormals are kept; one NaN or Inf in the input reaches every output (each output of a 2-D transform depends on every input).
+ * Buffers: float32, 3-D; dimension 2 is min 0, extent 1 (real) or 2 (complex: re, im), stride 1; dimension 0 has stride 1 (real) or 2
+ * (complex); dimension 1 any stride >= the row (-8 otherwise).  The output is exactly [0, N0) x [0, rows); the input covers that box
+ * of its own (-4) and may be larger: c2r reads rows 0 .. N1/2 only.  Input and output may not overlap (-8).  A bounds query fills the
+ * query buffers with those boxes, interleaved and dense.  No _auto_schedule twin: the reference builds none. */
+int fft_forward_r2c(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(fft_forward_r2c)
+int fft_inverse_c2r(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(fft_inverse_c2r)
+int fft_forward_c2c(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(fft_forward_c2c)
+int fft_inverse_c2c(struct halide_buffer_t *input, struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(fft_inverse_c2c)
+
 /* apps/linear_algebra/src/blas_l{1,2,3}_generators.cpp, the twelve f32 objects of src/CMakeLists.txt — the pipelines behind
  * halide_blas.h (here: hlmi_blas.h, which adds the wrappers and the hblas_s* calls).  All buffers float32; dimension 0 is innermost
  * with stride 1 and min 0 (-8 otherwise); matrices are column-major, the stride of dimension 1 any value >= extent 0.  V = 8, the

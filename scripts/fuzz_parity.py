@@ -672,6 +672,71 @@ def fuzz_linear_algebra(rng):
     return desc, ok
 
 
+FFT_SIZES = [n for n in range(2, 4097) if n <= 256 or n in (384, 512, 768, 1024, 2048, 4096)]
+
+
+def fuzz_fft(rng):
+    """One of the four 2-D transforms of apps/fft (c2c forward and inverse, r2c, c2r) at random allowed sizes (each dimension 2 .. 256
+    or one of a few larger ones, at most 2^16 points, both even for r2c and c2r), a random gain (1, 0, -1, a power of two or any
+    float), on the default or the one-thread-per-line path, input and output in device allocations with a row stride and a pointer
+    offset of their own (a c2r input sometimes taller than it is read, the rest NaN), noise in [-1, 1) and in a quarter of the cases a
+    few signed zeros, subnormals and large magnitudes, against tests/cpp/fft_check.c (tests/fft_checker.py) in the library's
+    canonical form with the library's table function.  Bit for bit, NaN for NaN; the bytes around both buffers must come back
+    unchanged."""
+    import fft_checker as fc
+    from parity_helpers import DevArray
+    fc.set_canon(hl.canon_fma())
+    fc.use_twiddles(hl.fft_twiddles_address())
+    kind = fc.KINDS[int(rng.integers(0, 4))]
+    real = kind in ("r2c", "c2r")
+    ok_sizes = [n for n in FFT_SIZES if hl.fft_size_ok(n) and not (real and n % 2)]
+    while True:
+        n0, n1 = (int(rng.choice(ok_sizes)) for _ in range(2))
+        if n0 * n1 <= 1 << 16:
+            break
+    general = rng.random() < 0.3
+    gain = float(f32([1.0, 0.0, -1.0, 1.0 / (n0 * n1), rng.random() * 4 - 2][int(rng.integers(0, 5))]))
+    ishape, oshape = fc.in_shape(kind, n0, n1), fc.out_shape(kind, n0, n1)
+    extra = int(rng.integers(0, 3)) if kind == "c2r" else 0
+    x = (rng.random((ishape[0] + extra,) + ishape[1:], dtype=f32) * 2 - 1).astype(f32)
+    special = rng.random() < 0.25
+    if special:
+        pool = np.array([0.0, -0.0, 1e-40, -3e-39, 2.0 ** -100, 1e30, -1e30], f32)
+        k = int(rng.integers(1, 6))
+        flat = x.reshape(-1)
+        flat[rng.integers(0, flat.size, k)] = rng.choice(pool, k)
+    if extra:
+        x[ishape[0]:] = np.nan
+    want = fc.run(kind, x, n1=n1, gain=gain)
+
+    def lay(comps):
+        if rng.random() < 0.35:
+            return 0, 0
+        return int(rng.choice([0, 2, 4, 1, 3])), 4 * int(rng.integers(0, 4))
+
+    def dev(shape, fill, pad, off):
+        rows, w, comps = shape if len(shape) == 3 else shape + (1,)
+        rs = w * comps + pad
+        a = DevArray(hl, (rows, w * comps), f32, row_stride=rs, offset=off, fill=None if fill is None else fill.reshape(rows, w * comps))
+        a.buf.device_detach()
+        a.buf = hl.Buffer.wrap_device(a.p.value + off, f32, [w, rows, comps], [comps, rs, 1])
+        return a
+
+    li, lo = lay(ishape[-1]), lay(oshape[-1])
+    i, o = dev(x.shape, x, *li), dev(oshape, None, *lo)
+    try:
+        (hl.debug_fft2d_general if general else hl.fft2d)(kind, i.buf, o.buf, gain, sizes=(n0, n1))
+        got = o.result().reshape(oshape)
+        i.result()
+    finally:
+        i.free(), o.free()
+    nan = np.isnan(want)
+    ok = bool(np.isnan(got[nan]).all()) and np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
+    desc = (f"fft {kind}{' general' if general else ''} {n0} x {n1} gain {gain}{' special values' if special else ''}{f' +{extra} NaN rows' if extra else ''}, "
+            f"(row pad, byte offset) input {li} output {lo}")
+    return desc, ok
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
@@ -681,6 +746,7 @@ CASES["compositing"] = fuzz_compositing   # integer throughout: its checker (tes
 CASES["hexagon_benchmarks"] = fuzz_hexagon_benchmarks   # all six entry points; integer throughout (tests/hexagon_benchmarks_checker.py)
 CASES["mat_mul"] = fuzz_mat_mul   # sized and general paths; one chain in both canonical forms (tests/mat_mul_checker.py)
 CASES["linear_algebra"] = fuzz_linear_algebra   # all twelve entry points, both paths (tests/linear_algebra_checker.py)
+CASES["fft"] = fuzz_fft   # all four kinds, both paths (tests/fft_checker.py)
 
 
 def stress(args, only):
