@@ -22,6 +22,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md
 VALU_F32_PEAK_TF = 157.3       # packed-FMA vector peak
 MFMA_BF16_PEAK_TF = 2500.0     # dense
 MFMA_F32_PEAK_TF = 157.3
+VALU_F64_PEAK_TF = 78.6        # the vendor's published f64 vector figure; scripts/ubench/valu_f64.hip measures the issue rate behind it
 
 
 def cpu_time(fn, budget_s=4.0, max_reps=8):
@@ -738,6 +739,93 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
             xm, ym, R = dev(mk(m)), dev(mk(m)), dev(mk(m, m))
             line(f"sger_{m}x{m}", f"apps/linear_algebra halide_sger_impl, {m}x{m} in place", lambda: hl.sger(2.0 ** -20, xm, ym, R),
                  lambda: G("halide_sger_impl", 2.0 ** -20, xm, ym, R), R, 8.0 * m * m + 8.0 * m, m * m, 50)
+            for b_ in (x, y, o, s, xm, ym, R):
+                b_.device_free()
+
+    # ---- linear_algebra, the f64 half: the blocks above at T = double.  "dgemm": the same shapes, each beside its one-thread-per-output
+    #      path (which the plan's choice must beat) and beside torch.addmm in float64 on the same operands (recorded, not thresholded:
+    #      it is not bound to the contract's order).  "linear_algebra_f64": dgemv (both), the vector routines and dger at the f32
+    #      block's element counts; for ddot, dasum and dgemv_notrans the contract's chain length is in the line ("chain_steps", V = 4).
+    if not only or "dgemm" in only or "linear_algebra_f64" in only:
+        import torch
+        D = np.float64
+        mkd = lambda *s: rng.random(s) * 2 - 1
+
+        def devd(m):
+            b = hl.Buffer(m)
+            b.copy_to_device()
+            return b
+
+    if not only or "dgemm" in only:
+        cases = [(ta, tb, n, n, n) for n in (768, 1024) for ta in (0, 1) for tb in (0, 1)] + [(0, 0, 4096, 4096, 4096), (0, 0, 4096, 512, 1024)]
+        for ta, tb, M, N, K in cases:
+            name = hl.dgemm_name(ta, tb)
+            A, B, Cm = devd(mkd(K, M)), devd(mkd(N, K)), devd(mkd(N, M))
+            o = hl.Buffer(np.zeros((N, M), D))
+            iters = 5 if M * N * K >= 2 ** 34 else 50
+            t = timed(lambda: hl.dgemm(ta, tb, 0.75, A, B, -1.5, Cm, o), o, iters)
+            clock = last_clock[0]
+            tg = timed(lambda: hl.debug_linear_algebra_general_f64(name, 0.75, A, B, -1.5, Cm, o), o, max(2, iters // 10))
+            extra = {"general_ms_per_call": round(tg * 1e3, 4), "default_over_general": round(t / tg, 4), "canon_fma": hl.canon_fma()}
+            tA, tB, tC = (torch.from_numpy(x.array).cuda() for x in (A, B, Cm))
+            opA, opB = (tA if ta else tA.T), (tB if tb else tB.T)   # (M, K) and (K, N) in torch's terms
+            torch.addmm(tC.T, opA, opB, beta=-1.5, alpha=0.75)
+            torch.cuda.synchronize()
+            tt = 1e30
+            for _ in range(args.samples):
+                t0 = time.perf_counter()
+                for _ in range(iters):
+                    torch.addmm(tC.T, opA, opB, beta=-1.5, alpha=0.75)
+                torch.cuda.synchronize()
+                tt = min(tt, (time.perf_counter() - t0) / iters)
+            del tA, tB, tC, opA, opB
+            extra["torch_addmm_f64_ms_per_call"] = round(tt * 1e3, 4)
+            last_clock[0] = clock
+            emit(f"dgemm_{name[13:]}_{M}x{N}x{K}", f"apps/linear_algebra {name}, M {M} N {N} K {K}, noise in [-1, 1), a 0.75 b -1.5", t, M * N, "valu_f64",
+                 2.0 * M * N * K / t / 1e12, VALU_F64_PEAK_TF, "TFLOP/s", extra)
+            for x in (A, B, Cm, o):
+                x.device_free()
+
+    if not only or "linear_algebra_f64" in only:
+        def line64(label, what, call, general, sync, nbytes, outputs, iters, more=None):
+            t = timed(call, sync, iters)
+            clock = last_clock[0]
+            tg = timed(general, sync, max(1, iters // 10))
+            last_clock[0] = clock
+            extra = {"general_ms_per_call": round(tg * 1e3, 4), "default_over_general": round(t / tg, 4), "moved_bytes": nbytes, **(more or {})}
+            if "chain_steps" in extra:
+                extra["ns_per_chain_step"] = round(t * 1e9 / extra["chain_steps"], 3)
+            if copy_gbs[0]:
+                extra["copy_frac"] = round(nbytes / t / 1e9 / copy_gbs[0], 4)
+            emit(label, what, t, outputs, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s", extra)
+
+        G64 = hl.debug_linear_algebra_general_f64
+        for n in (768, 4096, 8192):
+            A, x, y, o = devd(mkd(n, n)), devd(mkd(n)), devd(mkd(n)), hl.Buffer(np.zeros(n, D))
+            nbytes = 8.0 * (n * n + 3 * n)
+            line64(f"dgemv_notrans_{n}", f"apps/linear_algebra halide_dgemv_notrans, {n}x{n}", lambda: hl.dgemv(False, 0.75, A, x, -1.5, y, o),
+                   lambda: G64("halide_dgemv_notrans", 0.75, A, x, -1.5, y, o), o, nbytes, n, 50, {"chain_steps": n})
+            line64(f"dgemv_trans_{n}", f"apps/linear_algebra halide_dgemv_trans, {n}x{n}", lambda: hl.dgemv(True, 0.75, A, x, -1.5, y, o),
+                   lambda: G64("halide_dgemv_trans", 0.75, A, x, -1.5, y, o), o, nbytes, n, 50, {"chain_steps": n // 4 + 4})
+            for b_ in (A, x, y, o):
+                b_.device_free()
+        for lg in (20, 24):
+            n = 1 << lg
+            x, y, o, s = devd(mkd(n)), devd(mkd(n)), hl.Buffer(np.zeros(n, D)), hl.Buffer(np.zeros((), D))
+            line64(f"dcopy_2^{lg}", f"apps/linear_algebra halide_dcopy_impl, n 2^{lg}", lambda: hl.dcopy(x, o), lambda: G64("halide_dcopy_impl", 0.0, x, None, o), o, 16.0 * n, n, 50)
+            line64(f"dscal_2^{lg}", f"apps/linear_algebra halide_dscal_impl, n 2^{lg}", lambda: hl.dscal(0.75, x, o), lambda: G64("halide_dscal_impl", 0.75, x, None, o), o,
+                   16.0 * n, n, 50)
+            line64(f"daxpy_2^{lg}", f"apps/linear_algebra halide_daxpy_impl, n 2^{lg}", lambda: hl.daxpy(0.75, x, y, o), lambda: G64("halide_daxpy_impl", 0.75, x, y, o), o,
+                   24.0 * n, n, 50)
+            slow = 2 if lg == 24 else 10
+            line64(f"ddot_2^{lg}", f"apps/linear_algebra halide_ddot, n 2^{lg}: one wave, 4 chains", lambda: hl.ddot(x, y, s), lambda: G64("halide_ddot", x, y, s), s, 16.0 * n, 1,
+                   slow, {"chain_steps": n // 4})
+            line64(f"dasum_2^{lg}", f"apps/linear_algebra halide_dasum, n 2^{lg}: one wave, 4 chains", lambda: hl.dasum(x, s), lambda: G64("halide_dasum", x, s), s, 8.0 * n, 1,
+                   slow, {"chain_steps": n // 4})
+            m = 1 << (lg // 2)
+            xm, ym, R = devd(mkd(m)), devd(mkd(m)), devd(mkd(m, m))
+            line64(f"dger_{m}x{m}", f"apps/linear_algebra halide_dger_impl, {m}x{m} in place", lambda: hl.dger(2.0 ** -20, xm, ym, R),
+                   lambda: G64("halide_dger_impl", 2.0 ** -20, xm, ym, R), R, 16.0 * m * m + 16.0 * m, m * m, 50)
             for b_ in (x, y, o, s, xm, ym, R):
                 b_.device_free()
 

@@ -412,7 +412,7 @@ def _bind(name):
     md = metadata(name)
     argtypes = []
     for a in (md.arguments[i] for i in range(md.num_arguments)):
-        t = _BP if a.kind != 0 else {(2, 32): C.c_float, (0, 32): C.c_int32}.get((a.type.code, a.type.bits))
+        t = _BP if a.kind != 0 else {(2, 32): C.c_float, (2, 64): C.c_double, (0, 32): C.c_int32}.get((a.type.code, a.type.bits))
         if t is None:
             raise ImportError(f"{name}: no ctypes type for scalar argument {a.name.decode()} (type code {a.type.code}, {a.type.bits} bits)")
         argtypes.append(t)
@@ -439,7 +439,10 @@ _fn = {name: _bind(name) for name in
        + ["fft_forward_r2c", "fft_inverse_c2r", "fft_forward_c2c", "fft_inverse_c2c"]
        + ["halide_scopy_impl", "halide_sscal_impl", "halide_saxpy_impl", "halide_sdot", "halide_sasum", "halide_sgemv_notrans",
           "halide_sgemv_trans", "halide_sger_impl", "halide_sgemm_notrans", "halide_sgemm_transA", "halide_sgemm_transB",
-          "halide_sgemm_transAB"]}
+          "halide_sgemm_transAB"]
+       + ["halide_dcopy_impl", "halide_dscal_impl", "halide_daxpy_impl", "halide_ddot", "halide_dasum", "halide_dgemv_notrans",
+          "halide_dgemv_trans", "halide_dger_impl", "halide_dgemm_notrans", "halide_dgemm_transA", "halide_dgemm_transB",
+          "halide_dgemm_transAB"]}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -936,6 +939,77 @@ def debug_sgemv_general(trans, a, A, x, b, y, output=None) -> int:
     return debug_linear_algebra_general("halide_sgemv_trans" if trans else "halide_sgemv_notrans", a, A, x, b, y, y if output is None else output)
 
 
+# apps/linear_algebra, the f64 half: the same calls on float64 buffers with double scalars; the lane width of ddot, dasum and dgemv_trans
+# is LINEAR_ALGEBRA_F64_V = 4 (natural_vector_size(double) of the reference's AVX2 build), against 8 for the f32 half.
+LINEAR_ALGEBRA_F64 = ("halide_dcopy_impl", "halide_dscal_impl", "halide_daxpy_impl", "halide_ddot", "halide_dasum", "halide_dgemv_notrans",
+                      "halide_dgemv_trans", "halide_dger_impl", "halide_dgemm_notrans", "halide_dgemm_transA", "halide_dgemm_transB",
+                      "halide_dgemm_transAB")
+LINEAR_ALGEBRA_F64_V = 4
+
+
+def dcopy(x, result) -> int:
+    """result(i) = x(i)"""
+    return _check(_fn["halide_dcopy_impl"](0.0, _as_ptr(x), None, _as_ptr(result)))
+
+
+def dscal(a, x, result=None) -> int:
+    """result(i) = a * x(i); in place on x by default"""
+    return _check(_fn["halide_dscal_impl"](float(a), _as_ptr(x), None, _as_ptr(x if result is None else result)))
+
+
+def daxpy(a, x, y, result=None) -> int:
+    """result(i) = a * x(i) + y(i); in place on y by default"""
+    return _check(_fn["halide_daxpy_impl"](float(a), _as_ptr(x), _as_ptr(y), _as_ptr(y if result is None else result)))
+
+
+def ddot(x, y, result) -> int:
+    """result() = the V = 4 lane-chain dot product of the contract; result is a 0-dimensional buffer"""
+    return _check(_fn["halide_ddot"](_as_ptr(x), _as_ptr(y), _as_ptr(result)))
+
+
+def dasum(x, result) -> int:
+    """result() = the sum of |x(i)| in the contract's order"""
+    return _check(_fn["halide_dasum"](_as_ptr(x), _as_ptr(result)))
+
+
+def dgemv(trans, a, A, x, b, y, output=None) -> int:
+    """output = a op(A) x + b y for A of extents (M, N): notrans x[N], y[M]; trans x[M], y[N]; in place on y by default"""
+    name = "halide_dgemv_trans" if trans else "halide_dgemv_notrans"
+    return _check(_fn[name](float(a), _as_ptr(A), _as_ptr(x), float(b), _as_ptr(y), _as_ptr(y if output is None else output)))
+
+
+def dger(a, x, y, result) -> int:
+    """result(i, j) += (a * y(j)) * x(i), in place"""
+    return _check(_fn["halide_dger_impl"](float(a), _as_ptr(x), _as_ptr(y), _as_ptr(result)))
+
+
+def dgemm_name(transA, transB) -> str:
+    return "halide_dgemm_" + ("transAB" if transA and transB else "transA" if transA else "transB" if transB else "notrans")
+
+
+def dgemm(transA, transB, a, A, B, b, C, result=None) -> int:
+    """result = a op(A) op(B) + b C, k upward; a transposed operand must be square; in place on C by default"""
+    return _check(_fn[dgemm_name(transA, transB)](float(a), _as_ptr(A), _as_ptr(B), float(b), _as_ptr(C), _as_ptr(C if result is None else result)))
+
+
+def debug_linear_algebra_general_f64(name: str, *args) -> int:
+    """Test and measurement hook: the entry point `name` of LINEAR_ALGEBRA_F64, with the arguments of its C signature in order, with
+    one thread per output running the chain as written."""
+    if name not in LINEAR_ALGEBRA_F64:
+        raise ValueError(f"no f64 linear_algebra entry point named {name}")
+    md = metadata(name)
+    if len(args) != md.num_arguments:
+        raise TypeError(f"{name} takes {md.num_arguments} arguments, not {len(args)}")
+    scalars = [float(v) for v, i in zip(args, range(md.num_arguments)) if md.arguments[i].kind == 0]
+    bufs = [_as_ptr(v) for v, i in zip(args, range(md.num_arguments)) if md.arguments[i].kind != 0]
+    a, b = (scalars + [0.0, 0.0])[:2]
+    bufs += [None] * (4 - len(bufs))
+    fn = lib.hlmi_linear_algebra_general_f64
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, C.c_double, C.c_double, _BP, _BP, _BP, _BP]
+    return _check(fn(name.encode(), a, b, *bufs))
+
+
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:
     return _check(_fn["lens_blur"](_as_ptr(left_im), _as_ptr(right_im), int(slices), int(focus_depth), float(blur_radius_scale),
                         int(aperture_samples), _as_ptr(final)))
@@ -978,7 +1052,7 @@ def run_batch(name: str, frames, devices=None, streams_per_device: int = 1) -> i
         for j, v in enumerate(frame):
             a = md.arguments[j]
             if a.kind == 0:
-                box = C.c_float(v) if a.type.code == 2 else (C.c_int32(v) if a.type.bits == 32 else C.c_int64(v))
+                box = (C.c_double(v) if a.type.bits == 64 else C.c_float(v)) if a.type.code == 2 else (C.c_int32(v) if a.type.bits == 32 else C.c_int64(v))
                 keep.append(box)
                 argv[j] = C.cast(C.pointer(box), C.c_void_p)
             else:

@@ -36,6 +36,9 @@ constexpr bool CANON_FMA = HLMI_CANON_FMA != 0;
 __device__ __forceinline__ float mad(float a, float b, float c) { return CANON_FMA ? __builtin_fmaf(a, b, c) : a * b + c; }
 // a * b + c * d: the first product is the one contracted
 __device__ __forceinline__ float mad2(float a, float b, float c, float d) { return CANON_FMA ? __builtin_fmaf(a, b, c * d) : a * b + c * d; }
+// the same two forms in binary64 (linear_algebra_f64.hip)
+__device__ __forceinline__ double mad(double a, double b, double c) { return CANON_FMA ? __builtin_fma(a, b, c) : a * b + c; }
+__device__ __forceinline__ double mad2(double a, double b, double c, double d) { return CANON_FMA ? __builtin_fma(a, b, c * d) : a * b + c * d; }
 // c - a * b
 __device__ __forceinline__ float msub(float c, float a, float b) { return CANON_FMA ? __builtin_fmaf(-a, b, c) : c - a * b; }
 // a * b - c

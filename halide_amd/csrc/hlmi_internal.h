@@ -36,7 +36,7 @@ int hip_failed(void *uc, hipError_t e, const char *what);  // -> halide_error_co
 // ABI helpers
 constexpr uint32_t type_abi(int code, int bits) { return (uint32_t)code | ((uint32_t)bits << 8); }
 constexpr uint32_t T_U8 = type_abi(1, 8), T_I8 = type_abi(0, 8), T_U16 = type_abi(1, 16), T_I16 = type_abi(0, 16),
-                   T_I32 = type_abi(0, 32), T_F32 = type_abi(2, 32);
+                   T_I32 = type_abi(0, 32), T_F32 = type_abi(2, 32), T_F64 = type_abi(2, 64);
 inline uint32_t buf_type_abi(const halide_buffer_t *b) {
     uint32_t v;
     memcpy(&v, &b->type, 4);
@@ -69,13 +69,14 @@ struct Arg {
     unsigned has;       // scalars: bit DEF / MIN / MAX / EST set = sv[that] given
     halide_scalar_value_t sv[4];
     enum { DEF, MIN, MAX, EST };
-    Arg &set(int which, double v) {   // stored as the argument's own type (every scalar here is an int32 or a float)
+    Arg &set(int which, double v) {   // stored as the argument's own type (every scalar here is an int32, a float or a double)
         has |= 1u << which;
         if (type == T_F32) sv[which].u.f32 = (float)v;
+        else if (type == T_F64) sv[which].u.f64 = v;
         else sv[which].u.i32 = (int32_t)v;
         return *this;
     }
-    double get(int which) const { return type == T_F32 ? (double)sv[which].u.f32 : (double)sv[which].u.i32; }
+    double get(int which) const { return type == T_F32 ? (double)sv[which].u.f32 : type == T_F64 ? sv[which].u.f64 : (double)sv[which].u.i32; }
     Arg &def(double v) { return set(DEF, v); }
     Arg &range(double lo, double hi) { return set(MIN, lo).set(MAX, hi); }
     Arg &estimate(double v) { return set(EST, v); }
@@ -94,6 +95,7 @@ inline Arg out_buf(const char *name, uint32_t type, int dims, std::initializer_l
     return make_arg(name, halide_argument_kind_output_buffer, type, dims, est);
 }
 inline Arg scalar_f32(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_F32, 0); }
+inline Arg scalar_f64(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_F64, 0); }
 inline Arg scalar_i32(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_I32, 0); }
 
 // One entry point's table and everything RunGen's structs point into, built once from the table and never per call.  Initialised
@@ -425,6 +427,9 @@ extern "C" int hlmi_mat_mul_general(int32_t size, halide_buffer_t *A, halide_buf
 // order, the unused trailing ones null; a and b are read where the entry point has them.  Per call: no mode is kept anywhere.
 extern "C" int hlmi_linear_algebra_general(const char *name, float a, float b, halide_buffer_t *p0, halide_buffer_t *p1, halide_buffer_t *p2,
                                            halide_buffer_t *p3);
+// linear_algebra_f64.hip: the same hook for the twelve f64 entry points ("halide_ddot", "halide_dgemm_transA", ...)
+extern "C" int hlmi_linear_algebra_general_f64(const char *name, double a, double b, halide_buffer_t *p0, halide_buffer_t *p1, halide_buffer_t *p2,
+                                               halide_buffer_t *p3);
 
 // fft.hip: the fft generator instantiated at other sizes and gains (fft_forward_c2c is hlmi_fft2d(0, 16, 16, 1 / 256, ...)): the same
 // shim, plan and rules.  kind: 0 c2c forward, 1 c2c inverse, 2 r2c, 3 c2r; N0, N1 in 2 .. 4096 with radix factors 8, 6, 4, 2 only, both

@@ -35,10 +35,12 @@
 #include "hlmi_blas.h"
 #include "hlmi_device_math.h"
 #include "hlmi_internal.h"
+#include "linear_algebra_host.h"
 
 #include <math.h>
 
 using namespace hlmi;
+using namespace hlmi::la_host;
 
 namespace {
 
@@ -488,85 +490,7 @@ const ArgTable sger_table("halide_sger_impl", {scalar_f32("a"), in_buf("x", T_F3
 const ArgTable sgemm_tables[4] = {{"halide_sgemm_notrans", HLMI_SGEMM_ARGS}, {"halide_sgemm_transA", HLMI_SGEMM_ARGS},
                                   {"halide_sgemm_transB", HLMI_SGEMM_ARGS}, {"halide_sgemm_transAB", HLMI_SGEMM_ARGS}};   // index: tA + 2 * tB
 
-// ---------------------------------------------------------------------------------------------------------------- host: checks
-bool aligned16(const void *p) { return (uintptr_t)p % 16 == 0; }
-
-// elements from a buffer's first to one past its last, 0 for an empty one (dimension 0 has stride 1)
-uintptr_t span_elems(const halide_buffer_t *b) {
-    uintptr_t n = 1;
-    for (int d = 0; d < b->dimensions; d++) {
-        if (b->dim[d].extent <= 0) return 0;
-        n += (uintptr_t)(b->dim[d].extent - 1) * (uintptr_t)b->dim[d].stride;
-    }
-    return n;
-}
-
-bool same_layout(const halide_buffer_t *a, const halide_buffer_t *b) {
-    if (a->dimensions != b->dimensions) return false;
-    for (int d = 0; d < a->dimensions; d++)
-        if (a->dim[d].extent != b->dim[d].extent || a->dim[d].stride != b->dim[d].stride) return false;
-    return true;
-}
-
-// mat_mul.hip's overlap() for any shape: do the byte ranges of a and b meet, in host or in device memory.  With `exact_ok`, a that IS
-// b — the same first element and the same layout, the call every wrapper of halide_blas.h makes — does not count.
-bool overlap(const halide_buffer_t *a, const halide_buffer_t *b, bool exact_ok) {
-    if (a == b) return !exact_ok;
-    const uintptr_t na = 4 * span_elems(a), nb = 4 * span_elems(b);
-    auto hit = [&](uintptr_t pa, uintptr_t pb) {
-        if (!pa || !pb || !na || !nb) return false;
-        if (exact_ok && pa == pb && same_layout(a, b)) return false;
-        return pa < pb + nb && pb < pa + na;
-    };
-    return hit((uintptr_t)a->host, (uintptr_t)b->host) || hit((uintptr_t)a->device, (uintptr_t)b->device);
-}
-
-// records: min == 0, extent == the named value, and for a matrix a column stride that keeps columns apart
-void pin(void *uc, const BufArg &a, int d, int extent, const char *extent_name) {
-    char what[40], expect[64];
-    snprintf(what, sizeof what, "%s.min.%d", a.name, d);
-    check_equal(uc, what, a.buf->dim[d].min, "0", 0);
-    snprintf(what, sizeof what, "%s.extent.%d", a.name, d);
-    check_equal(uc, what, a.buf->dim[d].extent, extent_name, extent);
-    if (d == 1) {
-        snprintf(what, sizeof what, "%s.stride.1", a.name);
-        snprintf(expect, sizeof expect, "max(%s.stride.1, %s.extent.0)", a.name, a.name);
-        check_equal(uc, what, a.buf->dim[1].stride, expect, std::max(a.buf->dim[1].stride, a.buf->dim[0].extent));
-    }
-}
-
-// an extent the call derives its sizes from: the first of `cands` (buffer, dimension) that is real or, in a query, shaped; else 0
-struct Cand {
-    const halide_buffer_t *b;
-    int d;
-};
-int derive(std::initializer_list<Cand> cands) {
-    for (const Cand &c : cands)
-        if (c.b && buffer_known(c.b)) return c.b->dim[c.d].extent;
-    return 0;
-}
-
-int limit(void *uc, const char *entry, const char *what, int v, int max) {
-    if (v >= 0 && v <= max) return 0;
-    return report(uc, halide_error_code_constraint_violated, "Constraint violated: %s %s (%d) must be 0 .. %d", entry, what, v, max);
-}
-
-void answer1(halide_buffer_t *b, int n) {
-    const int mins[1] = {0}, ext[1] = {n};
-    answer_query(b, mins, ext);
-}
-void answer2(halide_buffer_t *b, int w, int h) {
-    const int mins[2] = {0, 0}, ext[2] = {w, h};
-    answer_query(b, mins, ext);
-}
-
-// null, type, dimensionality; returns 1 for a bounds query (the caller answers it), < 0 for an error
-int prologue(void *uc, const BufArg *args, int n) {
-    int r = check_not_null(uc, args, n);
-    if (r) return r;
-    if ((r = check_type_and_dims(uc, args, n))) return r;
-    return any_bounds_query(args, n) ? 1 : 0;
-}
+// the host-side checks (alignment, overlap, pins, derived extents, limits, query answers): linear_algebra_host.h, shared with the f64 half
 
 // ---------------------------------------------------------------------------------------------------------------- host: scopy, sscal, saxpy, sger
 enum ElemLaunch { EL_VEC4, EL_SCALAR, EL_GENERAL };
@@ -778,8 +702,6 @@ constexpr int gemm_tile(int M, int N) {
     return ((M + LARGE_TILE - 1) / LARGE_TILE) * ((N + LARGE_TILE - 1) / LARGE_TILE) >= LARGE_FROM_WGS ? LARGE_TILE : SMALL_TILE;
 }
 
-bool aligned16(const void *p, long col_stride) { return aligned16(p) && col_stride % 4 == 0; }
-
 // THE predicate.  The MFMA is a chain of fused steps: it is the contract's chain in the default build only, and needs one step at least.
 // There the aligned kernel takes a call whose M and N are multiples of its tile and whose K is one of KC, with all four buffers on 16
 // bytes and column strides a multiple of 16 bytes; the edge variant takes every other call; the general kernel runs where the caller
@@ -787,8 +709,8 @@ bool aligned16(const void *p, long col_stride) { return aligned16(p) && col_stri
 GemmPlan gemm_plan(const GGeom &g, bool general_only) {
     const int tile = gemm_tile(g.M, g.N);
     if (general_only || !dev::CANON_FMA || g.K == 0) return {GM_GENERAL, tile};
-    const bool fast = g.M % tile == 0 && g.N % tile == 0 && g.K % KC == 0 && aligned16(g.A, g.sa) && aligned16(g.B, g.sb) && aligned16(g.C, g.sc) &&
-                      aligned16(g.out, g.so);
+    const bool fast = g.M % tile == 0 && g.N % tile == 0 && g.K % KC == 0 && aligned16(g.A, g.sa, 4) && aligned16(g.B, g.sb, 4) && aligned16(g.C, g.sc, 4) &&
+                      aligned16(g.out, g.so, 4);
     return {fast ? GM_MFMA : GM_MFMA_EDGE, tile};
 }
 

@@ -22,7 +22,8 @@ import torch
 
 import halide_amd as hl
 
-_NP = {torch.uint8: np.uint8, torch.uint16: np.uint16, torch.int16: np.int16, torch.int32: np.int32, torch.float32: np.float32}
+_NP = {torch.uint8: np.uint8, torch.uint16: np.uint16, torch.int16: np.int16, torch.int32: np.int32, torch.float32: np.float32,
+       torch.float64: np.float64}
 
 
 class _Wrapped:
@@ -487,6 +488,87 @@ def sgemm(transA: bool, transB: bool, a: float, A: torch.Tensor, B: torch.Tensor
     return out
 
 
+# ---- the f64 half: the same six forms over float64 tensors
+def _la_check_f64(what, *pairs):
+    """pairs: (tensor, number of dimensions); a float32 tensor is refused, not converted"""
+    for t, nd in pairs:
+        if t.dim() != nd or t.dtype != torch.float64:
+            raise TypeError(f"{what} takes float64 tensors of {', '.join(str(n) for _, n in pairs)} dimensions")
+
+
+@torch.library.custom_op("hlmi::daxpy", mutates_args=())
+def daxpy(a: float, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """a * x + y over two float64 vectors of one length"""
+    _la_check_f64("daxpy", (x, 1), (y, 1))
+    if x.shape != y.shape:
+        raise TypeError("daxpy takes two vectors of one length")
+    out = torch.empty_like(y, memory_format=torch.contiguous_format)
+    with _Wrapped(x, y, out) as (bx, by, bo):
+        hl.daxpy(a, bx, by, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::ddot", mutates_args=())
+def ddot(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """the dot product in the contract's order (four lane chains, their sum, the tail): a 0-dimensional tensor"""
+    _la_check_f64("ddot", (x, 1), (y, 1))
+    if x.shape != y.shape:
+        raise TypeError("ddot takes two vectors of one length")
+    out = torch.empty((), dtype=torch.float64, device=x.device)
+    with _Wrapped(x, y, out) as (bx, by, bo):
+        hl.ddot(bx, by, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::dasum", mutates_args=())
+def dasum(x: torch.Tensor) -> torch.Tensor:
+    """the sum of |x| in the contract's order: a 0-dimensional tensor"""
+    _la_check_f64("dasum", (x, 1))
+    out = torch.empty((), dtype=torch.float64, device=x.device)
+    with _Wrapped(x, out) as (bx, bo):
+        hl.dasum(bx, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::dgemv", mutates_args=())
+def dgemv(trans: bool, a: float, A: torch.Tensor, x: torch.Tensor, b: float, y: torch.Tensor) -> torch.Tensor:
+    """a op(A) x + b y for A of shape (h, w): notrans x[h], y[w]; trans x[w], y[h]"""
+    _la_check_f64("dgemv", (A, 2), (x, 1), (y, 1))
+    h, w = A.shape
+    if (x.shape[0], y.shape[0]) != ((w, h) if trans else (h, w)):
+        raise TypeError("dgemv: the vectors do not fit the matrix")
+    out = torch.empty_like(y, memory_format=torch.contiguous_format)
+    with _Wrapped(A, x, y, out) as (bA, bx, by, bo):
+        hl.dgemv(trans, a, bA, bx, b, by, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::dger", mutates_args=())
+def dger(a: float, x: torch.Tensor, y: torch.Tensor, A: torch.Tensor) -> torch.Tensor:
+    """A + a x y' for x[m], y[n] and A of shape (n, m)"""
+    _la_check_f64("dger", (x, 1), (y, 1), (A, 2))
+    if tuple(A.shape) != (y.shape[0], x.shape[0]):
+        raise TypeError("dger: the vectors do not fit the matrix")
+    out = A.clone(memory_format=torch.contiguous_format)
+    with _Wrapped(x, y, out) as (bx, by, bo):
+        hl.dger(a, bx, by, bo)
+    return out
+
+
+@torch.library.custom_op("hlmi::dgemm", mutates_args=())
+def dgemm(transA: bool, transB: bool, a: float, A: torch.Tensor, B: torch.Tensor, b: float, C: torch.Tensor) -> torch.Tensor:
+    """a op(A) op(B) + b C with k upward; A of shape (K, M) as stored, B (N, K), C (N, M); a transposed operand must be square"""
+    _la_check_f64("dgemm", (A, 2), (B, 2), (C, 2))
+    K, M = A.shape
+    N = B.shape[0]
+    if B.shape[1] != K or tuple(C.shape) != (N, M) or (transA and M != K) or (transB and N != K):
+        raise TypeError("dgemm: the shapes do not fit (A (K, M), B (N, K), C (N, M); a transposed operand is square)")
+    out = torch.empty((N, M), dtype=torch.float64, device=C.device)
+    with _Wrapped(A, B, C, out) as (bA, bB, bC, bo):
+        hl.dgemm(transA, transB, a, bA, bB, b, bC, bo)
+    return out
+
+
 @torch.library.custom_op("hlmi::conv3x3a16", mutates_args=())
 def conv3x3a16(input: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     """apps/hexagon_benchmarks: (H, W) uint8 under a (3, 3) int8 mask (mask[i][j] multiplies in(x + j - 1, y + i - 1)), the sum wrapped
@@ -662,6 +744,36 @@ def _(a, x, y, A):
 
 
 @sgemm.register_fake
+def _(transA, transB, a, A, B, b, C):
+    return C.new_empty(tuple(C.shape))
+
+
+@daxpy.register_fake
+def _(a, x, y):
+    return y.new_empty(tuple(y.shape))
+
+
+@ddot.register_fake
+def _(x, y):
+    return x.new_empty(())
+
+
+@dasum.register_fake
+def _(x):
+    return x.new_empty(())
+
+
+@dgemv.register_fake
+def _(trans, a, A, x, b, y):
+    return y.new_empty(tuple(y.shape))
+
+
+@dger.register_fake
+def _(a, x, y, A):
+    return A.new_empty(tuple(A.shape))
+
+
+@dgemm.register_fake
 def _(transA, transB, a, A, B, b, C):
     return C.new_empty(tuple(C.shape))
 

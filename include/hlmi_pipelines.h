@@ -501,6 +501,43 @@ int halide_sgemm_transAB(float a, struct halide_buffer_t *A, struct halide_buffe
                          struct halide_buffer_t *result);
 HLMI_DECLARE_AUX(halide_sgemm_transAB)
 
+/* The f64 half of apps/linear_algebra: the twelve `halide_d*` objects of src/CMakeLists.txt, the same generators at T = double (here:
+ * hlmi_blas.h adds the wrappers and the hblas_d* calls).  The contract is the one above with three differences: every buffer is float64,
+ * the scalars a and b are doubles, and V = 4, the natural_vector_size(double) of the reference's x86-64 AVX2 build — ddot, dasum and
+ * dgemv_trans keep four lane chains.  mad and mad2 are the same two forms in binary64.  Shapes, aliasing, limits (vector lengths
+ * 0 .. 2^27, matrix extents 0 .. 8192), empty outputs (ddot and dasum of nothing write the eight bytes of +0) and bounds queries are
+ * as for the f32 half. */
+int halide_dcopy_impl(double a, struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_dcopy_impl)
+int halide_dscal_impl(double a, struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_dscal_impl)
+int halide_daxpy_impl(double a, struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_daxpy_impl)
+int halide_ddot(struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_ddot)
+int halide_dasum(struct halide_buffer_t *x, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_dasum)
+int halide_dgemv_notrans(double a, struct halide_buffer_t *A, struct halide_buffer_t *x, double b, struct halide_buffer_t *y,
+                         struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(halide_dgemv_notrans)
+int halide_dgemv_trans(double a, struct halide_buffer_t *A, struct halide_buffer_t *x, double b, struct halide_buffer_t *y,
+                       struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(halide_dgemv_trans)
+int halide_dger_impl(double a, struct halide_buffer_t *x, struct halide_buffer_t *y, struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_dger_impl)
+int halide_dgemm_notrans(double a, struct halide_buffer_t *A, struct halide_buffer_t *B, double b, struct halide_buffer_t *C,
+                         struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_dgemm_notrans)
+int halide_dgemm_transA(double a, struct halide_buffer_t *A, struct halide_buffer_t *B, double b, struct halide_buffer_t *C,
+                         struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_dgemm_transA)
+int halide_dgemm_transB(double a, struct halide_buffer_t *A, struct halide_buffer_t *B, double b, struct halide_buffer_t *C,
+                         struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_dgemm_transB)
+int halide_dgemm_transAB(double a, struct halide_buffer_t *A, struct halide_buffer_t *B, double b, struct halide_buffer_t *C,
+                         struct halide_buffer_t *result);
+HLMI_DECLARE_AUX(halide_dgemm_transAB)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,

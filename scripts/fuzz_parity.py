@@ -672,6 +672,97 @@ def fuzz_linear_algebra(rng):
     return desc, ok
 
 
+def fuzz_linear_algebra_f64(rng):
+    """One of the twelve f64 pipelines of apps/linear_algebra, drawn as fuzz_linear_algebra draws the f32 ones (vectors 0 .. 3000, matrix
+    extents 1 .. 200 within the variant's squareness rule, either path, device allocations with a column stride and a pointer offset
+    of 0 or 8 bytes, a third of the cases in place, a third with special values), against tests/cpp/linear_algebra_f64_check.c
+    (tests/linear_algebra_f64_checker.py) in the library's canonical form.  Bit for bit, NaN for NaN; the bytes around every buffer
+    must come back unchanged."""
+    import linear_algebra_f64_checker as ld
+    f64 = np.float64
+    ld.set_canon(hl.canon_fma())
+    name = ld.NAMES[int(rng.integers(0, len(ld.NAMES)))]
+    general = rng.random() < 0.3
+    a, b = (float(rng.random() * 4 - 2) for _ in range(2))
+    mk = lambda *s: rng.random(s) * 2 - 1
+    gemm = name in ld.GEMM_FLAGS
+    if gemm:
+        ta, tb = ld.GEMM_FLAGS[name]
+        M, N, K = (rdim(rng, 1, 200) for _ in range(3))
+        K = M if ta else K
+        N = K if tb else N
+        ins = {"A_": mk(K, M), "B_": mk(N, K), "C_": mk(N, M)}
+        order, out, alias_of = ("A_", "B_", "C_", "result"), "result", "C_"
+        want = lambda: ld.dgemm(ta, tb, a, ins["A_"], ins["B_"], b, ins["C_"])
+    elif name.startswith("halide_dgemv"):
+        t = name.endswith("_trans")
+        w, h = rdim(rng, 1, 200), rdim(rng, 1, 200)
+        ins = {"A": mk(h, w), "x": mk(w if t else h), "y": mk(h if t else w)}
+        order, out, alias_of = ("A", "x", "y", "output"), "output", "y"
+        want = lambda: ld.dgemv(t, a, ins["A"], ins["x"], b, ins["y"])
+    elif name == "halide_dger_impl":
+        w, h = rdim(rng, 1, 200), rdim(rng, 1, 200)
+        ins = {"x": mk(w), "y": mk(h), "result": mk(h, w)}
+        order, out, alias_of = ("x", "y", "result"), "result", None
+        want = lambda: ld.dger(a, ins["x"], ins["y"], ins["result"])
+    else:
+        n = int(rng.integers(0, 3001))
+        ins = {"x": mk(n)}
+        if name in ("halide_daxpy_impl", "halide_ddot"):
+            ins["y"] = mk(n)
+        order = ("x", "result") if name == "halide_dasum" else ("x", "y", "result")
+        out, alias_of = "result", {"halide_dscal_impl": "x", "halide_daxpy_impl": "y"}.get(name)
+        want = {"halide_dcopy_impl": lambda: ld.dcopy(ins["x"]), "halide_dscal_impl": lambda: ld.dscal(a, ins["x"]),
+                "halide_daxpy_impl": lambda: ld.daxpy(a, ins["x"], ins["y"]), "halide_ddot": lambda: ld.ddot(ins["x"], ins["y"]),
+                "halide_dasum": lambda: ld.dasum(ins["x"])}[name]
+    special = rng.random() < 0.33
+    if special:
+        pool = np.array([0.0, -0.0, 1e-310, -3e-309, np.inf, -np.inf, np.nan, 1.5e308, -1e308, 2.0 ** 600, 2.0 ** -600], f64)
+        for m in ins.values():
+            if m.size:
+                k = int(rng.integers(1, 4))
+                m.reshape(-1)[rng.integers(0, m.size, k)] = rng.choice(pool, k)
+    expect = want()
+    alias = alias_of is not None and rng.random() < 0.33
+    shapes = {k: v.shape for k, v in ins.items()}
+    shapes.setdefault(out, expect.shape)
+    lays, arrs = {}, {}
+    try:
+        for k in order:
+            if k == "y" and k not in ins:
+                arrs[k] = None
+                continue
+            if k == out and alias:
+                arrs[k] = arrs[alias_of]
+                continue
+            s = shapes[k]
+            lays[k] = ((s[1] + int(rng.choice([0, 2, 1, 3]))) if len(s) == 2 else None, 8 * int(rng.integers(0, 2)))
+            arrs[k] = ld.Arr(hl, "dev", s, lays[k][0], lays[k][1], fill=ins.get(k))
+        bufs = [None if arrs[k] is None else arrs[k].buf for k in order]
+        if name in ("halide_ddot", "halide_dasum"):
+            args = bufs
+        elif gemm or name.startswith("halide_dgemv"):
+            args = [a, bufs[0], bufs[1], b, bufs[2], bufs[3]]
+        else:
+            args = [a] + bufs
+        if general:
+            hl.debug_linear_algebra_general_f64(name, *args)
+        else:
+            hl._check(hl._fn[name](*[v.ptr if isinstance(v, hl.Buffer) else v for v in args]))
+        got = np.asarray(arrs[out].result()).reshape(expect.shape)
+        for k, v in arrs.items():
+            if v is not None and v is not arrs[out]:
+                v.result()   # the inputs and the bytes around them are as they were
+    finally:
+        for v in {id(v): v for v in arrs.values() if v is not None}.values():
+            v.free()
+    nan = np.isnan(expect)
+    ok = bool(np.isnan(got[nan]).all()) and np.array_equal(got.view(np.uint64)[~nan], expect.view(np.uint64)[~nan])
+    desc = (f"{name}{' general' if general else ''} shapes {shapes} a {a} b {b}{' special values' if special else ''}{' in place' if alias else ''}, "
+            f"(column stride, byte offset) {lays}")
+    return desc, ok
+
+
 FFT_SIZES = [n for n in range(2, 4097) if n <= 256 or n in (384, 512, 768, 1024, 2048, 4096)]
 
 
@@ -746,6 +837,7 @@ CASES["compositing"] = fuzz_compositing   # integer throughout: its checker (tes
 CASES["hexagon_benchmarks"] = fuzz_hexagon_benchmarks   # all six entry points; integer throughout (tests/hexagon_benchmarks_checker.py)
 CASES["mat_mul"] = fuzz_mat_mul   # sized and general paths; one chain in both canonical forms (tests/mat_mul_checker.py)
 CASES["linear_algebra"] = fuzz_linear_algebra   # all twelve entry points, both paths (tests/linear_algebra_checker.py)
+CASES["linear_algebra_f64"] = fuzz_linear_algebra_f64   # the f64 half, both paths (tests/linear_algebra_f64_checker.py)
 CASES["fft"] = fuzz_fft   # all four kinds, both paths (tests/fft_checker.py)
 
 
