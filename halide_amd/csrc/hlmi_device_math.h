@@ -36,7 +36,7 @@ constexpr bool CANON_FMA = HLMI_CANON_FMA != 0;
 __device__ __forceinline__ float mad(float a, float b, float c) { return CANON_FMA ? __builtin_fmaf(a, b, c) : a * b + c; }
 // a * b + c * d: the first product is the one contracted
 __device__ __forceinline__ float mad2(float a, float b, float c, float d) { return CANON_FMA ? __builtin_fmaf(a, b, c * d) : a * b + c * d; }
-// the same two forms in binary64 (linear_algebra_f64.hip)
+// the same two forms in binary64 (linear_algebra_core.h at T = double, linear_algebra_f64.hip)
 __device__ __forceinline__ double mad(double a, double b, double c) { return CANON_FMA ? __builtin_fma(a, b, c) : a * b + c; }
 __device__ __forceinline__ double mad2(double a, double b, double c, double d) { return CANON_FMA ? __builtin_fma(a, b, c * d) : a * b + c * d; }
 // c - a * b

@@ -422,12 +422,12 @@ extern "C" int hlmi_mat_mul_sized(int32_t size, halide_buffer_t *A, halide_buffe
 // and for bench_apps.py.  Per call: no mode is kept anywhere.
 extern "C" int hlmi_mat_mul_general(int32_t size, halide_buffer_t *A, halide_buffer_t *B, halide_buffer_t *out);
 
-// linear_algebra.hip: the named entry point ("halide_sdot", "halide_sgemm_transA", ...) with one thread per output running the chain
+// linear_algebra.hip (body: general_entry of linear_algebra_core.h): the named entry point ("halide_sdot", "halide_sgemm_transA", ...) with one thread per output running the chain
 // as written, for the tests (default == general bit for bit) and for bench_apps.py.  p0 .. p3: the entry point's buffers in its own
 // order, the unused trailing ones null; a and b are read where the entry point has them.  Per call: no mode is kept anywhere.
 extern "C" int hlmi_linear_algebra_general(const char *name, float a, float b, halide_buffer_t *p0, halide_buffer_t *p1, halide_buffer_t *p2,
                                            halide_buffer_t *p3);
-// linear_algebra_f64.hip: the same hook for the twelve f64 entry points ("halide_ddot", "halide_dgemm_transA", ...)
+// linear_algebra_f64.hip: the same general_entry for the twelve f64 entry points ("halide_ddot", "halide_dgemm_transA", ...)
 extern "C" int hlmi_linear_algebra_general_f64(const char *name, double a, double b, halide_buffer_t *p0, halide_buffer_t *p1, halide_buffer_t *p2,
                                                halide_buffer_t *p3);
 
