@@ -16,6 +16,11 @@
 //              [cell][z][12] that every pixel then reads at its own (z, z+1) with ds_read_b128; the x and z lerps run two
 //              channels per instruction (v_pk_mul_f32 / v_pk_add_f32)
 // fast_inverse (:170) is 1/x correctly rounded, as on the reference's CUDA path (src/runtime/ptx_dev.ll:61-66).
+//
+// Host path: bgu() reads top to bottom: check arguments -> device and buffers -> empty output -> plan -> workspace -> stages ->
+// mark_output_written.  bgu_plan() fills a BguPlan (BGeom, SGeom, workspace layout, which slice kernel runs with its LDS size and
+// whether the LDS window must be raised, grids) without a HIP call and refuses what the kernels' arithmetic cannot hold; BguBuffers
+// holds the pointers; bgu_stage_grid (bgu_hist, bgu_fit) and bgu_stage_slice launch from both.
 #include "hlmi_device_math.h"
 #include "hlmi_internal.h"
 
@@ -338,6 +343,88 @@ const ArgTable bgu_table("bgu", {
 
 int ceil_div_f(int a, int b) { return (int)ceilf((float)a / (float)b); }   // i32(ceil(f32(a) / b)), :275-278
 
+// ---- the plan of one call: geometry, workspace layout and the choice of the slice kernel, made by bgu_plan() before anything is
+// enqueued.  It holds no pointer (BguBuffers does); it lives on bgu()'s stack and the stages read it by reference.
+struct BguPlan {
+    BGeom g;
+    SGeom q;
+    size_t off_line, ws_bytes;   // workspace layout in floats: the blurred histogram at 0, then the fitted transforms
+    // slice_lds  what bgu_slice asks for: its four cell rows, 4 * nlc * nz * 12 floats
+    // direct     they do not fit 64 KB: bgu_slice_direct reads the transforms from L2 instead
+    // raise_lds  they fit, but not the 48 KB a kernel may ask for unless its window is raised first
+    bool direct, raise_lds;
+    size_t hist_lds, slice_lds;
+    dim3 hist_grid, fit_grid, slice_grid;
+};
+
+// the resolved pointers of one call: the inputs and where the plan's layout landed in the stream's arena
+struct BguBuffers {
+    LowRes S, V;
+    const float *sl;   // slice_loc at the output's origin, channel 0
+    float *hist, *line, *out;
+};
+
+// No HIP call, no lock, no allocation: a function of the checked arguments.  It refuses (through the error handler, with the code it
+// returns) what the kernels' float cell arithmetic and 32-bit grid offsets cannot hold.  The chain of every path: tests/test_launch_plans.py.
+int bgu_plan(void *uc, BguPlan &pl, float r_sigma, int s_sigma, const halide_buffer_t *splat_loc, const halide_buffer_t *slice_loc,
+             const halide_buffer_t *output) {
+    const int ox0 = output->dim[0].min, oy0 = output->dim[1].min, ow = output->dim[0].extent, oh = output->dim[1].extent;
+    // ---- geometry (oracle/bgu_oracle.c)
+    const int ufx = ceil_div_f(slice_loc->dim[0].extent, splat_loc->dim[0].extent), ufy = ceil_div_f(slice_loc->dim[1].extent, splat_loc->dim[1].extent);
+    const long bigl = (long)s_sigma * max(ufx, ufy);
+    // cell indices are floor(float(x) / float(big_sigma)) (:441-451): exact for coordinates below 2^20
+    if (bigl < 1 || bigl >= (1 << 20) || abs(ox0) >= (1 << 20) || abs(oy0) >= (1 << 20) || ow >= (1 << 20) || oh >= (1 << 20)) {
+        return report(uc, halide_error_code_buffer_extents_too_large, "bgu: coordinates or the cell size (%ld) exceed 2^20", bigl);
+    }
+    BGeom &g = pl.g;
+    g.s = s_sigma, g.big = (int)bigl;
+    g.inv_r = 1.0f / r_sigma, g.nb = (int)(1.0f / r_sigma), g.zmax = (int)rintf(g.inv_r);
+    g.nz = g.nb + 2, g.nhz = g.zmax + 1;
+    auto cell = [&](int v) { return (int)floorf((float)v / (float)g.big); };
+    g.cx0 = cell(ox0), g.cy0 = cell(oy0);
+    g.ncx = cell(ox0 + ow - 1) + 1 - g.cx0 + 1, g.ncy = cell(oy0 + oh - 1) + 1 - g.cy0 + 1;
+    g.nhx = g.ncx + 6, g.nhy = g.ncy + 6;
+    auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    pl.off_line = al((size_t)g.nhy * g.nhx * g.nz * NC);
+    pl.ws_bytes = (pl.off_line + al((size_t)g.ncy * g.ncx * g.nz * 12)) * sizeof(float);
+    if (pl.ws_bytes > ((size_t)1 << 32)) {
+        return report(uc, halide_error_code_buffer_allocation_too_large, "bgu: the grid needs %zu bytes", pl.ws_bytes);
+    }
+    SGeom &q = pl.q;
+    q.ox0 = ox0, q.oy0 = oy0, q.ow = ow, q.oh = oh;
+    q.nsub = (g.big + RB - 1) / RB;
+    q.nlc = (TW - 1) / g.big + 3;
+    q.s_sy = slice_loc->dim[1].stride, q.s_sc = slice_loc->dim[2].stride, q.o_sy = output->dim[1].stride, q.o_sc = output->dim[2].stride;
+    pl.hist_lds = (size_t)g.nhz * NC * sizeof(float);
+    pl.slice_lds = (size_t)4 * q.nlc * g.nz * 12 * sizeof(float);
+    pl.direct = pl.slice_lds > 64 * 1024, pl.raise_lds = !pl.direct && pl.slice_lds > 48 * 1024;
+    pl.hist_grid = dim3(g.nhx, g.nhy), pl.fit_grid = dim3((g.ncx + XT - 1) / XT, g.ncy, g.nz);
+    pl.slice_grid = pl.direct ? dim3((ow + 255) / 256, oh) : dim3((ow + TW - 1) / TW, (g.ncy - 1) * q.nsub);
+    return 0;
+}
+
+// ---- the two stages of the chain, in launch order.  Each takes the plan, the resolved pointers and the stream; a non-zero return
+// is the error code of the call.
+
+// stage 1, the grid: every cell's histogram blurred in z (bgu_hist), then the blurs in y and x and the fit (bgu_fit)
+int bgu_stage_grid(void *uc, const BguPlan &pl, const BguBuffers &b, hipStream_t st) {
+    HLMI_LAUNCH(uc, "bgu_hist", st, bgu_hist, pl.hist_grid, dim3(256), pl.hist_lds, b.S, b.V, pl.g, b.hist);
+    HLMI_LAUNCH(uc, "bgu_fit", st, bgu_fit, pl.fit_grid, dim3(512), 0, b.hist, pl.g, b.line);
+    return 0;
+}
+
+// stage 2, the slice: the only launch that touches the full-resolution image
+int bgu_stage_slice(void *uc, const BguPlan &pl, const BguBuffers &b, hipStream_t st) {
+    timing_note_bytes(24.0 * pl.q.ow * pl.q.oh);
+    if (pl.direct) {
+        HLMI_LAUNCH(uc, "bgu_slice_direct", st, bgu_slice_direct, pl.slice_grid, dim3(256), 0, b.line, b.sl, pl.g, pl.q, b.out);
+        return 0;
+    }
+    if (pl.raise_lds) (void)hipFuncSetAttribute((const void *)bgu_slice, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
+    HLMI_LAUNCH(uc, "bgu_slice", st, bgu_slice, pl.slice_grid, dim3(TW), pl.slice_lds, b.line, b.sl, pl.g, pl.q, b.out);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int bgu(float r_sigma, int32_t s_sigma, halide_buffer_t *splat_loc, halide_buffer_t *values, halide_buffer_t *slice_loc,
@@ -389,59 +476,20 @@ extern "C" int bgu(float r_sigma, int32_t s_sigma, halide_buffer_t *splat_loc, h
         mark_output_written(output);
         return 0;
     }
-    // ---- geometry (oracle/bgu_oracle.c)
-    const int ufx = ceil_div_f(slice_loc->dim[0].extent, splat_loc->dim[0].extent), ufy = ceil_div_f(slice_loc->dim[1].extent, splat_loc->dim[1].extent);
-    const long bigl = (long)s_sigma * max(ufx, ufy);
-    // cell indices are floor(float(x) / float(big_sigma)) (:441-451): exact for coordinates below 2^20
-    if (bigl < 1 || bigl >= (1 << 20) || abs(ox0) >= (1 << 20) || abs(oy0) >= (1 << 20) || ow >= (1 << 20) || oh >= (1 << 20)) {
-        return report(uc, halide_error_code_buffer_extents_too_large, "bgu: coordinates or the cell size (%ld) exceed 2^20", bigl);
-    }
-    BGeom g;
-    g.s = s_sigma, g.big = (int)bigl;
-    g.inv_r = 1.0f / r_sigma;
-    g.nb = (int)(1.0f / r_sigma);
-    g.zmax = (int)rintf(g.inv_r);
-    g.nz = g.nb + 2, g.nhz = g.zmax + 1;
-    auto cell = [&](int v) { return (int)floorf((float)v / (float)g.big); };
-    g.cx0 = cell(ox0), g.cy0 = cell(oy0);
-    g.ncx = cell(ox0 + ow - 1) + 1 - g.cx0 + 1, g.ncy = cell(oy0 + oh - 1) + 1 - g.cy0 + 1;
-    g.nhx = g.ncx + 6, g.nhy = g.ncy + 6;
-    auto low = [](const halide_buffer_t *b) {
-        LowRes L;
-        L.p = dev_ptr<float>(b);
-        L.x0 = b->dim[0].min, L.y0 = b->dim[1].min, L.c0 = b->dim[2].min;
-        L.w = b->dim[0].extent, L.h = b->dim[1].extent, L.c = b->dim[2].extent;
-        L.sy = b->dim[1].stride, L.sc = b->dim[2].stride;
-        return L;
-    };
-    const LowRes S = low(splat_loc), V = low(values);
-    auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t n_hist = al((size_t)g.nhy * g.nhx * g.nz * NC), n_line = al((size_t)g.ncy * g.ncx * g.nz * 12);
-    if ((n_hist + n_line) * sizeof(float) > ((size_t)1 << 32)) {
-        return report(uc, halide_error_code_buffer_allocation_too_large, "bgu: the grid needs %zu bytes", (n_hist + n_line) * sizeof(float));
-    }
+    BguPlan pl = {};
+    if ((r = bgu_plan(uc, pl, r_sigma, s_sigma, splat_loc, slice_loc, output))) return r;
+
     void *ws = nullptr;
-    if ((r = get_workspace(uc, ctx, (n_hist + n_line) * sizeof(float), &ws))) return r;
-    float *hist = (float *)ws, *line = hist + n_hist;
-    hipStream_t st = ctx.stream;
-    HLMI_LAUNCH(uc, "bgu_hist", st, bgu_hist, dim3(g.nhx, g.nhy), dim3(256), (size_t)g.nhz * NC * sizeof(float), S, V, g, hist);
-    HLMI_LAUNCH(uc, "bgu_fit", st, bgu_fit, dim3((g.ncx + XT - 1) / XT, g.ncy, g.nz), dim3(512), 0, hist, g, line);
-    SGeom q;
-    q.ox0 = ox0, q.oy0 = oy0, q.ow = ow, q.oh = oh;
-    q.nsub = (g.big + RB - 1) / RB;
-    q.nlc = (TW - 1) / g.big + 3;
-    q.s_sy = slice_loc->dim[1].stride, q.s_sc = slice_loc->dim[2].stride, q.o_sy = output->dim[1].stride, q.o_sc = output->dim[2].stride;
-    const float *sl = dev_ptr<float>(slice_loc) + (long)(oy0 - slice_loc->dim[1].min) * q.s_sy + (ox0 - slice_loc->dim[0].min) +
-                      (long)(0 - slice_loc->dim[2].min) * q.s_sc;
-    const size_t lds = (size_t)4 * q.nlc * g.nz * 12 * sizeof(float);
-    timing_note_bytes(24.0 * ow * oh);
-    if (lds <= 64 * 1024) {   // (grids whose four cell rows do not fit: the direct kernel)
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void *)bgu_slice, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        HLMI_LAUNCH(uc, "bgu_slice", st, bgu_slice, dim3((ow + TW - 1) / TW, (g.ncy - 1) * q.nsub), dim3(TW), lds, line, sl, g, q,
-                    dev_ptr<float>(output));
-    } else {
-        HLMI_LAUNCH(uc, "bgu_slice_direct", st, bgu_slice_direct, dim3((ow + 255) / 256, oh), dim3(256), 0, line, sl, g, q, dev_ptr<float>(output));
-    }
+    if ((r = get_workspace(uc, ctx, pl.ws_bytes, &ws))) return r;
+    auto low = [](const halide_buffer_t *b) {
+        const halide_dimension_t *d = b->dim;
+        return LowRes{dev_ptr<float>(b), d[0].min, d[1].min, d[2].min, d[0].extent, d[1].extent, d[2].extent, d[1].stride, d[2].stride};
+    };
+    const float *sl = dev_ptr<float>(slice_loc) + (long)(oy0 - slice_loc->dim[1].min) * pl.q.s_sy + (ox0 - slice_loc->dim[0].min) +
+                      (long)(0 - slice_loc->dim[2].min) * pl.q.s_sc;
+    const BguBuffers b = {low(splat_loc), low(values), sl, (float *)ws, (float *)ws + pl.off_line, dev_ptr<float>(output)};
+
+    if ((r = bgu_stage_grid(uc, pl, b, ctx.stream)) || (r = bgu_stage_slice(uc, pl, b, ctx.stream))) return r;
     mark_output_written(output);
     return 0;
 }

@@ -14,10 +14,13 @@
 // pre-blur stages), z in [0, zmax+1] with zmax = int(1/r_sigma + 0.5).  Grids of at most 16 planes (the two-launch path) keep the
 // blurz grid z-INNERMOST, G[y][x][z]: the (cell, bin) threads of the histogram kernel store one contiguous run per workgroup and
 // a tile row of bg_blur_slice is one contiguous run too; larger grids (the serial histogram + three launches) keep G[z][y][x].
+//
+// Host path: bilateral_grid() reads top to bottom: check arguments -> switches -> device and buffers -> empty output -> plan ->
+// workspace -> stages -> mark_output_written.  bg_plan() fills a BgPlan (geometry, workspace layout, vec / a32 / fused / one_launch,
+// which histogram kernel with its workgroup and LDS, grids) without a HIP call; BgBuffers holds the pointers; bg_stage_histogram and
+// bg_stage_blur_slice launch from both, and with_flags() (hlmi_internal.h) names the <ZP, A32, HIST> instantiation.
 #include "hlmi_device_math.h"
 #include "hlmi_internal.h"
-
-#include <stdlib.h>
 
 using namespace hlmi;
 
@@ -420,6 +423,116 @@ const ArgTable bg_table("bilateral_grid", {
     out_buf("bilateral_grid", T_F32, 2, {0, 1536, 0, 2560}),
 });
 
+// ---- run-time switches: environment variables, read into a BgSwitches by bilateral_grid() once per call — on every call, since the
+// parity tests flip them inside one process (env_flag, hlmi_internal.h).  Every alternative is bit-identical.
+//   HLMI_BG_     default  selects                                                                  flipped by (tests/test_bilateral_grid.py)
+//   NO_A32       0        1: 64-bit element indices in bg_blur_slice even where 32-bit byte       test_hip_64_bit_addressing_path_matches_oracle
+//                         offsets would do (see the kernel)
+//   ONE_LAUNCH   0        1: grids of at most 16 planes as ONE launch (bg_blur_slice<.., HIST =    the bg_path fixture
+//                         true>).  Built, bit-exact and NOT the default: 0.0297 against 0.0180 ms
+//                         per call at 1920x1080 — a cell's histogram is rebuilt by every tile whose
+//                         blur footprint holds it (4.4 x the work) and the histogram is work, not
+//                         latency, at the clock a call + sync pattern runs at
+//                         (profiles/r06_bg_one_launch_ab.txt)
+struct BgSwitches {
+    bool no_a32, one_launch;
+};
+
+// ---- the plan of one call: geometry, workspace layout and every path decision, made by bg_plan() before anything is enqueued.  It
+// holds no pointer (BgBuffers does); it lives on bilateral_grid()'s stack and the stages read it by reference.
+struct BgPlan {
+    BGeom g;
+    int ox0, oy0, ow, oh;
+    long in_sy, out_sy;
+    size_t off_bx, off_by, ws_bytes;   // workspace layout in float2: blurz at 0, then blurx and blury (three-launch path only)
+    // chain shape
+    //   vec         float4 staging in bg_histogram_blurz_par: rows 16-byte aligned at every staged column group
+    //   a32         32-bit addressing in bg_blur_slice (see the kernel)
+    //   fused       ZD <= FZ: blurx + blury + slice as bg_blur_slice; else bg_blurx, bg_blury, bg_slice
+    //   one_launch  fused, and the histogram inside it too (HLMI_BG_ONE_LAUNCH)
+    //   zp          z pitch of the fused kernels' tiles = bin slots per cell of the parallel histogram (12 or 16); 0: the serial histogram
+    bool vec, a32, fused, one_launch;
+    int zp;
+    // launch geometry: cells per histogram workgroup (HC of bg_histogram_blurz_par<zp>, T of bg_histogram_blurz) and the serial
+    // histogram's dynamic LDS; the grid of bg_blur_slice
+    int hist_cells;
+    size_t hist_lds;
+    dim3 hist_grid, hist_block, tile_grid;
+};
+
+// the resolved pointers of one call: the two images and where the plan's layout landed in the stream's arena
+struct BgBuffers {
+    const float *in;
+    float *out;
+    float2 *bz, *bx, *by;   // bx, by: three-launch path only
+};
+
+// No HIP call, no lock, no allocation: a function of the two checked buffers, the bin count, the switches and the input's device
+// address (its alignment).  The chain of every path: tests/test_launch_plans.py.
+void bg_plan(BgPlan &pl, const halide_buffer_t *input, const halide_buffer_t *output, float inv_r, int zmax, const BgSwitches &sw, uintptr_t din) {
+    BGeom &g = pl.g;
+    const int ow = pl.ow = output->dim[0].extent, oh = pl.oh = output->dim[1].extent;
+    const int ox0 = pl.ox0 = output->dim[0].min, oy0 = pl.oy0 = output->dim[1].min;
+    g.inv_r = inv_r, g.ZH = zmax + 1, g.ZD = zmax + 2;
+    g.ix0 = input->dim[0].min, g.ix1 = g.ix0 + input->dim[0].extent - 1;
+    g.iy0 = input->dim[1].min, g.iy1 = g.iy0 + input->dim[1].extent - 1;
+    g.gx0 = floor_div(ox0, S), g.gy0 = floor_div(oy0, S);
+    g.GX = floor_div(ox0 + ow - 1, S) + 1 - g.gx0 + 1, g.GY = floor_div(oy0 + oh - 1, S) + 1 - g.gy0 + 1;
+    g.HX = g.GX + 4, g.HY = g.GY + 4;
+
+    auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
+    pl.off_bx = al((size_t)g.HX * g.HY * g.ZD), pl.off_by = pl.off_bx + al((size_t)g.GX * g.HY * g.ZD);
+    pl.ws_bytes = (pl.off_by + al((size_t)g.GX * g.GY * g.ZD)) * sizeof(float2);
+
+    const long in_sy = pl.in_sy = input->dim[1].stride, out_sy = pl.out_sy = output->dim[1].stride;
+    // (cells start at multiples of 8 minus 4)
+    pl.vec = din % 16 == 0 && in_sy % 4 == 0 && floor_div(g.ix0, 4) * 4 == g.ix0;
+    // strides and row counts below 2^23, every buffer's byte span below 2^31
+    const long lim = 1L << 23, span = 1L << 29;
+    pl.a32 = in_sy >= 0 && out_sy >= 0 && in_sy < lim && out_sy < lim && input->dim[1].extent < lim && oh < lim &&
+             in_sy * (long)input->dim[1].extent < span && out_sy * (long)oh < span && (long)g.HX * g.HY < (1L << 24) &&
+             (long)g.HX * g.HY * g.ZD < (span >> 1) && !sw.no_a32;
+    pl.fused = g.ZD <= FZ;   // (grids of more planes — r_sigma < 1/14.5 — take the serial histogram and the three separate launches)
+    pl.one_launch = pl.fused && sw.one_launch;
+    pl.zp = g.ZD <= 12 ? 12 : (pl.fused ? 16 : 0);
+    int T = pl.zp ? HTH / pl.zp : 64;   // serial: as many cells as have their histograms in 64 KB of LDS
+    while (!pl.zp && T > 1 && (size_t)g.ZH * 2 * T * sizeof(float) > 65536) T >>= 1;
+    pl.hist_cells = T, pl.hist_lds = pl.zp ? 0 : (size_t)g.ZH * 2 * T * sizeof(float);
+    pl.hist_grid = dim3((g.HX + T - 1) / T, g.HY), pl.hist_block = dim3(T * (pl.zp ? pl.zp : 1));
+    pl.tile_grid = dim3((ow + FPX - 1) / FPX, (oh + 31) / 32);
+}
+
+// ---- the two stages of the chain, in launch order.  Each takes the plan, the resolved pointers and the stream; a non-zero return
+// is the error code of the call.  <ZP, A32, HIST> come from (zp == 12, a32, one_launch) through with_flags().
+
+// stage 1 (not on the one-launch path): the histogram of every cell, blurred in z
+int bg_stage_histogram(void *uc, const BgPlan &pl, const BgBuffers &b, hipStream_t st) {
+    if (!pl.zp) {
+        HLMI_LAUNCH(uc, "bg_histogram_blurz", st, bg_histogram_blurz, pl.hist_grid, pl.hist_block, pl.hist_lds, b.in, pl.in_sy, pl.g, b.bz);
+        return 0;
+    }
+    return with_flags([&](auto Z12) -> int {
+        HLMI_LAUNCH(uc, "bg_histogram_blurz", st, (bg_histogram_blurz_par<Z12.value ? 12 : 16>), pl.hist_grid, pl.hist_block, 0, b.in, pl.in_sy, pl.g, b.bz, (int)pl.vec);
+        return 0;
+    }, pl.zp == 12);
+}
+
+// stage 2: blur in x and y and slice — one launch over pixel tiles (which on the one-launch path builds its blurz cells itself), or three
+int bg_stage_blur_slice(void *uc, const BgPlan &pl, const BgBuffers &b, hipStream_t st) {
+    const BGeom &g = pl.g;
+    if (pl.fused) {
+        return with_flags([&](auto Z12, auto A32, auto HIST) -> int {
+            HLMI_LAUNCH(uc, HIST.value ? "bg_fused" : "bg_blur_slice", st, (bg_blur_slice<32, Z12.value ? 12 : 16, A32.value, HIST.value>), pl.tile_grid, dim3(256), 0,
+                        b.in, pl.in_sy, g, HIST.value ? (const float2 *)nullptr : b.bz, b.out, pl.out_sy, pl.ox0, pl.oy0, pl.ow, pl.oh);
+            return 0;
+        }, pl.zp == 12, pl.a32, pl.one_launch);
+    }
+    HLMI_LAUNCH(uc, "bg_blurx", st, bg_blurx, dim3((g.GX + 63) / 64, g.HY, g.ZD), dim3(64), 0, b.bz, g, b.bx);
+    HLMI_LAUNCH(uc, "bg_blury", st, bg_blury, dim3((g.GX + 63) / 64, g.GY, g.ZD), dim3(64), 0, b.bx, g, b.by);
+    HLMI_LAUNCH(uc, "bg_slice", st, bg_slice, dim3((pl.ow + 255) / 256, pl.oh), dim3(256), 0, b.in, pl.in_sy, g, b.by, b.out, pl.out_sy, pl.ox0, pl.oy0, pl.ow);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int bilateral_grid(halide_buffer_t *input, float r_sigma, halide_buffer_t *output) {
@@ -438,18 +551,13 @@ extern "C" int bilateral_grid(halide_buffer_t *input, float r_sigma, halide_buff
     }
     if ((r = check_shapes(uc, args, 2))) return r;
     const int ow = output->dim[0].extent, oh = output->dim[1].extent;
-    const int ox0 = output->dim[0].min, oy0 = output->dim[1].min;
-    if ((r = check_covers(uc, args[0], 0, ox0, ow)) || (r = check_covers(uc, args[0], 1, oy0, oh))) return r;
-
-    BGeom g;
-    g.inv_r = 1.0f / r_sigma;
-    const float zm = 1.0f * g.inv_r + 0.5f;
+    if ((r = check_covers(uc, args[0], 0, output->dim[0].min, ow)) || (r = check_covers(uc, args[0], 1, output->dim[1].min, oh))) return r;
+    const float inv_r = 1.0f / r_sigma, zm = 1.0f * inv_r + 0.5f;
     if (!(zm >= 0.0f && zm < 8192.0f)) {
         return report(uc, halide_error_code_param_too_small,
                       "Parameter r_sigma is %g: the grid would need %g range bins (supported: r_sigma >= 1/8191)", r_sigma, zm);
     }
-    const int zmax = (int)zm;
-    g.ZH = zmax + 1, g.ZD = zmax + 2;
+    const BgSwitches sw = {env_flag("HLMI_BG_NO_A32"), env_flag("HLMI_BG_ONE_LAUNCH")};
 
     DeviceCtx ctx;
     if ((r = to_device(uc, &ctx, args, 2))) return r;
@@ -457,80 +565,16 @@ extern "C" int bilateral_grid(halide_buffer_t *input, float r_sigma, halide_buff
         mark_output_written(output);
         return 0;
     }
-    g.ix0 = input->dim[0].min, g.ix1 = g.ix0 + input->dim[0].extent - 1;
-    g.iy0 = input->dim[1].min, g.iy1 = g.iy0 + input->dim[1].extent - 1;
-    g.gx0 = floor_div(ox0, S), g.gy0 = floor_div(oy0, S);
-    g.GX = floor_div(ox0 + ow - 1, S) + 1 - g.gx0 + 1, g.GY = floor_div(oy0 + oh - 1, S) + 1 - g.gy0 + 1;
-    g.HX = g.GX + 4, g.HY = g.GY + 4;
 
-    auto al = [](size_t n) { return (n + 63) & ~(size_t)63; };
-    const size_t n_bz = al((size_t)g.HX * g.HY * g.ZD), n_bx = al((size_t)g.GX * g.HY * g.ZD), n_by = al((size_t)g.GX * g.GY * g.ZD);
+    BgPlan pl = {};
+    bg_plan(pl, input, output, inv_r, (int)zm, sw, (uintptr_t)dev_ptr<float>(input));
+
     void *ws = nullptr;
-    if ((r = get_workspace(uc, ctx, (n_bz + n_bx + n_by) * sizeof(float2), &ws))) return r;
-    float2 *bz = (float2 *)ws, *bx = bz + n_bz, *by = bx + n_bx;
+    if ((r = get_workspace(uc, ctx, pl.ws_bytes, &ws))) return r;
+    float2 *bz = (float2 *)ws;
+    const BgBuffers b = {dev_ptr<float>(input), dev_ptr<float>(output), bz, bz + pl.off_bx, bz + pl.off_by};
 
-    const float *din = dev_ptr<float>(input);
-    const long in_sy = input->dim[1].stride, out_sy = output->dim[1].stride;
-    hipStream_t st = ctx.stream;
-    // float4 staging: rows 16-byte aligned at every staged column group (cells start at multiples of 8 minus 4)
-    const int vec = ((uintptr_t)din % 16 == 0 && in_sy % 4 == 0 && floor_div(g.ix0, 4) * 4 == g.ix0) ? 1 : 0;
-    // 32-bit addressing (see bg_blur_slice): strides and row counts below 2^23, every buffer's byte span below 2^31
-    const long lim = 1L << 23, span = 1L << 29;
-    const bool a32 = in_sy >= 0 && out_sy >= 0 && in_sy < lim && out_sy < lim && input->dim[1].extent < lim && oh < lim &&
-                     in_sy * (long)input->dim[1].extent < span && out_sy * (long)oh < span && (long)g.HX * g.HY < (1L << 24) &&
-                     (long)g.HX * g.HY * g.ZD < (span >> 1) && !env_flag("HLMI_BG_NO_A32");
-    // round 6: HLMI_BG_ONE_LAUNCH=1 runs grids of at most 16 planes as ONE launch (bg_blur_slice<.., HIST = true>).  Built, bit-exact
-    // (the parity tests run both paths) and NOT the default: 0.0297 against 0.0180 ms per call at 1920x1080 — a cell's histogram is
-    // rebuilt by every tile whose blur footprint holds it (4.4 x the work) and the histogram is work, not latency, at the clock a
-    // call + sync pattern runs at (profiles/r06_bg_one_launch_ab.txt)
-    const bool one_launch = g.ZD <= FZ && env_flag("HLMI_BG_ONE_LAUNCH");
-    if (one_launch) {
-#define HLMI_BG_ONE(ZP_, A32_)                                                                                                       \
-    HLMI_LAUNCH(uc, "bg_fused", st, (bg_blur_slice<32, ZP_, A32_, true>), dim3((ow + FPX - 1) / FPX, (oh + 31) / 32), dim3(256), 0, din, \
-                in_sy, g, (const float2 *)nullptr, dev_ptr<float>(output), out_sy, ox0, oy0, ow, oh)
-        if (g.ZD <= 12) {
-            if (a32) HLMI_BG_ONE(12, true);
-            else HLMI_BG_ONE(12, false);
-        } else {
-            if (a32) HLMI_BG_ONE(16, true);
-            else HLMI_BG_ONE(16, false);
-        }
-#undef HLMI_BG_ONE
-        mark_output_written(output);
-        return 0;
-    }
-    if (g.ZD <= 12) {
-        constexpr int HC = HTH / 12;
-        HLMI_LAUNCH(uc, "bg_histogram_blurz", st, bg_histogram_blurz_par<12>, dim3((g.HX + HC - 1) / HC, g.HY), dim3(HC * 12), 0, din,
-                    in_sy, g, bz, vec);
-    } else if (g.ZD <= 16) {
-        constexpr int HC = HTH / 16;
-        HLMI_LAUNCH(uc, "bg_histogram_blurz", st, bg_histogram_blurz_par<16>, dim3((g.HX + HC - 1) / HC, g.HY), dim3(HC * 16), 0, din,
-                    in_sy, g, bz, vec);
-    } else {
-        int T = 64;
-        while (T > 1 && (size_t)g.ZH * 2 * T * sizeof(float) > 65536) T >>= 1;
-        size_t sh = (size_t)g.ZH * 2 * T * sizeof(float);
-        HLMI_LAUNCH(uc, "bg_histogram_blurz", st, bg_histogram_blurz, dim3((g.HX + T - 1) / T, g.HY), dim3(T), sh, din, in_sy, g, bz);
-    }
-    if (g.ZD <= FZ) {   // (grids of more planes — r_sigma < 1/14.5 — take the serial histogram and the three separate launches)
-#define HLMI_BG_FUSED(ZP_, A32_)                                                                                                     \
-    HLMI_LAUNCH(uc, "bg_blur_slice", st, (bg_blur_slice<32, ZP_, A32_>), dim3((ow + FPX - 1) / FPX, (oh + 31) / 32), dim3(256), 0, din, \
-                in_sy, g, bz, dev_ptr<float>(output), out_sy, ox0, oy0, ow, oh)
-        if (g.ZD <= 12) {
-            if (a32) HLMI_BG_FUSED(12, true);
-            else HLMI_BG_FUSED(12, false);
-        } else {
-            if (a32) HLMI_BG_FUSED(16, true);
-            else HLMI_BG_FUSED(16, false);
-        }
-#undef HLMI_BG_FUSED
-    } else {
-        HLMI_LAUNCH(uc, "bg_blurx", st, bg_blurx, dim3((g.GX + 63) / 64, g.HY, g.ZD), dim3(64), 0, bz, g, bx);
-        HLMI_LAUNCH(uc, "bg_blury", st, bg_blury, dim3((g.GX + 63) / 64, g.GY, g.ZD), dim3(64), 0, bx, g, by);
-        HLMI_LAUNCH(uc, "bg_slice", st, bg_slice, dim3((ow + 255) / 256, oh), dim3(256), 0, din, in_sy, g, by, dev_ptr<float>(output),
-                    out_sy, ox0, oy0, ow);
-    }
+    if ((!pl.one_launch && (r = bg_stage_histogram(uc, pl, b, ctx.stream))) || (r = bg_stage_blur_slice(uc, pl, b, ctx.stream))) return r;
     mark_output_written(output);
     return 0;
 }

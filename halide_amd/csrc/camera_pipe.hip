@@ -11,15 +11,15 @@
 //   cp_demosaic one thread per Bayer quad: 10x10 raw window -> hot-pixel clamp -> 3x3x4 deinterleaved values in
 //               registers -> demosaic 4 pixels -> matrix -> curve -> u8 planes on [-1, W] x [-1, H]
 //   cp_sharpen  one thread per output pixel, 3 channels
-#include <mutex>
+//
+// Host path: camera_pipe() reads top to bottom: check arguments -> switch -> device and buffers -> empty output -> plan -> workspace
+// -> stages -> done with the set-up block -> mark_output_written.  cp_plan() fills a CpPlan (geometry, workspace layout, one_launch /
+// demosaic_vec / sharpen4 / dwords, grids) without a HIP call; CpBuffers holds the pointers; cp_stage_setup (the cached producer:
+// derived_acquire, cp_setup, filled) and cp_stage_frame (cp_fused, or cp_demosaic + a sharpen launch) launch from both.
 #include <string.h>
 
 #include "hlmi_device_math.h"
 #include "hlmi_internal.h"
-
-#include <stdio.h>
-
-#include <stdlib.h>
 
 using namespace hlmi;
 
@@ -458,6 +458,99 @@ struct SetupKey {
 static_assert(sizeof(SetupKey) <= DERIVED_KEY_BYTES, "key does not fit an entry");
 DerivedCache g_setups(4);
 
+// ---- run-time switch: an environment variable, read into a CpSwitches by camera_pipe() once per call — on every call, since the
+// tests flip it inside one process (env_flag, hlmi_internal.h).
+//   HLMI_CP_NO_SETUP_CACHE  default 0; 1: cp_setup runs in every call   (tests/test_camera_pipe.py: test_hip_setup_block_is_computed_once_…)
+struct CpSwitches {
+    bool no_setup_cache;
+};
+
+// ---- the plan of one call: geometry, workspace layout and every path decision, made by cp_plan() before anything is enqueued.  It
+// holds no pointer (CpBuffers does); it lives on camera_pipe()'s stack and the stages read it by reference.
+struct CpPlan {
+    // the output; the curved planes: logical width, row pitch (a multiple of 4 with >= 4 spare columns: cp_sharpen4 reads two dwords
+    // per row), rows; the Bayer quads cp_demosaic makes
+    int W, H, CWL, CW, CH, nqx, nqy;
+    long in_sy, o_sy, o_sc;
+    size_t off_cv, ws_bytes;  // workspace layout in bytes: a set-up block (used when none is cached), then the curved planes (two-launch path)
+    // chain shape
+    //   cache         the set-up block of matrices in memory the runtime owns is kept (!HLMI_CP_NO_SETUP_CACHE)
+    //   one_launch    cp_fused_tile's preconditions hold: cp_fused; else cp_demosaic and a sharpen launch, the curved planes through the workspace
+    //   demosaic_vec  cp_demosaic<true>: raw rows are read as aligned pairs
+    //   dwords        the output takes dword stores (cp_fused_tile's flag)
+    //   sharpen4      cp_sharpen4 (four pixels per thread, dword stores), else cp_sharpen
+    bool cache, one_launch, demosaic_vec, dwords, sharpen4;
+    dim3 frame_grid, sharpen_grid;   // cp_fused or cp_demosaic; the sharpen launch
+};
+
+// the resolved pointers of one call
+struct CpBuffers {
+    const uint16_t *raw;      // shifted(0, 0) of output pixel (ox, oy)
+    const float *m3, *m7;     // element (0, 0) of the matrices
+    CPSetup *setup;           // the cached block, or the workspace's
+    uint8_t *cv, *out;
+};
+
+// No HIP call, no lock, no allocation: a function of the checked buffers, the switch and the alignment of the first raw element and of
+// the output.  The chain of every path: tests/test_launch_plans.py.
+void cp_plan(CpPlan &pl, const halide_buffer_t *input, const halide_buffer_t *processed, const CpSwitches &sw, uintptr_t raw, uintptr_t dout) {
+    const int W = pl.W = processed->dim[0].extent, H = pl.H = processed->dim[1].extent;
+    pl.CWL = W + 2, pl.CW = (pl.CWL + 3 + 4) & ~3, pl.CH = H + 2;
+    pl.nqx = floor_div(W, 2) + 2, pl.nqy = floor_div(H, 2) + 2;
+    pl.in_sy = input->dim[1].stride, pl.o_sy = processed->dim[1].stride, pl.o_sc = processed->dim[2].stride;
+    pl.cache = !sw.no_setup_cache;
+    pl.demosaic_vec = pl.in_sy % 2 == 0 && raw % 4 == 0;
+    pl.one_launch = pl.demosaic_vec && W % 2 == 0;
+    pl.dwords = pl.o_sy % 4 == 0 && pl.o_sc % 4 == 0 && dout % 4 == 0, pl.sharpen4 = W % 4 == 0 && pl.dwords;
+    pl.off_cv = (sizeof(CPSetup) + 255) & ~(size_t)255;
+    pl.ws_bytes = pl.off_cv + (pl.one_launch ? 0 : (size_t)3 * pl.CW * pl.CH + 256);
+    pl.frame_grid = pl.one_launch ? dim3(((W + 63) / 64) * ((H + 2 * FTY - 1) / (2 * FTY))) : dim3((pl.nqx + 255) / 256, pl.nqy);
+    pl.sharpen_grid = dim3(((pl.sharpen4 ? W / 4 : W) + 255) / 256, H);
+}
+
+// ---- the two stages of the chain, in launch order.  Each takes the plan, the resolved pointers and the stream; a non-zero return
+// is the error code of the call.
+
+// stage 1, set-up: the block (matrix, curve, strength) of these matrices and scalars — found in the cache of derived device data, or made
+// by cp_setup, into the cache's entry or (not cacheable, every slot pinned) into the workspace
+int cp_stage_setup(void *uc, const DeviceCtx &ctx, const CpPlan &pl, CpBuffers &b, DerivedUse &use, const halide_buffer_t *matrix_3200,
+                   const halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast, float sharpen_strength, int blackLevel,
+                   int whiteLevel) {
+    const long s3 = matrix_3200->dim[1].stride, s7 = matrix_7000->dim[1].stride;
+    const long mo3 = (long)matrix_3200->dim[1].min * s3 + matrix_3200->dim[0].min, mo7 = (long)matrix_7000->dim[1].min * s7 + matrix_7000->dim[0].min;
+    b.m3 = dev_ptr<float>(matrix_3200) - mo3, b.m7 = dev_ptr<float>(matrix_7000) - mo7;
+    SetupKey key;
+    memset(&key, 0, sizeof key);
+    key.device = ctx.device;
+    key.h3 = matrix_3200->device, key.v3 = buffer_version(matrix_3200), key.h7 = matrix_7000->device, key.v7 = buffer_version(matrix_7000);
+    key.s3 = s3, key.s7 = s7, key.o3 = mo3, key.o7 = mo7;
+    key.color_temp = color_temp, key.gamma = gamma, key.contrast = contrast, key.sharpen = sharpen_strength;
+    key.black = blackLevel, key.white = whiteLevel;
+    if (int r = derived_acquire(uc, ctx, g_setups, &key, sizeof key, pl.off_cv, key.v3 != 0 && key.v7 != 0 && pl.cache, &use)) return r;
+    if (use.ptr) b.setup = (CPSetup *)use.ptr;
+    if (use.fill) {
+        HLMI_LAUNCH(uc, "cp_setup", ctx.stream, cp_setup, dim3(1), dim3(1024), 0, b.m3, s3, b.m7, s7, color_temp, gamma, contrast, sharpen_strength, blackLevel,
+                    whiteLevel, b.setup);
+        use.filled(ctx.stream);
+    }
+    return 0;
+}
+
+// stage 2, the frame: one launch over tiles, or — any other geometry — one thread per quad from global memory, the curved planes through
+// the workspace, and a sharpen launch
+int cp_stage_frame(void *uc, const CpPlan &pl, const CpBuffers &b, hipStream_t st) {
+    if (pl.one_launch) {
+        HLMI_LAUNCH(uc, "cp_fused", st, cp_fused_tile, pl.frame_grid, dim3(256), 0, b.raw, pl.in_sy, b.setup, b.out, pl.o_sy, pl.o_sc, pl.W, pl.H, (int)pl.dwords, (pl.W + 63) / 64);
+        return 0;
+    }
+    if (int r = with_flags([&](auto V) -> int {
+            HLMI_LAUNCH(uc, "cp_demosaic", st, cp_demosaic<V.value>, pl.frame_grid, dim3(256), 0, b.raw, pl.in_sy, b.setup, b.cv, pl.CW, pl.CH, pl.CWL, pl.nqx, pl.nqy);
+            return 0;
+        }, pl.demosaic_vec)) return r;
+    HLMI_LAUNCH(uc, "cp_sharpen", st, (pl.sharpen4 ? cp_sharpen4 : cp_sharpen), pl.sharpen_grid, dim3(256), 0, b.cv, pl.CW, pl.CH, b.setup, b.out, pl.o_sy, pl.o_sc, pl.W, pl.H);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200, halide_buffer_t *matrix_7000, float color_temp,
@@ -496,66 +589,28 @@ extern "C" int camera_pipe(halide_buffer_t *input, halide_buffer_t *matrix_3200,
     for (int i = 1; i <= 2; i++) {
         if ((r = check_covers(uc, args[i], 0, 0, 4)) || (r = check_covers(uc, args[i], 1, 0, 3))) return r;
     }
+    const CpSwitches sw = {env_flag("HLMI_CP_NO_SETUP_CACHE")};
     DeviceCtx ctx;
     if ((r = to_device(uc, &ctx, args, 4))) return r;
     if (W == 0 || H == 0) {
         mark_output_written(processed);
         return 0;
     }
-    const int CWL = W + 2, CW = (CWL + 3 + 4) & ~3, CH = H + 2;   // logical width; row pitch: a multiple of 4 with >= 4 spare
-                                                                 // columns (cp_sharpen4 reads two dwords per row)
-    const size_t setup_bytes = (sizeof(CPSetup) + 255) & ~(size_t)255;
-    void *ws = nullptr;
     // shifted(x, y) = input(x + 16, y + 12) in ABSOLUTE coordinates; output pixel (ox, oy) is X = 0 of the kernels
-    const long in_sy = input->dim[1].stride;
-    const uint16_t *raw = dev_ptr<uint16_t>(input) + (long)(oy + 12 - input->dim[1].min) * in_sy + (ox + 16 - input->dim[0].min);
-    const bool one_launch = in_sy % 2 == 0 && (uintptr_t)raw % 4 == 0 && W % 2 == 0;   // cp_fused_tile's preconditions
-    if ((r = get_workspace(uc, ctx, setup_bytes + (one_launch ? 0 : (size_t)3 * CW * CH + 256), &ws))) return r;   // the curved planes: only on the two-launch path
-    CPSetup *setup = (CPSetup *)ws;
-    uint8_t *cv = (uint8_t *)ws + setup_bytes;
-    hipStream_t st = ctx.stream;
-    const long mo3 = (long)matrix_3200->dim[1].min * matrix_3200->dim[1].stride + matrix_3200->dim[0].min;
-    const long mo7 = (long)matrix_7000->dim[1].min * matrix_7000->dim[1].stride + matrix_7000->dim[0].min;
-    const float *m3 = dev_ptr<float>(matrix_3200) - mo3;
-    const float *m7 = dev_ptr<float>(matrix_7000) - mo7;
-    SetupKey key;
-    memset(&key, 0, sizeof key);
-    key.device = ctx.device;
-    key.h3 = matrix_3200->device, key.v3 = buffer_version(matrix_3200), key.h7 = matrix_7000->device, key.v7 = buffer_version(matrix_7000);
-    key.s3 = matrix_3200->dim[1].stride, key.s7 = matrix_7000->dim[1].stride, key.o3 = mo3, key.o7 = mo7;
-    key.color_temp = color_temp, key.gamma = gamma, key.contrast = contrast, key.sharpen = sharpen_strength;
-    key.black = blackLevel, key.white = whiteLevel;
+    const uint16_t *raw = dev_ptr<uint16_t>(input) + (long)(oy + 12 - input->dim[1].min) * input->dim[1].stride + (ox + 16 - input->dim[0].min);
+    CpPlan pl = {};
+    cp_plan(pl, input, processed, sw, (uintptr_t)raw, (uintptr_t)dev_ptr<uint8_t>(processed));
+
+    void *ws = nullptr;
+    if ((r = get_workspace(uc, ctx, pl.ws_bytes, &ws))) return r;
+    CpBuffers b = {raw, nullptr, nullptr, (CPSetup *)ws, (uint8_t *)ws + pl.off_cv, dev_ptr<uint8_t>(processed)};
+
     DerivedUse use;
-    if ((r = derived_acquire(uc, ctx, g_setups, &key, sizeof key, setup_bytes, key.v3 != 0 && key.v7 != 0 && !env_flag("HLMI_CP_NO_SETUP_CACHE"), &use))) return r;
-    if (use.ptr) setup = (CPSetup *)use.ptr;
-    if (use.fill) {
-        HLMI_LAUNCH(uc, "cp_setup", st, cp_setup, dim3(1), dim3(1024), 0, m3, (long)matrix_3200->dim[1].stride, m7,
-                    (long)matrix_7000->dim[1].stride, color_temp, gamma, contrast, sharpen_strength, blackLevel, whiteLevel, setup);
-        use.filled(st);
+    if ((r = cp_stage_setup(uc, ctx, pl, b, use, matrix_3200, matrix_7000, color_temp, gamma, contrast, sharpen_strength, blackLevel, whiteLevel)) ||
+        (r = cp_stage_frame(uc, pl, b, ctx.stream))) {
+        return r;
     }
-    const int nqx = floor_div(W, 2) + 2, nqy = floor_div(H, 2) + 2;
-    const long o_sy = processed->dim[1].stride, o_sc = processed->dim[2].stride;
-    uint8_t *dout = dev_ptr<uint8_t>(processed);
-    if (one_launch) {
-        const int dwords = o_sy % 4 == 0 && o_sc % 4 == 0 && (uintptr_t)dout % 4 == 0;
-        HLMI_LAUNCH(uc, "cp_fused", st, cp_fused_tile, dim3(((W + 63) / 64) * ((H + 2 * FTY - 1) / (2 * FTY))), dim3(256), 0, raw, in_sy, setup, dout, o_sy, o_sc,
-                    W, H, dwords, (W + 63) / 64);
-        use.done(st);
-        mark_output_written(processed);
-        return 0;
-    }
-    // any other geometry: one thread per quad from global memory, the curved planes through the workspace, a sharpen launch
-    if (in_sy % 2 == 0 && (uintptr_t)raw % 4 == 0) {
-        HLMI_LAUNCH(uc, "cp_demosaic", st, cp_demosaic<true>, dim3((nqx + 255) / 256, nqy), dim3(256), 0, raw, in_sy, setup, cv, CW, CH, CWL, nqx, nqy);
-    } else {
-        HLMI_LAUNCH(uc, "cp_demosaic", st, cp_demosaic<false>, dim3((nqx + 255) / 256, nqy), dim3(256), 0, raw, in_sy, setup, cv, CW, CH, CWL, nqx, nqy);
-    }
-    if (W % 4 == 0 && o_sy % 4 == 0 && o_sc % 4 == 0 && (uintptr_t)dout % 4 == 0) {
-        HLMI_LAUNCH(uc, "cp_sharpen", st, cp_sharpen4, dim3((W / 4 + 255) / 256, H), dim3(256), 0, cv, CW, CH, setup, dout, o_sy, o_sc, W, H);
-    } else {
-        HLMI_LAUNCH(uc, "cp_sharpen", st, cp_sharpen, dim3((W + 255) / 256, H), dim3(256), 0, cv, CW, CH, setup, dout, o_sy, o_sc, W, H);
-    }
-    use.done(st);
+    use.done(ctx.stream);
     mark_output_written(processed);
     return 0;
 }

@@ -19,11 +19,15 @@
 //                      and 64-ci chunk A and B are staged in LDS (rows padded to 144 B), three chunks in flight
 //   Algorithmic bytes: input + output once (f32) + the bf16 filter: 27.6 + 25.7 + 0.3 MB at configs[4];
 //   flops 2 N H W CI CO 9 = 14.8 G.
-#include <mutex>
-
+//
+// Host path: conv_layer_bf16() reads top to bottom: check arguments -> switch -> device and buffers -> empty output -> plan -> stages
+// -> done with the filter image -> mark_output_written.  conv_bf16_plan() fills a ConvBf16Plan (CGeom, the filter layout and with it
+// the main kernel, the window size class, AR / ARp, LDS sizes, grids) without a HIP call; ConvBf16Buffers holds the pointers;
+// conv_stage_filter (the cached producer: derived_acquire, conv_filter_bf16, filled) and conv_stage_main (hipFuncSetAttribute and the
+// launch, once, in a lambda called with the kernel and its LDS size) launch from both.
 #include "hlmi_internal.h"
 
-#include <stdlib.h>
+#include <string.h>
 #include <type_traits>
 
 using namespace hlmi;
@@ -563,13 +567,106 @@ struct FilterKey {
 static_assert(sizeof(FilterKey) <= DERIVED_KEY_BYTES, "key does not fit an entry");
 DerivedCache g_filters(8);
 
+// ---- run-time switch: an environment variable, read into a ConvSwitches by conv_layer_bf16() once per call — on every call, since
+// the tests flip it inside one process (env_flag, hlmi_internal.h).
+//   HLMI_CONV_NO_FILTER_CACHE  default 0; 1: conv_filter_bf16 runs in every call   (tests/test_conv_layer.py: test_hip_bf16_filter_is_reordered_once_…)
+struct ConvSwitches {
+    bool no_filter_cache;
+};
+
+// ---- the plan of one call: which main kernel runs, on which filter layout, and how it is launched, made by conv_bf16_plan() before
+// anything is enqueued.  It holds no pointer (ConvBf16Buffers does); it lives on conv_layer_bf16()'s stack and the stages read it by reference.
+struct ConvBf16Plan {
+    CGeom g;
+    long NQ;            // input-linear positions: N (H + 2) (W + 2)
+    // layout  of the bf16 filter image (conv_filter_bf16<layout>) and with it the main kernel:
+    //   2  conv3x3_bf16_p: 256-position tiles, B through LDS; the window ARp takes 6 or 8 staging passes (`wide`: 8)
+    //   1  conv3x3_bf16_lin: 128-position tiles, for what conv3x3_bf16_p does not take; the window AR takes 8 or 12 passes (`wide`: 12)
+    //   0  conv3x3_bf16_mfma: the fallback for W > 125, im2col tiles of 128 pixels
+    int layout;
+    bool wide;
+    int AR, ARp;        // input-linear window of a 128- / 256-position tile
+    size_t sh_lin, sh_p, sh_mfma, wb_bytes;   // dynamic LDS of the three kernels; the filter image
+    bool cache;         // the image of a filter in memory the runtime owns is kept (!HLMI_CONV_NO_FILTER_CACHE)
+    FastDiv d_img, d_row;
+    dim3 filter_grid, main_grid;
+};
+
+// the resolved pointers of one call
+struct ConvBf16Buffers {
+    const float *in, *filt, *bias;
+    float *out;
+    uint16_t *wb;       // the filter image: the cache's entry, or (not cacheable, every slot pinned) the stream's arena
+};
+
+// No HIP call, no lock, no allocation: a function of the checked extents and the switch.
+void conv_bf16_plan(ConvBf16Plan &pl, const ConvSwitches &sw) {
+    const CGeom &g = pl.g;
+    pl.wb_bytes = (size_t)9 * g.CO * g.CI * sizeof(uint16_t);
+    pl.cache = !sw.no_filter_cache;
+    pl.AR = TP + 2 * (g.W + 2) + 2, pl.ARp = TQ + 2 * (g.W + 2) + 2;
+    pl.sh_lin = (size_t)2 * pl.AR * PL * sizeof(uint16_t);                  // two windows of 32-ci chunks, 80-byte rows
+    pl.sh_p = ((size_t)2 * pl.ARp * PL + 2 * BSLOT) * sizeof(uint16_t);     // two A windows, two B slots
+    pl.sh_mfma = (size_t)2 * (TP + TC) * PA * sizeof(uint16_t);             // 73.7 KB: above the 64 KB default window
+    const long NQ = pl.NQ = (long)g.N * (g.H + 2) * (g.W + 2);
+    const bool lin = pl.AR <= 32 * 12 && NQ < (1L << 31) && NQ * g.CI < (1L << 31);   // W <= 125
+    const bool pers = lin && pl.ARp <= 64 * 8 && pl.sh_p <= 160 * 1024 && g.CO % TC == 0 && g.CI % (2 * KL) == 0;
+    pl.layout = pers ? 2 : (lin ? 1 : 0);
+    pl.wide = pers ? pl.ARp > 64 * 6 : pl.AR > 32 * 8;
+    pl.d_img = make_fastdiv((uint32_t)((g.H + 2) * (g.W + 2))), pl.d_row = make_fastdiv((uint32_t)(g.W + 2));
+    pl.filter_grid = dim3((9 * g.CO * (g.CI / 2) + 255) / 256);
+    pl.main_grid = dim3((unsigned)(pers ? (NQ + TQ - 1) / TQ : lin ? (NQ + TP - 1) / TP : (g.npix + TP - 1) / TP), g.CO / TC);
+}
+
+// ---- the two stages of the chain, in launch order.  Each takes the plan, the resolved pointers and the stream; a non-zero return
+// is the error code of the call.
+
+// stage 1, the filter: its bf16 MFMA-B image is a function of the filter's contents only.  It is kept per (filter allocation, version,
+// layout) and the pre-pass re-runs only when the filter changed (uploaded again because the caller set host_dirty, written by another
+// pipeline, re-allocated).  Weights that stay resident — the inference case — pay the re-ordering once.
+int conv_stage_filter(void *uc, const DeviceCtx &ctx, const ConvBf16Plan &pl, ConvBf16Buffers &b, DerivedUse &use, const halide_buffer_t *filter) {
+    FilterKey key;
+    memset(&key, 0, sizeof key);
+    key.device = ctx.device, key.layout = pl.layout, key.handle = filter->device, key.version = buffer_version(filter);
+    int r = derived_acquire(uc, ctx, g_filters, &key, sizeof key, pl.wb_bytes, key.version != 0 && pl.cache, &use);
+    if (r) return r;
+    void *wb_mem = use.ptr;   // not cached: the image goes into the stream's arena
+    if (!wb_mem && (r = get_workspace(uc, ctx, pl.wb_bytes, &wb_mem))) return r;
+    b.wb = (uint16_t *)wb_mem;
+    if (use.fill) {
+        timing_note_bytes(6.0 * 9 * pl.g.CO * pl.g.CI);
+        auto pre = [&](auto *kernel) -> int {
+            HLMI_LAUNCH(uc, "conv_filter_bf16", ctx.stream, kernel, pl.filter_grid, dim3(256), 0, b.filt, b.wb, pl.g.CI, pl.g.CO);
+            return 0;
+        };
+        if ((r = pl.layout == 2 ? pre(conv_filter_bf16<2>) : pl.layout == 1 ? pre(conv_filter_bf16<1>) : pre(conv_filter_bf16<0>))) return r;
+        use.filled(ctx.stream);
+    }
+    return 0;
+}
+
+// stage 2, the main launch: every kernel asks for more LDS than the default window, which is raised first
+int conv_stage_main(void *uc, const ConvBf16Plan &pl, const ConvBf16Buffers &b, hipStream_t st) {
+    const CGeom &g = pl.g;
+    timing_note_bytes(4.0 * ((double)pl.NQ * g.CI + (double)g.npix * g.CO) + (double)pl.wb_bytes);
+    auto run = [&](auto *kernel, unsigned threads, size_t lds, auto... window) -> int {
+        HLMI_HIP(uc, hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HLMI_LAUNCH(uc, "conv3x3_bf16_mfma", st, kernel, pl.main_grid, dim3(threads), lds, b.in, b.wb, b.bias, b.out, g, window...);
+        return 0;
+    };
+    if (pl.layout == 2) return pl.wide ? run(conv3x3_bf16_p<8>, PT, pl.sh_p, pl.ARp, pl.d_img, pl.d_row) : run(conv3x3_bf16_p<6>, PT, pl.sh_p, pl.ARp, pl.d_img, pl.d_row);
+    if (pl.layout == 1) return pl.wide ? run(conv3x3_bf16_lin<12>, 256, pl.sh_lin, pl.AR, pl.d_img, pl.d_row) : run(conv3x3_bf16_lin<8>, 256, pl.sh_lin, pl.AR, pl.d_img, pl.d_row);
+    return run(conv3x3_bf16_mfma, 256, pl.sh_mfma);
+}
+
 }  // namespace
 
 extern "C" int conv_layer_bf16(halide_buffer_t *input, halide_buffer_t *filter, halide_buffer_t *bias, halide_buffer_t *relu) {
     void *uc = nullptr;
     BufArg args[4];
     conv_table.bufs(args, {input, filter, bias, relu});
-    CGeom g;
+    ConvBf16Plan pl = {};
+    CGeom &g = pl.g;
     bool query;
     int r = conv_check_args(uc, args, &g.CI, &g.CO, &g.W, &g.H, &g.N, &query);
     if (r || query) return r;
@@ -577,86 +674,21 @@ extern "C" int conv_layer_bf16(halide_buffer_t *input, halide_buffer_t *filter, 
         return report(uc, halide_error_code_constraint_violated,
                       "Constraint violated: conv_layer_bf16 needs input channels (%d) to be a multiple of %d", g.CI, KC);
     }
+    const ConvSwitches sw = {env_flag("HLMI_CONV_NO_FILTER_CACHE")};
     DeviceCtx ctx;
     if ((r = to_device(uc, &ctx, args, 4))) return r;
     g.npix = (long)g.W * g.H * g.N;
-    if (g.npix > 0) {
-        const size_t wb_bytes = (size_t)9 * g.CO * g.CI * sizeof(uint16_t);
-        const int pairs = 9 * g.CO * (g.CI / 2);
-        const int AR = TP + 2 * (g.W + 2) + 2;               // input-linear window of a 128-pixel tile
-        const size_t sh_lin = (size_t)2 * AR * PL * sizeof(uint16_t);   // two windows of 32-ci chunks, 80-byte rows
-        const long NQ = (long)g.N * (g.H + 2) * (g.W + 2);
-        const bool lin = AR <= 32 * 12 && NQ < (1L << 31) && NQ * g.CI < (1L << 31);   // W <= 125
-        // conv3x3_bf16_p: 256-position tiles, B through LDS (see the kernel); the older kernels stay for what it does not take
-        const int TQp = TQ;
-        const int ARp = TQp + 2 * (g.W + 2) + 2;
-        const size_t sh_p = ((size_t)2 * ARp * PL + 2 * BSLOT) * sizeof(uint16_t);   // two A windows, two B slots
-        const bool pers = lin && ARp <= 64 * 8 && sh_p <= 160 * 1024 && g.CO % TC == 0 && g.CI % (2 * KL) == 0;
-        const int layout = pers ? 2 : (lin ? 1 : 0);
-        // The bf16 MFMA-B image of the filter is a function of the filter's contents only: it is kept per (filter
-        // allocation, version, layout) and the pre-pass re-runs only when the filter changed (uploaded again because the
-        // caller set host_dirty, written by another pipeline, re-allocated).  Weights that stay resident — the
-        // inference case — pay the re-ordering once.
-        FilterKey key;
-        memset(&key, 0, sizeof key);
-        key.device = ctx.device, key.layout = layout, key.handle = filter->device, key.version = buffer_version(filter);
-        DerivedUse use;
-        if ((r = derived_acquire(uc, ctx, g_filters, &key, sizeof key, wb_bytes, key.version != 0 && !env_flag("HLMI_CONV_NO_FILTER_CACHE"), &use))) return r;
-        void *wb_mem = use.ptr;   // not cached: the image goes into the stream's arena
-        if (!wb_mem && (r = get_workspace(uc, ctx, wb_bytes, &wb_mem))) return r;
-        uint16_t *wb = (uint16_t *)wb_mem;
-        if (use.fill) {
-            timing_note_bytes(6.0 * 9 * g.CO * g.CI);
-            const dim3 fgrid((pairs + 255) / 256), fblock(256);
-            if (layout == 2) {
-                HLMI_LAUNCH(uc, "conv_filter_bf16", ctx.stream, conv_filter_bf16<2>, fgrid, fblock, 0, dev_ptr<float>(filter), wb, g.CI, g.CO);
-            } else if (layout == 1) {
-                HLMI_LAUNCH(uc, "conv_filter_bf16", ctx.stream, conv_filter_bf16<1>, fgrid, fblock, 0, dev_ptr<float>(filter), wb, g.CI, g.CO);
-            } else {
-                HLMI_LAUNCH(uc, "conv_filter_bf16", ctx.stream, conv_filter_bf16<0>, fgrid, fblock, 0, dev_ptr<float>(filter), wb, g.CI, g.CO);
-            }
-            use.filled(ctx.stream);
-        }
-        const FastDiv d_img = make_fastdiv((uint32_t)((g.H + 2) * (g.W + 2))), d_row = make_fastdiv((uint32_t)(g.W + 2));
-        if (pers) {
-            dim3 grid((unsigned)((NQ + TQp - 1) / TQp), g.CO / TC);
-            timing_note_bytes(4.0 * ((double)NQ * g.CI + (double)g.npix * g.CO) + (double)wb_bytes);
-            if (ARp <= 64 * 6) {
-                HLMI_HIP(uc, hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_bf16_p<6>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_p));
-                HLMI_LAUNCH(uc, "conv3x3_bf16_mfma", ctx.stream, conv3x3_bf16_p<6>, grid, dim3(PT), sh_p, dev_ptr<float>(input), wb,
-                            dev_ptr<float>(bias), dev_ptr<float>(relu), g, ARp, d_img, d_row);
-            } else {
-                HLMI_HIP(uc, hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_bf16_p<8>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_p));
-                HLMI_LAUNCH(uc, "conv3x3_bf16_mfma", ctx.stream, conv3x3_bf16_p<8>, grid, dim3(PT), sh_p, dev_ptr<float>(input), wb,
-                            dev_ptr<float>(bias), dev_ptr<float>(relu), g, ARp, d_img, d_row);
-            }
-        } else if (lin) {
-            dim3 grid((unsigned)((NQ + TP - 1) / TP), g.CO / TC);
-            timing_note_bytes(4.0 * ((double)NQ * g.CI + (double)g.npix * g.CO) + (double)wb_bytes);
-            if (AR <= 32 * 8) {
-                HLMI_HIP(uc, hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_bf16_lin<8>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_lin));
-                HLMI_LAUNCH(uc, "conv3x3_bf16_mfma", ctx.stream, conv3x3_bf16_lin<8>, grid, dim3(256), sh_lin, dev_ptr<float>(input),
-                            wb, dev_ptr<float>(bias), dev_ptr<float>(relu), g, AR, d_img, d_row);
-            } else {
-                HLMI_HIP(uc, hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_bf16_lin<12>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_lin));
-                HLMI_LAUNCH(uc, "conv3x3_bf16_mfma", ctx.stream, conv3x3_bf16_lin<12>, grid, dim3(256), sh_lin, dev_ptr<float>(input),
-                            wb, dev_ptr<float>(bias), dev_ptr<float>(relu), g, AR, d_img, d_row);
-            }
-        } else {
-            const size_t sh = (size_t)2 * (TP + TC) * PA * sizeof(uint16_t);  // 73.7 KB: above the 64 KB default window
-            HLMI_HIP(uc, hipFuncSetAttribute(reinterpret_cast<const void *>(conv3x3_bf16_mfma),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh));
-            dim3 grid((unsigned)((g.npix + TP - 1) / TP), g.CO / TC);
-            timing_note_bytes(4.0 * ((double)g.N * (g.H + 2) * (g.W + 2) * g.CI + (double)g.npix * g.CO) + (double)wb_bytes);
-            HLMI_LAUNCH(uc, "conv3x3_bf16_mfma", ctx.stream, conv3x3_bf16_mfma, grid, dim3(256), sh, dev_ptr<float>(input), wb,
-                        dev_ptr<float>(bias), dev_ptr<float>(relu), g);
-        }
-        use.done(ctx.stream);
+    if (g.npix == 0) {
+        mark_output_written(relu);
+        return 0;
     }
+
+    conv_bf16_plan(pl, sw);
+
+    ConvBf16Buffers b = {dev_ptr<float>(input), dev_ptr<float>(filter), dev_ptr<float>(bias), dev_ptr<float>(relu), nullptr};
+    DerivedUse use;
+    if ((r = conv_stage_filter(uc, ctx, pl, b, use, filter)) || (r = conv_stage_main(uc, pl, b, ctx.stream))) return r;
+    use.done(ctx.stream);
     mark_output_written(relu);
     return 0;
 }

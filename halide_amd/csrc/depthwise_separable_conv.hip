@@ -358,12 +358,11 @@ extern "C" int depthwise_separable_conv(halide_buffer_t *input, halide_buffer_t 
                              (long)g.W * g.in_sx + g.IC < (1L << 29) && (long)g.ow * g.out_sx + g.CO < (1L << 29) &&
                              (long)g.IC * g.d_s1 + g.FW * g.d_sx + g.FH * g.d_sy < (1L << 29) && (long)g.IC * g.p_s1 + g.CO < (1L << 29) &&
                              !env_flag("HLMI_DSC_NO_A32");
-            if (a32)
-                HLMI_LAUNCH(uc, "dsc_fused", ctx.stream, (dsc_fused_t<3, 3, 32, 16, TPX, true>), dim3((g.ow + TPX - 1) / TPX, g.oh, g.N), dim3(256),
-                            0, d_in, d_dw, d_pw, d_b, dev_ptr<float>(output), g);
-            else
-                HLMI_LAUNCH(uc, "dsc_fused", ctx.stream, (dsc_fused_t<3, 3, 32, 16, TPX, false>), dim3((g.ow + TPX - 1) / TPX, g.oh, g.N), dim3(256),
-                            0, d_in, d_dw, d_pw, d_b, dev_ptr<float>(output), g);
+            if ((r = with_flags([&](auto A32) -> int {
+                    HLMI_LAUNCH(uc, "dsc_fused", ctx.stream, (dsc_fused_t<3, 3, 32, 16, TPX, A32.value>), dim3((g.ow + TPX - 1) / TPX, g.oh, g.N),
+                                dim3(256), 0, d_in, d_dw, d_pw, d_b, dev_ptr<float>(output), g);
+                    return 0;
+                }, a32))) return r;
         } else {
             dim3 grid((g.ow + TP - 1) / TP, g.oh, g.N);
             HLMI_LAUNCH(uc, "dsc_fused", ctx.stream, dsc_fused, grid, dim3(256), sh, d_in, d_dw, d_pw, d_b, dev_ptr<float>(output), g);

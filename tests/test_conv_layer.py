@@ -77,9 +77,11 @@ def test_bf16_oracle_rounds_operands_to_nearest_even(oracle):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("n,h,w,ci,co", [(16, 56, 56, 128, 128), (5, 80, 100, 128, 128), (1, 1, 1, 64, 128),
-                                         (2, 7, 9, 64, 256), (3, 5, 13, 192, 128)])
+                                         (2, 7, 9, 64, 256), (3, 5, 13, 192, 128), (1, 3, 126, 64, 128)])
 def test_hip_bf16_matches_oracle_within_accumulation_tolerance(hl, oracle, n, h, w, ci, co):
-    """bf16 operands (same rounding as the oracle), f32 accumulation on the matrix cores in hardware order:
+    """The main kernel by shape (conv_bf16_plan): W <= 61 conv3x3_bf16_p<6> (56, 1, 9, 13), 62 <= W <= 125 conv3x3_bf16_p<8> (100), W > 125
+    the fallback conv3x3_bf16_mfma (126: three workgroups of 128 pixels, the last one partial).
+    bf16 operands (same rounding as the oracle), f32 accumulation on the matrix cores in hardware order:
     |gpu - oracle| <= 2e-6 * (|bias| + sum |products|) + 1e-6 — about 16 ulp of the accumulation scale for
     K = 9 CI <= 1728 terms."""
     inp, filt, bias = _data(n, h, w, ci, co, seed=3 * n + h + w)
