@@ -435,7 +435,7 @@ _fn = {name: _bind(name) for name in
         "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
        + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]
-       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"]
+       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"] + ["resnet50"]
        + ["fft_forward_r2c", "fft_inverse_c2r", "fft_forward_c2c", "fft_inverse_c2c"]
        + ["halide_scopy_impl", "halide_sscal_impl", "halide_saxpy_impl", "halide_sdot", "halide_sasum", "halide_sgemv_notrans",
           "halide_sgemv_trans", "halide_sger_impl", "halide_sgemm_notrans", "halide_sgemm_transA", "halide_sgemm_transB",
@@ -770,6 +770,131 @@ def mat_mul_sized(size, A, B, out) -> int:
 def debug_mat_mul_general(size, A, B, out) -> int:
     """Test and measurement hook: mat_mul_sized with one thread per output running a plain fmaf loop."""
     return _check(_mat_mul_hook("hlmi_mat_mul_general")(int(size), _as_ptr(A), _as_ptr(B), _as_ptr(out)))
+
+
+# apps/resnet_50: the f32 ResNet-50 forward pass (include/hlmi_pipelines.h).  Arrays are the Halide dimensions reversed: the image is
+# (224, 224, 3), a convolution's weights (CI, KH, KW, CO), fc1000_weights (2048, 1000).
+def _resnet50_group(suffix, conv=""):
+    return ([f"conv1_{suffix}"] + [f"br1_{conv}{suffix}_{i}" for i in range(4)]
+            + [f"{b}_{conv}{suffix}_{i}" for b in ("br2a", "br2b", "br2c") for i in range(16)])
+
+
+# the 267 arguments between `input` and `final_output`, in signature order (Resnet50Generator.cpp:31-66)
+RESNET50_PARAM_NAMES = tuple(sum((_resnet50_group(s) for s in ("gamma", "beta", "mu", "sig")), [])
+                             + ["conv1_weights"] + _resnet50_group("weights", "conv_")[1:] + ["fc1000_weights", "fc1000_bias"])
+RESNET50_BLOCKS = (3, 4, 6, 3)   # bottleneck blocks per stage; br1 exists in the first block of each
+
+
+def _resnet50_args(input, params, output):
+    if isinstance(params, dict):
+        missing = [n for n in RESNET50_PARAM_NAMES if n not in params]
+        if missing or len(params) != len(RESNET50_PARAM_NAMES):
+            raise ValueError(f"resnet50: parameters missing {missing[:4]}, unknown {[k for k in params if k not in RESNET50_PARAM_NAMES][:4]}")
+        params = [params[n] for n in RESNET50_PARAM_NAMES]
+    if len(params) != len(RESNET50_PARAM_NAMES):
+        raise ValueError(f"resnet50 takes {len(RESNET50_PARAM_NAMES)} parameters, not {len(params)}")
+    return [_as_ptr(input)] + [_as_ptr(b) for b in params] + [_as_ptr(output)]
+
+
+def resnet50(input, params, output) -> int:
+    """apps/resnet_50: f32 [3, 224, 224] and the 267 parameters -> the softmax probabilities of the classes in `output`'s box, any box
+    inside [0, 1000).  `params`: a sequence in signature order (RESNET50_PARAM_NAMES) or a dict by argument name."""
+    return _check(_fn["resnet50"](*_resnet50_args(input, params, output)))
+
+
+def debug_resnet50_general(input, params, output) -> int:
+    """Test and measurement hook: resnet50 with every convolution on the one-thread-per-output kernel."""
+    fn = lib.hlmi_resnet50_general
+    fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_void_p)]
+    args = _resnet50_args(input, params, output)
+    return _check(fn((C.c_void_p * len(args))(*[None if a is None else C.cast(a, C.c_void_p) for a in args])))
+
+
+RESNET50_LAYER_MODES = ("raw", "scaled", "scaled_relu", "residual_relu")
+
+
+def debug_resnet50_layer(input, weights, gamma, beta, mu, sig, residual, stride, pad, mode, output, general_only=False) -> int:
+    """Test and measurement hook: ONE convolution layer of any shape through resnet50's plan and kernels.  input [CI, W, H], weights
+    [CO, KW, KH, CI], four vectors [CO], output [CO, OW, OH]; mode: an index into or a name of RESNET50_LAYER_MODES; residual is read
+    in the last mode only (None otherwise)."""
+    fn = lib.hlmi_debug_resnet50_layer
+    fn.restype, fn.argtypes = C.c_int, [_BP] * 7 + [C.c_int32] * 4 + [_BP]
+    mode = RESNET50_LAYER_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    return _check(fn(*[_as_ptr(b) for b in (input, weights, gamma, beta, mu, sig, residual)], int(stride), int(pad), mode, int(bool(general_only)),
+                     _as_ptr(output)))
+
+
+def debug_resnet50_maxpool(input, k, stride, pad, output) -> int:
+    """Test hook: resnet50's max pool with a k x k window at any size, [C, W, H] -> [C, OW, OH]."""
+    fn = lib.hlmi_debug_resnet50_maxpool
+    fn.restype, fn.argtypes = C.c_int, [_BP, C.c_int32, C.c_int32, C.c_int32, _BP]
+    return _check(fn(_as_ptr(input), int(k), int(stride), int(pad), _as_ptr(output)))
+
+
+def debug_resnet50_tail(input, fc_weights, fc_bias, output) -> int:
+    """Test hook: resnet50's tail at any size: [C, W, H] -> mean over W x H -> fc (weights [N, C], bias [N]) -> softmax -> [N]."""
+    fn = lib.hlmi_debug_resnet50_tail
+    fn.restype, fn.argtypes = C.c_int, [_BP] * 4
+    return _check(fn(*[_as_ptr(b) for b in (input, fc_weights, fc_bias, output)]))
+
+
+def _resnet50_keys():
+    """{argument name: state-dict key}, the way the reference's process.cpp:143-239 names its files (dots for underscores)"""
+    keys = {"conv1_weights": "conv1.weight", "fc1000_weights": "fc.weight", "fc1000_bias": "fc.bias"}
+    bn = {"gamma": "weight", "beta": "bias", "mu": "running_mean", "sig": "running_var"}
+    for s, k in bn.items():
+        keys[f"conv1_{s}"] = f"bn1.{k}"
+    block = 0
+    for stage, n in enumerate(RESNET50_BLOCKS):
+        for i in range(n):
+            layer = f"layer{stage + 1}.{i}"
+            if i == 0:
+                keys[f"br1_conv_weights_{stage}"] = f"{layer}.downsample.0.weight"
+                for s, k in bn.items():
+                    keys[f"br1_{s}_{stage}"] = f"{layer}.downsample.1.{k}"
+            for j, br in enumerate(("br2a", "br2b", "br2c")):
+                keys[f"{br}_conv_weights_{block}"] = f"{layer}.conv{j + 1}.weight"
+                for s, k in bn.items():
+                    keys[f"{br}_{s}_{block}"] = f"{layer}.bn{j + 1}.{k}"
+            block += 1
+    return keys
+
+
+RESNET50_STATE_DICT_KEYS = _resnet50_keys()
+
+
+def resnet50_params_from_state_dict(sd) -> dict:
+    """{argument name: float32 array} from a torchvision-style ResNet-50 state dict (tensors or arrays): 4-D weights (co, ci, h, w)
+    transposed (1, 2, 3, 0) to Halide's (co, kx, ky, ci) innermost first, fc.weight transposed, as the reference's load_weights.py
+    does; keys the network does not read (num_batches_tracked) are ignored."""
+    out = {}
+    for name in RESNET50_PARAM_NAMES:
+        v = sd[RESNET50_STATE_DICT_KEYS[name]]
+        a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v).astype(np.float32)
+        if a.ndim == 4:
+            a = a.transpose(1, 2, 3, 0)
+        elif a.ndim == 2:
+            a = a.transpose(1, 0)
+        out[name] = np.ascontiguousarray(a)
+    return out
+
+
+def resnet50_load_weight_dir(path) -> dict:
+    """{argument name: float32 array} from a directory of the reference's `<key>.data` + `<key>_shape.data` pairs (process.cpp:45-72;
+    `<key>`: the state-dict key with dots replaced by underscores; the shape file: int32 count, then the Halide extents, innermost
+    first)."""
+    out = {}
+    for name in RESNET50_PARAM_NAMES:
+        base = os.path.join(path, RESNET50_STATE_DICT_KEYS[name].replace(".", "_"))
+        shape = np.fromfile(base + "_shape.data", dtype=np.int32)
+        if shape.size < 1 or shape[0] != shape.size - 1:
+            raise ValueError(f"{base}_shape.data: not a shape file")
+        data = np.fromfile(base + ".data", dtype=np.float32)
+        extents = [int(e) for e in shape[1:]]
+        if data.size != int(np.prod(extents)):
+            raise ValueError(f"{base}.data: {data.size} floats for extents {extents}")
+        out[name] = data.reshape(extents[::-1])
+    return out
 
 
 # apps/fft: the four objects the reference builds (16 x 16) and the generator at other sizes and gains (include/hlmi_pipelines.h).  A

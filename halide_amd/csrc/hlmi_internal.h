@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <initializer_list>
+#include <memory>
 #include <mutex>
 #include <optional>
 #include <stdarg.h>
@@ -102,14 +103,17 @@ inline Arg scalar_i32(const char *name) { return make_arg(name, halide_argument_
 // dynamically (the pointers lead into the object itself), which no consumer can observe: tests/cpp/rungen_registration.cpp calls
 // <name>_metadata() from a static initialiser of the EXECUTABLE, which runs after those of the library it links, and hlmi_rungen
 // comes in through dlopen, which returns after them.
-constexpr int MAX_ARGS = 10;
+// The storage fits the table: three arrays of `n` entries made by the constructor and never resized, so the pointers RunGen's
+// structs hold into them stay valid for the life of the table (resnet50 has 269 lines, most tables two or three).
 struct HLMI_LOCAL ArgTable {
     int n = 0;
-    Arg spec[MAX_ARGS];
-    halide_filter_argument_t args[MAX_ARGS];
-    const int64_t *est_ptrs[MAX_ARGS][8];
+    using EstPtrs = const int64_t *[8];
+    const std::unique_ptr<Arg[]> spec;
+    const std::unique_ptr<halide_filter_argument_t[]> args;
+    const std::unique_ptr<EstPtrs[]> est_ptrs;
     halide_filter_metadata_t md;   // version 1, kTargetString, `name`
-    ArgTable(const char *name, std::initializer_list<Arg> table);
+    ArgTable(const char *name, std::initializer_list<Arg> table) : ArgTable(name, table.begin(), table.size()) {}
+    ArgTable(const char *name, const Arg *table, size_t count);   // a table built at run time (resnet50's: generated names)
     ArgTable(const ArgTable &) = delete;   // (nor moved: args and md point into *this)
     // the same arguments under another entry point's name (the resize variants of one element type)
     halide_filter_metadata_t named(const char *name) const { return {md.version, md.num_arguments, md.arguments, md.target, name}; }
@@ -442,6 +446,20 @@ extern "C" int hlmi_fft2d_general(int32_t kind, int32_t N0, int32_t N1, float ga
 extern "C" void hlmi_fft_twiddles(int32_t n, int32_t sign, float gain, float *out);
 extern "C" int hlmi_fft_radix_factor(int32_t N, int32_t *R);
 extern "C" int hlmi_fft_size_ok(int32_t N);
+
+// resnet50.hip: the same call in argv form (269 halide_buffer_t *) with every convolution on the one-thread-per-output kernel, for the
+// tests (default == general bit for bit) and for scripts/resnet50_times.py.  Per call: no mode is kept anywhere.
+extern "C" int hlmi_resnet50_general(void **argv);
+// resnet50.hip: ONE convolution layer of any shape through the network's plan predicate and kernels.  input [CI, W, H], weights
+// [CO, KW, KH, CI], the four per-channel vectors [CO], output (and residual) [CO, OW, OH] with compute_shape's extents; every min 0 (-8).
+// mode: 0 the raw chain, 1 normalise and scale, 2 + ReLU, 3 + residual + ReLU; residual is looked at in mode 3 only and may be null
+// otherwise.  general_only != 0: the one-thread-per-output kernel.
+extern "C" int hlmi_debug_resnet50_layer(halide_buffer_t *input, halide_buffer_t *weights, halide_buffer_t *gamma, halide_buffer_t *beta, halide_buffer_t *mu,
+                                         halide_buffer_t *sig, halide_buffer_t *residual, int32_t stride, int32_t pad, int32_t mode, int32_t general_only,
+                                         halide_buffer_t *output);
+// resnet50.hip: the max pool (k x k window) and the tail (mean over W x H, fc with weights [N, C] and bias [N], softmax) at any size
+extern "C" int hlmi_debug_resnet50_maxpool(halide_buffer_t *input, int32_t k, int32_t stride, int32_t pad, halide_buffer_t *output);
+extern "C" int hlmi_debug_resnet50_tail(halide_buffer_t *input, halide_buffer_t *fc_weights, halide_buffer_t *fc_bias, halide_buffer_t *output);
 
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;

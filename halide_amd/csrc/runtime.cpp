@@ -26,9 +26,11 @@ namespace hlmi {
 
 const char *const kTargetString = "x86-64-linux-hip-gfx950";
 
-ArgTable::ArgTable(const char *name, std::initializer_list<Arg> table) {
-    for (const Arg &s : table) {
-        if (n == MAX_ARGS || (s.n_est != 0 && s.n_est != 2 * s.dims) || s.n_est > 8) {
+ArgTable::ArgTable(const char *name, const Arg *table, size_t count)
+    : spec(new Arg[count]), args(new halide_filter_argument_t[count]), est_ptrs(new EstPtrs[count]) {
+    for (size_t t = 0; t < count; t++) {
+        const Arg &s = table[t];
+        if ((s.n_est != 0 && s.n_est != 2 * s.dims) || s.n_est > 8) {
             fprintf(stderr, "hlmi: malformed argument table line %s.%s\n", name, s.name);
             abort();
         }
@@ -44,7 +46,7 @@ ArgTable::ArgTable(const char *name, std::initializer_list<Arg> table) {
         for (int e = 0; e < s.n_est; e++) est_ptrs[i][e] = &spec[i].est[e];
         if (s.n_est) a.buffer_estimates = est_ptrs[i];
     }
-    md = {1, n, args, kTargetString, name};
+    md = {1, n, args.get(), kTargetString, name};
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -71,25 +73,32 @@ static std::atomic<halide_free_t> g_free{default_free};
 // ---- recorded check failures (see hlmi_internal.h: the entry prologue) ------------------------------
 struct PendingFailure {
     bool any = false;
-    uint32_t key = 0;  // (phase << 24) | (buffer rank << 16) | (dimension << 8) | kind — smaller = checked earlier
+    uint64_t key = 0;  // (phase << 40) | (buffer rank << 16) | (dimension << 8) | kind — smaller = checked earlier
     int code = 0;
     char msg[512];
 };
 static thread_local PendingFailure t_fail;
 static thread_local const BufArg *t_args = nullptr;
 static thread_local int t_nargs = 0;
-static thread_local int t_rank[16];
+static thread_local std::vector<int> t_rank;    // t_rank[i]: how many of the call's buffer names sort before args[i]'s
+static thread_local std::vector<int> t_order;   // the inverse: argument indices in name order
+constexpr int NO_RANK = 0xffffff;               // a name the call does not have: behind every buffer
 
 static int rank_of(const char *name, size_t len) {
-    for (int i = 0; i < t_nargs && i < 16; i++) {
+    for (int i = 0; i < t_nargs; i++) {
         if (strlen(t_args[i].name) == len && strncmp(t_args[i].name, name, len) == 0) return t_rank[i];
     }
-    return 15;
+    return NO_RANK;
+}
+// the rank of an element of the call's own array without a search (resnet50 has 269 buffers)
+static int rank_of(const BufArg &a) {
+    if (&a >= t_args && &a < t_args + t_nargs) return t_rank[&a - t_args];
+    return rank_of(a.name, strlen(a.name));
 }
 
 static int record(int phase, int rank, int dim, int kind, int code, const char *fmt, ...) __attribute__((format(printf, 6, 7)));
 static int record(int phase, int rank, int dim, int kind, int code, const char *fmt, ...) {
-    uint32_t key = ((uint32_t)phase << 24) | ((uint32_t)(rank & 0xff) << 16) | ((uint32_t)(dim & 0xff) << 8) | (uint32_t)(kind & 0xff);
+    uint64_t key = ((uint64_t)phase << 40) | ((uint64_t)(rank & 0xffffff) << 16) | ((uint64_t)(dim & 0xff) << 8) | (uint64_t)(kind & 0xff);
     if (t_fail.any && t_fail.key <= key) return 0;
     t_fail.any = true, t_fail.key = key, t_fail.code = code;
     va_list ap;
@@ -149,11 +158,14 @@ int check_not_null(void *uc, const BufArg *args, int n) {
                           args[i].name);
         }
     }
-    for (int i = 0; i < n && i < 16; i++) {
-        int r = 0;
-        for (int j = 0; j < n; j++) r += strcmp(args[j].name, args[i].name) < 0;
-        t_rank[i] = r;
-    }
+    t_order.resize(n), t_rank.resize(n);
+    for (int i = 0; i < n; i++) t_order[i] = i;
+    std::sort(t_order.begin(), t_order.end(), [&](int a, int b) {   // (in place: no allocation on the way into an entry point)
+        const int c = strcmp(args[a].name, args[b].name);
+        return c < 0 || (c == 0 && a < b);
+    });
+    for (int j = 0; j < n; j++)   // equal names share a rank: the number of names strictly before them
+        t_rank[t_order[j]] = j > 0 && strcmp(args[t_order[j - 1]].name, args[t_order[j]].name) == 0 ? t_rank[t_order[j - 1]] : j;
     return 0;
 }
 
@@ -167,10 +179,9 @@ bool any_bounds_query(const BufArg *args, int n) {
 int check_type_and_dims(void *uc, const BufArg *args, int n) {
     const bool query = any_bounds_query(args, n);
     // buffers in name order; per buffer the type first, then the dimensionality
-    for (int rank = 0; rank < n; rank++) {
-        for (int i = 0; i < n; i++) {
-            if (i < 16 && t_rank[i] != rank) continue;
-            const BufArg &a = args[i];
+    {
+        for (int j = 0; j < n; j++) {
+            const BufArg &a = args[t_order[j]];
             const char *io = a.is_output ? "Output" : "Input";
             uint32_t given = buf_type_abi(a.buf);
             if (given != a.type) {
@@ -201,7 +212,7 @@ int check_shape(void *uc, const BufArg &a) {
     (void)uc;
     const halide_buffer_t *b = a.buf;
     const char *io = a.is_output ? "Output" : "Input";
-    const int rank = rank_of(a.name, strlen(a.name));
+    const int rank = rank_of(a);
     if (b->dimensions > 0 && b->dim[0].stride != 1) {
         record(4, rank, 0, 0, halide_error_code_constraint_violated, "Constraint violated: %s.stride.0 (%d) == 1 (1)",
                a.name, b->dim[0].stride);
@@ -260,7 +271,7 @@ int check_covers(void *uc, const BufArg &a, int d, int req_min, int req_extent) 
     int64_t req_max = (int64_t)req_min + req_extent - 1, have_max = (int64_t)dm.min + dm.extent - 1;
     if (req_min < dm.min || req_max > have_max) {
         const bool before = req_min < dm.min;
-        record(5, rank_of(a.name, strlen(a.name)), d, 0, halide_error_code_access_out_of_bounds,
+        record(5, rank_of(a), d, 0, halide_error_code_access_out_of_bounds,
                "%s buffer %s is accessed at %lld, which is %s the %s (%lld) in dimension %d",
                a.is_output ? "Output" : "Input", a.name, (long long)(before ? req_min : req_max),
                before ? "before" : "beyond", before ? "min" : "max", (long long)(before ? dm.min : have_max), d);
@@ -273,7 +284,7 @@ int check_equal(void *uc, const char *what, int val, const char *expect_what, in
     if (val != expect) {
         // what = "<buffer>.<stride|min|extent>.<dim>"
         const char *dot = strchr(what, '.');
-        int rank = 15, dim = 0, kind = 3;
+        int rank = NO_RANK, dim = 0, kind = 3;
         if (dot) {
             rank = rank_of(what, (size_t)(dot - what));
             kind = dot[1] == 's' ? 0 : (dot[1] == 'm' ? 1 : 2);
@@ -289,7 +300,7 @@ int check_equal(void *uc, const char *what, int val, const char *expect_what, in
 int check_host_aligned(void *uc, const BufArg &a, int alignment) {
     (void)uc;
     if ((uintptr_t)a.buf->host % (uintptr_t)alignment != 0) {
-        record(7, rank_of(a.name, strlen(a.name)), 0, 0, halide_error_code_unaligned_host_ptr,
+        record(7, rank_of(a), 0, 0, halide_error_code_unaligned_host_ptr,
                "The host pointer of %s is not aligned to a %d bytes boundary.", a.name, alignment);
     }
     return 0;

@@ -371,6 +371,24 @@ def mat_mul(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
     return out
 
 
+@torch.library.custom_op("hlmi::resnet50", mutates_args=())
+def resnet50(input: torch.Tensor, params: list[torch.Tensor]) -> torch.Tensor:
+    """apps/resnet_50: a (224, 224, 3) float32 image (Halide's (c, x, y) reversed) and the 267 parameters in signature order
+    (hl.RESNET50_PARAM_NAMES; convolution weights as (CI, KH, KW, CO), fc1000_weights as (2048, 1000)) -> (1000,) float32
+    probabilities.  float32 only."""
+    if len(params) != len(hl.RESNET50_PARAM_NAMES):
+        raise TypeError(f"resnet50 takes {len(hl.RESNET50_PARAM_NAMES)} parameters, not {len(params)}")
+    for t in (input, *params):
+        if t.dtype != torch.float32:
+            raise TypeError("resnet50 takes float32 tensors only")
+    if tuple(input.shape) != (224, 224, 3):
+        raise TypeError("resnet50 takes a (224, 224, 3) image")
+    out = torch.empty((1000,), dtype=torch.float32, device=input.device)
+    with _Wrapped(input, *params, out) as bufs:
+        hl.resnet50(bufs[0], bufs[1:-1], bufs[-1])
+    return out
+
+
 @torch.library.custom_op("hlmi::fft2d", mutates_args=())
 def fft2d(input: torch.Tensor, kind: str, gain: float) -> torch.Tensor:
     """apps/fft at any allowed size: kind "c2c_forward" / "c2c_inverse" take and return a complex array, "r2c" takes a real (N1, N0)
@@ -709,6 +727,11 @@ def _(layers, ops):
 @mat_mul.register_fake
 def _(A, B):
     return A.new_empty(tuple(A.shape))
+
+
+@resnet50.register_fake
+def _(input, params):
+    return input.new_empty((1000,))
 
 
 @fft2d.register_fake

@@ -538,6 +538,47 @@ int halide_dgemm_transAB(double a, struct halide_buffer_t *A, struct halide_buff
                          struct halide_buffer_t *result);
 HLMI_DECLARE_AUX(halide_dgemm_transAB)
 
+/* apps/resnet_50/Resnet50Generator.cpp:31-66,383 — the f32 ResNet-50 forward pass at its one fixed shape, 3 x 224 x 224 -> 1000 softmax
+ * probabilities.  One generator, one entry point, 269 buffers in the generator's declaration order; an array member i is `<array>_<i>`:
+ *   input [3, 224, 224];
+ *   four groups `X` = gamma, beta, mu, sig of 53 vectors each: conv1_X [64], br1_X_0 .. 3, br2a_X_0 .. 15, br2b_X_0 .. 15, br2c_X_0 .. 15, each
+ *   [CO] of its convolution;   the weights in the same order: conv1_weights, br1_conv_weights_0 .. 3, br2a_conv_weights_0 .. 15,
+ *   br2b_conv_weights_0 .. 15, br2c_conv_weights_0 .. 15, each [CO, KW, KH, CI];   fc1000_weights [1000, 2048], fc1000_bias [1000];
+ *   final_output [<= 1000].
+ * Everything is float32, dimension 0 innermost with stride 1 (-8 otherwise), every min 0; activations are (c, x, y), convolution weights
+ * (co, kx, ky, ci) — what the reference's load_weights.py writes and process.cpp:74-78 loads.
+ * Shapes (:70-113): stem 7 x 7, stride 2, pad 3 -> 64 channels; max pool 3 x 3, stride 2, pad 1; four stages (mid channels, blocks, stride) =
+ * (64, 3, 1), (128, 4, 2), (256, 6, 2), (512, 3, 2) of bottleneck blocks br2a 1 x 1 -> mid, br2b 3 x 3 pad 1 -> mid, br2c 1 x 1 -> 4 mid; the
+ * stage's stride sits on br2b and br1 of its first block; br1 (1 x 1 -> 4 mid, on the block's input) exists in blocks 0, 3, 7, 13.  Output
+ * extents are compute_shape's (:245-251): (2 pad + in - k + 1 + stride - 1) / stride, truncating.
+ * Arithmetic, with mad(a, b, c) = a * b + c fused in the default build and rounded twice with HLMI_CANON_FMA=0:
+ *   conv       one chain per output from +0, k = (ky KW + kx) CI + ci strictly upward: acc = mad(w(co, kx, ky, ci), padded(ci, s i + kx - p,
+ *              s j + ky - p), acc).  A tap outside the image is a step with the value +0 (constant_exterior), not a skipped step: w * 0 can
+ *              be -0 or NaN.  No step is added to an odd K (conv1: K = 147).  br1 and every pad-0 layer read no exterior.
+ *   norm+scale inlined into the consumer: t = (v - mu(c)) / sqrt(sig(c) + 1e-5f), correctly rounded sqrt and IEEE division, then
+ *              mad(t, gamma(c), beta(c))
+ *   relu       max(0.0f, v) as conv_layer's: v > 0 ? v : +0, so a NaN becomes +0
+ *   residual   shortcut + scaled_2c, a plain add, then relu; the shortcut is the previous block's output or br1's scaled value (no relu)
+ *   max pool   from -inf (the float type's minimum, as Halide's inline maximum), r.x fastest then r.y: acc = v > acc ? v : acc; the +0
+ *              exterior takes part
+ *   avg pool   from +0, acc = mad(n, v, acc) with n = 1.0f / 49.0f evaluated in float, r.x fastest
+ *   fc         from bias(c): acc = mad(w(c, k), pool(k), acc), k = 0 .. 2047 upward
+ *   softmax    e(c) = exp(fc(c)) with the reference's halide_exp; S = plain adds from +0 over c = 0 .. 999 upward; out(c) = e(c) / S.  No
+ *              maximum is subtracted: a logit past exp's range gives inf / inf = NaN here as in the reference.
+ * Protocol: final_output may be any box inside [0, 1000): only those classes are stored, the sum still runs over all 1000 and every input
+ * is required in full.  A class outside [0, 1000) is a read of fc1000_bias / fc1000_weights outside theirs (-4, as in the reference).  Every
+ * input must cover its box (-4) and may be larger or have padded strides.  A bounds query answers every input's fixed box and, for an
+ * output without a shape, [0, 1000).  No _auto_schedule twin: the reference builds none.
+ * HLMI_RN50_INPUTS(X) is the list of the 268 inputs in order, X(name) for each: callers with tables of their own may use it too. */
+#define HLMI_RN50_R4(X, a) X(a##_0) X(a##_1) X(a##_2) X(a##_3)
+#define HLMI_RN50_R16(X, a) HLMI_RN50_R4(X, a) X(a##_4) X(a##_5) X(a##_6) X(a##_7) X(a##_8) X(a##_9) X(a##_10) X(a##_11) X(a##_12) X(a##_13) X(a##_14) X(a##_15)
+#define HLMI_RN50_GROUP(X, s) X(conv1_##s) HLMI_RN50_R4(X, br1_##s) HLMI_RN50_R16(X, br2a_##s) HLMI_RN50_R16(X, br2b_##s) HLMI_RN50_R16(X, br2c_##s)
+#define HLMI_RN50_WEIGHTS(X) X(conv1_weights) HLMI_RN50_R4(X, br1_conv_weights) HLMI_RN50_R16(X, br2a_conv_weights) HLMI_RN50_R16(X, br2b_conv_weights) HLMI_RN50_R16(X, br2c_conv_weights)
+#define HLMI_RN50_INPUTS(X) X(input) HLMI_RN50_GROUP(X, gamma) HLMI_RN50_GROUP(X, beta) HLMI_RN50_GROUP(X, mu) HLMI_RN50_GROUP(X, sig) HLMI_RN50_WEIGHTS(X) X(fc1000_weights) X(fc1000_bias)
+#define HLMI_RN50_PARAM(name) struct halide_buffer_t *name,
+int resnet50(HLMI_RN50_INPUTS(HLMI_RN50_PARAM) struct halide_buffer_t *final_output);
+HLMI_DECLARE_AUX(resnet50)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,
