@@ -22,6 +22,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md
 VALU_F32_PEAK_TF = 157.3       # packed-FMA vector peak
 MFMA_BF16_PEAK_TF = 2500.0     # dense
 MFMA_F32_PEAK_TF = 157.3
+MFMA_I8_PEAK_TOPS = 5000.0     # dense: twice the bf16 rate (MI355X_MICROARCH.md, the I8 row of the MFMA table)
 VALU_F64_PEAK_TF = 78.6        # the vendor's published f64 vector figure; scripts/ubench/valu_f64.hip measures the issue rate behind it
 
 
@@ -590,6 +591,85 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
         extra["size_4096"] = fields[4096]
         emit("mat_mul", "apps/cuda_mat_mul, f32 1024x1024 = B @ A as a k-ordered fmaf chain, noise in [-1, 1)", t1024, 1024 * 1024, "mfma",
              2.0 * 1024 ** 3 / t1024 / 1e12, MFMA_F32_PEAK_TF, "TFLOP/s", extra)
+
+    # ---- hannk_conv / hannk_depthwise: the quantised convolution pair of apps/hannk's op library on MobileNet-v1 224 shapes, each at batch
+    #      1 and batch 32, device-resident operands, the filter tiled once outside the timed calls.  conv: 2 * outputs * k integer ops
+    #      against the dense i8 matrix-core peak; depthwise: input + output bytes against membench's copy rate of the same run.  Beside
+    #      each: the same call with one thread per output (hlmi_hannk_general), which the default path must beat wherever the plan
+    #      chooses it, and torch.nn.functional.conv2d in f16 on the same shape in the same run: recorded, not thresholded, and not
+    #      comparable bit for bit (another arithmetic).
+    def hannk_layer(kind, ci, co, k, stride, size, batch):
+        import torch
+        pad = k // 2
+        x = rng.integers(0, 256, (batch, size, size, ci), dtype=np.uint8)
+        out_size = hl.hannk_conv_out_extent(size, k, stride, 1, pad)
+        bias = hl.Buffer(rng.integers(-4096, 4096, co).astype(np.int32))
+        az, fz = 128, 131
+        if kind == "conv":
+            inp = hl.Buffer(hl.hannk_pad_input(x, az, hl.HANNK_VECTOR_REDUCTION, (pad, pad)))
+            filt = hl.hannk_tile_filter(rng.integers(0, 256, (co, k, k, ci), dtype=np.uint8), fz)
+            entry, extra_args = "conv_u8_u8_u8", []
+            fn = hl.conv_u8_u8_u8
+        else:
+            inp = hl.Buffer(hl.hannk_pad_input(x, az, hl.HANNK_DEPTHWISE_VECTOR, (pad, pad)))
+            filt = hl.Buffer(rng.integers(0, 256, (k, k, co), dtype=np.uint8))
+            entry, extra_args = "depthwise_conv_uint8", [0]
+            fn = hl.depthwise_conv_uint8
+        o = hl.Buffer(np.zeros((batch, out_size, out_size, co), np.uint8))
+        for b_ in (inp, filt, bias):
+            b_.copy_to_device()
+        q = (1518500250, 9 if kind == "conv" else 5, 128, 0, 255)
+        call = lambda: fn(inp, az, filt, fz, bias, (stride, stride), (1, 1), *q, o)
+        general = lambda: hl.debug_hannk_general(entry, inp, az, filt, fz, bias, stride, stride, 1, 1, *extra_args, *q, o)
+        outputs = batch * out_size * out_size * co
+        iters = 200 if outputs * (ci if kind == "conv" else 1) * k * k < 1 << 30 else 50
+        t = timed(call, o, iters)
+        clock = last_clock[0]
+        tg = timed(general, o, max(2, iters // 10))
+        # the same shape in f16 through torch (MIOpen / hipBLASLt), channels_last
+        tx = torch.from_numpy(x).cuda().permute(0, 3, 1, 2).half().contiguous(memory_format=torch.channels_last)
+        tw = torch.randn((co, 1 if kind == "depthwise" else ci, k, k), dtype=torch.float16, device="cuda").contiguous(memory_format=torch.channels_last)
+        groups = co if kind == "depthwise" else 1
+        tconv = lambda: torch.nn.functional.conv2d(tx, tw, None, stride, pad, 1, groups)
+        tconv()
+        torch.cuda.synchronize()
+        tt = 1e30
+        for _ in range(args.samples):
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                tconv()
+            torch.cuda.synchronize()
+            tt = min(tt, (time.perf_counter() - t0) / iters)
+        del tx, tw
+        last_clock[0] = clock
+        plan = hl.debug_hannk_conv_plan(batch * out_size * out_size, co, k * k * -(-ci // 4)) if kind == "conv" else None
+        k_, kg = kernels(call, o), kernels(general, o)
+        d = {"shape": f"{k}x{k} s{stride} {ci}->{co} at {size}^2, batch {batch}", "ms_per_call": round(t * 1e3, 4), "kernels_ms": k_,
+             "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kg}, "fast_path_faster": bool(t < tg),
+             "kernel_faster": bool(sum(k_.values()) < sum(kg.values())), "torch_f16_conv2d_ms": round(tt * 1e3, 4), "clock_state": clock}
+        if kind == "conv":
+            ops = 2.0 * outputs * ci * k * k
+            d.update({"alg_ops": ops, "tops": round(ops / t / 1e12, 3), "i8_peak_frac": round(ops / t / 1e12 / MFMA_I8_PEAK_TOPS, 5), "plan": plan,
+                      "torch_f16_tflops": round(ops / tt / 1e12, 3)})
+        else:
+            nbytes = float(x.size + outputs)
+            d.update({"alg_bytes": nbytes, "gbs": round(nbytes / t / 1e9, 1)})
+            if copy_gbs[0]:
+                d["of_copy_rate"] = round(nbytes / t / 1e9 / copy_gbs[0], 4)
+        return d, t
+
+    if not only or "hannk_conv" in only:
+        layers = [hannk_layer("conv", ci, co, k, s, size, batch) for (ci, co, k, s, size) in ((3, 32, 3, 2, 224), (512, 512, 1, 1, 14), (1024, 1024, 1, 1, 7))
+                  for batch in (1, 32)]
+        d0, t0_ = layers[3]   # pointwise 512 -> 512 at 14^2, batch 32
+        emit("hannk_conv", "apps/hannk conv_u8_u8_u8, MobileNet-v1 224 layers (u8 operands, i32 accumulate on the i8 MFMA); headline: " + d0["shape"],
+             t0_, 32 * 14 * 14, "mfma_i8", d0["tops"], MFMA_I8_PEAK_TOPS, "TOP/s",
+             {"layers": [d for d, _ in layers], "torch_note": "torch.nn.functional.conv2d in f16, channels_last, same shape and run; another arithmetic"})
+    if not only or "hannk_depthwise" in only:
+        layers = [hannk_layer("depthwise", 512, 512, 3, 1, 14, batch) for batch in (1, 32)]
+        d0, t0_ = layers[1]
+        emit("hannk_depthwise", "apps/hannk depthwise_conv_uint8, MobileNet-v1 224: " + d0["shape"], t0_, 32 * 14 * 14, "hbm", d0["gbs"], HBM_PEAK_GBS, "GB/s",
+             {"layers": [d for d, _ in layers], "torch_note": "torch.nn.functional.conv2d in f16 with groups = channels, same shape and run"})
 
     # ---- fft: apps/fft's c2c, r2c and c2r at 16^2 (the size the reference builds; launch-bound), 256^2, 1024^2 and 4096^2, device buffers,
     #      gain 1.  The two line passes move each complex array twice in and twice out: "moved_bytes" is that, its rate stands beside

@@ -403,16 +403,34 @@ def _as_ptr(b):
 
 # ---------------------------------------------------------------------------------------------------
 # pipelines — argument order and meaning exactly as in include/hlmi_pipelines.h
+# apps/hannk's op library is built with C++ name mangling, every symbol in namespace hannk (include/aot/halide/<name>.h): the
+# Itanium names of <name>, <name>_argv and <name>_metadata, the parameter lists spelled as the compiler spells them
+# (P15halide_buffer_t the first buffer, S1_ every further one, h uint8_t, i int32_t)
+_HANNK_CONV_PARAMS = "P15halide_buffer_thS1_hS1_iiiiiihhhS1_"
+_HANNK_DW_PARAMS = "P15halide_buffer_thS1_hS1_iiiiiiihhhS1_"
+_HANNK_PARAMS = {"tile_conv_filter_uint8": "P15halide_buffer_thhS1_", "conv_u8_u8_u8": _HANNK_CONV_PARAMS, "conv_u8_u8_i16": _HANNK_CONV_PARAMS,
+                 "depthwise_conv_uint8": _HANNK_DW_PARAMS, "depthwise_conv_broadcast_uint8": _HANNK_DW_PARAMS}
+HANNK_OPS = tuple(_HANNK_PARAMS)
+
+
+def _symbol(name, suffix=""):
+    """The exported symbol of entry point `name` (+ "_argv" / "_metadata"): the name itself, or hannk's mangled one."""
+    if name not in _HANNK_PARAMS:
+        return name + suffix
+    full = name + suffix
+    return f"_ZN5hannk{len(full)}{full}E" + {"": _HANNK_PARAMS[name], "_argv": "PPv", "_metadata": "v"}[suffix]
+
+
 def _bind(name):
     """The entry point `name` with the argtypes its own `<name>_metadata()` states (one table per entry point in the library:
     csrc/hlmi_internal.h); None when the library does not export it."""
-    fn = getattr(lib, name, None)
-    if fn is None or getattr(lib, name + "_metadata", None) is None:
+    fn = getattr(lib, _symbol(name), None)
+    if fn is None or getattr(lib, _symbol(name, "_metadata"), None) is None:
         return None
     md = metadata(name)
     argtypes = []
     for a in (md.arguments[i] for i in range(md.num_arguments)):
-        t = _BP if a.kind != 0 else {(2, 32): C.c_float, (2, 64): C.c_double, (0, 32): C.c_int32}.get((a.type.code, a.type.bits))
+        t = _BP if a.kind != 0 else {(2, 32): C.c_float, (2, 64): C.c_double, (0, 32): C.c_int32, (1, 8): C.c_uint8}.get((a.type.code, a.type.bits))
         if t is None:
             raise ImportError(f"{name}: no ctypes type for scalar argument {a.name.decode()} (type code {a.type.code}, {a.type.bits} bits)")
         argtypes.append(t)
@@ -422,7 +440,7 @@ def _bind(name):
 
 
 def metadata(name: str) -> halide_filter_metadata_t:
-    fn = getattr(lib, name + "_metadata")
+    fn = getattr(lib, _symbol(name, "_metadata"))
     fn.restype = C.POINTER(halide_filter_metadata_t)
     return fn().contents
 
@@ -442,7 +460,8 @@ _fn = {name: _bind(name) for name in
           "halide_sgemm_transAB"]
        + ["halide_dcopy_impl", "halide_dscal_impl", "halide_daxpy_impl", "halide_ddot", "halide_dasum", "halide_dgemv_notrans",
           "halide_dgemv_trans", "halide_dger_impl", "halide_dgemm_notrans", "halide_dgemm_transA", "halide_dgemm_transB",
-          "halide_dgemm_transAB"]}
+          "halide_dgemm_transAB"]
+       + list(HANNK_OPS)}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -1135,6 +1154,169 @@ def debug_linear_algebra_general_f64(name: str, *args) -> int:
     return _check(fn(name.encode(), a, b, *bufs))
 
 
+# apps/hannk's op library: the quantised convolution pair and the filter re-tiler (include/aot/halide/<name>.h).
+# Arrays are the Halide dimensions reversed: an activation [c, x, y, b] is an array of shape (B, H, W, C) — NHWC —, the tiled filter
+# [4, 16, ci / 4, co / 16, fx, fy] one of shape (FH, FW, CO16, CQ, 16, 4), a depthwise filter [c, fx, fy] one of shape (FH, FW, C).
+HANNK_VECTOR_REDUCTION, HANNK_ACCUM_VECTOR_SIZE, HANNK_DEPTHWISE_VECTOR = 4, 16, 16
+
+
+def tile_conv_filter_uint8(input, input_zero, output_zero, output) -> int:
+    """u8 [ci, x, y, co] -> the u8 [4, 16, ci / 4, co / 16, x, y] filter conv_u8_u8_* reads; entries outside the input are output_zero."""
+    return _check(_fn["tile_conv_filter_uint8"](_as_ptr(input), int(input_zero), int(output_zero), _as_ptr(output)))
+
+
+def _hannk_conv_args(input, input_zero, filter, filter_zero, bias, stride, dilation, extra, multiplier, shift, output_zero, output_min, output_max,
+                     output):
+    return ([_as_ptr(input), int(input_zero), _as_ptr(filter), int(filter_zero), _as_ptr(bias), int(stride[0]), int(stride[1]), int(dilation[0]),
+             int(dilation[1])] + extra + [int(multiplier), int(shift), int(output_zero), int(output_min), int(output_max), _as_ptr(output)])
+
+
+def conv_u8_u8_u8(input, input_zero, filter, filter_zero, bias, stride, dilation, multiplier, shift, output_zero, output_min, output_max, output) -> int:
+    """input u8 [c, x, y, b], tiled filter, bias i32 [c] -> u8 [c, x, y, b]; stride and dilation are (x, y) pairs."""
+    return _check(_fn["conv_u8_u8_u8"](*_hannk_conv_args(input, input_zero, filter, filter_zero, bias, stride, dilation, [], multiplier, shift,
+                                                         output_zero, output_min, output_max, output)))
+
+
+def conv_u8_u8_i16(input, input_zero, filter, filter_zero, bias, stride, dilation, multiplier, shift, output_zero, output_min, output_max, output) -> int:
+    """conv_u8_u8_u8 with an int16 output: quantize_i16 only, output_zero / min / max are not read."""
+    return _check(_fn["conv_u8_u8_i16"](*_hannk_conv_args(input, input_zero, filter, filter_zero, bias, stride, dilation, [], multiplier, shift,
+                                                          output_zero, output_min, output_max, output)))
+
+
+def depthwise_conv_uint8(input, input_zero, filter, filter_zero, bias, stride, dilation, multiplier, shift, output_zero, output_min, output_max, output,
+                         input_stride_x=0) -> int:
+    """input u8 [c, x, y, b] (channels padded to a multiple of 16), filter u8 [c, fx, fy], bias i32 [c] -> u8 [c, x, y, b]."""
+    return _check(_fn["depthwise_conv_uint8"](*_hannk_conv_args(input, input_zero, filter, filter_zero, bias, stride, dilation, [int(input_stride_x)],
+                                                                multiplier, shift, output_zero, output_min, output_max, output)))
+
+
+def depthwise_conv_broadcast_uint8(input, input_zero, filter, filter_zero, bias, stride, dilation, multiplier, shift, output_zero, output_min,
+                                   output_max, output, input_stride_x=0) -> int:
+    """depthwise_conv_uint8 with the input's one channel feeding every output channel."""
+    return _check(_fn["depthwise_conv_broadcast_uint8"](*_hannk_conv_args(input, input_zero, filter, filter_zero, bias, stride, dilation,
+                                                                          [int(input_stride_x)], multiplier, shift, output_zero, output_min, output_max,
+                                                                          output)))
+
+
+def debug_hannk_general(name: str, *args) -> int:
+    """Test and measurement hook: the entry point `name` of HANNK_OPS, with the arguments of its C signature in order (stride and
+    dilation as four scalars), with one thread per output running the contract's loops as written."""
+    if name not in HANNK_OPS:
+        raise ValueError(f"no hannk entry point named {name}")
+    md = metadata(name)
+    if len(args) != md.num_arguments:
+        raise TypeError(f"{name} takes {md.num_arguments} arguments, not {len(args)}")
+    keep, argv = [], (C.c_void_p * md.num_arguments)()
+    for j, v in enumerate(args):
+        a = md.arguments[j]
+        box = (C.c_uint8(int(v)) if a.type.bits == 8 else C.c_int32(int(v))) if a.kind == 0 else (v.raw if isinstance(v, Buffer) else v.contents)
+        keep.append(box)
+        argv[j] = C.cast(C.pointer(box), C.c_void_p)
+    fn = lib.hlmi_hannk_general
+    fn.restype, fn.argtypes = C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]
+    return _check(fn(name.encode(), argv))
+
+
+def debug_hannk_quantize(fn, acc, multiplier, shift, zero=0, lo=0, hi=255) -> np.ndarray:
+    """Test hook: the device's epilogue alone on an int32 array: fn 0 or "i16" = quantize_i16 (int16 result), fn 1 or "u8" =
+    quantize_and_relu_u8 (uint8 result)."""
+    fn = {"i16": 0, "u8": 1}.get(fn, fn)
+    acc = np.ascontiguousarray(acc, np.int32)
+    out = np.zeros(acc.shape, np.int16 if fn == 0 else np.uint8)
+    f = lib.hlmi_debug_hannk_quantize
+    f.restype = C.c_int
+    f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_uint8, C.c_uint8, C.c_uint8, C.c_void_p]
+    rc = f(int(fn), acc.ctypes.data, acc.size, int(multiplier), int(shift), int(zero), int(lo), int(hi), out.ctypes.data)
+    if rc != 0:
+        raise HalideError(-1, f"hlmi_debug_hannk_quantize failed ({rc})")
+    return out
+
+
+def debug_hannk_conv_plan(npix, channels, quads, cus=256) -> dict:
+    """What conv_u8_u8_*'s plan chooses for `npix` output pixels, `channels` output channels and `quads` = fw * fh * ci / 4 on `cus`
+    compute units (aligned operands; HLMI_HANNK_SPLIT_K is read as in a call)."""
+    out = (C.c_int32 * 3)()
+    f = lib.hlmi_debug_hannk_conv_plan
+    f.restype, f.argtypes = C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    if f(int(npix), int(channels), int(quads), int(cus), out) != 0:
+        raise ValueError("hlmi_debug_hannk_conv_plan: sizes must be positive")
+    return {"mfma": bool(out[0]), "splits": int(out[1]), "wave_tiles": int(out[2])}
+
+
+def _pair(v):
+    return (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))
+
+
+def hannk_conv_out_extent(size, filt, stride, dilation, padding) -> int:
+    """outputs along one axis: the positions x with x * stride + (filt - 1) * dilation inside the padded input"""
+    return (int(size) + 2 * int(padding) - (int(filt) - 1) * int(dilation) - 1) // int(stride) + 1
+
+
+def hannk_pad_input(input, input_zero, channel_multiple, padding) -> np.ndarray:
+    """What the interpreter does to an activation before a conv op: (B, H, W, C) u8 -> a 64-byte aligned array with the channel axis
+    padded to `channel_multiple` and `padding` = (x, y) pixels on each side of W and H, every new element input_zero."""
+    input = np.asarray(input)
+    b, h, w, c = input.shape
+    px, py = _pair(padding)
+    cp = -(-c // channel_multiple) * channel_multiple
+    out = aligned_array((b, h + 2 * py, w + 2 * px, cp), np.uint8, 64, 1)
+    out[...] = np.uint8(input_zero)
+    out[:, py:py + h, px:px + w, :c] = input
+    return out
+
+
+def hannk_tile_filter(filter, filter_zero) -> "Buffer":
+    """(CO, FH, FW, CI) u8 (Halide [ci, fx, fy, co]) -> the tiled filter as a Buffer, padded entries filter_zero: one
+    tile_conv_filter_uint8 call, the re-tiling a model pays once."""
+    filter = np.ascontiguousarray(filter, np.uint8)
+    co, fh, fw, ci = filter.shape
+    tiled = Buffer(aligned_array((fh, fw, -(-co // 16), -(-ci // 4), 16, 4), np.uint8, 64, 1))
+    tile_conv_filter_uint8(Buffer(filter), filter_zero, filter_zero, tiled)
+    return tiled
+
+
+def hannk_conv2d(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, multiplier, shift, output_zero=0, output_min=0,
+                 output_max=255, out_dtype=np.uint8, tiled_filter=None) -> np.ndarray:
+    """A quantised 2-D convolution as the interpreter runs one: input (B, H, W, C) u8, filter (CO, FH, FW, CI) u8, bias int32 (CO,) ->
+    (B, OH, OW, CO) u8 or int16.  The channel axis is padded to a multiple of 4 and the image by `padding` with input_zero, the
+    filter is tiled (or `tiled_filter` of hannk_tile_filter is used), then conv_u8_u8_u8 / conv_u8_u8_i16 runs."""
+    (sx, sy), (dx, dy), (px, py) = _pair(stride), _pair(dilation), _pair(padding)
+    filter = np.asarray(filter)
+    co, fh, fw, ci = filter.shape
+    b, h, w, c = np.asarray(input).shape
+    if c != ci:
+        raise ValueError(f"input has {c} channels, the filter {ci}")
+    if np.dtype(out_dtype) not in (np.dtype(np.uint8), np.dtype(np.int16)):
+        raise TypeError("out_dtype is uint8 or int16")
+    padded = hannk_pad_input(input, input_zero, HANNK_VECTOR_REDUCTION, (px, py))
+    tiled = hannk_tile_filter(filter, filter_zero) if tiled_filter is None else tiled_filter
+    out = Buffer(np.zeros((b, hannk_conv_out_extent(h, fh, sy, dy, py), hannk_conv_out_extent(w, fw, sx, dx, px), co), out_dtype))
+    fn = conv_u8_u8_u8 if np.dtype(out_dtype) == np.dtype(np.uint8) else conv_u8_u8_i16
+    fn(Buffer(padded), input_zero, tiled, filter_zero, Buffer(np.ascontiguousarray(bias, np.int32)), (sx, sy), (dx, dy), multiplier, shift,
+       output_zero, output_min, output_max, out)
+    return out.numpy()
+
+
+def hannk_depthwise_conv2d(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, multiplier, shift, output_zero=0, output_min=0,
+                           output_max=255) -> np.ndarray:
+    """A quantised depthwise convolution: input (B, H, W, C) u8, filter (FH, FW, C) u8, bias int32 (C,) -> (B, OH, OW, C) u8.  The
+    channel axis is padded to a multiple of 16 and the image by `padding` with input_zero; an input of ONE channel under a filter of
+    several runs the broadcast variant."""
+    (sx, sy), (dx, dy), (px, py) = _pair(stride), _pair(dilation), _pair(padding)
+    filter = np.ascontiguousarray(filter, np.uint8)
+    fh, fw, co = filter.shape
+    b, h, w, c = np.asarray(input).shape
+    broadcast = c == 1 and co > 1
+    if not broadcast and c != co:
+        raise ValueError(f"input has {c} channels, the filter {co}")
+    padded = hannk_pad_input(input, input_zero, 1 if broadcast else HANNK_DEPTHWISE_VECTOR, (px, py))
+    out = Buffer(np.zeros((b, hannk_conv_out_extent(h, fh, sy, dy, py), hannk_conv_out_extent(w, fw, sx, dx, px), co), np.uint8))
+    fn = depthwise_conv_broadcast_uint8 if broadcast else depthwise_conv_uint8
+    fn(Buffer(padded), input_zero, Buffer(filter), filter_zero, Buffer(np.ascontiguousarray(bias, np.int32)), (sx, sy), (dx, dy), multiplier, shift,
+       output_zero, output_min, output_max, out)
+    return out.numpy()
+
+
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:
     return _check(_fn["lens_blur"](_as_ptr(left_im), _as_ptr(right_im), int(slices), int(focus_depth), float(blur_radius_scale),
                         int(aperture_samples), _as_ptr(final)))
@@ -1167,7 +1349,7 @@ def run_batch(name: str, frames, devices=None, streams_per_device: int = 1) -> i
     brings them back from there.  Returns 0 or raises HalideError with the first failing frame's code."""
     md = metadata(name)
     n_args = md.num_arguments
-    fn = getattr(lib, name + "_argv")
+    fn = getattr(lib, _symbol(name, "_argv"))
     keep = []          # ctypes objects that must outlive the call
     argvs = (C.POINTER(C.c_void_p) * max(len(frames), 1))()
     for i, frame in enumerate(frames):
@@ -1177,7 +1359,7 @@ def run_batch(name: str, frames, devices=None, streams_per_device: int = 1) -> i
         for j, v in enumerate(frame):
             a = md.arguments[j]
             if a.kind == 0:
-                box = (C.c_double(v) if a.type.bits == 64 else C.c_float(v)) if a.type.code == 2 else (C.c_int32(v) if a.type.bits == 32 else C.c_int64(v))
+                box = (C.c_double(v) if a.type.bits == 64 else C.c_float(v)) if a.type.code == 2 else (C.c_int32(v) if a.type.bits == 32 else C.c_uint8(v) if a.type.bits == 8 else C.c_int64(v))
                 keep.append(box)
                 argv[j] = C.cast(C.pointer(box), C.c_void_p)
             else:

@@ -70,14 +70,17 @@ struct Arg {
     unsigned has;       // scalars: bit DEF / MIN / MAX / EST set = sv[that] given
     halide_scalar_value_t sv[4];
     enum { DEF, MIN, MAX, EST };
-    Arg &set(int which, double v) {   // stored as the argument's own type (every scalar here is an int32, a float or a double)
+    Arg &set(int which, double v) {   // stored as the argument's own type: an int32, a uint8, a float or a double
         has |= 1u << which;
         if (type == T_F32) sv[which].u.f32 = (float)v;
         else if (type == T_F64) sv[which].u.f64 = v;
+        else if (type == T_U8) sv[which].u.u8 = (uint8_t)v;
         else sv[which].u.i32 = (int32_t)v;
         return *this;
     }
-    double get(int which) const { return type == T_F32 ? (double)sv[which].u.f32 : type == T_F64 ? sv[which].u.f64 : (double)sv[which].u.i32; }
+    double get(int which) const {
+        return type == T_F32 ? (double)sv[which].u.f32 : type == T_F64 ? sv[which].u.f64 : type == T_U8 ? (double)sv[which].u.u8 : (double)sv[which].u.i32;
+    }
     Arg &def(double v) { return set(DEF, v); }
     Arg &range(double lo, double hi) { return set(MIN, lo).set(MAX, hi); }
     Arg &estimate(double v) { return set(EST, v); }
@@ -98,6 +101,7 @@ inline Arg out_buf(const char *name, uint32_t type, int dims, std::initializer_l
 inline Arg scalar_f32(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_F32, 0); }
 inline Arg scalar_f64(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_F64, 0); }
 inline Arg scalar_i32(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_I32, 0); }
+inline Arg scalar_u8(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_U8, 0); }
 
 // One entry point's table and everything RunGen's structs point into, built once from the table and never per call.  Initialised
 // dynamically (the pointers lead into the object itself), which no consumer can observe: tests/cpp/rungen_registration.cpp calls
@@ -460,6 +464,20 @@ extern "C" int hlmi_debug_resnet50_layer(halide_buffer_t *input, halide_buffer_t
 // resnet50.hip: the max pool (k x k window) and the tail (mean over W x H, fc with weights [N, C] and bias [N], softmax) at any size
 extern "C" int hlmi_debug_resnet50_maxpool(halide_buffer_t *input, int32_t k, int32_t stride, int32_t pad, halide_buffer_t *output);
 extern "C" int hlmi_debug_resnet50_tail(halide_buffer_t *input, halide_buffer_t *fc_weights, halide_buffer_t *fc_bias, halide_buffer_t *output);
+
+// hannk_conv.hip: the named entry point of apps/hannk's op library ("tile_conv_filter_uint8", "conv_u8_u8_u8", "conv_u8_u8_i16",
+// "depthwise_conv_uint8", "depthwise_conv_broadcast_uint8") in argv form with one thread per output running the contract's loops as
+// written, for the tests (default == general byte for byte) and for bench_apps.py.  -1 for an unknown name.  Per call: no mode is
+// kept anywhere.
+extern "C" int hlmi_hannk_general(const char *name, void **argv);
+// hannk_conv.hip, test hook: the device's epilogue alone on host arrays of n elements: fn 0 = quantize_i16 (out: int16_t[n]; zero, lo
+// and hi are not read), fn 1 = quantize_and_relu_u8 (out: uint8_t[n]).  Returns 0, < 0 = HIP error.
+extern "C" int hlmi_debug_hannk_quantize(int fn, const int32_t *acc, size_t n, int32_t multiplier, int32_t shift, uint8_t zero, uint8_t lo, uint8_t hi,
+                                         void *out);
+// hannk_conv.hip: what conv_*'s plan chooses for `npix` output pixels, `channels` output channels and `quads` = fw * fh * ci / 4 on
+// `cus` compute units with aligned operands: out = {1 if the MFMA kernel runs, k splits (1 = none), wave tiles}.  The switch
+// HLMI_HANNK_SPLIT_K (unset = the plan's choice, n >= 1 = that many splits where the k blocks allow) is read like in a call.
+extern "C" int hlmi_debug_hannk_conv_plan(int64_t npix, int32_t channels, int32_t quads, int32_t cus, int32_t *out);
 
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;

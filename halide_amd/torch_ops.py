@@ -823,3 +823,77 @@ def _(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_sample
 @bgu.register_fake
 def _(r_sigma, s_sigma, splat_loc, values, slice_loc):
     return torch.empty_like(slice_loc)
+
+
+# apps/hannk's quantised convolutions on NHWC uint8 tensors: the memory order of the ops' [c, x, y, b] buffers.  Padding happens on the
+# device with torch (the interpreter's pad op), the filter is tiled by the library's own kernel, and the op runs on torch's stream.
+def _hannk_check(name, *tensors):
+    for t in tensors:
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{name}: activations and filters are uint8 tensors, not {t.dtype}")
+
+
+def _hannk_pad(input, zero, channel_multiple, padding):
+    c = input.shape[3]
+    cp = -(-c // channel_multiple) * channel_multiple
+    if cp == c and padding[0] == 0 and padding[1] == 0:
+        return input.contiguous()
+    return torch.nn.functional.pad(input, (0, cp - c, padding[0], padding[0], padding[1], padding[1]), value=zero).contiguous()
+
+
+def _hannk_out_hw(input, fh, fw, stride, dilation, padding):
+    return (hl.hannk_conv_out_extent(input.shape[1], fh, stride[1], dilation[1], padding[1]),
+            hl.hannk_conv_out_extent(input.shape[2], fw, stride[0], dilation[0], padding[0]))
+
+
+@torch.library.custom_op("hlmi::hannk_conv2d", mutates_args=())
+def hannk_conv2d(input: torch.Tensor, filter: torch.Tensor, bias: torch.Tensor, input_zero: int, filter_zero: int, stride: list[int],
+                 dilation: list[int], padding: list[int], multiplier: int, shift: int, output_zero: int, output_min: int, output_max: int,
+                 out_int16: bool) -> torch.Tensor:
+    """apps/hannk conv: input (B, H, W, CI) uint8, filter (CO, FH, FW, CI) uint8, bias (CO,) int32 -> (B, OH, OW, CO) uint8, or int16 with
+    out_int16; stride, dilation and padding are (x, y) pairs, the padding is input_zero."""
+    _hannk_check("hannk_conv2d", input, filter)
+    co, fh, fw, ci = filter.shape
+    if input.shape[3] != ci:
+        raise RuntimeError(f"hannk_conv2d: the input has {input.shape[3]} channels, the filter {ci}")
+    padded = _hannk_pad(input, input_zero, hl.HANNK_VECTOR_REDUCTION, padding)
+    tiled = torch.empty((fh, fw, -(-co // 16), -(-ci // 4), 16, 4), dtype=torch.uint8, device=input.device)
+    oh, ow = _hannk_out_hw(input, fh, fw, stride, dilation, padding)
+    out = torch.empty((input.shape[0], oh, ow, co), dtype=torch.int16 if out_int16 else torch.uint8, device=input.device)
+    with _Wrapped(padded, filter.contiguous(), tiled, bias.contiguous(), out) as (a, f, t, b, o):
+        hl.tile_conv_filter_uint8(f, filter_zero, filter_zero, t)
+        (hl.conv_u8_u8_i16 if out_int16 else hl.conv_u8_u8_u8)(a, input_zero, t, filter_zero, b, stride, dilation, multiplier, shift, output_zero,
+                                                             output_min, output_max, o)
+    return out
+
+
+@torch.library.custom_op("hlmi::hannk_depthwise_conv2d", mutates_args=())
+def hannk_depthwise_conv2d(input: torch.Tensor, filter: torch.Tensor, bias: torch.Tensor, input_zero: int, filter_zero: int, stride: list[int],
+                           dilation: list[int], padding: list[int], multiplier: int, shift: int, output_zero: int, output_min: int,
+                           output_max: int) -> torch.Tensor:
+    """apps/hannk depthwise conv: input (B, H, W, C) uint8, filter (FH, FW, C) uint8, bias (C,) int32 -> (B, OH, OW, C) uint8; an input of
+    one channel under a filter of several is broadcast."""
+    _hannk_check("hannk_depthwise_conv2d", input, filter)
+    fh, fw, c = filter.shape
+    broadcast = input.shape[3] == 1 and c > 1
+    if not broadcast and input.shape[3] != c:
+        raise RuntimeError(f"hannk_depthwise_conv2d: the input has {input.shape[3]} channels, the filter {c}")
+    padded = _hannk_pad(input, input_zero, 1 if broadcast else hl.HANNK_DEPTHWISE_VECTOR, padding)
+    oh, ow = _hannk_out_hw(input, fh, fw, stride, dilation, padding)
+    out = torch.empty((input.shape[0], oh, ow, c), dtype=torch.uint8, device=input.device)
+    with _Wrapped(padded, filter.contiguous(), bias.contiguous(), out) as (a, f, b, o):
+        (hl.depthwise_conv_broadcast_uint8 if broadcast else hl.depthwise_conv_uint8)(a, input_zero, f, filter_zero, b, stride, dilation, multiplier,
+                                                                                     shift, output_zero, output_min, output_max, o)
+    return out
+
+
+@hannk_conv2d.register_fake
+def _(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, multiplier, shift, output_zero, output_min, output_max, out_int16):
+    oh, ow = _hannk_out_hw(input, filter.shape[1], filter.shape[2], stride, dilation, padding)
+    return input.new_empty((input.shape[0], oh, ow, filter.shape[0]), dtype=torch.int16 if out_int16 else torch.uint8)
+
+
+@hannk_depthwise_conv2d.register_fake
+def _(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, multiplier, shift, output_zero, output_min, output_max):
+    oh, ow = _hannk_out_hw(input, filter.shape[0], filter.shape[1], stride, dilation, padding)
+    return input.new_empty((input.shape[0], oh, ow, filter.shape[2]))

@@ -1,0 +1,26 @@
+/* depthwise_conv_uint8.h — stands in for the header the reference's generator emits next to depthwise_conv_uint8.a (apps/hannk/halide/CMakeLists.txt builds the op
+ * library with c_plus_plus_name_mangling: C++ only, every symbol in namespace hannk): code written against the reference
+ * (#include "halide/depthwise_conv_uint8.h" with -Iinclude/aot) includes this file unchanged and links libhlmi.so instead of the AOT object. */
+#ifndef HLMI_AOT_HALIDE_DEPTHWISE_CONV_UINT8_H
+#define HLMI_AOT_HALIDE_DEPTHWISE_CONV_UINT8_H
+#if defined(__has_include)
+#if __has_include("HalideRuntime.h")
+#include "HalideRuntime.h"
+#endif
+#endif
+#include <stdint.h>
+#include "../../hlmi_abi.h"
+#include "hannk_target.h"
+#ifndef __cplusplus
+#error "the hannk op library is built with C++ name mangling"
+#endif
+namespace hannk {
+/* input u8 [c, x, y, b], filter u8 [c, fx, fy], bias i32 [c] -> output u8 [c, x, y, b]; input_stride_x is not read */
+int depthwise_conv_uint8(struct halide_buffer_t *_input_buffer, uint8_t _input_zero, struct halide_buffer_t *_filter_buffer, uint8_t _filter_zero,
+    struct halide_buffer_t *_bias_buffer, int32_t _stride_x, int32_t _stride_y, int32_t _dilation_x, int32_t _dilation_y,
+    int32_t _input_stride_x, int32_t _output_multiplier, int32_t _output_shift, uint8_t _output_zero, uint8_t _output_min, uint8_t _output_max,
+    struct halide_buffer_t *_output_buffer);
+int depthwise_conv_uint8_argv(void **args);
+const struct halide_filter_metadata_t *depthwise_conv_uint8_metadata();
+}  // namespace hannk
+#endif

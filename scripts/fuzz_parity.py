@@ -828,6 +828,120 @@ def fuzz_fft(rng):
     return desc, ok
 
 
+def _nhwc(rng, shape, row_multiple, fill):
+    """a (B, H, W, C) uint8 view holding `fill`: dense, or inside a larger allocation with longer rows and planes further apart (strides
+    kept multiples of `row_multiple`, the first element on a 64-byte boundary as the interpreter allocates)"""
+    b, h, w, c = shape
+    rs = w * c + (int(rng.integers(1, 4)) * row_multiple if rng.random() < 0.5 else 0)
+    ps = rs * h + (int(rng.integers(1, 4)) * row_multiple if rng.random() < 0.5 else 0)
+    raw = np.full(ps * b + 64, 0xA5, np.uint8)
+    off = -raw.ctypes.data % 64
+    v = np.lib.stride_tricks.as_strided(raw[off:], (b, h, w, c), (ps, rs, c, 1))
+    v[...] = fill
+    return v, raw
+
+
+def _hannk_quant(rng):
+    return int(rng.integers(1 << 29, 1 << 31)), int(rng.integers(4, 13)), int(rng.integers(0, 256)), int(rng.integers(0, 40)), int(rng.integers(200, 256))
+
+
+def fuzz_hannk_conv(rng):
+    """conv_u8_u8_u8 or conv_u8_u8_i16 on random channels (1 .. 150 in, 1 .. 70 out), filter 1 .. 4 square or not, strides and dilations
+    1 .. 3, zero points, an output box with mins of its own cropped out of a larger input, padded rows and planes on both sides, the
+    default path (any split-K the plan takes, or one forced by HLMI_HANNK_SPLIT_K) or the general one, against tests/cpp/hannk_check.c.
+    Compared byte for byte; the bytes around the output must come back unchanged."""
+    import hannk_checker as hk
+    ci, co = rdim(rng, 1, 150), rdim(rng, 1, 70)
+    fw, fh = int(rng.integers(1, 5)), int(rng.integers(1, 5))
+    (sx, sy), (dx, dy) = rng.integers(1, 4, 2), rng.integers(1, 4, 2)
+    ow, oh, ob = rdim(rng, 1, 40), rdim(rng, 1, 12), int(rng.integers(1, 4))
+    omin = [0] + [int(v) for v in rng.integers(-3, 4, 3)]
+    i16, general = rng.random() < 0.3, rng.random() < 0.25
+    split = None if general or rng.random() < 0.6 else int(rng.integers(1, 7))
+    az, fz = int(rng.integers(0, 256)), int(rng.integers(0, 256))
+    cp = -(-ci // 4) * 4
+    # the input: the region the box reads plus a margin on every side
+    ext = lambda o, s, f, d: (o - 1) * s + (f - 1) * d + 1
+    mx, my = int(rng.integers(0, 3)), int(rng.integers(0, 3))
+    imin = [0, omin[1] * sx - mx, omin[2] * sy - my, omin[3]]
+    noise = rng.integers(0, 256, (ob, ext(oh, sy, fh, dy) + 2 * my, ext(ow, sx, fw, dx) + 2 * mx, cp), dtype=np.uint8)
+    noise[..., ci:] = az
+    inp, _keep_i = _nhwc(rng, noise.shape, 4, noise)
+    filt = rng.integers(0, 256, (co, fh, fw, ci), dtype=np.uint8)
+    tiled = hk.tile(filt, fz)
+    bias = rng.integers(-(1 << 24), 1 << 24, co).astype(np.int32)
+    q = _hannk_quant(rng)
+    want = hk.conv(inp, tiled, bias, [co, ow, oh, ob], (sx, sy), (dx, dy), az, fz, *q, np.int16 if i16 else np.uint8, in_mins=imin, out_mins=omin)
+    out_raw = np.full((ob, oh, ow * co + 3), 0x5A5A if i16 else 0x5A, np.int16 if i16 else np.uint8)
+    o = hl.Buffer(np.lib.stride_tricks.as_strided(out_raw, (ob, oh, ow, co), tuple(v * out_raw.itemsize for v in (oh * (ow * co + 3), ow * co + 3, co, 1))),
+                  mins=omin)
+    tb = hl.Buffer(hl.aligned_array(tiled.shape, np.uint8, 64, 1))
+    tb.array[...] = tiled
+    name = "conv_u8_u8_i16" if i16 else "conv_u8_u8_u8"
+    args = [hl.Buffer(inp, mins=imin), az, tb, fz, hl.Buffer(bias), int(sx), int(sy), int(dx), int(dy), *q, o]
+    prev = os.environ.pop("HLMI_HANNK_SPLIT_K", None)
+    try:
+        if split is not None:
+            os.environ["HLMI_HANNK_SPLIT_K"] = str(split)
+        if general:
+            hl.debug_hannk_general(name, *args)
+        else:
+            hl._check(hl._fn[name](*[a.ptr if isinstance(a, hl.Buffer) else a for a in args]))
+        got = o.numpy()
+    finally:
+        os.environ.pop("HLMI_HANNK_SPLIT_K", None)
+        if prev is not None:
+            os.environ["HLMI_HANNK_SPLIT_K"] = prev
+    ok = np.array_equal(got, want) and bool((out_raw[:, :, ow * co:] == (0x5A5A if i16 else 0x5A)).all())
+    desc = (f"{name}{' general' if general else ''} {ci}->{co} filter {fw}x{fh} stride ({sx},{sy}) dilation ({dx},{dy}) out {ow}x{oh}x{ob} at {omin[1:]} "
+            f"zeros ({az},{fz}) quant {q} split {split} input strides {[v for v in inp.strides]}")
+    return desc, ok
+
+
+def fuzz_hannk_depthwise(rng):
+    """depthwise_conv_uint8 or its broadcast variant on random channels (1 .. 70), filter 1 .. 5 (3 x 3 in a third of the cases), strides
+    and dilations 1 .. 3, zero points, a cropped output box, padded input rows (multiples of 16), either path, against
+    tests/cpp/hannk_check.c, byte for byte."""
+    import hannk_checker as hk
+    c = rdim(rng, 1, 70)
+    fw, fh = (3, 3) if rng.random() < 0.33 else (int(rng.integers(1, 6)), int(rng.integers(1, 6)))
+    (sx, sy), (dx, dy) = rng.integers(1, 4, 2), rng.integers(1, 4, 2)
+    ow, oh, ob = rdim(rng, 1, 30), rdim(rng, 1, 14), int(rng.integers(1, 4))
+    omin = [0] + [int(v) for v in rng.integers(-3, 4, 3)]
+    broadcast, general = rng.random() < 0.25, rng.random() < 0.25
+    az, fz = int(rng.integers(0, 256)), int(rng.integers(0, 256))
+    cp = 1 if broadcast else -(-c // 16) * 16
+    ext = lambda o, s, f, d: (o - 1) * s + (f - 1) * d + 1
+    imin = [0, omin[1] * sx, omin[2] * sy, omin[3]]
+    noise = rng.integers(0, 256, (ob, ext(oh, sy, fh, dy), ext(ow, sx, fw, dx), cp), dtype=np.uint8)
+    inp, _keep_i = _nhwc(rng, noise.shape, 16, noise) if not broadcast else (noise, None)
+    filt = rng.integers(0, 256, (fh, fw, c), dtype=np.uint8)
+    bias = rng.integers(-(1 << 16), 1 << 16, c).astype(np.int32)
+    q = _hannk_quant(rng)
+    q = (q[0], int(rng.integers(0, 8)), *q[2:])
+    want = hk.depthwise(inp, filt, bias, [c, ow, oh, ob], (sx, sy), (dx, dy), az, fz, *q, broadcast, in_mins=imin, out_mins=omin)
+    o = hl.Buffer(np.full((ob, oh, ow, c), 0x5A, np.uint8), mins=omin)
+    name = "depthwise_conv_broadcast_uint8" if broadcast else "depthwise_conv_uint8"
+    args = [hl.Buffer(inp, mins=imin), az, hl.Buffer(filt), fz, hl.Buffer(bias), int(sx), int(sy), int(dx), int(dy), 0, *q, o]
+    vector = None if general or rng.random() < 0.3 else 1   # these outputs are below the plan's threshold: force its kernel
+    prev = os.environ.pop("HLMI_HANNK_DW_VECTOR", None)
+    try:
+        if vector is not None:
+            os.environ["HLMI_HANNK_DW_VECTOR"] = str(vector)
+        if general:
+            hl.debug_hannk_general(name, *args)
+        else:
+            hl._check(hl._fn[name](*[a.ptr if isinstance(a, hl.Buffer) else a for a in args]))
+    finally:
+        os.environ.pop("HLMI_HANNK_DW_VECTOR", None)
+        if prev is not None:
+            os.environ["HLMI_HANNK_DW_VECTOR"] = prev
+    ok = np.array_equal(o.numpy(), want)
+    desc = (f"{name}{' general' if general else ''} c {c} filter {fw}x{fh} stride ({sx},{sy}) dilation ({dx},{dy}) out {ow}x{oh}x{ob} at {omin[1:]} "
+            f"zeros ({az},{fz}) quant {q} vector {vector}")
+    return desc, ok
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
@@ -839,6 +953,8 @@ CASES["mat_mul"] = fuzz_mat_mul   # sized and general paths; one chain in both c
 CASES["linear_algebra"] = fuzz_linear_algebra   # all twelve entry points, both paths (tests/linear_algebra_checker.py)
 CASES["linear_algebra_f64"] = fuzz_linear_algebra_f64   # the f64 half, both paths (tests/linear_algebra_f64_checker.py)
 CASES["fft"] = fuzz_fft   # all four kinds, both paths (tests/fft_checker.py)
+CASES["hannk_conv"] = fuzz_hannk_conv   # both output types, both paths, split-K; integer throughout (tests/hannk_checker.py)
+CASES["hannk_depthwise"] = fuzz_hannk_depthwise   # both variants, both paths
 
 
 def stress(args, only):
