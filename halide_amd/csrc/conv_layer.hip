@@ -14,9 +14,10 @@
 //   workgroup = 4 waves = 128 pixels x 128 output channels; wave = 2x2 accumulators of 32x32
 //   per (ky, kx, 32-ci chunk): A (128 px x 32 ci, 128 B contiguous per pixel) and B (32 ci x 128 co, 512 B rows)
 //   are staged in LDS k-major; operands are one f32 VGPR per lane: A[i = lane&31][k = lane>>5], B[k][j = lane&31].
-//   Epilogue: ReLU, C/D map row = (reg&3) + 8*(reg>>2) + 4*(lane>>5) -> pixel, col = lane&31 -> co: each
+//   Epilogue: ReLU, C/D map row = chain::cd_row(reg) + 4*(lane>>5) -> pixel, col = lane&31 -> co: each
 //   half-wave stores 128 contiguous bytes.
 // bf16 MFMA path (`conv_layer_bf16`, BASELINE configs[4]): see conv_layer_bf16.hip.
+#include "f32_chain_gemm.h"
 #include "hlmi_internal.h"
 
 using namespace hlmi;
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(256) void conv3x3_f32_mfma(const float *__restrict_
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int row = chain::cd_row(r) + 4 * (lane >> 5);
             const long p = p0 + 64 * wm + 32 * a + row;
             if (p < g.npix) {
 #pragma unroll

@@ -6,24 +6,20 @@
 // src/CMakeLists.txt.  The contract, the checks, the entry points' bodies and every kernel but the one below are in
 // linear_algebra_core.h; a vectorised reduction keeps the V = 8 lane sums of the reference's x86-64 AVX2 build.
 // This file holds the named constants, the extern "C" surface and
-//   sgemm (four variants)          sgemm_mfma<W, FAST, TA, TB>: mat_mul.hip's tile loop for M != N != K.  The variants are the
-//                                  2 x 2 of "opA is i-contiguous or k-contiguous" x "opB is k-contiguous or j-contiguous": an
-//                                  operand contiguous along its tile dimension is copied straight into LDS, one contiguous along
-//                                  k is turned k-major on the way in.  transAB needs no swap of roles here: the product commutes,
-//                                  and k still runs upward.  k strictly upward, no zero-padded step (an odd K ends in a VALU fmaf
-//                                  on the accumulator registers through the C/D map), global loads two chunks ahead, LDS
-//                                  double-buffered, the mad2 epilogue on the accumulator registers with C read in the 128-byte
-//                                  half-wave rows the store uses.  v_mfma_f32_32x32x2_f32 is a chain of fused steps, so these
+//   sgemm (four variants)          sgemm_mfma<W, FAST, TA, TB>: chain::tile() of f32_chain_gemm.h, the tile loop mat_mul.hip shares,
+//                                  for M != N != K.  The variants are the 2 x 2 of "opA is i-contiguous or k-contiguous" x "opB is
+//                                  k-contiguous or j-contiguous", which is the tile's "straight or turned" per operand.  transAB
+//                                  needs no swap of roles here: the product commutes, and k still runs upward.  The epilogue is
+//                                  mad2 on the accumulator registers.  v_mfma_f32_32x32x2_f32 is a chain of fused steps, so these
 //                                  kernels exist in the default build only: with HLMI_CANON_FMA=0 (each product rounded before
 //                                  the add) the plan always answers the one-thread-per-output kernel.
+#include "f32_chain_gemm.h"
 #include "linear_algebra_core.h"
 
 using namespace hlmi;
 using namespace hlmi::la_host;
 
 namespace {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int V = 8;                     // natural_vector_size(float) of the reference's x86-64 AVX2 target: a choice
 constexpr int MAX_VECTOR = 134217728;    // vector lengths 0 .. 2^27
@@ -36,7 +32,8 @@ constexpr int GEMV_U = 8;                // k steps per unrolled group of the tw
 constexpr int SMALL_TILE = 64;           // sgemm workgroup tile with one accumulator per wave
 constexpr int LARGE_TILE = 128;          // sgemm workgroup tile with 2 x 2 accumulators per wave
 constexpr int LARGE_FROM_WGS = 256;      // the large tile where it still leaves this many workgroups (x 4 waves = 256 CUs x 4 SIMDs)
-constexpr int KC = 32;                   // k steps per staged chunk of the small tile; the large tile stages KC / 2
+constexpr int KC = 32;                   // the tile loop's chunk, as gemm_plan() and the tests read it: a K that is no multiple of it has a short last chunk
+static_assert(KC == chain::KC, "gemm_plan() plans for the chunk that chain::tile() stages");
 
 using GGeom = la::GGeom<float>;
 
@@ -54,168 +51,21 @@ const auto &tables = la::tables<F32>;
 
 // ---------------------------------------------------------------------------------------------------------------- sgemm
 #if HLMI_CANON_FMA
-// mat_mul.hip's mm_mfma for M != N != K with either operand stored either way.  x = i (the MFMA's column, contiguous in C and the
-// result), y = j.  Operand X[k][x] = opA(x, k): A[k * sa + x] (straight) or, TA, A[x * sa + k] (turned).  Operand Y[k][y] = opB(k, y):
-// B[y * sb + k] (turned) or, TB, B[k * sb + y] (straight).
+// chain::tile() with x = i (the MFMA's column, contiguous in C and the result), y = j.  Operand X[k][x] = opA(x, k): A[k * sa + x]
+// (straight) or, TA, A[x * sa + k] (turned).  Operand Y[k][y] = opB(k, y): B[y * sb + k] (turned) or, TB, B[k * sb + y] (straight).
+struct SgemmOps {
+    static __device__ __forceinline__ int M(const GGeom &g) { return g.M; }
+    static __device__ __forceinline__ int N(const GGeom &g) { return g.N; }
+    static __device__ __forceinline__ int K(const GGeom &g) { return g.K; }
+    // result(x, y) = mad2(a, ab, b, C(x, y)): C is read where the result is written, in the 128-byte half-wave rows the store uses
+    static __device__ __forceinline__ void store(const GGeom &g, int x, int y, float acc) {
+        g.out[(long)y * g.so + x] = dev::mad2(g.a, acc, g.b, g.C[(long)y * g.sc + x]);
+    }
+};
+
 template<int W, bool FAST, bool TA, bool TB>
 __global__ __launch_bounds__(256) void sgemm_mfma(GGeom g) {
-    constexpr int T = 64 * W;          // tile edge
-    constexpr int KCH = KC / W;        // k per chunk
-    constexpr bool XTURN = TA, YTURN = !TB;
-    constexpr int XP = XTURN ? T + 1 : T, YP = YTURN ? T + 1 : T;   // LDS pitches: conflict-light scalar stores / float4 stores
-    constexpr int TQ = T / 4;          // float4 per LDS row of a straight operand
-    constexpr int KQ = KCH / 4;        // float4 per tile row of a turned operand
-    static_assert(KCH * T / 4 == 512, "two float4 per thread and operand");
-    __shared__ __attribute__((aligned(16))) float sX[2][KCH * XP];  // [k][x]
-    __shared__ __attribute__((aligned(16))) float sY[2][KCH * YP];  // [k][y]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wy = (wave >> 1) * 32 * W, wx = (wave & 1) * 32 * W;   // wave tile origin inside the workgroup tile
-    const int x0 = blockIdx.x * T, y0 = blockIdx.y * T;
-    const int K = g.K;
-
-    // float4 number f of a chunk of one operand: `t0` the tile's origin in the operand's tile dimension, `tn` that dimension's extent
-    auto load_op = [&](auto turned, const float *base, long stride, int t0, int tn, int k0, int f, float4 &p) {
-        if constexpr (decltype(turned)::value) {
-            const int tt = f / KQ, kk = 4 * (f % KQ);   // tile row tt, first k
-            if constexpr (FAST) {
-                p = *reinterpret_cast<const float4 *>(base + (long)(t0 + tt) * stride + k0 + kk);
-            } else {   // clamped: what lies past the matrix is loaded from its last row / column and never reaches a stored result
-                const float *r = base + (long)min(t0 + tt, tn - 1) * stride;
-                p = make_float4(r[min(k0 + kk, K - 1)], r[min(k0 + kk + 1, K - 1)], r[min(k0 + kk + 2, K - 1)], r[min(k0 + kk + 3, K - 1)]);
-            }
-        } else {
-            const int kk = f / TQ, tc = 4 * (f % TQ);   // row k, first tile column
-            if constexpr (FAST) {
-                p = *reinterpret_cast<const float4 *>(base + (long)(k0 + kk) * stride + t0 + tc);
-            } else {
-                const float *r = base + (long)min(k0 + kk, K - 1) * stride;
-                p = make_float4(r[min(t0 + tc, tn - 1)], r[min(t0 + tc + 1, tn - 1)], r[min(t0 + tc + 2, tn - 1)], r[min(t0 + tc + 3, tn - 1)]);
-            }
-        }
-    };
-    auto stage_op = [&](auto turned, float *buf, int pitch, int f, const float4 &p) {
-        if constexpr (decltype(turned)::value) {
-            const int tt = f / KQ, kk = 4 * (f % KQ);
-            buf[(kk + 0) * pitch + tt] = p.x;
-            buf[(kk + 1) * pitch + tt] = p.y;
-            buf[(kk + 2) * pitch + tt] = p.z;
-            buf[(kk + 3) * pitch + tt] = p.w;
-        } else {
-            const int kk = f / TQ, tc = 4 * (f % TQ);
-            *reinterpret_cast<float4 *>(&buf[kk * pitch + tc]) = p;
-        }
-    };
-    constexpr std::integral_constant<bool, XTURN> xturn{};
-    constexpr std::integral_constant<bool, YTURN> yturn{};
-
-    // Two chunks in flight: two float4 of each operand per thread and chunk, float4 number f = tid and tid + 256 of the chunk
-    float4 ax0, ax1, ay0, ay1, bx0, bx1, by0, by1;   // set a: even chunks, set b: odd chunks (named registers, as in mat_mul.hip)
-    auto load = [&](int k0, float4 &rx0, float4 &rx1, float4 &ry0, float4 &ry1) {
-        load_op(xturn, g.A, g.sa, x0, g.M, k0, tid, rx0);
-        load_op(yturn, g.B, g.sb, y0, g.N, k0, tid, ry0);
-        load_op(xturn, g.A, g.sa, x0, g.M, k0, tid + 256, rx1);
-        load_op(yturn, g.B, g.sb, y0, g.N, k0, tid + 256, ry1);
-    };
-    auto stage = [&](int buf, const float4 &rx0, const float4 &rx1, const float4 &ry0, const float4 &ry1) {
-        stage_op(xturn, sX[buf], XP, tid, rx0);
-        stage_op(yturn, sY[buf], YP, tid, ry0);
-        stage_op(xturn, sX[buf], XP, tid + 256, rx1);
-        stage_op(yturn, sY[buf], YP, tid + 256, ry1);
-    };
-
-    floatx16 acc[W][W];
-#pragma unroll
-    for (int a = 0; a < W; a++)
-#pragma unroll
-        for (int b = 0; b < W; b++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[a][b][r] = 0.0f;
-
-    // one MFMA step: k = 2 * s (lanes 0 .. 31) and 2 * s + 1 (lanes 32 .. 63), in that order inside the instruction
-    auto step = [&](const float *pa, const float *pb, int s) {
-        float av[W], bv[W];
-#pragma unroll
-        for (int a = 0; a < W; a++) av[a] = pa[2 * s * YP + 32 * a];
-#pragma unroll
-        for (int b = 0; b < W; b++) bv[b] = pb[2 * s * XP + 32 * b];
-#pragma unroll
-        for (int a = 0; a < W; a++)
-#pragma unroll
-            for (int b = 0; b < W; b++) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-    };
-
-    // Chunk c is computed from LDS buffer c & 1 while the loads of chunk c + 2 are issued and, after the MFMAs, chunk c + 1 (loaded one
-    // whole chunk earlier) goes to the other buffer, last read in iteration c - 1 behind that iteration's barrier.
-    const int nchunk = (K + KCH - 1) / KCH;
-    auto chunk = [&](int c, float4 &nx0, float4 &nx1, float4 &ny0, float4 &ny1, const float4 &sx0, const float4 &sx1, const float4 &sy0, const float4 &sy1) {
-        const int buf = c & 1;
-        load(min(c + 2, nchunk - 1) * KCH, nx0, nx1, ny0, ny1);   // unconditional (past the end: the last chunk again, never staged into a buffer that is read)
-        const float *pa = sY[buf] + (lane >> 5) * YP + wy + (lane & 31);
-        const float *pb = sX[buf] + (lane >> 5) * XP + wx + (lane & 31);
-        const int kc = FAST ? KCH : min(KCH, K - c * KCH);   // k steps this chunk holds
-        if (FAST || kc == KCH) {
-            // a whole chunk: every operand read from LDS first, so that the reads of later steps are in flight under the MFMAs of earlier ones
-            float av[KCH / 2][W], bv[KCH / 2][W];
-#pragma unroll
-            for (int s = 0; s < KCH / 2; s++) {
-#pragma unroll
-                for (int a = 0; a < W; a++) av[s][a] = pa[2 * s * YP + 32 * a];
-#pragma unroll
-                for (int b = 0; b < W; b++) bv[s][b] = pb[2 * s * XP + 32 * b];
-            }
-            __builtin_amdgcn_sched_barrier(0);   // or the scheduler sinks each read to its MFMA again, to save registers
-#pragma unroll
-            for (int s = 0; s < KCH / 2; s++)
-#pragma unroll
-                for (int a = 0; a < W; a++)
-#pragma unroll
-                    for (int b = 0; b < W; b++) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s][a], bv[s][b], acc[a][b], 0, 0, 0);
-        } else {
-#pragma unroll 1
-            for (int s = 0; s < kc / 2; s++) step(pa, pb, s);
-            if (kc & 1) {
-                // The last step of an odd K has no partner: a zero-padded one would turn a chain that ends in -0 into +0.  It is a
-                // VALU fmaf on each accumulator register instead, operands picked through the C/D map.
-                const float *ky = sY[buf] + (kc - 1) * YP + wy + 4 * (lane >> 5);
-                const float *kx = sX[buf] + (kc - 1) * XP + wx + (lane & 31);
-#pragma unroll
-                for (int a = 0; a < W; a++)
-#pragma unroll
-                    for (int b = 0; b < W; b++) {
-                        const float xv = kx[32 * b];
-#pragma unroll
-                        for (int r = 0; r < 16; r++) {
-                            const int row = (r & 3) + 8 * (r >> 2);
-                            acc[a][b][r] = __builtin_fmaf(xv, ky[32 * a + row], acc[a][b][r]);
-                        }
-                    }
-            }
-        }
-        stage(buf ^ 1, sx0, sx1, sy0, sy1);
-        __syncthreads();
-    };
-    load(0, ax0, ax1, ay0, ay1);
-    stage(0, ax0, ax1, ay0, ay1);
-    load(min(1, nchunk - 1) * KCH, bx0, bx1, by0, by1);
-    __syncthreads();
-#pragma unroll 1
-    for (int c = 0; c < nchunk; c += 2) {
-        chunk(c, ax0, ax1, ay0, ay1, bx0, bx1, by0, by1);
-        if (c + 1 < nchunk) chunk(c + 1, bx0, bx1, by0, by1, ax0, ax1, ay0, ay1);
-    }
-
-    // ---- epilogue: result(x, y) = mad2(a, ab, b, C(x, y)), x = lane & 31 contiguous; C is read where the result is written
-#pragma unroll
-    for (int a = 0; a < W; a++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int y = y0 + wy + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-#pragma unroll
-            for (int b = 0; b < W; b++) {
-                const int x = x0 + wx + 32 * b + (lane & 31);
-                if (FAST || (y < g.N && x < g.M)) g.out[(long)y * g.so + x] = dev::mad2(g.a, acc[a][b][r], g.b, g.C[(long)y * g.sc + x]);
-            }
-        }
+    chain::tile<W, FAST, TA, !TB, SgemmOps>(g);
 }
 #endif   // HLMI_CANON_FMA
 

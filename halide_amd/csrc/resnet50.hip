@@ -17,7 +17,7 @@
 // (64 x 112 x 112 = 256 x 56 x 56 floats, 3.2 MB) used in rotation, then the pooled vector, the logits and their exponentials.
 //
 // Convolution kernels (conv_plan() is the one place that chooses):
-//   resnet50_conv_mfma     implicit GEMM on `v_mfma_f32_32x32x2_f32`, a k-ordered chain of fused steps (mat_mul.hip), 4 waves on a tile of
+//   resnet50_conv_mfma     implicit GEMM on `v_mfma_f32_32x32x2_f32`, a k-ordered chain of fused steps (f32_chain_gemm.h), 4 waves on a tile of
 //                          64 co x 64 output pixels.  MFMA operand "B"[k][j] is w(co = j, k): row k of the weights is co-contiguous at
 //                          an offset computed from (ky, kx, ci), copied straight.  Operand "A"[i][k] is the activation of pixel i at
 //                          tap k: ci-contiguous in memory, +0 where the tap is outside the image, turned k-major on the way into LDS.
@@ -32,6 +32,7 @@
 //                          leave the tile loop nothing to overlap, and there the plain chain measured faster
 // The other kernels are one thread per output: resnet50_maxpool, resnet50_avgpool, resnet50_fc (lanes along c, so the weight loads
 // coalesce) and resnet50_softmax (one workgroup; the 1000-step sum is one serial chain by contract).
+#include "f32_chain_gemm.h"
 #include "hlmi_internal.h"
 #include "hlmi_device_math.h"
 
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(64 * NCO * NPX) void rn_conv_mfma(CGeom g) {
                 const float *ka = sA + (kc - 1) * AP + wp * 32 + 4 * (lane >> 5);
                 const float wv = sW[(kc - 1) * WP + wc * 32 + (lane & 31)];
 #pragma unroll
-                for (int r = 0; r < 16; r++) acc[r] = __builtin_fmaf(wv, ka[(r & 3) + 8 * (r >> 2)], acc[r]);
+                for (int r = 0; r < 16; r++) acc[r] = __builtin_fmaf(wv, ka[chain::cd_row(r)], acc[r]);
             }
         }
     };
@@ -184,13 +185,13 @@ __global__ __launch_bounds__(64 * NCO * NPX) void rn_conv_mfma(CGeom g) {
         __syncthreads();
     }
 
-    // ---- epilogue on the accumulator registers: C/D map row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) = pixel, col = lane & 31 = co
+    // ---- epilogue on the accumulator registers: C/D map row = chain::cd_row(reg) + 4 (lane >> 5) = pixel, col = lane & 31 = co
     const int co = co0 + wc * 32 + (lane & 31);
     if (co < g.CO) {
         const Chan ch = rn_chan(g, co);
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            const int px = wp * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int px = wp * 32 + chain::cd_row(r) + 4 * (lane >> 5);
             if (p0 + px < npix) g.out[sPo[px] + co] = rn_finish(g, ch, acc[r], sPr[px] + co);
         }
     }

@@ -940,6 +940,28 @@ def test_gemm_large_tile_of_the_transposed_variants(hl, canon_lib, name):
     assert ran == (["sgemm_mfma"] if hl.canon_fma() else ["sgemm_general"])
 
 
+LARGE_EDGE_DIMS = {"halide_sgemm_transA": (385, 8065, 385), "halide_sgemm_transB": (8065, 385, 385), "halide_sgemm_transAB": (1921, 1921, 1921)}
+
+
+def test_the_large_tile_edge_shapes_are_the_smallest_their_rules_allow():
+    """256 workgroups of 128 x 128 with no extent above MAX_EXTENT are 4 x 64 tiles where only one of M, N is tied to K (one extent more
+    than 3 and than 63 tiles: 385 and 8065, both off the tile, K = 385 odd) and 16 x 16 where both are (one more than 15 tiles: 1921)"""
+    wgs = lambda M, N: -(-M // LARGE_TILE) * -(-N // LARGE_TILE)
+    for name, (M, N, K) in LARGE_EDGE_DIMS.items():
+        tA, tB = la.GEMM_FLAGS[name]
+        assert (not tA or M == K) and (not tB or N == K) and max(M, N, K) <= MAX_EXTENT
+        assert wgs(M, N) >= LARGE_FROM_WGS and K % 2 == 1 and (M % LARGE_TILE or N % LARGE_TILE)
+        assert wgs(M - 1, N) < LARGE_FROM_WGS and wgs(M, N - 1) < LARGE_FROM_WGS   # one less either way and the plan takes the small tile
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", tuple(LARGE_EDGE_DIMS))
+def test_gemm_large_tile_edge_kernel_of_the_transposed_variants(hl, canon_lib, name):
+    """sgemm_mfma<2, false, ., .> of each transposed variant: ragged tiles, a short last chunk and the odd last step on the VALU"""
+    ran = _run(hl, name, _inputs(name, LARGE_EDGE_DIMS[name], seed=10))
+    assert ran == (["sgemm_mfma_edge"] if hl.canon_fma() else ["sgemm_general"])
+
+
 @pytest.mark.gpu
 @PATHS
 @EACH
