@@ -671,6 +671,65 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
         emit("hannk_depthwise", "apps/hannk depthwise_conv_uint8, MobileNet-v1 224: " + d0["shape"], t0_, 32 * 14 * 14, "hbm", d0["gbs"], HBM_PEAK_GBS, "GB/s",
              {"layers": [d for d, _ in layers], "torch_note": "torch.nn.functional.conv2d in f16 with groups = channels, same shape and run"})
 
+    # ---- hannk_pool / hannk_softmax / hannk_add: the memory- and latency-bound ops of apps/hannk's op library on the shapes a MobileNet
+    #      runs them at, each at batch 1 and 32, device-resident operands.  Input + output bytes against membench's copy rate of the same
+    #      run (`of_copy_rate`, absent when membench is not part of the run); beside each the same call with one thread per output
+    #      (hlmi_hannk_general): wherever the default path is not faster, the plan's predicate is wrong.
+    def hannk_nn_line(shape, entry, fn_args, out, nbytes):
+        """fn_args: the entry point's C arguments in order (device-resident Buffers), out among them"""
+        call = lambda: hl._check(hl._fn[entry](*[a.ptr if isinstance(a, hl.Buffer) else a for a in fn_args]))
+        general = lambda: hl.debug_hannk_general(entry, *fn_args)
+        t = timed(call, out, 200)
+        clock = last_clock[0]
+        tg = timed(general, out, 20)
+        last_clock[0] = clock
+        k_, kg = kernels(call, out), kernels(general, out)
+        d = {"shape": shape, "entry": entry, "ms_per_call": round(t * 1e3, 4), "kernels_ms": k_, "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kg},
+             "fast_path_faster": bool(t < tg), "kernel_faster": bool(sum(k_.values()) < sum(kg.values())), "alg_bytes": float(nbytes),
+             "gbs": round(nbytes / t / 1e9, 2), "kernel_gbs": round(nbytes / (sum(k_.values()) / 1e3) / 1e9, 2), "clock_state": clock}
+        if copy_gbs[0]:
+            d["of_copy_rate"] = round(nbytes / t / 1e9 / copy_gbs[0], 5)
+            d["kernel_of_copy_rate"] = round(d["kernel_gbs"] / copy_gbs[0], 5)
+        return d, t
+
+    def dev(a, mins=None):
+        b_ = hl.Buffer(a, mins=mins)
+        b_.copy_to_device()
+        return b_
+
+    if not only or "hannk_pool" in only:
+        lines = []
+        for batch in (1, 32):
+            x = dev(rng.integers(0, 256, (batch, 7, 7, 1024), dtype=np.uint8))
+            o = hl.Buffer(np.zeros((batch, 1, 1, 1024), np.uint8))
+            lines.append(hannk_nn_line(f"average 7x7 over 7^2 x 1024, batch {batch}", "average_pool_uint8", [x, 1, 1, 7, 7, 0, 255, o], o, x.array.size + o.array.size))
+            o2 = hl.Buffer(np.zeros((batch, 1, 1, 1024), np.uint8))
+            lines.append(hannk_nn_line(f"mean over 7 x 7 x 1024, batch {batch}", "mean_uint8", [x, 0, 1, 0, 7, 0, 7, 0, 1, o2], o2, x.array.size + o2.array.size))
+            y = dev(rng.integers(0, 256, (batch, 112, 112, 64), dtype=np.uint8), mins=(0, 1, 1, 0))   # "same" padding: translated by 1
+            o3 = hl.Buffer(np.zeros((batch, 56, 56, 64), np.uint8))
+            lines.append(hannk_nn_line(f"max 3x3 s2 over 112^2 x 64, batch {batch}", "max_pool_uint8", [y, 2, 2, 3, 3, 0, 255, o3], o3, y.array.size + o3.array.size))
+        d0, t0_ = lines[5]   # the max pool at batch 32
+        emit("hannk_pool", "apps/hannk average_pool_uint8, mean_uint8 and max_pool_uint8; headline: " + d0["shape"], t0_, 32 * 56 * 56, "hbm", d0["gbs"],
+             HBM_PEAK_GBS, "GB/s", {"layers": [d for d, _ in lines]})
+    if not only or "hannk_softmax" in only:
+        lines = []
+        for batch in (1, 32):
+            x = dev(rng.integers(0, 256, (batch, 1001), dtype=np.uint8))
+            o = hl.Buffer(np.zeros((batch, 1001), np.uint8))
+            lines.append(hannk_nn_line(f"softmax on {batch} rows of 1001", "softmax_uint8", [x, 23637, 9, 0, 16384, 6, o], o, 2 * x.array.size))
+        d0, t0_ = lines[1]
+        emit("hannk_softmax", "apps/hannk softmax_uint8 (input scale 1/16, output scale 1/256); headline: " + d0["shape"], t0_, 32 * 1001, "hbm", d0["gbs"],
+             HBM_PEAK_GBS, "GB/s", {"layers": [d for d, _ in lines]})
+    if not only or "hannk_add" in only:
+        lines = []
+        for batch in (1, 32):
+            a_, b_ = dev(rng.integers(0, 256, (batch * 56 * 56, 24), dtype=np.uint8)), dev(rng.integers(0, 256, (batch * 56 * 56, 24), dtype=np.uint8))
+            o = hl.Buffer(np.zeros((batch * 56 * 56, 24), np.uint8))
+            lines.append(hannk_nn_line(f"add on 56^2 x 24, batch {batch}", "add_uint8_uint8", [a_, 120, 640, b_, 7, 384, 100, 0, 255, o], o, 3 * o.array.size))
+        d0, t0_ = lines[1]
+        emit("hannk_add", "apps/hannk add_uint8_uint8, MobileNet-v2's residual add; headline: " + d0["shape"], t0_, 32 * 56 * 56, "hbm", d0["gbs"], HBM_PEAK_GBS,
+             "GB/s", {"layers": [d for d, _ in lines]})
+
     # ---- fft: apps/fft's c2c, r2c and c2r at 16^2 (the size the reference builds; launch-bound), 256^2, 1024^2 and 4096^2, device buffers,
     #      gain 1.  The two line passes move each complex array twice in and twice out: "moved_bytes" is that, its rate stands beside
     #      membench's copy rate of the same run ("copy_frac"); "launch_bound": moving those bytes at that rate would take under a tenth

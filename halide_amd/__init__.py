@@ -13,6 +13,7 @@ gfx950 device is usable every pipeline call raises ``HalideError`` (code -29).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 
@@ -411,14 +412,24 @@ _HANNK_DW_PARAMS = "P15halide_buffer_thS1_hS1_iiiiiiihhhS1_"
 _HANNK_PARAMS = {"tile_conv_filter_uint8": "P15halide_buffer_thhS1_", "conv_u8_u8_u8": _HANNK_CONV_PARAMS, "conv_u8_u8_i16": _HANNK_CONV_PARAMS,
                  "depthwise_conv_uint8": _HANNK_DW_PARAMS, "depthwise_conv_broadcast_uint8": _HANNK_DW_PARAMS}
 HANNK_OPS = tuple(_HANNK_PARAMS)
+# the pooling, reduction, elementwise and normalisation ops: s int16_t, t uint16_t, j uint32_t
+_HANNK_POOL_PARAMS = "P15halide_buffer_tiiiihhS1_"
+_HANNK_NN_PARAMS = {"average_pool_uint8": _HANNK_POOL_PARAMS, "max_pool_uint8": _HANNK_POOL_PARAMS, "mean_uint8": "P15halide_buffer_tiiiiiiiiS1_",
+                    "add_uint8_uint8": "P15halide_buffer_thsS1_hshhhS1_", "mul_uint8_uint8_uint8": "P15halide_buffer_thS1_hhijhhS1_",
+                    "softmax_uint8": "P15halide_buffer_tsthstS1_", "l2_normalization_uint8": "P15halide_buffer_thS1_"}
+HANNK_NN_OPS = tuple(_HANNK_NN_PARAMS)
+_HANNK_ALL_PARAMS = {**_HANNK_PARAMS, **_HANNK_NN_PARAMS}
+# ctypes of a scalar argument by (halide type code, bits)
+_SCALAR_CTYPES = {(2, 32): C.c_float, (2, 64): C.c_double, (0, 32): C.c_int32, (1, 8): C.c_uint8, (0, 16): C.c_int16, (1, 16): C.c_uint16,
+                  (1, 32): C.c_uint32}
 
 
 def _symbol(name, suffix=""):
     """The exported symbol of entry point `name` (+ "_argv" / "_metadata"): the name itself, or hannk's mangled one."""
-    if name not in _HANNK_PARAMS:
+    if name not in _HANNK_ALL_PARAMS:
         return name + suffix
     full = name + suffix
-    return f"_ZN5hannk{len(full)}{full}E" + {"": _HANNK_PARAMS[name], "_argv": "PPv", "_metadata": "v"}[suffix]
+    return f"_ZN5hannk{len(full)}{full}E" + {"": _HANNK_ALL_PARAMS[name], "_argv": "PPv", "_metadata": "v"}[suffix]
 
 
 def _bind(name):
@@ -430,7 +441,7 @@ def _bind(name):
     md = metadata(name)
     argtypes = []
     for a in (md.arguments[i] for i in range(md.num_arguments)):
-        t = _BP if a.kind != 0 else {(2, 32): C.c_float, (2, 64): C.c_double, (0, 32): C.c_int32, (1, 8): C.c_uint8}.get((a.type.code, a.type.bits))
+        t = _BP if a.kind != 0 else _SCALAR_CTYPES.get((a.type.code, a.type.bits))
         if t is None:
             raise ImportError(f"{name}: no ctypes type for scalar argument {a.name.decode()} (type code {a.type.code}, {a.type.bits} bits)")
         argtypes.append(t)
@@ -461,7 +472,7 @@ _fn = {name: _bind(name) for name in
        + ["halide_dcopy_impl", "halide_dscal_impl", "halide_daxpy_impl", "halide_ddot", "halide_dasum", "halide_dgemv_notrans",
           "halide_dgemv_trans", "halide_dger_impl", "halide_dgemm_notrans", "halide_dgemm_transA", "halide_dgemm_transB",
           "halide_dgemm_transAB"]
-       + list(HANNK_OPS)}
+       + list(HANNK_OPS) + list(HANNK_NN_OPS)}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -1199,9 +1210,9 @@ def depthwise_conv_broadcast_uint8(input, input_zero, filter, filter_zero, bias,
 
 
 def debug_hannk_general(name: str, *args) -> int:
-    """Test and measurement hook: the entry point `name` of HANNK_OPS, with the arguments of its C signature in order (stride and
-    dilation as four scalars), with one thread per output running the contract's loops as written."""
-    if name not in HANNK_OPS:
+    """Test and measurement hook: the entry point `name` of HANNK_OPS or HANNK_NN_OPS, with the arguments of its C signature in order
+    (stride and dilation as four scalars), with one thread per output running the contract's loops as written."""
+    if name not in _HANNK_ALL_PARAMS:
         raise ValueError(f"no hannk entry point named {name}")
     md = metadata(name)
     if len(args) != md.num_arguments:
@@ -1209,7 +1220,7 @@ def debug_hannk_general(name: str, *args) -> int:
     keep, argv = [], (C.c_void_p * md.num_arguments)()
     for j, v in enumerate(args):
         a = md.arguments[j]
-        box = (C.c_uint8(int(v)) if a.type.bits == 8 else C.c_int32(int(v))) if a.kind == 0 else (v.raw if isinstance(v, Buffer) else v.contents)
+        box = _SCALAR_CTYPES[(a.type.code, a.type.bits)](int(v)) if a.kind == 0 else (v.raw if isinstance(v, Buffer) else v.contents)
         keep.append(box)
         argv[j] = C.cast(C.pointer(box), C.c_void_p)
     fn = lib.hlmi_hannk_general
@@ -1315,6 +1326,221 @@ def hannk_depthwise_conv2d(input, filter, bias, input_zero, filter_zero, stride,
     fn(Buffer(padded), input_zero, Buffer(filter), filter_zero, Buffer(np.ascontiguousarray(bias, np.int32)), (sx, sy), (dx, dy), multiplier, shift,
        output_zero, output_min, output_max, out)
     return out.numpy()
+
+# apps/hannk's op library, second half: pooling, mean, add, mul, softmax and L2 normalisation (include/aot/halide/<name>.h, DESIGN.md
+# 5.13).  Raw calls first, arguments as in the C signature; then what the interpreter's ops.cpp does around each of them.
+def average_pool_uint8(input, stride, filter, output_min, output_max, output) -> int:
+    """u8 [c, x, y, b] -> u8 [c, x, y, b]; stride and filter are (x, y) pairs; taps outside the input do not count."""
+    return _check(_fn["average_pool_uint8"](_as_ptr(input), int(stride[0]), int(stride[1]), int(filter[0]), int(filter[1]), int(output_min),
+                                            int(output_max), _as_ptr(output)))
+
+
+def max_pool_uint8(input, stride, filter, output_min, output_max, output) -> int:
+    return _check(_fn["max_pool_uint8"](_as_ptr(input), int(stride[0]), int(stride[1]), int(filter[0]), int(filter[1]), int(output_min),
+                                        int(output_max), _as_ptr(output)))
+
+
+def mean_uint8(input, mins, extents, output) -> int:
+    """u8 [c, x, y, b] -> u8 [c, x, y, b]: output(p) = the rounded mean of input over p + [mins, mins + extents), Halide order (c first)."""
+    a = [int(v) for pair in zip(mins, extents) for v in pair]
+    return _check(_fn["mean_uint8"](_as_ptr(input), *a, _as_ptr(output)))
+
+
+def add_uint8_uint8(input1, input1_zero, input1_multiplier, input2, input2_zero, input2_multiplier, output_zero, output_min, output_max, output) -> int:
+    return _check(_fn["add_uint8_uint8"](_as_ptr(input1), int(input1_zero), int(input1_multiplier), _as_ptr(input2), int(input2_zero),
+                                         int(input2_multiplier), int(output_zero), int(output_min), int(output_max), _as_ptr(output)))
+
+
+def mul_uint8_uint8_uint8(input1, input1_zero, input2, input2_zero, output_zero, output_multiplier, output_shift, output_min, output_max, output) -> int:
+    return _check(_fn["mul_uint8_uint8_uint8"](_as_ptr(input1), int(input1_zero), _as_ptr(input2), int(input2_zero), int(output_zero),
+                                               int(output_multiplier), int(output_shift), int(output_min), int(output_max), _as_ptr(output)))
+
+
+def softmax_uint8(input, beta_multiplier, beta_shift, output_zero, output_multiplier, output_shift, output) -> int:
+    return _check(_fn["softmax_uint8"](_as_ptr(input), int(beta_multiplier), int(beta_shift), int(output_zero), int(output_multiplier),
+                                       int(output_shift), _as_ptr(output)))
+
+
+def l2_normalization_uint8(input, input_zero, output) -> int:
+    return _check(_fn["l2_normalization_uint8"](_as_ptr(input), int(input_zero), _as_ptr(output)))
+
+
+def debug_hannk_approx(fn, q, x, q_x=0, bits=32) -> np.ndarray:
+    """Test hook: the device's approx_log2 / approx_exp2 / approx_reciprocal / approx_reciprocal_sqrt (fn 0 .. 3 or the name) of
+    common_halide.cpp in Int(bits), over an int32 array."""
+    fn = {"approx_log2": 0, "approx_exp2": 1, "approx_reciprocal": 2, "approx_reciprocal_sqrt": 3}.get(fn, fn)
+    x = np.ascontiguousarray(x, np.int32)
+    out = np.zeros(x.shape, np.int32)
+    f = lib.hlmi_debug_hannk_approx
+    f.restype, f.argtypes = C.c_int, [C.c_int, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_int32, C.c_void_p]
+    rc = f(int(fn), int(q), x.ctypes.data, x.size, int(q_x), int(bits), out.ctypes.data)
+    if rc != 0:
+        raise HalideError(-1, f"hlmi_debug_hannk_approx failed ({rc})")
+    return out
+
+
+def hannk_int_float(x, bits):
+    """ops.cpp's IntFloat<intN_t>(x): x = mantissa * 2^exponent / 2^(bits - 1) -> (mantissa(), exponent()) as its accessors return them."""
+    log2_one = bits - 1
+    m, e = math.frexp(float(np.float32(x)))
+    ml = int(math.floor(abs(m) * (1 << log2_one) + 0.5)) * (1 if m >= 0 else -1)   # std::round
+    if ml == 1 << log2_one:
+        ml, e = ml >> 1, e + 1
+    return ml, e
+
+
+def _int_float_scaled(x, bits, power):
+    log2_one = bits - 1
+    m, e = hannk_int_float(x, bits)
+    e += power
+    return (0 if e < -log2_one else m), max(-log2_one, min(log2_one, e))
+
+
+def hannk_output_range(activation, zero, scale):
+    """ops.cpp's get_quantized_min_max: activation None / "relu" / "relu6" / "relu_n1_to_1" -> (min, max)"""
+    lo, hi = 0, 255
+    rnd = lambda v: int(math.floor(abs(v) + 0.5)) * (1 if v >= 0 else -1)
+    if activation in (None, "none"):
+        pass
+    elif activation == "relu":
+        lo = int(zero)
+    elif activation == "relu6":
+        lo, hi = int(zero), int(zero) + rnd(6.0 / scale)
+    elif activation == "relu_n1_to_1":
+        lo, hi = int(zero) + rnd(-1.0 / scale), int(zero) + rnd(1.0 / scale)
+    else:
+        raise ValueError(f"unsupported activation {activation}")
+    return max(lo, 0), min(hi, 255)
+
+
+def hannk_compute_padding(stride, in_size, filter_size, out_size) -> int:
+    return max(0, (out_size - 1) * stride + filter_size - in_size) // 2
+
+
+def hannk_pool2d(kind, input, filter, stride, padding="same", output_min=0, output_max=255) -> np.ndarray:
+    """Pool2DOp::execute: input (B, H, W, C) u8 -> (B, OH, OW, C) u8, kind "average" or "max", padding "same" or "valid".  Nothing is
+    padded: the input is translated by compute_padding and the op leaves the taps outside it out."""
+    input = np.ascontiguousarray(input, np.uint8)
+    (fw, fh), (sx, sy) = _pair(filter), _pair(stride)
+    b, h, w, c = input.shape
+    if padding == "same":
+        ow, oh = -(-w // sx), -(-h // sy)
+    elif padding == "valid":
+        ow, oh = (w - fw) // sx + 1, (h - fh) // sy + 1
+    else:
+        raise ValueError("padding is 'same' or 'valid'")
+    inb = Buffer(input, mins=(0, hannk_compute_padding(sx, w, fw, ow), hannk_compute_padding(sy, h, fh, oh), 0))
+    out = Buffer(np.zeros((b, oh, ow, c), np.uint8))
+    {"average": average_pool_uint8, "max": max_pool_uint8}[kind](inb, (sx, sy), (fw, fh), output_min, output_max, out)
+    return out.numpy()
+
+
+def hannk_mean(input, axes, keepdims=True) -> np.ndarray:
+    """ReductionOp::execute (Mean): input u8 of rank <= 4 (numpy order, padded to rank 4 in front), `axes` numpy axes to reduce."""
+    input = np.ascontiguousarray(input, np.uint8)
+    nd = input.ndim
+    axes = sorted({a % nd for a in np.atleast_1d(axes)})
+    in4 = input.reshape((1,) * (4 - nd) + input.shape)
+    red4 = [a + 4 - nd for a in axes]
+    out_shape = tuple(1 if a in red4 else in4.shape[a] for a in range(4))
+    mins, extents = [0] * 4, [1] * 4
+    for a in red4:
+        extents[3 - a] = in4.shape[a]
+    out = Buffer(np.zeros(out_shape, np.uint8))
+    mean_uint8(Buffer(in4), mins, extents, out)
+    res = out.numpy().reshape(tuple(1 if a in axes else input.shape[a] for a in range(nd)))
+    return res if keepdims else res.reshape(tuple(input.shape[a] for a in range(nd) if a not in axes))
+
+
+def _hannk_rank2(a, shape):
+    """`a` broadcast against `shape` as the [x, y] operand of add / mul: the innermost axis is dimension 0 (stride 0 where `a` has one
+    element there), everything outside it one dimension 1 (which needs `a` to be the full shape there)"""
+    a = np.asarray(a, np.uint8)
+    full = tuple(shape)
+    if a.shape == full:
+        return np.ascontiguousarray(a).reshape(-1, full[-1])
+    lead = full[:-1]
+    a = a.reshape((1,) * (len(full) - a.ndim) + a.shape)
+    if a.shape[-1] == 1 and a.shape[:-1] == lead:
+        rows = np.ascontiguousarray(a).reshape(-1, 1)
+        return np.lib.stride_tricks.as_strided(rows, shape=(rows.shape[0], full[-1]), strides=(rows.strides[0], 0), writeable=False)
+    return np.ascontiguousarray(np.broadcast_to(a, full)).reshape(-1, full[-1])
+
+
+def hannk_add_multipliers(scale1, scale2, out_scale, sign2=1):
+    """add_uint8's (input1_multiplier, input2_multiplier): lround(scale * 2^16 / (out_scale * 2^6)), the second times sign2"""
+    f32 = np.float32
+    lround = lambda v: int(math.floor(abs(float(v)) + 0.5)) * (1 if v >= 0 else -1)
+    so = f32(out_scale) * f32(1 << 6)
+    return lround(f32(scale1) * f32(1 << 16) / so), lround(f32(scale2) * f32(1 << 16) / so) * int(sign2)
+
+
+def hannk_mul_params(scale1, scale2, out_scale):
+    """mul_uint8's (output_multiplier, output_shift): IntFloat<int32_t>(scale1 * scale2 / out_scale) * 2^-12"""
+    f32 = np.float32
+    m, e = _int_float_scaled(f32(scale1) * f32(scale2) / f32(out_scale), 32, -12)
+    return m, -e
+
+
+def hannk_add(in1, q1, in2, q2, qout, activation=None, sign2=1) -> np.ndarray:
+    """ops.cpp's add_uint8: q = (scale, zero) of each tensor; sign2 = -1 subtracts.  An operand with one element along the innermost
+    axis is passed with a stride of 0, not expanded."""
+    shape = np.broadcast_shapes(np.shape(in1), np.shape(in2))
+    m1, m2 = hannk_add_multipliers(q1[0], q2[0], qout[0], sign2)
+    lo, hi = hannk_output_range(activation, qout[1], qout[0])
+    a, b = _hannk_rank2(in1, shape), _hannk_rank2(in2, shape)
+    out = Buffer(np.zeros(a.shape, np.uint8))
+    add_uint8_uint8(Buffer(a), q1[1], m1, Buffer(b), q2[1], m2, qout[1], lo, hi, out)
+    return out.numpy().reshape(shape)
+
+
+def hannk_mul(in1, q1, in2, q2, qout, activation=None) -> np.ndarray:
+    """ops.cpp's mul_uint8: the multiplier is IntFloat<int32_t>(s1 * s2 / sout) * 2^-12."""
+    shape = np.broadcast_shapes(np.shape(in1), np.shape(in2))
+    m, shift = hannk_mul_params(q1[0], q2[0], qout[0])
+    lo, hi = hannk_output_range(activation, qout[1], qout[0])
+    a, b = _hannk_rank2(in1, shape), _hannk_rank2(in2, shape)
+    out = Buffer(np.zeros(a.shape, np.uint8))
+    mul_uint8_uint8_uint8(Buffer(a), q1[1], Buffer(b), q2[1], qout[1], m, shift, lo, hi, out)
+    return out.numpy().reshape(shape)
+
+
+def hannk_softmax_params(in_scale, beta, out_scale):
+    """SoftmaxOp::execute: (beta_multiplier, beta_shift, output_multiplier, output_shift), the extra factor of two on the output included"""
+    f32 = np.float32
+    beta2 = f32(beta) * f32(np.log2(np.exp(f32(1.0))))
+    bm, be = _int_float_scaled(beta2 * f32(in_scale), 16, -6)
+    om, oe = _int_float_scaled(f32(out_scale), 16, 1)
+    return bm, -be, om, -oe
+
+
+def _hannk_rows(fn, input, axis):
+    """input of any rank, the op over numpy `axis`: rank 2 keeps the caller's memory and transposes the buffers as ops.cpp does (dimension
+    0 then has the row stride); other ranks are brought to (rows, n)"""
+    input = np.asarray(input, np.uint8)
+    axis %= input.ndim
+    if input.ndim == 2:
+        src = np.ascontiguousarray(input)
+        dst = np.zeros(src.shape, np.uint8)
+        view = (lambda a: a) if axis == 1 else (lambda a: a.T)
+        out = Buffer(view(dst))
+        fn(Buffer(view(src)), out)
+        out.numpy()
+        return dst
+    moved = np.ascontiguousarray(np.moveaxis(input, axis, -1))
+    out = Buffer(np.zeros((moved.size // moved.shape[-1], moved.shape[-1]), np.uint8))
+    fn(Buffer(moved.reshape(out.array.shape)), out)
+    return np.moveaxis(out.numpy().reshape(moved.shape), -1, axis)
+
+
+def hannk_softmax(input, in_scale, beta=1.0, out_scale=1.0 / 256, out_zero=0, axis=-1) -> np.ndarray:
+    bm, bs, om, osh = hannk_softmax_params(in_scale, beta, out_scale)
+    return _hannk_rows(lambda i, o: softmax_uint8(i, bm, bs, out_zero, om, osh, o), input, axis)
+
+
+def hannk_l2_normalization(input, input_zero, axis=-1) -> np.ndarray:
+    """L2NormalizationOp::execute: the output has scale 1 / 128 and zero point 128"""
+    return _hannk_rows(lambda i, o: l2_normalization_uint8(i, input_zero, o), input, axis)
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

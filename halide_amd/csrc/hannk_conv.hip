@@ -42,6 +42,8 @@
 // Host path: every entry point reads top to bottom: check arguments -> bounds query -> device and buffers -> empty output -> plan ->
 // stages -> mark_output_written.  hannk_conv_plan() chooses kernel, tiling and splits without a HIP call.
 #include "hlmi_internal.h"
+#include "hannk_entry.h"
+#include "hannk_math.h"
 
 #include "aot/halide/hannk_target.h"
 
@@ -72,31 +74,9 @@ FastDiv make_fastdiv(uint32_t d) {
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv &f) { return (uint32_t)(((unsigned long long)n * f.m) >> f.sh); }
 
 // ---------------------------------------------------------------------------------------------------------------- the epilogue
-struct Quant {
-    int32_t multiplier, shift;
-    int32_t zero, lo, hi;   // u8 values
-};
-// sat_i32((i64(a) * b + 2^30) >> 31): saturates at INT32_MIN * INT32_MIN only
-__host__ __device__ inline int32_t multiply_2x_high(int32_t a, int32_t b) {
-    const int64_t p = ((int64_t)a * b + ((int64_t)1 << 30)) >> 31;
-    return p > 0x7fffffffLL ? 0x7fffffff : (int32_t)p;
-}
-// run-time signed shift (src/FindIntrinsics.cpp: lower_rounding_shift_right): s < 0 is a wrapping left shift
-__host__ __device__ inline int32_t rounding_shift_right(int32_t a, int32_t s) {
-    if (s > 0) return (a >> (s & 31)) + ((a >> ((s - 1) & 31)) & 1);
-    return (int32_t)((uint32_t)a << ((-s) & 31));
-}
-__host__ __device__ inline int32_t quantize_i16(int32_t acc, const Quant &q) {
-    const int32_t v = rounding_shift_right(multiply_2x_high(acc, q.multiplier), q.shift);
-    return v < -32768 ? -32768 : v > 32767 ? 32767 : v;
-}
-__host__ __device__ inline int32_t quantize_and_relu_u8(int32_t acc, const Quant &q) {
-    int32_t v = quantize_i16(acc, q) + q.zero;
-    v = v > 32767 ? 32767 : v;                 // saturating_add in int16
-    v = v < 0 ? 0 : v > 255 ? 255 : v;         // u8_sat
-    v = v < q.hi ? v : q.hi;                   // Halide's clamp = max(min(v, hi), lo): lo wins where the two cross
-    return v > q.lo ? v : q.lo;
-}
+// Quant, multiply_2x_high, rounding_shift_right, quantize_i16 and quantize_and_relu_u8 are in hannk_math.h, shared with hannk_nn.hip
+using namespace hlmi::hannk_math;
+using namespace hlmi::hannk_entry;
 
 // four consecutive channels c .. c + 3 of one pixel: one packed store where all four exist and the address allows it
 template<bool I16>
@@ -442,18 +422,7 @@ __global__ __launch_bounds__(256) void hannk_dw(DwGeom g) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host: tables
-// The tables state every type with lanes = 1 (L), as the reference's metadata does (ConvOp::filter_type hands arguments[2].type to the
-// buffer it allocates); a buffer may come with lanes 0 (this library's other callers) or 1 (Halide::Runtime::Buffer): own_lanes().
-constexpr uint32_t L1 = 1u << 16;
-inline Arg L(Arg a) {
-    a.type |= L1;
-    return a;
-}
-template<int N>
-void own_lanes(BufArg (&args)[N]) {
-    for (BufArg &a : args)
-        if (a.buf && (buf_type_abi(a.buf) >> 16) <= 1) a.type = (a.type & 0xffffu) | (buf_type_abi(a.buf) & L1);
-}
+// (L, own_lanes, blocks_ok, check_stride_multiple and check_dim are in hannk_entry.h, shared with hannk_nn.hip)
 #define HLMI_HANNK_CONV_HEAD(FD)                                                                                                            \
     L(in_buf("input", T_U8, 4)), L(scalar_u8("input_zero")), L(in_buf("filter", T_U8, FD)), L(scalar_u8("filter_zero")), L(in_buf("bias", T_I32, 1)), \
         L(scalar_i32("stride_x")), L(scalar_i32("stride_y")), L(scalar_i32("dilation_x")), L(scalar_i32("dilation_y"))
@@ -469,33 +438,6 @@ const ArgTable dwb_table("depthwise_conv_broadcast_uint8", {HLMI_HANNK_CONV_HEAD
 #undef HLMI_HANNK_CONV_HEAD
 #undef HLMI_HANNK_CONV_TAIL
 
-int blocks_ok(void *uc, const char *what, long threads, unsigned *blocks) {
-    const long n = (threads + 255) / 256;
-    if (n > 0x7fffffffL) return report(uc, halide_error_code_buffer_extents_too_large, "%s: %ld workgroups exceed one launch", what, n);
-    *blocks = (unsigned)n;
-    return 0;
-}
-
-// "<buffer>.stride.<d> is a multiple of m", in the words of the reference's constraint (stride == stride / m * m)
-void check_stride_multiple(void *uc, const char *buffer, const halide_buffer_t *b, int d, int m) {
-    char what[64], expect[96];
-    snprintf(what, sizeof what, "%s.stride.%d", buffer, d);
-    snprintf(expect, sizeof expect, "%s.stride.%d / %d * %d", buffer, d, m, m);
-    const int s = b->dim[d].stride;
-    check_equal(uc, what, s, expect, s - ((s % m) + m) % m);   // Halide's division rounds toward -inf
-}
-void check_dim(void *uc, const char *buffer, const halide_buffer_t *b, int d, const int *min, const int *extent, const int *stride) {
-    char what[64], expect[32];
-    const int *want[3] = {stride, min, extent};
-    const int have[3] = {b->dim[d].stride, b->dim[d].min, b->dim[d].extent};
-    const char *field[3] = {"stride", "min", "extent"};
-    for (int k = 0; k < 3; k++) {
-        if (!want[k]) continue;
-        snprintf(what, sizeof what, "%s.%s.%d", buffer, field[k], d);
-        snprintf(expect, sizeof expect, "%d", *want[k]);
-        check_equal(uc, what, have[k], expect, *want[k]);
-    }
-}
 const int k0 = 0, k1 = 1, k4 = VR, k16 = VT, k64 = FTILE;
 
 // the input region of an output span [omin, omin + oext) under stride s and taps 0 .. (f - 1) * d
@@ -853,7 +795,7 @@ extern "C" int hlmi_hannk_general(const char *name, void **argv) {
     if (!strcmp(name, "conv_u8_u8_i16")) return argv_call(conv_entry<true, true>, argv);
     if (!strcmp(name, "depthwise_conv_uint8")) return argv_call(dw_entry<false, true>, argv);
     if (!strcmp(name, "depthwise_conv_broadcast_uint8")) return argv_call(dw_entry<true, true>, argv);
-    return -1;
+    return hannk_nn_general(name, argv);   // the pooling, reduction, elementwise and normalisation ops
 }
 
 extern "C" int hlmi_debug_hannk_conv_plan(int64_t npix, int32_t channels, int32_t quads, int32_t cus, int32_t *out) {

@@ -37,7 +37,7 @@ int hip_failed(void *uc, hipError_t e, const char *what);  // -> halide_error_co
 // ABI helpers
 constexpr uint32_t type_abi(int code, int bits) { return (uint32_t)code | ((uint32_t)bits << 8); }
 constexpr uint32_t T_U8 = type_abi(1, 8), T_I8 = type_abi(0, 8), T_U16 = type_abi(1, 16), T_I16 = type_abi(0, 16),
-                   T_I32 = type_abi(0, 32), T_F32 = type_abi(2, 32), T_F64 = type_abi(2, 64);
+                   T_I32 = type_abi(0, 32), T_U32 = type_abi(1, 32), T_F32 = type_abi(2, 32), T_F64 = type_abi(2, 64);
 inline uint32_t buf_type_abi(const halide_buffer_t *b) {
     uint32_t v;
     memcpy(&v, &b->type, 4);
@@ -70,16 +70,24 @@ struct Arg {
     unsigned has;       // scalars: bit DEF / MIN / MAX / EST set = sv[that] given
     halide_scalar_value_t sv[4];
     enum { DEF, MIN, MAX, EST };
-    Arg &set(int which, double v) {   // stored as the argument's own type: an int32, a uint8, a float or a double
+    // stored as the argument's own type (lanes aside): a float, a double, a uint8, an int16, a uint16, a uint32, otherwise an int32
+    Arg &set(int which, double v) {
         has |= 1u << which;
-        if (type == T_F32) sv[which].u.f32 = (float)v;
-        else if (type == T_F64) sv[which].u.f64 = v;
-        else if (type == T_U8) sv[which].u.u8 = (uint8_t)v;
+        const uint32_t t = type & 0xffffu;
+        if (t == T_F32) sv[which].u.f32 = (float)v;
+        else if (t == T_F64) sv[which].u.f64 = v;
+        else if (t == T_U8) sv[which].u.u8 = (uint8_t)v;
+        else if (t == T_I16) sv[which].u.i16 = (int16_t)v;
+        else if (t == T_U16) sv[which].u.u16 = (uint16_t)v;
+        else if (t == T_U32) sv[which].u.u32 = (uint32_t)v;
         else sv[which].u.i32 = (int32_t)v;
         return *this;
     }
     double get(int which) const {
-        return type == T_F32 ? (double)sv[which].u.f32 : type == T_F64 ? sv[which].u.f64 : type == T_U8 ? (double)sv[which].u.u8 : (double)sv[which].u.i32;
+        const uint32_t t = type & 0xffffu;
+        return t == T_F32 ? (double)sv[which].u.f32 : t == T_F64 ? sv[which].u.f64 : t == T_U8 ? (double)sv[which].u.u8 :
+               t == T_I16 ? (double)sv[which].u.i16 : t == T_U16 ? (double)sv[which].u.u16 : t == T_U32 ? (double)sv[which].u.u32 :
+                            (double)sv[which].u.i32;
     }
     Arg &def(double v) { return set(DEF, v); }
     Arg &range(double lo, double hi) { return set(MIN, lo).set(MAX, hi); }
@@ -102,6 +110,9 @@ inline Arg scalar_f32(const char *name) { return make_arg(name, halide_argument_
 inline Arg scalar_f64(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_F64, 0); }
 inline Arg scalar_i32(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_I32, 0); }
 inline Arg scalar_u8(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_U8, 0); }
+inline Arg scalar_i16(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_I16, 0); }
+inline Arg scalar_u16(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_U16, 0); }
+inline Arg scalar_u32(const char *name) { return make_arg(name, halide_argument_kind_input_scalar, T_U32, 0); }
 
 // One entry point's table and everything RunGen's structs point into, built once from the table and never per call.  Initialised
 // dynamically (the pointers lead into the object itself), which no consumer can observe: tests/cpp/rungen_registration.cpp calls
@@ -478,6 +489,15 @@ extern "C" int hlmi_debug_hannk_quantize(int fn, const int32_t *acc, size_t n, i
 // `cus` compute units with aligned operands: out = {1 if the MFMA kernel runs, k splits (1 = none), wave tiles}.  The switch
 // HLMI_HANNK_SPLIT_K (unset = the plan's choice, n >= 1 = that many splits where the k blocks allow) is read like in a call.
 extern "C" int hlmi_debug_hannk_conv_plan(int64_t npix, int32_t channels, int32_t quads, int32_t cus, int32_t *out);
+
+// hannk_nn.hip: the seven further ops of the library ("average_pool_uint8", "max_pool_uint8", "mean_uint8", "add_uint8_uint8",
+// "mul_uint8_uint8_uint8", "softmax_uint8", "l2_normalization_uint8") with one thread per output: what hlmi_hannk_general forwards
+// the names it does not know to.  -1 for an unknown name.
+HLMI_LOCAL int hannk_nn_general(const char *name, void **argv);
+// hannk_nn.hip, test hook: the device's approx_* helpers (hannk_math.h) alone over host arrays of n int32 arguments, one launch.
+// fn 0 = approx_log2(q, x, q_x, Int(bits)), 1 = approx_exp2(q, x, q_x, Int(bits)) of an i32 x, 2 = approx_reciprocal(q, x, Int(bits)),
+// 3 = approx_reciprocal_sqrt(q, x, Int(bits)); bits is 16 or 32; out: int32_t[n].  Returns 0, -1 = bad argument, < -1 = HIP error.
+extern "C" int hlmi_debug_hannk_approx(int fn, int32_t q, const int32_t *x, size_t n, int32_t q_x, int32_t bits, int32_t *out);
 
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;

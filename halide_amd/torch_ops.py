@@ -897,3 +897,130 @@ def _(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, m
 def _(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, multiplier, shift, output_zero, output_min, output_max):
     oh, ow = _hannk_out_hw(input, filter.shape[0], filter.shape[1], stride, dilation, padding)
     return input.new_empty((input.shape[0], oh, ow, filter.shape[2]))
+
+
+# apps/hannk's pooling, mean, add, mul, softmax and L2 normalisation on uint8 tensors (NHWC where the op is spatial), parameters derived
+# from float scales as the interpreter's ops.cpp derives them (hl.hannk_* have the derivations).
+def _hannk_pool_out(input, filter, stride, padding):
+    h, w = input.shape[1], input.shape[2]
+    if padding == "same":
+        return -(-h // stride[1]), -(-w // stride[0])
+    if padding == "valid":
+        return (h - filter[1]) // stride[1] + 1, (w - filter[0]) // stride[0] + 1
+    raise RuntimeError("hannk_pool2d: padding is 'same' or 'valid'")
+
+
+@torch.library.custom_op("hlmi::hannk_pool2d", mutates_args=())
+def hannk_pool2d(input: torch.Tensor, kind: str, filter: list[int], stride: list[int], padding: str, output_min: int, output_max: int) -> torch.Tensor:
+    """Pool2DOp: input (B, H, W, C) uint8 -> (B, OH, OW, C) uint8; kind "average" or "max", filter and stride (x, y) pairs, padding "same" or
+    "valid" (nothing is padded: the input is translated and the taps outside it do not count)."""
+    _hannk_check("hannk_pool2d", input)
+    if kind not in ("average", "max"):
+        raise RuntimeError("hannk_pool2d: kind is 'average' or 'max'")
+    oh, ow = _hannk_pool_out(input, filter, stride, padding)
+    out = torch.empty((input.shape[0], oh, ow, input.shape[3]), dtype=torch.uint8, device=input.device)
+    with _Wrapped(input.contiguous(), out) as (a, o):
+        a.set_min(0, hl.hannk_compute_padding(stride[0], input.shape[2], filter[0], ow), hl.hannk_compute_padding(stride[1], input.shape[1], filter[1], oh), 0)
+        (hl.average_pool_uint8 if kind == "average" else hl.max_pool_uint8)(a, stride, filter, output_min, output_max, o)
+    return out
+
+
+@torch.library.custom_op("hlmi::hannk_mean", mutates_args=())
+def hannk_mean(input: torch.Tensor, axes: list[int]) -> torch.Tensor:
+    """ReductionOp (Mean): input uint8 of rank <= 4, the reduced axes kept with extent 1"""
+    _hannk_check("hannk_mean", input)
+    nd = input.dim()
+    red = sorted({a % nd for a in axes})
+    in4 = input.contiguous().reshape((1,) * (4 - nd) + tuple(input.shape))
+    extents = [1] * 4
+    for a in red:
+        extents[3 - (a + 4 - nd)] = in4.shape[a + 4 - nd]
+    out = torch.empty(tuple(1 if a - (4 - nd) in red else in4.shape[a] for a in range(4)), dtype=torch.uint8, device=input.device)
+    with _Wrapped(in4, out) as (a, o):
+        hl.mean_uint8(a, [0, 0, 0, 0], extents, o)
+    return out.reshape(tuple(1 if a in red else input.shape[a] for a in range(nd)))
+
+
+def _hannk_rank2_pair(name, in1, in2):
+    _hannk_check(name, in1, in2)
+    shape = torch.broadcast_shapes(in1.shape, in2.shape)
+    n = shape[-1] if len(shape) else 1
+    return shape, in1.broadcast_to(shape).contiguous().reshape(-1, n), in2.broadcast_to(shape).contiguous().reshape(-1, n)
+
+
+@torch.library.custom_op("hlmi::hannk_add", mutates_args=())
+def hannk_add(in1: torch.Tensor, scale1: float, zero1: int, in2: torch.Tensor, scale2: float, zero2: int, out_scale: float, out_zero: int,
+              activation: str) -> torch.Tensor:
+    """add_uint8: activation "none", "relu", "relu6" or "relu_n1_to_1" """
+    shape, a2, b2 = _hannk_rank2_pair("hannk_add", in1, in2)
+    m1, m2 = hl.hannk_add_multipliers(scale1, scale2, out_scale)
+    lo, hi = hl.hannk_output_range(activation, out_zero, out_scale)
+    out = torch.empty_like(a2)
+    with _Wrapped(a2, b2, out) as (a, b, o):
+        hl.add_uint8_uint8(a, zero1, m1, b, zero2, m2, out_zero, lo, hi, o)
+    return out.reshape(shape)
+
+
+@torch.library.custom_op("hlmi::hannk_mul", mutates_args=())
+def hannk_mul(in1: torch.Tensor, scale1: float, zero1: int, in2: torch.Tensor, scale2: float, zero2: int, out_scale: float, out_zero: int,
+              activation: str) -> torch.Tensor:
+    shape, a2, b2 = _hannk_rank2_pair("hannk_mul", in1, in2)
+    m, shift = hl.hannk_mul_params(scale1, scale2, out_scale)
+    lo, hi = hl.hannk_output_range(activation, out_zero, out_scale)
+    out = torch.empty_like(a2)
+    with _Wrapped(a2, b2, out) as (a, b, o):
+        hl.mul_uint8_uint8_uint8(a, zero1, b, zero2, out_zero, m, shift, lo, hi, o)
+    return out.reshape(shape)
+
+
+def _hannk_rows_op(name, input, axis, call):
+    _hannk_check(name, input)
+    moved = input.movedim(axis, -1).contiguous()
+    rows = moved.reshape(-1, moved.shape[-1])
+    out = torch.empty_like(rows)
+    with _Wrapped(rows, out) as (a, o):
+        call(a, o)
+    return out.reshape(moved.shape).movedim(-1, axis).contiguous()
+
+
+@torch.library.custom_op("hlmi::hannk_softmax", mutates_args=())
+def hannk_softmax(input: torch.Tensor, in_scale: float, beta: float, out_scale: float, out_zero: int, axis: int) -> torch.Tensor:
+    bm, bs, om, osh = hl.hannk_softmax_params(in_scale, beta, out_scale)
+    return _hannk_rows_op("hannk_softmax", input, axis, lambda a, o: hl.softmax_uint8(a, bm, bs, out_zero, om, osh, o))
+
+
+@torch.library.custom_op("hlmi::hannk_l2_normalization", mutates_args=())
+def hannk_l2_normalization(input: torch.Tensor, input_zero: int, axis: int) -> torch.Tensor:
+    return _hannk_rows_op("hannk_l2_normalization", input, axis, lambda a, o: hl.l2_normalization_uint8(a, input_zero, o))
+
+
+@hannk_pool2d.register_fake
+def _(input, kind, filter, stride, padding, output_min, output_max):
+    oh, ow = _hannk_pool_out(input, filter, stride, padding)
+    return input.new_empty((input.shape[0], oh, ow, input.shape[3]))
+
+
+@hannk_mean.register_fake
+def _(input, axes):
+    red = {a % input.dim() for a in axes}
+    return input.new_empty(tuple(1 if a in red else input.shape[a] for a in range(input.dim())))
+
+
+@hannk_add.register_fake
+def _(in1, scale1, zero1, in2, scale2, zero2, out_scale, out_zero, activation):
+    return in1.new_empty(torch.broadcast_shapes(in1.shape, in2.shape))
+
+
+@hannk_mul.register_fake
+def _(in1, scale1, zero1, in2, scale2, zero2, out_scale, out_zero, activation):
+    return in1.new_empty(torch.broadcast_shapes(in1.shape, in2.shape))
+
+
+@hannk_softmax.register_fake
+def _(input, in_scale, beta, out_scale, out_zero, axis):
+    return torch.empty_like(input)
+
+
+@hannk_l2_normalization.register_fake
+def _(input, input_zero, axis):
+    return torch.empty_like(input)

@@ -1,0 +1,24 @@
+/* mean_uint8.h — stands in for the header the reference's generator emits next to mean_uint8.a (apps/hannk/halide/CMakeLists.txt builds the op
+ * library with c_plus_plus_name_mangling: C++ only, every symbol in namespace hannk): code written against the reference
+ * (#include "halide/mean_uint8.h" with -Iinclude/aot) includes this file unchanged and links libhlmi.so instead of the AOT object. */
+#ifndef HLMI_AOT_HALIDE_MEAN_UINT8_H
+#define HLMI_AOT_HALIDE_MEAN_UINT8_H
+#if defined(__has_include)
+#if __has_include("HalideRuntime.h")
+#include "HalideRuntime.h"
+#endif
+#endif
+#include <stdint.h>
+#include "../../hlmi_abi.h"
+#include "hannk_target.h"
+#ifndef __cplusplus
+#error "the hannk op library is built with C++ name mangling"
+#endif
+namespace hannk {
+/* input u8 [c, x, y, b] -> output u8 [c, x, y, b]: the rounded mean over the region [d_min, d_min + d_extent) around each output */
+int mean_uint8(struct halide_buffer_t *_input_buffer, int32_t _c_min, int32_t _c_extent, int32_t _x_min, int32_t _x_extent, int32_t _y_min,
+    int32_t _y_extent, int32_t _b_min, int32_t _b_extent, struct halide_buffer_t *_output_buffer);
+int mean_uint8_argv(void **args);
+const struct halide_filter_metadata_t *mean_uint8_metadata();
+}  // namespace hannk
+#endif

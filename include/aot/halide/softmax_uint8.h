@@ -1,0 +1,24 @@
+/* softmax_uint8.h — stands in for the header the reference's generator emits next to softmax_uint8.a (apps/hannk/halide/CMakeLists.txt builds the op
+ * library with c_plus_plus_name_mangling: C++ only, every symbol in namespace hannk): code written against the reference
+ * (#include "halide/softmax_uint8.h" with -Iinclude/aot) includes this file unchanged and links libhlmi.so instead of the AOT object. */
+#ifndef HLMI_AOT_HALIDE_SOFTMAX_UINT8_H
+#define HLMI_AOT_HALIDE_SOFTMAX_UINT8_H
+#if defined(__has_include)
+#if __has_include("HalideRuntime.h")
+#include "HalideRuntime.h"
+#endif
+#endif
+#include <stdint.h>
+#include "../../hlmi_abi.h"
+#include "hannk_target.h"
+#ifndef __cplusplus
+#error "the hannk op library is built with C++ name mangling"
+#endif
+namespace hannk {
+/* input u8 [x, y] -> output u8 [x, y]: softmax over the input's dimension 0; the beta multiplier and shift carry log2(e) */
+int softmax_uint8(struct halide_buffer_t *_input_buffer, int16_t _beta_multiplier, uint16_t _beta_shift, uint8_t _output_zero,
+    int16_t _output_multiplier, uint16_t _output_shift, struct halide_buffer_t *_output_buffer);
+int softmax_uint8_argv(void **args);
+const struct halide_filter_metadata_t *softmax_uint8_metadata();
+}  // namespace hannk
+#endif

@@ -125,6 +125,7 @@ enum hlmi_error_code {
     halide_error_code_requirement_failed = -27,
     halide_error_code_buffer_extents_negative = -28,
     halide_error_code_gpu_device_error = -29,
+    halide_error_code_specialize_fail = -31,
     halide_error_code_device_wrap_native_failed = -32,
     halide_error_code_device_detach_native_failed = -33,
     halide_error_code_host_is_null = -34,

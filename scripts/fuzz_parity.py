@@ -942,6 +942,115 @@ def fuzz_hannk_depthwise(rng):
     return desc, ok
 
 
+def _hannk_nn_call(name, args, general, env):
+    """the entry point (or its general path) under the given HLMI_HANNK_* switches, restored afterwards"""
+    keys = ["HLMI_HANNK_" + k for k in ("POOL_VECTOR", "POOL_SPLIT", "MEAN_SPLIT", "EW_VECTOR", "ROWS_WAVE", "ROWS_KEEP")]
+    prev = {k: os.environ.pop(k, None) for k in keys}
+    try:
+        for k, v in env.items():
+            os.environ["HLMI_HANNK_" + k] = str(v)
+        if general:
+            hl.debug_hannk_general(name, *args)
+        else:
+            hl._check(hl._fn[name](*[a.ptr if isinstance(a, hl.Buffer) else a for a in args]))
+    finally:
+        for k in keys:
+            os.environ.pop(k, None)
+            if prev[k] is not None:
+                os.environ[k] = prev[k]
+
+
+def fuzz_hannk_pool(rng):
+    """average_pool_uint8, max_pool_uint8 or mean_uint8: random channels (1 .. 70), filters 1 .. 8, strides 1 .. 3, an input translated so
+    that windows cross its edges or miss it, clamps that may cross; mean over a random region of a random subset of the dimensions; the
+    plan's kernel, a forced one or the general path, against tests/cpp/hannk_nn_check.c, byte for byte."""
+    import hannk_nn_checker as hk
+    general = rng.random() < 0.25
+    c, ob = rdim(rng, 1, 70), int(rng.integers(1, 3))
+    if rng.random() < 0.3:
+        rext = [int(rng.integers(2, 9)) if rng.random() < 0.5 else 1 for _ in range(4)]
+        oext = [c if rext[0] == 1 else 1, rdim(rng, 1, 6), rdim(rng, 1, 5), ob]
+        omin, rmin = [int(v) for v in rng.integers(-2, 3, 4)], [int(v) for v in rng.integers(-2, 3, 4)]
+        imin = [omin[d] + rmin[d] - int(rng.integers(0, 2)) for d in range(4)]
+        iext = [omin[d] + rmin[d] - imin[d] + oext[d] + rext[d] - 1 + int(rng.integers(0, 2)) for d in range(4)]
+        inp = rng.integers(0, 256, tuple(reversed(iext)), dtype=np.uint8)
+        want = hk.mean(inp, oext, rmin, rext, imin, omin)
+        o = hl.Buffer(np.full(want.shape, 0x5A, np.uint8), mins=omin)
+        env = {} if general or rng.random() < 0.5 else {"MEAN_SPLIT": int(rng.integers(0, 2))}
+        _hannk_nn_call("mean_uint8", [hl.Buffer(inp, mins=imin)] + [v for pair in zip(rmin, rext) for v in pair] + [o], general, env)
+        return f"mean_uint8{' general' if general else ''} in {iext} at {imin} out {oext} at {omin} region {rext} at {rmin} {env}", np.array_equal(o.numpy(), want)
+    kind = "average" if rng.random() < 0.5 else "max"
+    w, h = rdim(rng, 1, 20), rdim(rng, 1, 14)
+    (fw, fh), (sx, sy) = rng.integers(1, 9, 2), rng.integers(1, 4, 2)
+    ow, oh = rdim(rng, 1, 12), rdim(rng, 1, 8)
+    imin = [0, int(rng.integers(-3, 4)), int(rng.integers(-3, 4)), 0]
+    omin = [0, int(rng.integers(-2, 2)), int(rng.integers(-2, 2)), 0]
+    lo, hi = (int(rng.integers(0, 60)), int(rng.integers(190, 256))) if rng.random() < 0.8 else (int(rng.integers(0, 256)), int(rng.integers(0, 256)))
+    cp = c if rng.random() < 0.5 else -(-c // 4) * 4 + 4 * int(rng.integers(0, 2))   # pixels padded to quads: the dword kernels
+    store = rng.integers(0, 256, (ob, h, w, cp), dtype=np.uint8)
+    inp = store[..., :c]
+    want = hk.pool(kind, inp, (c, ow, oh, ob), (sx, sy), (fw, fh), lo, hi, imin, omin)
+    o = hl.Buffer(np.full(want.shape, 0x5A, np.uint8), mins=omin)
+    env = {} if general or rng.random() < 0.4 else {"POOL_SPLIT": int(rng.integers(0, 2))} if rng.random() < 0.7 else {"POOL_VECTOR": 0}
+    _hannk_nn_call(f"{kind}_pool_uint8", [hl.Buffer(inp, mins=imin), int(sx), int(sy), int(fw), int(fh), lo, hi, o], general, env)
+    desc = (f"{kind}_pool_uint8{' general' if general else ''} c {c} (pixel stride {cp}) in {w}x{h} at {imin[1:3]} out {ow}x{oh}x{ob} at {omin[1:3]} "
+            f"filter {fw}x{fh} stride ({sx},{sy}) clamp ({lo},{hi}) {env}")
+    return desc, np.array_equal(o.numpy(), want)
+
+
+def fuzz_hannk_elementwise(rng):
+    """add_uint8_uint8, mul_uint8_uint8_uint8, softmax_uint8 or l2_normalization_uint8 on 1 .. 6 rows of 1 .. 1500 bytes in padded rows:
+    either operand of add / mul broadcast through a stride of 0, multipliers and shifts over their whole ranges; softmax and
+    l2_normalization on dense or transposed buffers; the plan's kernel, a forced one or the general path, against
+    tests/cpp/hannk_nn_check.c, byte for byte."""
+    import hannk_nn_checker as hk
+    general = rng.random() < 0.25
+    h = int(rng.integers(1, 7))
+    op = ("add", "mul", "softmax", "l2")[int(rng.integers(0, 4))]
+    if op in ("add", "mul"):
+        w = rdim(rng, 1, 300)
+        ops = []
+        for k in range(2):
+            if rng.random() < 0.2 and (k == 0 or ops[0].strides[1] != 0):
+                ops.append(np.broadcast_to(rng.integers(0, 256, (h, 1), dtype=np.uint8), (h, w)))
+            else:
+                ops.append(rng.integers(0, 256, (h, w + int(rng.integers(0, 20))), dtype=np.uint8)[:, :w])
+        z1, z2, oz = (int(v) for v in rng.integers(0, 256, 3))
+        lo, hi = int(rng.integers(0, 60)), int(rng.integers(190, 256))
+        o = hl.Buffer(np.full((h, w), 0x5A, np.uint8))
+        if op == "add":
+            m1, m2 = (int(v) for v in rng.integers(-32768, 32768, 2))
+            want = hk.add(ops[0], z1, m1, ops[1], z2, m2, oz, lo, hi, (w, h))
+            name, args = "add_uint8_uint8", [hl.Buffer(ops[0]), z1, m1, hl.Buffer(ops[1]), z2, m2, oz, lo, hi, o]
+        else:
+            mult, shift = int(rng.integers(-(1 << 31), 1 << 31)), int(rng.integers(0, 32))
+            want = hk.mul(ops[0], z1, ops[1], z2, oz, mult, shift, lo, hi, (w, h))
+            name, args = "mul_uint8_uint8_uint8", [hl.Buffer(ops[0]), z1, hl.Buffer(ops[1]), z2, oz, mult, shift, lo, hi, o]
+        env = {} if general or rng.random() < 0.5 else {"EW_VECTOR": int(rng.integers(0, 2))}
+        _hannk_nn_call(name, args, general, env)
+        return f"{name}{' general' if general else ''} {w}x{h} strides {[a.strides for a in ops]} {args[1:-1]} {env}", np.array_equal(o.numpy(), want)
+    n = rdim(rng, 1, 1500)
+    transposed = rng.random() < 0.2
+    store = rng.integers(0, 256, (n, h) if transposed else (h, n), dtype=np.uint8)
+    if rng.random() < 0.3:
+        store[...] = rng.integers(0, 60, store.shape, dtype=np.uint8)
+    inp = store.T if transposed else store
+    dst = np.full(store.shape, 0x5A, np.uint8)
+    o = hl.Buffer(dst.T if transposed else dst)
+    if op == "softmax":
+        bm, bs, oz = int(rng.integers(1, 32768)), int(rng.integers(0, 16)), int(rng.integers(0, 8))
+        om, osh = int(rng.integers(1, 32768)), int(rng.integers(0, 16))
+        want = hk.softmax(inp, bm, bs, oz, om, osh)
+        name, args = "softmax_uint8", [hl.Buffer(inp), bm, bs, oz, om, osh, o]
+    else:
+        zero = int(rng.integers(0, 256))
+        want = hk.l2_normalization(inp, zero)
+        name, args = "l2_normalization_uint8", [hl.Buffer(inp), zero, o]
+    env = {} if general or rng.random() < 0.5 else {"ROWS_KEEP": 0} if rng.random() < 0.6 else {"ROWS_WAVE": 0}
+    _hannk_nn_call(name, args, general, env)
+    return f"{name}{' general' if general else ''} {h} rows of {n}{' transposed' if transposed else ''} {args[1:-1]} {env}", np.array_equal(np.ascontiguousarray(o.numpy()), want)
+
+
 CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
@@ -955,6 +1064,8 @@ CASES["linear_algebra_f64"] = fuzz_linear_algebra_f64   # the f64 half, both pat
 CASES["fft"] = fuzz_fft   # all four kinds, both paths (tests/fft_checker.py)
 CASES["hannk_conv"] = fuzz_hannk_conv   # both output types, both paths, split-K; integer throughout (tests/hannk_checker.py)
 CASES["hannk_depthwise"] = fuzz_hannk_depthwise   # both variants, both paths
+CASES["hannk_pool"] = fuzz_hannk_pool   # both pools and mean, every kernel of their plans (tests/hannk_nn_checker.py)
+CASES["hannk_elementwise"] = fuzz_hannk_elementwise   # add, mul, softmax, l2_normalization, every kernel of their plans
 
 
 def stress(args, only):
