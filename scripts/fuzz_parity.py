@@ -828,15 +828,15 @@ def fuzz_fft(rng):
     return desc, ok
 
 
-def _nhwc(rng, shape, row_multiple, fill):
-    """a (B, H, W, C) uint8 view holding `fill`: dense, or inside a larger allocation with longer rows and planes further apart (strides
-    kept multiples of `row_multiple`, the first element on a 64-byte boundary as the interpreter allocates)"""
+def _nhwc(shape, pixel_stride, row_pad, plane_pad, fill):
+    """a (B, H, W, C) uint8 view holding `fill` inside an allocation of its own: pixels `pixel_stride` bytes apart (C = dense), rows and
+    planes longer by `row_pad` and `plane_pad`, the first element on a 64-byte boundary as the interpreter allocates; every other byte 0xA5"""
     b, h, w, c = shape
-    rs = w * c + (int(rng.integers(1, 4)) * row_multiple if rng.random() < 0.5 else 0)
-    ps = rs * h + (int(rng.integers(1, 4)) * row_multiple if rng.random() < 0.5 else 0)
+    rs = w * pixel_stride + row_pad
+    ps = rs * h + plane_pad
     raw = np.full(ps * b + 64, 0xA5, np.uint8)
     off = -raw.ctypes.data % 64
-    v = np.lib.stride_tricks.as_strided(raw[off:], (b, h, w, c), (ps, rs, c, 1))
+    v = np.lib.stride_tricks.as_strided(raw[off:], (b, h, w, c), (ps, rs, pixel_stride, 1))
     v[...] = fill
     return v, raw
 
@@ -845,101 +845,185 @@ def _hannk_quant(rng):
     return int(rng.integers(1 << 29, 1 << 31)), int(rng.integers(4, 13)), int(rng.integers(0, 256)), int(rng.integers(0, 40)), int(rng.integers(200, 256))
 
 
-def fuzz_hannk_conv(rng):
-    """conv_u8_u8_u8 or conv_u8_u8_i16 on random channels (1 .. 150 in, 1 .. 70 out), filter 1 .. 4 square or not, strides and dilations
-    1 .. 3, zero points, an output box with mins of its own cropped out of a larger input, padded rows and planes on both sides, the
-    default path (any split-K the plan takes, or one forced by HLMI_HANNK_SPLIT_K) or the general one, against tests/cpp/hannk_check.c.
-    Compared byte for byte; the bytes around the output must come back unchanged."""
-    import hannk_checker as hk
-    ci, co = rdim(rng, 1, 150), rdim(rng, 1, 70)
+def _hannk_conv_splits(npix, co, quads, forced, cus=256):
+    """hannk_conv_plan's split count (halide_amd/csrc/hannk_conv.hip), restated: the draw may not ask the library"""
+    nkb = -(-quads // 16)
+    wave_tiles = -(-npix // 32) * -(-(-(-co // 16)) // 2)
+    want = forced if forced is not None else min(-(-4 * cus // wave_tiles), 16) if wave_tiles < 4 * cus else 1
+    splits = max(1, min(want, nkb if forced is not None else nkb // 2))
+    return -(-nkb // -(-nkb // splits))
+
+
+def _slice_of_wider(rng, c, probability):
+    """(pixel stride, first channel): c channels of pixels that hold more, as a ConcatenationOp's or a PadOp's alias has them"""
+    if rng.random() >= probability:
+        return c, 0
+    extra = int(rng.integers(1, 10))
+    return c + extra, int(rng.integers(0, extra + 1))
+
+
+def draw_hannk_conv(rng):
+    """the parameters of one fuzz_hannk_conv case and the classes they fall in; no array, no library, no device"""
+    ci = 16 * int(rng.integers(1, 9)) if rng.random() < 0.25 else rdim(rng, 1, 150)
+    co = rdim(rng, 1, 70)
     fw, fh = int(rng.integers(1, 5)), int(rng.integers(1, 5))
-    (sx, sy), (dx, dy) = rng.integers(1, 4, 2), rng.integers(1, 4, 2)
+    (sx, sy), (dx, dy) = (int(v) for v in rng.integers(1, 4, 2)), (int(v) for v in rng.integers(1, 4, 2))
     ow, oh, ob = rdim(rng, 1, 40), rdim(rng, 1, 12), int(rng.integers(1, 4))
-    omin = [0] + [int(v) for v in rng.integers(-3, 4, 3)]
-    i16, general = rng.random() < 0.3, rng.random() < 0.25
-    split = None if general or rng.random() < 0.6 else int(rng.integers(1, 7))
-    az, fz = int(rng.integers(0, 256)), int(rng.integers(0, 256))
+    d = dict(ci=ci, co=co, fw=fw, fh=fh, stride=(sx, sy), dilation=(dx, dy), out=(ow, oh, ob), omin=[0] + [int(v) for v in rng.integers(-3, 4, 3)])
+    d["i16"], d["general"] = bool(rng.random() < 0.34), bool(rng.random() < 0.2)
+    d["split"] = None if d["general"] or rng.random() < 0.55 else int(rng.integers(1, 7))
+    d["az"], d["fz"] = int(rng.integers(0, 256)), int(rng.integers(0, 256))
+    d["margin"] = (int(rng.integers(0, 3)), int(rng.integers(0, 3)))
+    cp = -(-ci // 4) * 4
+    d["in_pixel_stride"] = cp + (4 * int(rng.integers(1, 6)) if rng.random() < 0.3 else 0)
+    d["in_pads"] = tuple(4 * int(rng.integers(1, 4)) if rng.random() < 0.5 else 0 for _ in range(2))
+    d["out_pixel_stride"], d["out_channel"] = _slice_of_wider(rng, co, 0.4)
+    d["out_pads"] = (3, int(rng.integers(0, 6)))
+    d["quant"] = _hannk_quant(rng)
+    d["seed"] = int(rng.integers(0, 1 << 32))
+    # classes
+    d["vec"] = (cp // 4) % 4 == 0
+    d["splits"] = 1 if d["general"] else _hannk_conv_splits(ow * oh * ob, co, fw * fh * (cp // 4), d["split"])
+    d["kernel"] = "general" if d["general"] else ("mfma", d["vec"], d["splits"] > 1, d["i16"])
+    d["sliced_output"] = d["out_pixel_stride"] > co
+    return d
+
+
+def _with_env(name, value, fn):
+    prev = os.environ.pop(name, None)
+    try:
+        if value is not None:
+            os.environ[name] = str(value)
+        return fn()
+    finally:
+        os.environ.pop(name, None)
+        if prev is not None:
+            os.environ[name] = prev
+
+
+def run_hannk_conv(d):
+    """one drawn case on the device against tests/cpp/hannk_check.c.  The output lies in a device allocation of the case's own
+    (parity_helpers.DevTensor): every byte of it outside the output's elements must come back unchanged, those between two pixels'
+    channels included; and the kernels launched must be the ones the draw's classes name."""
+    import hannk_checker as hk
+    from parity_helpers import DevTensor, launches
+    rng = np.random.default_rng(d["seed"])
+    ci, co, fw, fh, (sx, sy), (dx, dy), (ow, oh, ob), omin, (mx, my) = d["ci"], d["co"], d["fw"], d["fh"], d["stride"], d["dilation"], d["out"], d["omin"], d["margin"]
+    az, fz, q, odt = d["az"], d["fz"], d["quant"], np.int16 if d["i16"] else np.uint8
     cp = -(-ci // 4) * 4
     # the input: the region the box reads plus a margin on every side
-    ext = lambda o, s, f, d: (o - 1) * s + (f - 1) * d + 1
-    mx, my = int(rng.integers(0, 3)), int(rng.integers(0, 3))
+    ext = lambda o, s, f, dil: (o - 1) * s + (f - 1) * dil + 1
     imin = [0, omin[1] * sx - mx, omin[2] * sy - my, omin[3]]
     noise = rng.integers(0, 256, (ob, ext(oh, sy, fh, dy) + 2 * my, ext(ow, sx, fw, dx) + 2 * mx, cp), dtype=np.uint8)
     noise[..., ci:] = az
-    inp, _keep_i = _nhwc(rng, noise.shape, 4, noise)
+    inp, _keep_i = _nhwc(noise.shape, d["in_pixel_stride"], *d["in_pads"], noise)
     filt = rng.integers(0, 256, (co, fh, fw, ci), dtype=np.uint8)
     tiled = hk.tile(filt, fz)
     bias = rng.integers(-(1 << 24), 1 << 24, co).astype(np.int32)
-    q = _hannk_quant(rng)
-    want = hk.conv(inp, tiled, bias, [co, ow, oh, ob], (sx, sy), (dx, dy), az, fz, *q, np.int16 if i16 else np.uint8, in_mins=imin, out_mins=omin)
-    out_raw = np.full((ob, oh, ow * co + 3), 0x5A5A if i16 else 0x5A, np.int16 if i16 else np.uint8)
-    o = hl.Buffer(np.lib.stride_tricks.as_strided(out_raw, (ob, oh, ow, co), tuple(v * out_raw.itemsize for v in (oh * (ow * co + 3), ow * co + 3, co, 1))),
-                  mins=omin)
-    tb = hl.Buffer(hl.aligned_array(tiled.shape, np.uint8, 64, 1))
-    tb.array[...] = tiled
-    name = "conv_u8_u8_i16" if i16 else "conv_u8_u8_u8"
-    args = [hl.Buffer(inp, mins=imin), az, tb, fz, hl.Buffer(bias), int(sx), int(sy), int(dx), int(dy), *q, o]
-    prev = os.environ.pop("HLMI_HANNK_SPLIT_K", None)
+    want = hk.conv(inp, tiled, bias, [co, ow, oh, ob], (sx, sy), (dx, dy), az, fz, *q, odt, in_mins=imin, out_mins=omin)
+    P, k = d["out_pixel_stride"], d["out_channel"]
+    rs = ow * P + d["out_pads"][0]
+    o = DevTensor(hl, (ob, oh, ow, co), (rs * oh + d["out_pads"][1], rs, P, 1), offset=k * np.dtype(odt).itemsize, mins=omin, dtype=odt)
     try:
-        if split is not None:
-            os.environ["HLMI_HANNK_SPLIT_K"] = str(split)
-        if general:
-            hl.debug_hannk_general(name, *args)
+        tb = hl.Buffer(hl.aligned_array(tiled.shape, np.uint8, 64, 1))
+        tb.array[...] = tiled
+        name = "conv_u8_u8_i16" if d["i16"] else "conv_u8_u8_u8"
+        args = [hl.Buffer(inp, mins=imin), az, tb, fz, hl.Buffer(bias), sx, sy, dx, dy, *q, o.buf]
+        if d["general"]:
+            call = lambda: hl.debug_hannk_general(name, *args)
         else:
-            hl._check(hl._fn[name](*[a.ptr if isinstance(a, hl.Buffer) else a for a in args]))
-        got = o.numpy()
+            call = lambda: hl._check(hl._fn[name](*[a.ptr if isinstance(a, hl.Buffer) else a for a in args]))
+        ran = _with_env("HLMI_HANNK_SPLIT_K", d["split"], lambda: launches(hl, call))
+        try:
+            ok = np.array_equal(o.result(), want)
+        except AssertionError:      # bytes outside the output were written
+            ok = False
+        expect = ["hannk_conv_general"] if d["general"] else ["hannk_conv_finish", "hannk_conv_mfma"] if d["splits"] > 1 else ["hannk_conv_mfma"]
+        ok = ok and ran == expect
     finally:
-        os.environ.pop("HLMI_HANNK_SPLIT_K", None)
-        if prev is not None:
-            os.environ["HLMI_HANNK_SPLIT_K"] = prev
-    ok = np.array_equal(got, want) and bool((out_raw[:, :, ow * co:] == (0x5A5A if i16 else 0x5A)).all())
-    desc = (f"{name}{' general' if general else ''} {ci}->{co} filter {fw}x{fh} stride ({sx},{sy}) dilation ({dx},{dy}) out {ow}x{oh}x{ob} at {omin[1:]} "
-            f"zeros ({az},{fz}) quant {q} split {split} input strides {[v for v in inp.strides]}")
+        o.free()
+    desc = (f"{name}{' general' if d['general'] else ''} {ci}->{co} filter {fw}x{fh} stride ({sx},{sy}) dilation ({dx},{dy}) out {ow}x{oh}x{ob} at {omin[1:]} "
+            f"zeros ({az},{fz}) quant {q} split {d['split']} ({d['splits']} planned, ran {ran}) input strides {[v for v in inp.strides]} "
+            f"output channels {k}..{k + co} of {P}")
+    return desc, ok
+
+
+def fuzz_hannk_conv(rng):
+    """conv_u8_u8_u8 or conv_u8_u8_i16 (a third) on random channels (1 .. 150 in, a multiple of 16 in a quarter of the cases; 1 .. 70 out),
+    filter 1 .. 4 square or not, strides and dilations 1 .. 3, zero points, an output box with mins of its own cropped out of a larger input,
+    padded pixels, rows and planes on the input, an output that is a channel slice of wider pixels, the default path (any split-K the
+    plan takes, or one forced by HLMI_HANNK_SPLIT_K) or the general one, against tests/cpp/hannk_check.c.  Compared byte for byte; the
+    bytes around and between the output's pixels must come back unchanged."""
+    return run_hannk_conv(draw_hannk_conv(rng))
+
+
+def draw_hannk_depthwise(rng):
+    """the parameters of one fuzz_hannk_depthwise case and the classes they fall in; no array, no library, no device"""
+    c = rdim(rng, 1, 70)
+    fw, fh = (3, 3) if rng.random() < 0.4 else (int(rng.integers(1, 6)), int(rng.integers(1, 6)))
+    (sx, sy), (dx, dy) = (int(v) for v in rng.integers(1, 4, 2)), (int(v) for v in rng.integers(1, 4, 2))
+    d = dict(c=c, fw=fw, fh=fh, stride=(sx, sy), dilation=(dx, dy), out=(rdim(rng, 1, 30), rdim(rng, 1, 14), int(rng.integers(1, 4))),
+             omin=[0] + [int(v) for v in rng.integers(-3, 4, 3)])
+    d["broadcast"], d["general"] = bool(rng.random() < 0.3), bool(rng.random() < 0.25)
+    d["az"], d["fz"] = int(rng.integers(0, 256)), int(rng.integers(0, 256))
+    cp = 1 if d["broadcast"] else -(-c // 16) * 16
+    d["in_pixel_stride"] = cp + (16 * int(rng.integers(1, 3)) if not d["broadcast"] and rng.random() < 0.3 else 0)
+    d["in_pads"] = tuple(16 * int(rng.integers(1, 4)) if not d["broadcast"] and rng.random() < 0.5 else 0 for _ in range(2))
+    d["out_pixel_stride"], d["out_channel"] = _slice_of_wider(rng, c, 0.4)
+    d["out_pads"] = (int(rng.integers(0, 6)), int(rng.integers(0, 6)))
+    q = _hannk_quant(rng)
+    d["quant"] = (q[0], int(rng.integers(0, 8)), *q[2:])
+    d["vector"] = None if d["general"] or rng.random() < 0.3 else 1   # these outputs are below the plan's threshold: force its kernel
+    d["seed"] = int(rng.integers(0, 1 << 32))
+    # classes
+    d["kernel"] = ("general", d["broadcast"]) if d["vector"] is None else ("dw", (fw, fh) == (3, 3), d["broadcast"])
+    d["sliced_output"] = d["out_pixel_stride"] > c
+    return d
+
+
+def run_hannk_depthwise(d):
+    """one drawn case on the device against tests/cpp/hannk_check.c, the output in a device allocation of the case's own as in run_hannk_conv"""
+    import hannk_checker as hk
+    from parity_helpers import DevTensor, launches
+    rng = np.random.default_rng(d["seed"])
+    c, fw, fh, (sx, sy), (dx, dy), (ow, oh, ob), omin = d["c"], d["fw"], d["fh"], d["stride"], d["dilation"], d["out"], d["omin"]
+    az, fz, q, broadcast = d["az"], d["fz"], d["quant"], d["broadcast"]
+    cp = 1 if broadcast else -(-c // 16) * 16
+    ext = lambda o, s, f, dil: (o - 1) * s + (f - 1) * dil + 1
+    imin = [0, omin[1] * sx, omin[2] * sy, omin[3]]
+    noise = rng.integers(0, 256, (ob, ext(oh, sy, fh, dy), ext(ow, sx, fw, dx), cp), dtype=np.uint8)
+    inp, _keep_i = _nhwc(noise.shape, d["in_pixel_stride"], *d["in_pads"], noise) if not broadcast else (noise, None)
+    filt = rng.integers(0, 256, (fh, fw, c), dtype=np.uint8)
+    bias = rng.integers(-(1 << 16), 1 << 16, c).astype(np.int32)
+    want = hk.depthwise(inp, filt, bias, [c, ow, oh, ob], (sx, sy), (dx, dy), az, fz, *q, broadcast, in_mins=imin, out_mins=omin)
+    P, k = d["out_pixel_stride"], d["out_channel"]
+    rs = ow * P + d["out_pads"][0]
+    o = DevTensor(hl, (ob, oh, ow, c), (rs * oh + d["out_pads"][1], rs, P, 1), offset=k, mins=omin)
+    try:
+        name = "depthwise_conv_broadcast_uint8" if broadcast else "depthwise_conv_uint8"
+        args = [hl.Buffer(inp, mins=imin), az, hl.Buffer(filt), fz, hl.Buffer(bias), sx, sy, dx, dy, 0, *q, o.buf]
+        if d["general"]:
+            call = lambda: hl.debug_hannk_general(name, *args)
+        else:
+            call = lambda: hl._check(hl._fn[name](*[a.ptr if isinstance(a, hl.Buffer) else a for a in args]))
+        ran = _with_env("HLMI_HANNK_DW_VECTOR", d["vector"], lambda: launches(hl, call))
+        try:
+            ok = np.array_equal(o.result(), want)
+        except AssertionError:      # bytes outside the output were written
+            ok = False
+        ok = ok and ran == (["hannk_dw_general"] if d["kernel"][0] == "general" else ["hannk_dw"])
+    finally:
+        o.free()
+    desc = (f"{name}{' general' if d['general'] else ''} c {c} filter {fw}x{fh} stride ({sx},{sy}) dilation ({dx},{dy}) out {ow}x{oh}x{ob} at {omin[1:]} "
+            f"zeros ({az},{fz}) quant {q} vector {d['vector']} (ran {ran}) input strides {[v for v in inp.strides]} output channels {k}..{k + c} of {P}")
     return desc, ok
 
 
 def fuzz_hannk_depthwise(rng):
-    """depthwise_conv_uint8 or its broadcast variant on random channels (1 .. 70), filter 1 .. 5 (3 x 3 in a third of the cases), strides
-    and dilations 1 .. 3, zero points, a cropped output box, padded input rows (multiples of 16), either path, against
-    tests/cpp/hannk_check.c, byte for byte."""
-    import hannk_checker as hk
-    c = rdim(rng, 1, 70)
-    fw, fh = (3, 3) if rng.random() < 0.33 else (int(rng.integers(1, 6)), int(rng.integers(1, 6)))
-    (sx, sy), (dx, dy) = rng.integers(1, 4, 2), rng.integers(1, 4, 2)
-    ow, oh, ob = rdim(rng, 1, 30), rdim(rng, 1, 14), int(rng.integers(1, 4))
-    omin = [0] + [int(v) for v in rng.integers(-3, 4, 3)]
-    broadcast, general = rng.random() < 0.25, rng.random() < 0.25
-    az, fz = int(rng.integers(0, 256)), int(rng.integers(0, 256))
-    cp = 1 if broadcast else -(-c // 16) * 16
-    ext = lambda o, s, f, d: (o - 1) * s + (f - 1) * d + 1
-    imin = [0, omin[1] * sx, omin[2] * sy, omin[3]]
-    noise = rng.integers(0, 256, (ob, ext(oh, sy, fh, dy), ext(ow, sx, fw, dx), cp), dtype=np.uint8)
-    inp, _keep_i = _nhwc(rng, noise.shape, 16, noise) if not broadcast else (noise, None)
-    filt = rng.integers(0, 256, (fh, fw, c), dtype=np.uint8)
-    bias = rng.integers(-(1 << 16), 1 << 16, c).astype(np.int32)
-    q = _hannk_quant(rng)
-    q = (q[0], int(rng.integers(0, 8)), *q[2:])
-    want = hk.depthwise(inp, filt, bias, [c, ow, oh, ob], (sx, sy), (dx, dy), az, fz, *q, broadcast, in_mins=imin, out_mins=omin)
-    o = hl.Buffer(np.full((ob, oh, ow, c), 0x5A, np.uint8), mins=omin)
-    name = "depthwise_conv_broadcast_uint8" if broadcast else "depthwise_conv_uint8"
-    args = [hl.Buffer(inp, mins=imin), az, hl.Buffer(filt), fz, hl.Buffer(bias), int(sx), int(sy), int(dx), int(dy), 0, *q, o]
-    vector = None if general or rng.random() < 0.3 else 1   # these outputs are below the plan's threshold: force its kernel
-    prev = os.environ.pop("HLMI_HANNK_DW_VECTOR", None)
-    try:
-        if vector is not None:
-            os.environ["HLMI_HANNK_DW_VECTOR"] = str(vector)
-        if general:
-            hl.debug_hannk_general(name, *args)
-        else:
-            hl._check(hl._fn[name](*[a.ptr if isinstance(a, hl.Buffer) else a for a in args]))
-    finally:
-        os.environ.pop("HLMI_HANNK_DW_VECTOR", None)
-        if prev is not None:
-            os.environ["HLMI_HANNK_DW_VECTOR"] = prev
-    ok = np.array_equal(o.numpy(), want)
-    desc = (f"{name}{' general' if general else ''} c {c} filter {fw}x{fh} stride ({sx},{sy}) dilation ({dx},{dy}) out {ow}x{oh}x{ob} at {omin[1:]} "
-            f"zeros ({az},{fz}) quant {q} vector {vector}")
-    return desc, ok
+    """depthwise_conv_uint8 or its broadcast variant on random channels (1 .. 70), filter 1 .. 5 (3 x 3 in two fifths of the cases), strides
+    and dilations 1 .. 3, zero points, a cropped output box that may be a channel slice of wider pixels, padded input pixels, rows and
+    planes (multiples of 16), either path, against tests/cpp/hannk_check.c, byte for byte, the bytes between the output's pixels included."""
+    return run_hannk_depthwise(draw_hannk_depthwise(rng))
 
 
 def _hannk_nn_call(name, args, general, env):

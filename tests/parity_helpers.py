@@ -2,7 +2,7 @@
 the checkers themselves (checker_lib.py): bit comparison, launch names, calling an entry point by its metadata, loading the
 fuzzer; and what test_buffer_layouts.py and test_special_values.py add for the older pipelines: arrays with padded rows and planes
 in host memory or in a device allocation of the test's own (HostArray, DevArray), NaN-aware bit comparison, kernel constants read
-from the source.  Plain functions and classes that take the product module `hl` as an argument; no fixtures."""
+from the source; and what the hannk ops' tests share: DevTensor, a device array of any rank, strides and byte offset.  Plain functions and classes that take the product module `hl` as an argument; no fixtures."""
 import ctypes as C
 import importlib.util
 import os
@@ -122,6 +122,44 @@ class DevArray(_Strided):
         back = np.empty_like(self.flat)
         assert self.hip.hipMemcpy(C.c_void_p(back.ctypes.data), self.p, C.c_size_t(back.nbytes), 2) == 0   # device to host
         return self._checked(back, self.flat)
+
+    def free(self):
+        self.buf.device_detach()
+        assert self.hip.hipFree(self.p) == 0
+
+
+class DevTensor:
+    """An array of `dtype`, numpy `shape` and element `strides` (any rank, any strides that do not overlap) inside a flat device allocation
+    of its own, `offset` BYTES after its 256-byte aligned start, every other byte 0xA5; wrapped as a device-only buffer.  result() reads
+    the whole allocation back and checks that no byte outside the array changed: between rows, between pixels, before and after."""
+    SENTINEL = 0xA5
+
+    def __init__(self, hl, shape, strides=None, offset=0, mins=None, fill=None, dtype=np.uint8):
+        self.hl, self.hip, self.dtype = hl, hl.hip_runtime(), np.dtype(dtype)
+        if strides is None:
+            strides = [int(np.prod(shape[k + 1:])) for k in range(len(shape))]
+        es = self.dtype.itemsize
+        n = offset + (sum((e - 1) * s for e, s in zip(shape, strides)) + 1) * es + 16
+        self.flat = np.full(n, self.SENTINEL, np.uint8)
+        self.shape, self.strides, self.offset = tuple(shape), tuple(strides), offset
+        self.view(self.flat)[...] = 0 if fill is None else fill
+        self.p = C.c_void_p()
+        assert self.hip.hipMalloc(C.byref(self.p), C.c_size_t(n)) == 0 and self.p.value % 256 == 0
+        assert self.hip.hipMemcpy(self.p, C.c_void_p(self.flat.ctypes.data), C.c_size_t(n), 1) == 0
+        self.buf = hl.Buffer.wrap_device(self.p.value + offset, self.dtype, shape[::-1], strides[::-1], mins)
+
+    def view(self, flat):
+        return np.ndarray(self.shape, self.dtype, buffer=flat, offset=self.offset, strides=tuple(s * self.dtype.itemsize for s in self.strides))
+
+    def result(self):
+        self.buf.device_sync()
+        back = np.empty_like(self.flat)
+        assert self.hip.hipMemcpy(C.c_void_p(back.ctypes.data), self.p, C.c_size_t(back.nbytes), 2) == 0
+        got = self.view(back).copy()
+        self.view(back)[...] = self.view(self.flat)
+        bad = np.flatnonzero(back != self.flat)
+        assert bad.size == 0, f"{bad.size} bytes outside the array were written, the first {int(bad[0]) - self.offset} bytes after its first element"
+        return got
 
     def free(self):
         self.buf.device_detach()

@@ -8,7 +8,14 @@ The contract is integer only.  Three evaluators face each other:
     general path (one thread per output) and the `_argv` form, compared byte for byte.
 The CPU part holds the checker to the second evaluator, pins the epilogue's known answers, the two algebraic identities the kernels rest on and
 the entry protocol; the GPU part holds the library to the checker on shapes chosen for what can go wrong.  Arrays are NHWC: the Halide
-dimensions [c, x, y, b] reversed."""
+dimensions [c, x, y, b] reversed.
+
+Which shapes those are is itself tested on the CPU: test_the_shapes_reach_every_variant restates the host's predicates and asserts that
+the tables reach every instance of hannk_conv_mfma<VEC, SPLIT, I16>, hannk_dw<K3, BCAST> and hannk_dw_general<BCAST> and every class of
+tails and split geometry; test_the_seeded_slice_reaches_the_kernels does the same for the 40 + 40 cases of scripts/fuzz_parity.py that
+test_seeded_fuzz_slice runs.  The checker itself is held to float64 (test_checker_is_within_one_of_float64).  The layouts of aliased
+tensors (an output or input that is a channel slice of wider pixels, filters with gaps, i16 rows off an 8-byte boundary) lie in device
+allocations full of sentinels (parity_helpers.DevTensor): every byte outside the array proper must come back unchanged."""
 import ctypes as C
 import os
 import subprocess
@@ -17,7 +24,7 @@ import numpy as np
 import pytest
 
 import hannk_checker as hk
-from parity_helpers import DevArray, HostArray, gpu_present, launches
+from parity_helpers import DevArray, DevTensor, HostArray, gpu_present, launches, load_fuzz_parity
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
@@ -72,9 +79,9 @@ def np_quantize(acc, m, s, zero=0, lo=0, hi=255, i16=False):
     return np.maximum(np.minimum(u, hi), lo).astype(np.uint8)
 
 
-def np_conv_acc(inp, filt, bias, out_whb, stride, dilation, az, fz, origin=(0, 0)):
-    """inp (B, H, W, CP) with CP >= CI, filt (CO, FH, FW, CI) UNTILED, -> the wrapped int32 accumulators (OB, OH, OW, CO) as int64; channels
-    CI .. CP of the input meet filter_zero (the tiler's padding) and add nothing"""
+def np_conv_acc(inp, filt, bias, out_whb, stride, dilation, az, fz, origin=(0, 0), wrap=True):
+    """inp (B, H, W, CP) with CP >= CI, filt (CO, FH, FW, CI) UNTILED, -> the wrapped int32 accumulators (OB, OH, OW, CO) as int64 (the exact
+    sums where `wrap` is off); channels CI .. CP of the input meet filter_zero (the tiler's padding) and add nothing"""
     co, fh, fw, ci = filt.shape
     ow, oh, ob = out_whb
     acc = np.zeros((ob, oh, ow, co), np.int64) + np.asarray(bias, np.int64)[:co]
@@ -85,10 +92,10 @@ def np_conv_acc(inp, filt, bias, out_whb, stride, dilation, az, fz, origin=(0, 0
             xs = origin[0] + rx * dilation[0] + stride[0] * np.arange(ow)
             a = inp[:ob][:, ys][:, :, xs][..., :ci].astype(np.int64) - az
             acc += np.einsum("byxi,oi->byxo", a, f[:, ry, rx, :])
-    return wrap32(acc)
+    return wrap32(acc) if wrap else acc
 
 
-def np_depthwise_acc(inp, filt, bias, out_whb, stride, dilation, az, fz, broadcast=False):
+def np_depthwise_acc(inp, filt, bias, out_whb, stride, dilation, az, fz, broadcast=False, wrap=True):
     fh, fw, c = filt.shape
     ow, oh, ob = out_whb
     acc = np.zeros((ob, oh, ow, c), np.int64) + np.asarray(bias, np.int64)[:c]
@@ -99,7 +106,7 @@ def np_depthwise_acc(inp, filt, bias, out_whb, stride, dilation, az, fz, broadca
             a = inp[:ob][:, ys][:, :, xs].astype(np.int64) - az
             a = a[..., :1] if broadcast else a[..., :c]
             acc += a * (filt[ry, rx, :].astype(np.int64) - fz)
-    return wrap32(acc)
+    return wrap32(acc) if wrap else acc
 
 
 def in_extent(out, filt, stride, dilation):
@@ -149,6 +156,11 @@ CONV_SHAPES = {   # ci, co, fw, fh, stride, dilation, ow, oh, ob
     "k_tail_2p5_tiles": (68, 40, 3, 3, (2, 1), (2, 1), 19, 3, 1),
     "long_k": (520, 16, 1, 1, (1, 1), (1, 1), 7, 1, 1),
     "vector_k": (32, 48, 3, 1, (1, 1), (1, 1), 37, 2, 1),     # ci % 16 == 0: the 16-byte fragment path, 2 pixel tiles and a tail
+    # the rows test_the_shapes_reach_every_variant needs besides (q = fw * fh * ceil(ci / 4) channel quads, kb = ceil(q / 16) k-blocks)
+    "vec_k_tail_plan_split": (80, 40, 3, 1, (1, 1), (1, 1), 7, 5, 1),    # 60 q, 4 kb: the plan splits in 2; a lane group of padding; 35 pixels; 3 co tiles
+    "vec_c18_two_batches": (64, 18, 5, 1, (1, 1), (1, 1), 8, 4, 2),      # 80 q, 5 kb: forced 3 gives 2, 2, 1; C % 4 == 2; a wave tile per batch
+    "c5_two_k_blocks": (6, 5, 3, 3, (1, 1), (1, 1), 10, 5, 1),           # 18 q, 2 kb: split only by force; 50 pixels
+    "vec_one_k_block": (16, 32, 2, 2, (1, 1), (1, 1), 8, 4, 1),          # 16 q, exactly one k-block: never split; 32 pixels
 }
 DW_SHAPES = {     # c, fw, fh, stride, dilation, ow, oh, ob
     "c16_3x3": (16, 3, 3, (1, 1), (1, 1), 5, 5, 1),
@@ -156,6 +168,11 @@ DW_SHAPES = {     # c, fw, fh, stride, dilation, ow, oh, ob
     "c7_1x1": (7, 1, 1, (1, 1), (1, 1), 6, 5, 1),
     "c20_3x3_d2": (20, 3, 3, (1, 1), (2, 2), 7, 6, 1),
     "c33_2x3_s12": (33, 2, 3, (1, 2), (1, 1), 5, 9, 2),       # a filter that is not square, more rows than a thread's four
+    # C % 4 and OH % 4 both zero, or both not and two batches, under a 3 x 3 filter and under another
+    "c8_3x3_oh4": (8, 3, 3, (1, 1), (1, 1), 5, 4, 1),
+    "c7_3x3_oh5_b2": (7, 3, 3, (2, 1), (1, 1), 4, 5, 2),
+    "c12_2x3_oh8": (12, 2, 3, (1, 1), (1, 2), 3, 8, 1),
+    "c21_1x2_oh6_b2": (21, 1, 2, (1, 2), (1, 1), 5, 6, 2),
 }
 
 
@@ -164,9 +181,107 @@ def conv_case(name, seed=0, **kw):
     return Case(ci, co, fw, fh, st, di, ow, oh, ob, seed, **kw)
 
 
-def dw_case(name, seed=0, **kw):
+def dw_case(name, seed=0, broadcast=False, **kw):
     c, fw, fh, st, di, ow, oh, ob = DW_SHAPES[name]
-    return Case(c, c, fw, fh, st, di, ow, oh, ob, seed, depthwise=True, **kw)
+    return Case(1 if broadcast else c, c, fw, fh, st, di, ow, oh, ob, seed, depthwise=True, broadcast=broadcast, **kw)
+
+
+# ------------------------------------------------------------------------------------------------------------------ the kernel instances
+# What runs, as (row of CONV_SHAPES, HLMI_HANNK_SPLIT_K or None for the plan's own choice), and what each run reaches: the host's
+# predicates (hannk_conv_plan, conv_stage_main, dw_entry in halide_amd/csrc/hannk_conv.hip) restated; the split count comes from the hook.
+CONV_RUNS = [(name, None) for name in sorted(CONV_SHAPES)] + [
+    ("vec_k_tail_plan_split", "1"), ("vec_c18_two_batches", "3"), ("c5_two_k_blocks", "2"), ("c5_two_k_blocks", "5"), ("long_k", "1"),
+    ("k_tail_2p5_tiles", "3")]
+DW_RUNS = [(name, broadcast, vector) for name in sorted(DW_SHAPES) for broadcast in (False, True) for vector in (None, "1")]
+KB_QUADS, WAVE_PX, DW_ROWS, DW_MIN_THREADS = 16, 32, 4, 256 * 256
+
+
+def conv_splits(hl, name, switch, monkeypatch, cus=256):
+    """(splits, k-blocks) of the plan for a row under the switch"""
+    ci, co, fw, fh, _, _, ow, oh, ob = CONV_SHAPES[name]
+    quads = fw * fh * -(-ci // 4)
+    monkeypatch.delenv("HLMI_HANNK_SPLIT_K", raising=False)
+    if switch is not None:
+        monkeypatch.setenv("HLMI_HANNK_SPLIT_K", switch)
+    plan = hl.debug_hannk_conv_plan(ow * oh * ob, co, quads, cus)
+    assert plan["mfma"]
+    return plan["splits"], -(-quads // KB_QUADS)
+
+
+def conv_classes(hl, name, switch, monkeypatch):
+    ci, co, fw, fh, _, _, ow, oh, ob = CONV_SHAPES[name]
+    cq, npix = -(-ci // 4), ow * oh * ob
+    quads = fw * fh * cq
+    splits, nkb = conv_splits(hl, name, switch, monkeypatch)
+    vec, split = cq % 4 == 0, splits > 1
+    got = {("instance", vec, split, i16) for i16 in (False, True)}
+    got.add(("chosen by", "the plan" if switch is None else "the switch", vec, split))
+    got.add("C % 16 == 0" if co % 16 == 0 else "C % 4 == 0 != C % 16" if co % 4 == 0 else "C % 4 != 0")
+    if co % 4 and split:
+        got.add("C % 4 != 0 under SPLIT")
+    got.add("an odd count of co tiles" if -(-co // 16) % 2 else "an even count of co tiles")
+    tail = npix % WAVE_PX
+    got.add("pixel tail 0" if tail == 0 else "pixel tail 1..16" if tail <= 16 else "pixel tail 17..31")
+    if ob > 1 and (ow * oh) % WAVE_PX:
+        got.add("a wave tile crosses the batch boundary")
+    got.add("k tail 0" if quads % KB_QUADS == 0 else "k tail")
+    if vec and quads % KB_QUADS:       # CQ % 4 == 0: the tail is 4, 8 or 12 quads, the lane groups past it load nothing
+        got.add("VEC, a lane group of padding")
+    if split:
+        per = -(-nkb // splits)
+        assert splits == -(-nkb // per) and 0 < nkb - (splits - 1) * per <= per
+        got.add("splits of equal length" if nkb == splits * per else "a shorter last split")
+        if switch is not None and int(switch) > nkb:
+            got.add("a forced count above the k-blocks")
+        if quads % KB_QUADS:           # the last k-block is in the last split: it holds quads % 16 real quads and the padding
+            got.add("a last split with real and padded k")
+    return got
+
+
+CONV_CLASSES = ([("instance", vec, split, i16) for vec in (False, True) for split in (False, True) for i16 in (False, True)]
+                + [("chosen by", who, vec, split) for who in ("the plan", "the switch") for vec in (False, True) for split in (False, True)]
+                + ["C % 16 == 0", "C % 4 == 0 != C % 16", "C % 4 != 0", "C % 4 != 0 under SPLIT", "an odd count of co tiles", "an even count of co tiles",
+                   "pixel tail 0", "pixel tail 1..16", "pixel tail 17..31", "a wave tile crosses the batch boundary", "k tail 0", "k tail",
+                   "VEC, a lane group of padding", "splits of equal length", "a shorter last split", "a forced count above the k-blocks",
+                   "a last split with real and padded k"])
+
+
+def dw_instance(name, broadcast, vector):
+    """the kernel instance dw_entry launches for an aligned input: (launch name, template arguments)"""
+    c, fw, fh, _, _, ow, oh, ob = DW_SHAPES[name]
+    threads = -(-c // 4) * ow * -(-oh // DW_ROWS) * ob
+    if vector != "0" and (vector is not None or threads >= DW_MIN_THREADS):
+        return ("hannk_dw", (fw, fh) == (3, 3), broadcast)
+    return ("hannk_dw_general", broadcast)
+
+
+def dw_classes(name, broadcast, vector):
+    c, _, _, _, _, _, oh, ob = DW_SHAPES[name]
+    inst = dw_instance(name, broadcast, vector)
+    return {(inst, "C % 4 == 0" if c % 4 == 0 else "C % 4 != 0"), (inst, "OH % 4 == 0" if oh % DW_ROWS == 0 else "OH % 4 != 0")} | ({(inst, "ob > 1")} if ob > 1 else set())
+
+
+DW_INSTANCES = [("hannk_dw", k3, bcast) for k3 in (False, True) for bcast in (False, True)] + [("hannk_dw_general", bcast) for bcast in (False, True)]
+DW_CLASSES = [(inst, what) for inst in DW_INSTANCES for what in ("C % 4 == 0", "C % 4 != 0", "OH % 4 == 0", "OH % 4 != 0", "ob > 1")]
+
+
+def test_the_shapes_reach_every_variant(hl, monkeypatch):
+    """the counterpart of test_resnet50.py's test of the same name: every instance of hannk_conv_mfma<VEC, SPLIT, I16> and of the
+    depthwise kernels, and every class of sizes in which their tails, clamps and split ranges differ, has a run in the tables above"""
+    reached = {}
+    for name, switch in CONV_RUNS:
+        for cls in conv_classes(hl, name, switch, monkeypatch):
+            reached.setdefault(cls, []).append((name, switch))
+    for name, broadcast, vector in DW_RUNS:
+        for cls in dw_classes(name, broadcast, vector):
+            reached.setdefault(cls, []).append((name, broadcast, vector))
+    missing = [cls for cls in CONV_CLASSES + DW_CLASSES if not reached.get(cls)]
+    assert not missing, missing
+    assert set(reached) <= set(CONV_CLASSES + DW_CLASSES), set(reached) - set(CONV_CLASSES + DW_CLASSES)
+    # the rows the issue names are what it says of them
+    assert conv_splits(hl, "vec_k_tail_plan_split", None, monkeypatch) == (2, 4) and conv_splits(hl, "vec_c18_two_batches", "3", monkeypatch) == (3, 5)
+    assert conv_splits(hl, "c5_two_k_blocks", "5", monkeypatch) == (2, 2) and conv_splits(hl, "c5_two_k_blocks", None, monkeypatch) == (1, 2)
+    assert conv_splits(hl, "vec_one_k_block", None, monkeypatch) == (1, 1)
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU: the checker
@@ -275,6 +390,84 @@ def test_recentring_identity():
                 sf = int((fp + 128).sum()) - 128 * (K + pad)
                 got = wrap32(wrap32(int((ap * fp).sum())) - wrap32(fzp * sa) - wrap32(azp * sf) + wrap32(K * azp * fzp))
                 assert got == direct, (K, az, fz, fill)
+
+
+def test_checker_is_within_one_of_float64(capsys):
+    """Both evaluators above were written from one reading of the generator; this one is not.  On every row of CONV_SHAPES and DW_SHAPES,
+    under random multipliers and every shift 0 .. 12, the checker's u8 and i16 results are within 1 of
+    clip(round(acc * m / 2^(31 + s)) + zero), computed in float64 from the exact int64 sum, wherever that sum fits int32 (beyond it the
+    contract wraps and the real quotient is another number).  The bound is derived: multiply_2x_high and the rounding shift each round
+    to nearest, so the result is within 1/2 + 2^-(s + 1) <= 1 of the real quotient q (1/2 of it at s = 0, where nothing is shifted);
+    round(q) is within 1/2 of q; the two integers are less than 2 apart.  (float64 holds acc * m to 2^-53 of its size, 2^-22 after the
+    division: far from moving a rounding by a whole step.)"""
+    rng = np.random.default_rng(77)
+    worst, inside, compared = 0, {"u8": 0, "i16": 0}, 0
+    for depthwise, names in ((False, sorted(CONV_SHAPES)), (True, sorted(DW_SHAPES))):
+        for name in names:
+            for s in range(13):
+                m, zero = int(rng.integers(1 << 26, 1 << 31)), int(rng.integers(0, 256))
+                c = (dw_case if depthwise else conv_case)(name, seed=100 + s, quant=(m, s, zero, 0, 255))
+                acc = (np_depthwise_acc if depthwise else np_conv_acc)(c.inp, c.filt, c.bias, c.out_whb, c.stride, c.dilation, c.az, c.fz, wrap=False)
+                fits = (acc >= I32_MIN) & (acc <= I32_MAX)
+                real = np.rint(acc.astype(np.float64) * m / 2.0 ** (31 + s))
+                for key, dt, z, lo, hi in (("u8", np.uint8, zero, 0, 255), ("i16", np.int16, 0, -32768, 32767)):
+                    if depthwise and key == "i16":
+                        continue
+                    want = np.clip(real + z, lo, hi)
+                    diff = np.abs(c.want(dt).astype(np.float64) - want)[fits]
+                    worst = max(worst, int(diff.max()))
+                    inside[key] += int(np.count_nonzero((want[fits] > lo) & (want[fits] < hi)))
+                    compared += diff.size
+    with capsys.disabled():
+        print(f"\n  checker against float64: worst difference {worst} over {compared} results, {inside} of them strictly inside their range")
+    assert inside["u8"] > 10000 and inside["i16"] > 10000, "the multipliers and shifts must leave results that are not clipped"
+    assert worst <= 1
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU: the fuzzer's cases
+FUZZ_SEED, FUZZ_CASES = 20261021, 40
+
+
+def test_the_fuzzer_has_the_cases():
+    """scripts/fuzz_parity.py keeps the two cases, each as a draw that touches neither the library nor the device and a run"""
+    src = open(os.path.join(ROOT, "scripts", "fuzz_parity.py")).read()
+    for name in ("hannk_conv", "hannk_depthwise"):
+        assert f"def fuzz_{name}(rng):" in src and f'CASES["{name}"] = fuzz_{name}' in src and f"def case_{name}" not in src
+        assert f"def draw_{name}(rng):" in src and f"def run_{name}(d):" in src and f"return run_{name}(draw_{name}(rng))" in src
+        draw = src.split(f"def draw_{name}(rng):")[1].split("\ndef ")[0]
+        assert "hl." not in draw and "hk." not in draw and "import" not in draw, name
+
+
+def drawn_cases(mod):
+    """the parameters of test_seeded_fuzz_slice's cases, in its order"""
+    r = np.random.default_rng(FUZZ_SEED)
+    return [mod.draw_hannk_conv(r) for _ in range(FUZZ_CASES)], [mod.draw_hannk_depthwise(r) for _ in range(FUZZ_CASES)]
+
+
+def test_the_seeded_slice_reaches_the_kernels(hl, monkeypatch):
+    """conditions on the draw, not measurements: the 40 + 40 cases of the fixed seed hold every MFMA instance twice, the general conv
+    four times, a sliced output eight times and each instance of hannk_dw once; and the draw's own restatement of the plan is the hook's"""
+    conv, dw = drawn_cases(load_fuzz_parity())
+    kernels = [d["kernel"] for d in conv]
+    for vec in (False, True):
+        for split in (False, True):
+            for i16 in (False, True):
+                assert kernels.count(("mfma", vec, split, i16)) >= 2, (vec, split, i16, kernels)
+    assert kernels.count("general") >= 4
+    assert sum(d["sliced_output"] for d in conv + dw) >= 8 and sum(d["sliced_output"] for d in conv) >= 4 and sum(d["sliced_output"] for d in dw) >= 4
+    assert sum(d["ci"] % 16 == 0 for d in conv) >= 8 and sum(d["i16"] for d in conv) >= 10
+    assert sum(d["in_pixel_stride"] > -(-d["ci"] // 4) * 4 for d in conv) >= 4
+    dwk = [d["kernel"] for d in dw]
+    for k3 in (False, True):
+        for bcast in (False, True):
+            assert dwk.count(("dw", k3, bcast)) >= 1, (k3, bcast, dwk)
+    for d in conv:
+        if not d["general"]:
+            monkeypatch.delenv("HLMI_HANNK_SPLIT_K", raising=False)
+            if d["split"] is not None:
+                monkeypatch.setenv("HLMI_HANNK_SPLIT_K", str(d["split"]))
+            ow, oh, ob = d["out"]
+            assert hl.debug_hannk_conv_plan(ow * oh * ob, d["co"], d["fw"] * d["fh"] * -(-d["ci"] // 4))["splits"] == d["splits"], d
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU: the entry protocol
@@ -537,6 +730,9 @@ def test_plan_has_a_split_k_threshold(hl, monkeypatch):
     assert hl.debug_hannk_conv_plan(7, 16, 130)["splits"] == 1
     monkeypatch.setenv("HLMI_HANNK_SPLIT_K", "9")
     assert hl.debug_hannk_conv_plan(7, 16, 130)["splits"] == 9 and hl.debug_hannk_conv_plan(7, 16, 16)["splits"] == 1
+    for setting, splits in (("0", 1), ("-3", 1), ("1000000", 9)):   # no split below 1; never more splits than the 9 k-blocks of 130 quads
+        monkeypatch.setenv("HLMI_HANNK_SPLIT_K", setting)
+        assert hl.debug_hannk_conv_plan(7, 16, 130)["splits"] == splits, setting
 
 
 def test_consumer_builds_against_the_headers():
@@ -823,6 +1019,238 @@ def test_hip_tile_filter_and_its_output_fed_to_conv(hl, ci, co):
     m, s, z, lo, hi = c.quant
     hl.conv_u8_u8_u8(inp, c.az, tiled, c.fz, hl.Buffer(c.bias), c.stride, c.dilation, m, s, z, lo, hi, out)
     assert np.array_equal(out.numpy(), c.want()) and np.array_equal(out.numpy(), c.second())
+
+
+# ---- every kernel instance (the tables beside CONV_SHAPES and DW_SHAPES)
+def host_operands(hl, c):
+    """input, filter and bias of a Case in fresh host buffers, aligned as the interpreter allocates"""
+    inp = hl.Buffer(hl.aligned_array(c.inp.shape, np.uint8, 64, 1))
+    inp.array[...] = c.inp
+    if c.depthwise:
+        return inp, hl.Buffer(c.filt.copy()), hl.Buffer(c.bias.copy())
+    filt = hl.Buffer(hl.aligned_array(c.tiled.shape, np.uint8, 64, 1))
+    filt.array[...] = c.tiled
+    return inp, filt, hl.Buffer(c.bias.copy())
+
+
+def call_entry(hl, name, args, general=False):
+    if general:
+        return hl.debug_hannk_general(name, *args)
+    return hl._check(hl._fn[name](*[a.ptr if isinstance(a, hl.Buffer) else a for a in args]))
+
+
+def direct_launches(hl, c, out_dtype=np.uint8):
+    ow, oh, ob = c.out_whb
+    out = hl.Buffer(np.zeros((ob, oh, ow, c.co), out_dtype))
+    args = conv_args(hl, c, *host_operands(hl, c), out)
+    ran = launches(hl, lambda: call_entry(hl, entry_name(c, out_dtype), args))
+    assert np.array_equal(out.numpy(), c.want(out_dtype))
+    return ran
+
+
+@gpu
+@pytest.mark.parametrize("out_dtype", [np.uint8, np.int16], ids=["u8", "i16"])
+@pytest.mark.parametrize("name,switch", CONV_RUNS, ids=[f"{n}-{'plan' if s is None else 'split' + s}" for n, s in CONV_RUNS])
+def test_hip_conv_every_instance(hl, on_stream, monkeypatch, name, switch, out_dtype):
+    """every run of CONV_RUNS, all paths, both output types, on both kinds of stream; hannk_conv_finish runs where the row's class says
+    SPLIT.  A frame queue's plan sees a quarter of the compute units: where that changes the plan's own choice the launch list is
+    held to the class on the device-wide stream only."""
+    splits, _ = conv_splits(hl, name, switch, monkeypatch)
+    on_a_quarter, _ = conv_splits(hl, name, switch, monkeypatch, cus=64)
+    c = conv_case(name, seed=24)
+    assert_all_paths(hl, c, out_dtype, f"{name} {switch}")
+    ran = direct_launches(hl, c, out_dtype)
+    assert "hannk_conv_mfma" in ran
+    if on_stream == "device" or (splits > 1) == (on_a_quarter > 1):
+        assert ("hannk_conv_finish" in ran) == (splits > 1), (ran, splits)
+
+
+@gpu
+@pytest.mark.parametrize("name,broadcast,vector", DW_RUNS, ids=[f"{n}-{'broadcast' if b else 'plain'}-{'vector' if v else 'plan'}" for n, b, v in DW_RUNS])
+def test_hip_depthwise_every_instance(hl, on_stream, monkeypatch, name, broadcast, vector):
+    monkeypatch.delenv("HLMI_HANNK_DW_VECTOR", raising=False)
+    if vector is not None:
+        monkeypatch.setenv("HLMI_HANNK_DW_VECTOR", vector)
+    c = dw_case(name, seed=56, broadcast=broadcast)
+    assert_all_paths(hl, c, np.uint8, f"{name} {broadcast} {vector}")
+    assert direct_launches(hl, c) == [dw_instance(name, broadcast, vector)[0]]
+
+
+# ---- the layouts an aliased tensor has: the reference's interpreter turns ConcatenationOp, SplitOp and PadOp into offset aliases, so a conv
+# writes (and reads) channels [k, k + C) of pixels that hold P > C
+OUT_SLICES = [(8, 24, 0), (8, 24, 8), (10, 24, 3), (12, 13, 0)]   # (C, P, k); P = 13: the packed store's alignment rotates from pixel to pixel
+SLICE_IDS = [f"c{nc}_of_{p}_at_{k}" for nc, p, k in OUT_SLICES]
+CONV_SLICE_PATHS = {   # HLMI_HANNK_SPLIT_K, the general hook, the launches
+    "mfma": ("1", False, ["hannk_conv_mfma"]),
+    "split": ("2", False, ["hannk_conv_finish", "hannk_conv_mfma"]),
+    "general": (None, True, ["hannk_conv_general"]),
+}
+
+
+def out_slice(hl, c, pixel_stride, channel, out_dtype=np.uint8):
+    """a device tensor of the Case's output extents: channels [channel, channel + C) of pixels `pixel_stride` elements apart"""
+    ow, oh, ob = c.out_whb
+    return DevTensor(hl, (ob, oh, ow, c.co), (oh * ow * pixel_stride, ow * pixel_stride, pixel_stride, 1), offset=channel * np.dtype(out_dtype).itemsize,
+                     dtype=out_dtype)
+
+
+@gpu
+@pytest.mark.parametrize("path", sorted(CONV_SLICE_PATHS))
+@pytest.mark.parametrize("out_dtype", [np.uint8, np.int16], ids=["u8", "i16"])
+@pytest.mark.parametrize("nc,pixel_stride,channel", OUT_SLICES, ids=SLICE_IDS)
+def test_hip_conv_output_is_a_channel_slice(hl, monkeypatch, nc, pixel_stride, channel, out_dtype, path):
+    """store4 picks its packed store from the address: the bytes are the checker's and those between one pixel's channels and the next
+    (and before the first, after the last) come back untouched, from the MFMA kernel, from hannk_conv_finish and from the general kernel"""
+    switch, general, names = CONV_SLICE_PATHS[path]
+    monkeypatch.delenv("HLMI_HANNK_SPLIT_K", raising=False)
+    if switch is not None:
+        monkeypatch.setenv("HLMI_HANNK_SPLIT_K", switch)
+    c = Case(8, nc, 3, 3, (1, 1), (1, 1), 8, 5, 1, seed=41)
+    dst = out_slice(hl, c, pixel_stride, channel, out_dtype)
+    try:
+        args = conv_args(hl, c, *host_operands(hl, c), dst.buf)
+        ran = launches(hl, lambda: call_entry(hl, entry_name(c, out_dtype), args, general))
+        assert ran == names
+        assert np.array_equal(dst.result(), c.want(out_dtype))
+    finally:
+        dst.free()
+
+
+@gpu
+@pytest.mark.parametrize("broadcast", [False, True], ids=["plain", "broadcast"])
+@pytest.mark.parametrize("nc,pixel_stride,channel", OUT_SLICES, ids=SLICE_IDS)
+def test_hip_depthwise_output_is_a_channel_slice(hl, monkeypatch, nc, pixel_stride, channel, broadcast):
+    monkeypatch.setenv("HLMI_HANNK_DW_VECTOR", "1")
+    c = Case(1 if broadcast else nc, nc, 3, 3, (1, 1), (1, 1), 8, 5, 1, seed=42, depthwise=True, broadcast=broadcast)
+    dst = out_slice(hl, c, pixel_stride, channel)
+    try:
+        args = conv_args(hl, c, *host_operands(hl, c), dst.buf)
+        ran = launches(hl, lambda: call_entry(hl, entry_name(c), args))
+        assert ran == ["hannk_dw"]
+        assert np.array_equal(dst.result(), c.want())
+    finally:
+        dst.free()
+
+
+CONV_INPUT_SLICES = {   # ci, the pixel stride above CP, the first channel (= byte) inside the wider pixel, the kernel
+    "vec_fragments_4_byte_aligned": (16, 4, 4, "hannk_conv_mfma"),     # ci % 16 == 0: the 16-byte fragments lie at 4 + 20 n
+    "pixels_20_wider": (6, 20, 4, "hannk_conv_mfma"),
+    "first_channel_2": (6, 4, 2, "hannk_conv_general"),                # not a dword boundary: the MFMA kernel's loads may not take it
+}
+
+
+@gpu
+@pytest.mark.parametrize("out_dtype", [np.uint8, np.int16], ids=["u8", "i16"])
+@pytest.mark.parametrize("name", sorted(CONV_INPUT_SLICES))
+def test_hip_conv_input_is_a_channel_slice(hl, monkeypatch, name, out_dtype):
+    """the input as CP channels of wider pixels in a device allocation: pixel, row and plane strides above the dense ones, sentinels
+    in every gap (a gap byte read as a channel changes the sum)"""
+    monkeypatch.delenv("HLMI_HANNK_SPLIT_K", raising=False)
+    ci, wider, first, kernel = CONV_INPUT_SLICES[name]
+    c = Case(ci, 20, 3, 3, (1, 1), (1, 1), 6, 4, 2, seed=43)
+    B, IH, IW, CP = c.inp.shape
+    P = CP + wider
+    src = DevTensor(hl, c.inp.shape, ((IW * P + 4) * IH + 8, IW * P + 4, P, 1), offset=first, fill=c.inp)
+    try:
+        ow, oh, ob = c.out_whb
+        out = hl.Buffer(np.zeros((ob, oh, ow, c.co), out_dtype))
+        _, filt, bias = host_operands(hl, c)
+        ran = launches(hl, lambda: call_entry(hl, entry_name(c, out_dtype), conv_args(hl, c, src.buf, filt, bias, out)))
+        assert kernel in ran and (kernel == "hannk_conv_mfma" or ran == [kernel]), ran
+        assert np.array_equal(out.numpy(), c.want(out_dtype))
+    finally:
+        src.free()
+
+
+@gpu
+@pytest.mark.parametrize("first,kernel", [(16, "hannk_dw"), (2, "hannk_dw_general")])
+def test_hip_depthwise_input_is_a_channel_slice(hl, monkeypatch, first, kernel):
+    """20 channels (32 with the padding) of pixels 48 bytes apart, from channel 16 on (hannk_dw) and from byte 2 on (no dword loads)"""
+    monkeypatch.setenv("HLMI_HANNK_DW_VECTOR", "1")
+    c = Case(20, 20, 3, 3, (1, 1), (1, 1), 6, 5, 2, seed=44, depthwise=True)
+    B, IH, IW, CP = c.inp.shape
+    P = CP + 16
+    src = DevTensor(hl, c.inp.shape, ((IW * P + 16) * IH + 32, IW * P + 16, P, 1), offset=first, fill=c.inp)
+    try:
+        out = hl.Buffer(np.zeros((2, 5, 6, 20), np.uint8))
+        _, filt, bias = host_operands(hl, c)
+        ran = launches(hl, lambda: call_entry(hl, entry_name(c), conv_args(hl, c, src.buf, filt, bias, out)))
+        assert ran == [kernel]
+        assert np.array_equal(out.numpy(), c.want())
+    finally:
+        src.free()
+
+
+@gpu
+@pytest.mark.parametrize("general", [False, True], ids=["default", "general"])
+def test_hip_filters_with_gaps(hl, monkeypatch, general):
+    """the tiled filter with dim(3), dim(4) and dim(5) strides above the dense ones by multiples of 64 and sentinels between the tiles;
+    the depthwise filter with padded dim(1) and dim(2) strides"""
+    monkeypatch.delenv("HLMI_HANNK_SPLIT_K", raising=False)
+    monkeypatch.setenv("HLMI_HANNK_DW_VECTOR", "1")
+    c = Case(20, 40, 3, 2, (1, 1), (1, 1), 7, 5, 1, seed=45)
+    FH, FW, CO16, CQ = c.tiled.shape[:4]
+    s3 = CQ * 64 + 64
+    s4 = CO16 * s3 + 128
+    s5 = FW * s4 + 64
+    filt = DevTensor(hl, c.tiled.shape, (s5, s4, s3, 64, 4, 1), offset=64, fill=c.tiled)
+    try:
+        for out_dtype in (np.uint8, np.int16):
+            out = hl.Buffer(np.zeros((1, 5, 7, 40), out_dtype))
+            inp, _, bias = host_operands(hl, c)
+            ran = launches(hl, lambda: call_entry(hl, entry_name(c, out_dtype), conv_args(hl, c, inp, filt.buf, bias, out), general))
+            assert ("hannk_conv_general" if general else "hannk_conv_mfma") in ran
+            assert np.array_equal(out.numpy(), c.want(out_dtype)), out_dtype
+    finally:
+        filt.free()
+    for broadcast in (False, True):
+        c = Case(1 if broadcast else 21, 21, 3, 3, (1, 1), (1, 1), 5, 6, 1, seed=46, depthwise=True, broadcast=broadcast)
+        filt = DevTensor(hl, c.filt.shape, (3 * (21 + 3) + 5, 21 + 3, 1), offset=3, fill=c.filt)
+        try:
+            out = hl.Buffer(np.zeros((1, 6, 5, 21), np.uint8))
+            inp, _, bias = host_operands(hl, c)
+            ran = launches(hl, lambda: call_entry(hl, entry_name(c), conv_args(hl, c, inp, filt.buf, bias, out), general))
+            assert ran == ["hannk_dw_general" if general else "hannk_dw"]
+            assert np.array_equal(out.numpy(), c.want()), broadcast
+        finally:
+            filt.free()
+
+
+@gpu
+@pytest.mark.parametrize("split", ["1", None], ids=["unsplit", "plan"])    # the stores of hannk_conv_mfma; of hannk_conv_finish (the plan splits in 5)
+@pytest.mark.parametrize("off", [2, 4, 6])
+def test_hip_conv_i16_cropped_output_and_padded_rows(hl, monkeypatch, off, split):
+    """test_hip_conv_cropped_output_and_padded_rows for conv_u8_u8_i16: the output box at non-zero mins inside rows an odd count of
+    elements long (the 8-byte store's predicate changes from row to row) and planes padded further, its first element 2, 4 and 6 bytes
+    off an 8-byte boundary; every byte around it is a sentinel that must come back"""
+    monkeypatch.delenv("HLMI_HANNK_SPLIT_K", raising=False)
+    if split is not None:
+        monkeypatch.setenv("HLMI_HANNK_SPLIT_K", split)
+    c = conv_case("k_tail_2p5_tiles", seed=47)
+    ow, oh, ob = c.out_whb
+    B, IH, IW, CP = c.inp.shape
+    omins, imins = [0, 3, -2, 5], [0, 6, -2, 5]
+    rs = ow * c.co + 5
+    dst = DevTensor(hl, (ob, oh, ow, c.co), (rs * oh + 3, rs, c.co, 1), offset=off, mins=omins, dtype=np.int16)
+    try:
+        inp, filt, bias = host_operands(hl, c)
+        inp = hl.Buffer(inp.array, mins=imins)
+        ran = launches(hl, lambda: call_entry(hl, "conv_u8_u8_i16", conv_args(hl, c, inp, filt, bias, dst.buf)))
+        assert ran == (["hannk_conv_mfma"] if split else ["hannk_conv_finish", "hannk_conv_mfma"]), ran
+        assert np.array_equal(dst.result(), c.want(np.int16))
+    finally:
+        dst.free()
+
+
+@gpu
+def test_seeded_fuzz_slice():
+    """scripts/fuzz_parity.py's cases of conv and depthwise, 40 of each from the seed test_the_seeded_slice_reaches_the_kernels draws from"""
+    mod = load_fuzz_parity()
+    r = np.random.default_rng(FUZZ_SEED)
+    for name in ("hannk_conv", "hannk_depthwise"):
+        for i in range(FUZZ_CASES):
+            desc, ok = mod.CASES[name](r)
+            assert ok, f"{name} case {i}: {desc}"
 
 
 def explicit_pad(x, zero, channel_multiple, px, py):

@@ -13,11 +13,10 @@ import numpy as np
 import pytest
 
 import hannk_nn_checker as hk
-from parity_helpers import gpu_present, launches, load_fuzz_parity
+from parity_helpers import DevTensor, gpu_present, launches, load_fuzz_parity
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NN_OPS = ("average_pool_uint8", "max_pool_uint8", "mean_uint8", "add_uint8_uint8", "mul_uint8_uint8_uint8", "softmax_uint8", "l2_normalization_uint8")
-SENTINEL = 0xA5
 
 
 # ------------------------------------------------------------------------------------------------------------------ the numpy evaluator
@@ -814,41 +813,6 @@ def run_paths(hl, name, make_args, want, what="", paths=("direct", "general", "a
         assert got.shape == want.shape and got.dtype == want.dtype, (what, path)
         bad = got != want
         assert not bad.any(), f"{name} {what} {path}: {np.count_nonzero(bad)} of {got.size} differ, first at {tuple(np.argwhere(bad)[0])}"
-
-
-class DevTensor:
-    """A u8 array of numpy `shape` and element `strides` inside a flat device allocation of its own, `offset` bytes after its 256-byte
-    aligned start, every other byte SENTINEL; wrapped as a device-only buffer.  result() reads the whole allocation back and checks that
-    nothing outside the array changed."""
-
-    def __init__(self, hl, shape, strides=None, offset=0, mins=None, fill=None):
-        self.hl, self.hip = hl, hl.hip_runtime()
-        if strides is None:
-            strides = [int(np.prod(shape[k + 1:])) for k in range(len(shape))]
-        n = offset + sum((e - 1) * s for e, s in zip(shape, strides)) + 1 + 16
-        self.flat = np.full(n, SENTINEL, np.uint8)
-        self.shape, self.strides, self.offset = tuple(shape), tuple(strides), offset
-        self.view(self.flat)[...] = 0 if fill is None else fill
-        self.p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.p), C.c_size_t(n)) == 0 and self.p.value % 256 == 0
-        assert self.hip.hipMemcpy(self.p, C.c_void_p(self.flat.ctypes.data), C.c_size_t(n), 1) == 0
-        self.buf = hl.Buffer.wrap_device(self.p.value + offset, np.uint8, shape[::-1], strides[::-1], mins)
-
-    def view(self, flat):
-        return np.lib.stride_tricks.as_strided(flat[self.offset:], self.shape, self.strides)
-
-    def result(self):
-        self.buf.device_sync()
-        back = np.empty_like(self.flat)
-        assert self.hip.hipMemcpy(C.c_void_p(back.ctypes.data), self.p, C.c_size_t(back.nbytes), 2) == 0
-        got = self.view(back).copy()
-        self.view(back)[...] = self.view(self.flat)
-        assert np.array_equal(back, self.flat), "bytes outside the array were written"
-        return got
-
-    def free(self):
-        self.buf.device_detach()
-        assert self.hip.hipFree(self.p) == 0
 
 
 def pool_args(inb, k, lo, hi, out):
