@@ -418,7 +418,11 @@ _HANNK_NN_PARAMS = {"average_pool_uint8": _HANNK_POOL_PARAMS, "max_pool_uint8": 
                     "add_uint8_uint8": "P15halide_buffer_thsS1_hshhhS1_", "mul_uint8_uint8_uint8": "P15halide_buffer_thS1_hhijhhS1_",
                     "softmax_uint8": "P15halide_buffer_tsthstS1_", "l2_normalization_uint8": "P15halide_buffer_thS1_"}
 HANNK_NN_OPS = tuple(_HANNK_NN_PARAMS)
-_HANNK_ALL_PARAMS = {**_HANNK_PARAMS, **_HANNK_NN_PARAMS}
+# the elementwise programs, the data movers and the shallow depthwise variant
+_HANNK_PROGRAM_PARAMS = {"elementwise_5xuint8_1xuint8": "P15halide_buffer_t" + "S1_" * 6, "elementwise_5xint16_1xuint8int16": "P15halide_buffer_t" + "S1_" * 7,
+                         "depthwise_conv_shallow_uint8": _HANNK_DW_PARAMS, "copy_uint8_uint8": "P15halide_buffer_tiS1_", "fill_uint8": "hP15halide_buffer_t", "upsample_channels_uint8": "P15halide_buffer_tiS1_"}
+HANNK_PROGRAM_OPS = tuple(_HANNK_PROGRAM_PARAMS)
+_HANNK_ALL_PARAMS = {**_HANNK_PARAMS, **_HANNK_NN_PARAMS, **_HANNK_PROGRAM_PARAMS}
 # ctypes of a scalar argument by (halide type code, bits)
 _SCALAR_CTYPES = {(2, 32): C.c_float, (2, 64): C.c_double, (0, 32): C.c_int32, (1, 8): C.c_uint8, (0, 16): C.c_int16, (1, 16): C.c_uint16,
                   (1, 32): C.c_uint32}
@@ -472,7 +476,7 @@ _fn = {name: _bind(name) for name in
        + ["halide_dcopy_impl", "halide_dscal_impl", "halide_daxpy_impl", "halide_ddot", "halide_dasum", "halide_dgemv_notrans",
           "halide_dgemv_trans", "halide_dger_impl", "halide_dgemm_notrans", "halide_dgemm_transA", "halide_dgemm_transB",
           "halide_dgemm_transAB"]
-       + list(HANNK_OPS) + list(HANNK_NN_OPS)}
+       + list(HANNK_OPS) + list(HANNK_NN_OPS) + list(HANNK_PROGRAM_OPS)}
 
 
 def local_laplacian(input, levels, alpha, beta, output) -> int:
@@ -1210,7 +1214,7 @@ def depthwise_conv_broadcast_uint8(input, input_zero, filter, filter_zero, bias,
 
 
 def debug_hannk_general(name: str, *args) -> int:
-    """Test and measurement hook: the entry point `name` of HANNK_OPS or HANNK_NN_OPS, with the arguments of its C signature in order
+    """Test and measurement hook: the entry point `name` of HANNK_OPS, HANNK_NN_OPS or HANNK_PROGRAM_OPS, with the arguments of its C signature in order
     (stride and dilation as four scalars), with one thread per output running the contract's loops as written."""
     if name not in _HANNK_ALL_PARAMS:
         raise ValueError(f"no hannk entry point named {name}")
@@ -1541,6 +1545,319 @@ def hannk_softmax(input, in_scale, beta=1.0, out_scale=1.0 / 256, out_zero=0, ax
 def hannk_l2_normalization(input, input_zero, axis=-1) -> np.ndarray:
     """L2NormalizationOp::execute: the output has scale 1 / 128 and zero point 128"""
     return _hannk_rows(lambda i, o: l2_normalization_uint8(i, input_zero, o), input, axis)
+
+
+# apps/hannk's op library, third part: the elementwise programs, copy, fill and upsample_channels (include/aot/halide/<name>.h, DESIGN.md
+# 5.14).  Raw calls first, arguments as in the C signature; then the assembler and what the interpreter's ops.cpp / lower.cpp do around them.
+def elementwise_5xuint8_1xuint8(inputs_0, inputs_1, inputs_2, inputs_3, inputs_4, program, output) -> int:
+    """five u8 [x, y] inputs (dimension 0 stride 1 or 0), program i16 [5, n], n <= 20 -> u8 [x, y]: u8_sat of the last slot"""
+    return _check(_fn["elementwise_5xuint8_1xuint8"](_as_ptr(inputs_0), _as_ptr(inputs_1), _as_ptr(inputs_2), _as_ptr(inputs_3), _as_ptr(inputs_4),
+                                                     _as_ptr(program), _as_ptr(output)))
+
+
+def elementwise_5xint16_1xuint8int16(inputs_0, inputs_1, inputs_2, inputs_3, inputs_4, program, output_0, output_1) -> int:
+    """five i16 [x, y] inputs -> output_0 u8 = u8_sat(the last slot but one), output_1 i16 = the last slot"""
+    return _check(_fn["elementwise_5xint16_1xuint8int16"](_as_ptr(inputs_0), _as_ptr(inputs_1), _as_ptr(inputs_2), _as_ptr(inputs_3), _as_ptr(inputs_4),
+                                                          _as_ptr(program), _as_ptr(output_0), _as_ptr(output_1)))
+
+
+def copy_uint8_uint8(input, pad_value, output) -> int:
+    """u8 [c, x, y, b] -> u8 [c, x, y, b]; channels outside the input's dimension 0 are uint8(pad_value)"""
+    return _check(_fn["copy_uint8_uint8"](_as_ptr(input), int(pad_value), _as_ptr(output)))
+
+
+def fill_uint8(value, output) -> int:
+    return _check(_fn["fill_uint8"](int(value), _as_ptr(output)))
+
+
+def upsample_channels_uint8(input, factor, output) -> int:
+    """output(c, x, y, b) = input(c / factor, x, y, b), Halide's division (c / 0 == 0)"""
+    return _check(_fn["upsample_channels_uint8"](_as_ptr(input), int(factor), _as_ptr(output)))
+
+
+def depthwise_conv_shallow_uint8(input, input_zero, filter, filter_zero, bias, stride, dilation, input_stride_x, multiplier, shift, output_zero,
+                                 output_min, output_max, output) -> int:
+    """depthwise_conv_uint8 with c and x fused into dimension 0: input u8 [c, 1, y, b], filter u8 [D, fx, fy], bias i32 [D] -> u8 [c, 1, y, b];
+    the tap rx reads the input at c + rx * dilation_x * input_stride_x; filter and bias are read at (c % 16) % D."""
+    return _check(_fn["depthwise_conv_shallow_uint8"](*_hannk_conv_args(input, input_zero, filter, filter_zero, bias, stride, dilation,
+                                                                        [int(input_stride_x)], multiplier, shift, output_zero, output_min, output_max,
+                                                                        output)))
+
+
+def hannk_can_be_shallow(channels, width, stride_x=1) -> bool:
+    """ops.cpp:931-939, :1012: the channel vector is a multiple of the channel count, the fused row is at least one vector wide, stride_x is 1"""
+    return int(stride_x) == 1 and channels > 0 and HANNK_DEPTHWISE_VECTOR % channels == 0 and channels * width >= HANNK_DEPTHWISE_VECTOR
+
+
+def hannk_depthwise_conv2d_shallow(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, multiplier, shift, output_zero=0,
+                                   output_min=0, output_max=255) -> np.ndarray:
+    """hannk_depthwise_conv2d through the shallow variant, as DepthwiseConv2DOp::execute takes it (ops.cpp:1007-1023): the image is padded
+    with input_zero but its channels are not; c and x of input and output are fused in place.  Refuses (ValueError) what can_be_shallow
+    refuses."""
+    (sx, sy), (dx, dy), (px, py) = _pair(stride), _pair(dilation), _pair(padding)
+    filter = np.ascontiguousarray(filter, np.uint8)
+    fh, fw, c = filter.shape
+    b, h, w, ci = np.asarray(input).shape
+    if ci != c:
+        raise ValueError(f"input has {ci} channels, the filter {c}")
+    if not hannk_can_be_shallow(c, w + 2 * px, sx):
+        raise ValueError("not shallow: stride_x is 1, the channel count divides 16 and channels * padded width >= 16")
+    padded = hannk_pad_input(input, input_zero, 1, (px, py))
+    oh, ow = hannk_conv_out_extent(h, fh, sy, dy, py), hannk_conv_out_extent(w, fw, 1, dx, px)
+    out = np.zeros((b, oh, 1, ow * c), np.uint8)
+    fused = padded.reshape(b, h + 2 * py, 1, (w + 2 * px) * c)
+    ob = Buffer(out)
+    depthwise_conv_shallow_uint8(Buffer(fused), input_zero, Buffer(filter), filter_zero, Buffer(np.ascontiguousarray(bias, np.int32)), (1, sy), (dx, dy),
+                                 c, multiplier, shift, output_zero, output_min, output_max, ob)
+    return ob.numpy().reshape(b, oh, ow, c)
+
+
+def debug_hannk_program_approx(fn, x, q, q_x, width=16) -> np.ndarray:
+    """Test hook: the device's approx_log2p1_exp2 / approx_log2m1_exp2 / approx_logistic / approx_tanh (fn 0 .. 3 or the name) in Int(16):
+    x the i16 argument, q the result's precision, q_x the argument's (each 0 .. 15), broadcast against each other; `width` (16 or 32) is
+    the width of the count q_x."""
+    fn = {"approx_log2p1_exp2": 0, "approx_log2m1_exp2": 1, "approx_logistic": 2, "approx_tanh": 3}.get(fn, fn)
+    shape = np.broadcast_shapes(np.shape(x), np.shape(q), np.shape(q_x))
+    x, q, q_x = (np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int32), shape)) for v in (x, q, q_x))
+    out = np.zeros(shape, np.int32)
+    f = lib.hlmi_debug_hannk_program_approx
+    f.restype, f.argtypes = C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]
+    rc = f(int(fn), x.ctypes.data, q.ctypes.data, q_x.ctypes.data, x.size, int(width), out.ctypes.data)
+    if rc != 0:
+        raise HalideError(-1, f"hlmi_debug_hannk_program_approx failed ({rc})")
+    return out
+
+
+class ElementwiseAssembler:
+    """interpreter/elementwise_program.{h,cpp}: builds the [n, 5] int16 program (rows of op, arg1, arg2, arg3, arg4) the elementwise entry
+    points run.  Methods return Slot objects; an int where the reference has an int16_t overload is an immediate."""
+    Noop, Add, Sub, MulAdd, MulShift, Shift, Min, Max, Clamp, Logistic, Tanh = range(11)
+    InstructionSize = 5
+
+    class Slot:
+        def __init__(self, index):
+            self.index = int(index)
+
+    def __init__(self, capacity=None):
+        self.rows = []
+        self.capacity = capacity
+
+    def _instruction(self, op, a, b, arg3=0, arg4=0):
+        if self.capacity is not None and len(self.rows) >= self.capacity:
+            raise ValueError("the program buffer is full")
+        for v in (arg3, arg4):
+            if not -32768 <= int(v) <= 32767:
+                raise ValueError(f"immediate {v} is no int16")
+        self.rows.append((op, a.index, b.index, int(arg3), int(arg4)))
+        return self.Slot(len(self.rows))
+
+    def _binary(self, op, a, b, imm):
+        if isinstance(b, self.Slot):
+            return self._instruction(op, a, b, imm)
+        return self._instruction(op, a, self.constant(0), b)
+
+    def constant(self, value):
+        return self.Slot(0) if value == 0 else self._instruction(self.Add, self.Slot(0), self.Slot(0), value)
+
+    def input(self, index):
+        return self.Slot(-index - 1)
+
+    def add(self, a, b, add_b=0):
+        return self._binary(self.Add, a, b, add_b)
+
+    def sub(self, a, b, add_b=0):
+        return self._binary(self.Sub, a, b, add_b)
+
+    def mul(self, a, b, add_b=0):
+        return self._binary(self.MulAdd, a, b, add_b)
+
+    def mul_add(self, a, b, add):
+        if isinstance(b, self.Slot):
+            return self._instruction(self.MulAdd, a, b, 0, add)
+        return self._instruction(self.MulAdd, a, self.constant(0), b, add)
+
+    def mul_shift(self, a, b, shift):
+        if isinstance(b, self.Slot):
+            return self._instruction(self.MulShift, a, b, 0, shift)
+        return self._instruction(self.MulShift, a, self.constant(0), b, shift)
+
+    def shift(self, a, b, extra_shift=0):
+        return self._binary(self.Shift, a, b, extra_shift)
+
+    def min(self, a, b, add_b=0):
+        return self._binary(self.Min, a, b, add_b)
+
+    def max(self, a, b, add_b=0):
+        return self._binary(self.Max, a, b, add_b)
+
+    def clamp(self, x, lo, hi):
+        return self._instruction(self.Clamp, x, x, lo, hi)   # op2 is unused: x again, as the reference does
+
+    def logistic(self, q, a, q_a):
+        if isinstance(q_a, self.Slot):
+            return self._instruction(self.Logistic, a, q_a, 0, q)
+        return self._instruction(self.Logistic, a, self.constant(0), q_a, q)
+
+    def tanh(self, q, a, q_a):
+        if isinstance(q_a, self.Slot):
+            return self._instruction(self.Tanh, a, q_a, 0, q)
+        return self._instruction(self.Tanh, a, self.constant(0), q_a, q)
+
+    def assemble(self, outputs) -> np.ndarray:
+        """The program whose last len(outputs) slots are `outputs`: where they are not there already, each is reloaded by adding 0."""
+        needed = len(self.rows) - len(outputs) + 1
+        if [o.index for o in outputs] != list(range(needed, needed + len(outputs))):
+            for o in outputs:
+                self.add(o, 0)
+        return np.array(self.rows, np.int16).reshape(-1, 5)
+
+
+def hannk_logistic_program(in_scale, in_zero) -> np.ndarray:
+    """UnaryOp::execute, Logistic (ops.cpp:1797-1813): the output has scale 1 / 256 and zero point 0"""
+    m, e = _int_float_scaled(np.float32(in_scale), 16, -6)
+    if e > 0:
+        raise ValueError("the input scale is too large for the logistic program")
+    p = ElementwiseAssembler(64 // 5)
+    scaled = p.mul_shift(p.sub(p.input(0), int(in_zero)), m, 15 - 6)
+    return p.assemble([p.logistic(8, scaled, -e)])
+
+
+def hannk_tanh_program(in_scale, in_zero) -> np.ndarray:
+    """UnaryOp::execute, Tanh (ops.cpp:1820-1833): the output has scale 1 / 128 and zero point 128"""
+    m, e = _int_float_scaled(np.float32(in_scale), 16, -6)
+    if e > 0:
+        raise ValueError("the input scale is too large for the tanh program")
+    p = ElementwiseAssembler(64 // 5)
+    scaled = p.mul_shift(p.sub(p.input(0), int(in_zero)), m, 15 - 6)
+    return p.assemble([p.add(p.tanh(7, scaled, -e), 128)])
+
+
+def hannk_lstm_program() -> np.ndarray:
+    """The elementwise part of the LSTM cell (lower.cpp:44-69) on inputs (input gate, input modulation gate, forget gate, output gate,
+    previous state), all int16 -> the outputs (activation u8, state i16)"""
+    p = ElementwiseAssembler(256 // 5)
+    q = 15
+    input_gate = p.logistic(q, p.input(0), q - 3)
+    input_modulation_gate = p.tanh(q, p.input(1), q - 3)
+    forget_gate = p.logistic(q, p.input(2), q - 3)
+    output_gate = p.logistic(q, p.input(3), q - 3)
+    input_times_input_modulation = p.mul_shift(input_gate, input_modulation_gate, q + 4)
+    prev_state_times_forget_state = p.mul(forget_gate, p.input(4))
+    state = p.add(input_times_input_modulation, prev_state_times_forget_state)
+    activation = p.mul_add(output_gate, p.tanh(7, state, q - 4), 128)
+    state = p.add(state, 0)
+    return p.assemble([activation, state])
+
+
+def _hannk_program_rank2(a, shape, dtype):
+    """`a` broadcast against `shape` as an [x, y] operand: stride 0 along the innermost axis where `a` has one element there"""
+    a = np.asarray(a, dtype)
+    full = tuple(shape)
+    n = full[-1] if full else 1
+    a = a.reshape((1,) * (len(full) - a.ndim) + a.shape)
+    if a.shape == full:
+        return np.ascontiguousarray(a).reshape(-1, n)
+    if a.shape[-1] == 1 and a.shape[:-1] == full[:-1]:
+        rows = np.ascontiguousarray(a).reshape(-1, 1)
+        return np.lib.stride_tricks.as_strided(rows, shape=(rows.shape[0], n), strides=(rows.strides[0], 0), writeable=False)
+    return np.ascontiguousarray(np.broadcast_to(a, full)).reshape(-1, n)
+
+
+def hannk_elementwise(inputs, program, outputs=1):
+    """ElementwiseProgramOp::execute: one to five inputs of one dtype, uint8 or int16 (the last is repeated up to five, as ops.cpp:1080-1084
+    does), broadcast against each other; program an [n, 5] int16 array.  uint8 inputs -> the uint8 result (outputs = 1); int16 inputs ->
+    the pair (uint8, int16) (outputs = 2): the two variants the library has."""
+    if not 1 <= len(inputs) <= 5:
+        raise ValueError("one to five inputs")
+    dtype = np.asarray(inputs[0]).dtype
+    if dtype == np.dtype(np.uint8):
+        want = 1
+    elif dtype == np.dtype(np.int16):
+        want = 2
+    else:
+        raise TypeError("the inputs are uint8 or int16")
+    if outputs != want:
+        raise ValueError(f"{dtype} inputs have {want} output(s)")
+    shape = np.broadcast_shapes(*[np.shape(a) for a in inputs])
+    arrs = [_hannk_program_rank2(a, shape, dtype) for a in inputs]
+    bufs = [Buffer(a) for a in arrs]
+    bufs += [bufs[-1]] * (5 - len(bufs))
+    prog = Buffer(np.ascontiguousarray(program, np.int16).reshape(-1, 5))
+    out0 = Buffer(np.zeros(arrs[0].shape, np.uint8))
+    if want == 1:
+        elementwise_5xuint8_1xuint8(*bufs, prog, out0)
+        return out0.numpy().reshape(shape)
+    out1 = Buffer(np.zeros(arrs[0].shape, np.int16))
+    elementwise_5xint16_1xuint8int16(*bufs, prog, out0, out1)
+    return out0.numpy().reshape(shape), out1.numpy().reshape(shape)
+
+
+def hannk_logistic(x, in_scale, in_zero) -> np.ndarray:
+    """UnaryOp Logistic on a uint8 array of any shape: the result has scale 1 / 256 and zero point 0"""
+    return hannk_elementwise([np.asarray(x, np.uint8)], hannk_logistic_program(in_scale, in_zero))
+
+
+def hannk_tanh(x, in_scale, in_zero) -> np.ndarray:
+    """UnaryOp Tanh: the result has scale 1 / 128 and zero point 128"""
+    return hannk_elementwise([np.asarray(x, np.uint8)], hannk_tanh_program(in_scale, in_zero))
+
+
+def hannk_lstm_elementwise(input_gate, input_modulation_gate, forget_gate, output_gate, prev_state):
+    """The LSTM cell's elementwise program on five int16 arrays -> (activation uint8, state int16)"""
+    return hannk_elementwise([np.asarray(a, np.int16) for a in (input_gate, input_modulation_gate, forget_gate, output_gate, prev_state)],
+                             hannk_lstm_program(), outputs=2)
+
+
+def hannk_pad(input, padding, pad_value) -> np.ndarray:
+    """PadOp::execute on a uint8 array of rank <= 4 (numpy order, padded to rank 4 in front): `padding` is one (before, after) pair per numpy
+    axis.  The borders are filled dimension by dimension with fill_uint8, the rest is one copy_uint8_uint8; where 3 channels become 4
+    the copy pads the channel itself (ops.cpp:1266-1271)."""
+    input = np.ascontiguousarray(input, np.uint8)
+    nd = input.ndim
+    if nd > 4 or len(padding) != nd:
+        raise ValueError("rank <= 4 and one (before, after) pair per axis")
+    in4 = input.reshape((1,) * (4 - nd) + input.shape)
+    pads = [(0, 0)] * (4 - nd) + [(int(b), int(a)) for b, a in padding]
+    if any(b < 0 or a < 0 for b, a in pads):
+        raise ValueError("paddings are not negative")
+    out = np.zeros(tuple(s + b + a for s, (b, a) in zip(in4.shape, pads)), np.uint8)
+    # Halide dimension d is numpy axis 3 - d; the input is translated by the padding in front of it
+    imin = [pads[3 - d][0] for d in range(4)]
+    imax = [imin[d] + in4.shape[3 - d] - 1 for d in range(4)]
+    omin, omax = [0] * 4, [out.shape[3 - d] - 1 for d in range(4)]
+
+    def crop():
+        view = out[tuple(slice(omin[3 - ax], omax[3 - ax] + 1) for ax in range(4))]
+        return Buffer(view, mins=tuple(omin))
+
+    fill_min_dim = 1 if in4.shape[3] == 3 and out.shape[3] == 4 else 0
+    for d in range(3, fill_min_dim - 1, -1):
+        lo, hi = omin[d], omax[d]
+        if lo < imin[d]:
+            omin[d], omax[d] = lo, imin[d] - 1
+            b = crop()
+            fill_uint8(pad_value, b)
+            b.numpy()
+        if hi > imax[d]:
+            omin[d], omax[d] = imax[d] + 1, hi
+            b = crop()
+            fill_uint8(pad_value, b)
+            b.numpy()
+        omin[d], omax[d] = max(lo, imin[d]), min(hi, imax[d])
+    b = crop()
+    copy_uint8_uint8(Buffer(in4, mins=tuple(imin)), pad_value, b)
+    b.numpy()
+    return out.reshape(tuple(out.shape[4 - nd:]))
+
+
+def hannk_upsample_channels(input, factor) -> np.ndarray:
+    """(B, H, W, C) uint8 -> (B, H, W, C * factor): channel c of the result is channel c // factor of the input (depth multiplier > 1)"""
+    input = np.ascontiguousarray(input, np.uint8)
+    if input.ndim != 4 or int(factor) < 1:
+        raise ValueError("a (B, H, W, C) array and a factor >= 1")
+    out = Buffer(np.zeros(input.shape[:3] + (input.shape[3] * int(factor),), np.uint8))
+    upsample_channels_uint8(Buffer(input), factor, out)
+    return out.numpy()
 
 
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:

@@ -1,7 +1,7 @@
 // hannk_conv.hip — the quantised convolution ops of apps/hannk's op library (apps/hannk/halide/conv_generator.cpp,
 // depthwise_conv_generator.cpp, common_halide.cpp), C++-mangled in namespace hannk as the reference builds them:
 //   hannk::tile_conv_filter_uint8, hannk::conv_u8_u8_u8, hannk::conv_u8_u8_i16, hannk::depthwise_conv_uint8,
-//   hannk::depthwise_conv_broadcast_uint8, each with _argv and _metadata (include/aot/halide/<name>.h).
+//   hannk::depthwise_conv_broadcast_uint8, hannk::depthwise_conv_shallow_uint8, each with _argv and _metadata (include/aot/halide/<name>.h).
 //
 // The contract is integer throughout and is the same in both builds of the library: no float is touched.
 //   tile    output(ci, bi, co, bo, x, y) = u8(i16(in(co*4 + ci, x, y, bo*16 + bi)) - i16(input_zero) + output_zero), in = input_zero
@@ -9,6 +9,8 @@
 //   conv    acc(c, x, y, b) = bias(c) + sum over ry, rx, rz of (in(rz, x*sx + rx*dx, y*sy + ry*dy, b) - input_zero)
 //                                                              * (filter(rz % 4, c % 16, rz / 4, c / 16, rx, ry) - filter_zero), mod 2^32
 //   depthw. acc(c, x, y, b) = bias(c) + sum over ry, rx of (filter(c, rx, ry) - filter_zero) * (in(c * inv, x*sx + rx*dx, y*sy + ry*dy, b) - input_zero)
+//   shallow the depthwise sum with c the fused c-x index of an output whose x is 0: filter and bias at (c % 16) % D, the input at
+//           (c + rx*dx*input_stride_x, 0, y*sy + ry*dy, b): a template flag on the two depthwise kernels
 //   out     quantize_i16 = i16_sat(rounding_shift_right(multiply_2x_high(acc, multiplier), shift)); quantize_and_relu_u8 =
 //           max(min(u8_sat(sat_add_i16(quantize_i16, zero)), hi), lo)
 // The layout constants (4, 16, 16) are in include/aot/halide/hannk_target.h.
@@ -350,10 +352,16 @@ struct DwGeom {
     long f_sx, f_sy;
     int sx, sy, dx, dy, FW, FH;
     int az, fz;
+    int D;                    // the shallow variant: the filter's extent 0
     Quant q;
 };
+// The shallow variant (depthwise_conv_generator.cpp:75-83, :124-125): c is the fused c-x index of an output whose dimension 1 is {0, 1};
+// filter and bias repeat at multiples of the channel vector, then of the filter's depth.  The host passes input_stride_x as in_sx, so
+// with x = 0 the tap address rx * dx * in_sx is the generator's c + rx * dilation_x * input_stride_x.
+template<bool SHALLOW>
+__device__ __forceinline__ int dw_filter_c(const DwGeom &g, int c) { return SHALLOW ? (c % DV) % g.D : c; }
 
-template<bool BCAST>
+template<bool BCAST, bool SHALLOW = false>
 __global__ __launch_bounds__(256) void hannk_dw_general(DwGeom g) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)g.C * g.OW * g.OH * g.OB) return;
@@ -361,11 +369,12 @@ __global__ __launch_bounds__(256) void hannk_dw_general(DwGeom g) {
     const long p = i / g.C;
     const int x = (int)(p % g.OW), y = (int)((p / g.OW) % g.OH), b = (int)(p / ((long)g.OW * g.OH));
     const uint8_t *in = g.in + b * g.in_sb + (long)y * g.sy * g.in_sy + (long)x * g.sx * g.in_sx + (BCAST ? 0 : c);
-    uint32_t acc = (uint32_t)g.bias[c];
+    const int fc = dw_filter_c<SHALLOW>(g, c);
+    uint32_t acc = (uint32_t)g.bias[fc];
     for (int ry = 0; ry < g.FH; ry++)
         for (int rx = 0; rx < g.FW; rx++) {
             const int a = in[(long)ry * g.dy * g.in_sy + (long)rx * g.dx * g.in_sx];
-            const int w = g.filt[c + rx * g.f_sx + ry * g.f_sy];
+            const int w = g.filt[fc + rx * g.f_sx + ry * g.f_sy];
             acc += (uint32_t)((w - g.fz) * (a - g.az));
         }
     g.out[b * g.o_sb + y * g.o_sy + x * g.o_sx + c] = (uint8_t)quantize_and_relu_u8((int32_t)acc, g.q);
@@ -373,8 +382,9 @@ __global__ __launch_bounds__(256) void hannk_dw_general(DwGeom g) {
 
 // K3: the 3 x 3 specialisation (taps in registers, loops unrolled).  A thread: channels 4 cq .. 4 cq + 3 of DW_ROWS output rows of
 // one (x, b).  The input covers round_up(C, 16) channels (checked), so the dword at channel 4 cq is inside it whenever 4 cq < C; filter
-// and bias are read at [0, C) only.
-template<bool K3, bool BCAST>
+// and bias are read at [0, C) only.  SHALLOW: the plan has checked that C is a multiple of 4 and every tap offset too, so each dword
+// lies inside the fused row.
+template<bool K3, bool BCAST, bool SHALLOW = false>
 __global__ __launch_bounds__(256) void hannk_dw(DwGeom g) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const int nq = (g.C + 3) / 4, nyb = (g.OH + DW_ROWS - 1) / DW_ROWS;
@@ -386,7 +396,7 @@ __global__ __launch_bounds__(256) void hannk_dw(DwGeom g) {
     const int y0 = (int)(p % nyb) * DW_ROWS, b = (int)(p / nyb);
     const int FW = K3 ? 3 : g.FW, FH = K3 ? 3 : g.FH;
     constexpr int UNR = K3 ? 3 : 1;
-    auto tap = [&](int c, int rx, int ry) { return c < g.C ? (int)g.filt[c + rx * g.f_sx + ry * g.f_sy] - g.fz : 0; };
+    auto tap = [&](int c, int rx, int ry) { return c < g.C ? (int)g.filt[dw_filter_c<SHALLOW>(g, c) + rx * g.f_sx + ry * g.f_sy] - g.fz : 0; };
     // offset_c = bias - input_zero * sum of the zeroed taps
     uint32_t off[4];
     int w[K3 ? 9 : 1][4];
@@ -399,7 +409,7 @@ __global__ __launch_bounds__(256) void hannk_dw(DwGeom g) {
                 if (K3) w[ry * 3 + rx][r] = v;
                 s += v;
             }
-        off[r] = (c0 + r < g.C ? (uint32_t)g.bias[c0 + r] : 0u) - (uint32_t)g.az * (uint32_t)s;
+        off[r] = (c0 + r < g.C ? (uint32_t)g.bias[dw_filter_c<SHALLOW>(g, c0 + r)] : 0u) - (uint32_t)g.az * (uint32_t)s;
     }
     const uint8_t *in = g.in + b * g.in_sb + (long)x * g.sx * g.in_sx + (BCAST ? 0 : c0);
     for (int y = y0; y < min(y0 + DW_ROWS, g.OH); y++) {
@@ -435,6 +445,7 @@ const ArgTable conv_u8_table("conv_u8_u8_u8", {HLMI_HANNK_CONV_HEAD(6), HLMI_HAN
 const ArgTable conv_i16_table("conv_u8_u8_i16", {HLMI_HANNK_CONV_HEAD(6), HLMI_HANNK_CONV_TAIL(T_I16)});
 const ArgTable dw_table("depthwise_conv_uint8", {HLMI_HANNK_CONV_HEAD(3), L(scalar_i32("input_stride_x")), HLMI_HANNK_CONV_TAIL(T_U8)});
 const ArgTable dwb_table("depthwise_conv_broadcast_uint8", {HLMI_HANNK_CONV_HEAD(3), L(scalar_i32("input_stride_x")), HLMI_HANNK_CONV_TAIL(T_U8)});
+const ArgTable dws_table("depthwise_conv_shallow_uint8", {HLMI_HANNK_CONV_HEAD(3), L(scalar_i32("input_stride_x")), HLMI_HANNK_CONV_TAIL(T_U8)});
 #undef HLMI_HANNK_CONV_HEAD
 #undef HLMI_HANNK_CONV_TAIL
 
@@ -660,13 +671,16 @@ bool dw_vector(long threads, bool aligned, std::optional<int> forced) {
     return forced ? *forced != 0 : threads >= DW_MIN_THREADS;
 }
 
-template<bool BCAST, bool GENERAL>
+// SHALLOW (depthwise_conv_shallow_uint8): the output's dimension 1 is {0, 1} and dimension 0 the fused c-x index; the
+// input is read at (c + rx * dilation_x * input_stride_x, 0, y * stride_y + ry * dilation_y, b); filter and bias at (c % 16) % D of their
+// own [0, D); no alignment is required and neither filter nor bias follows the output's extent.  Its dword kernel needs what the
+// plain variant's constraints give for free: every tap offset, the row strides and the fused extent multiples of 4.
+template<bool BCAST, bool GENERAL, bool SHALLOW = false>
 int dw_entry(halide_buffer_t *input, uint8_t input_zero, halide_buffer_t *filter, uint8_t filter_zero, halide_buffer_t *bias, int32_t stride_x,
              int32_t stride_y, int32_t dilation_x, int32_t dilation_y, int32_t input_stride_x, int32_t output_multiplier, int32_t output_shift,
              uint8_t output_zero, uint8_t output_min, uint8_t output_max, halide_buffer_t *output) {
-    (void)input_stride_x;   // the shallow variant's
     void *uc = nullptr;
-    const ArgTable &table = BCAST ? dwb_table : dw_table;
+    const ArgTable &table = SHALLOW ? dws_table : BCAST ? dwb_table : dw_table;
     BufArg args[4];
     table.bufs(args, {input, filter, bias, output});
     own_lanes(args);
@@ -674,7 +688,44 @@ int dw_entry(halide_buffer_t *input, uint8_t input_zero, halide_buffer_t *filter
     if (r || (r = check_type_and_dims(uc, args, 4))) return r;
     halide_dimension_t *id = input->dim, *fd = filter->dim, *bd = bias->dim, *od = output->dim;
     const int C = od[0].extent, CIN = BCAST ? 1 : (std::max(C, 1) + DV - 1) / DV * DV;
-    if (any_bounds_query(args, 4)) {
+    if constexpr (SHALLOW) {
+        const int D = std::max(fd[0].extent, 1);
+        // the fused row: channels [0, C) shifted by the taps 0 .. (FW - 1) * dilation_x * input_stride_x
+        const long t = (long)(std::max(fd[1].extent, 1) - 1) * dilation_x * input_stride_x;
+        const long lo = std::min(0L, t), hi = (long)std::max(C, 1) - 1 + std::max(0L, t);
+        if (lo < -(1L << 30) || hi > (1L << 30))
+            return report(uc, halide_error_code_buffer_extents_too_large, "depthwise_conv_shallow_uint8: the taps span %ld elements", hi - lo + 1);
+        int ymin, yext;
+        in_span(od[2].min, std::max(od[2].extent, 1), stride_y, std::max(fd[2].extent, 1), dilation_y, &ymin, &yext);
+        if (any_bounds_query(args, 4)) {
+            const int mins[4] = {(int)lo, 0, ymin, od[3].min}, ext[4] = {(int)(hi - lo + 1), 1, yext, od[3].extent};
+            answer_query(input, mins, ext);
+            const int fmin[3] = {0, 0, 0}, fext[3] = {D, std::max(fd[1].extent, 1), std::max(fd[2].extent, 1)}, bext[1] = {D};
+            answer_query(filter, fmin, fext);
+            answer_query(bias, fmin, bext);
+            return 0;
+        }
+        // ---- constraints (depthwise_conv_generator.cpp:93-94, :138-146)
+        check_dim(uc, "input", input, 0, &k0, nullptr, nullptr);
+        check_dim(uc, "filter", filter, 0, &k0, nullptr, &k1);
+        check_dim(uc, "filter", filter, 1, &k0, nullptr, nullptr);
+        check_dim(uc, "filter", filter, 2, &k0, nullptr, nullptr);
+        check_dim(uc, "bias", bias, 0, &k0, nullptr, &k1);
+        check_dim(uc, "output", output, 0, &k0, nullptr, &k1);
+        check_dim(uc, "output", output, 1, &k0, &k1, nullptr);
+        check_dim(uc, "output", output, 3, &id[3].min, &id[3].extent, nullptr);
+        if ((r = check_shapes(uc, args, 4))) return r;
+        if (C > 0 && od[2].extent > 0 && od[3].extent > 0) {
+            check_covers(uc, args[1], 0, 0, D);   // filter(c % D, ...) and bias(c % D): [0, D)
+            check_covers(uc, args[2], 0, 0, D);
+            if (fd[1].extent > 0 && fd[2].extent > 0) {
+                check_covers(uc, args[0], 0, (int)lo, (int)(hi - lo + 1));
+                check_covers(uc, args[0], 1, 0, 1);
+                check_covers(uc, args[0], 2, ymin, yext);
+            }
+        }
+    }
+    if (!SHALLOW && any_bounds_query(args, 4)) {
         // DepthwiseConv2DOp::prepare reads the channel alignment from the input's extent 0
         int mins[4] = {0, 0, 0, od[3].min}, ext[4] = {CIN, 0, 0, od[3].extent};
         in_span(od[1].min, std::max(od[1].extent, 1), stride_x, std::max(fd[1].extent, 1), dilation_x, &mins[1], &ext[1]);
@@ -685,6 +736,7 @@ int dw_entry(halide_buffer_t *input, uint8_t input_zero, halide_buffer_t *filter
         answer_query(bias, fmin, bext);
         return 0;
     }
+    if constexpr (!SHALLOW) {
     // ---- constraints (depthwise_conv_generator.cpp:93-94, :138-168)
     check_dim(uc, "input", input, 0, &k0, BCAST ? &k1 : nullptr, nullptr);
     if (!BCAST)
@@ -696,9 +748,10 @@ int dw_entry(halide_buffer_t *input, uint8_t input_zero, halide_buffer_t *filter
     check_dim(uc, "output", output, 0, &k0, nullptr, &k1);
     check_dim(uc, "output", output, 3, &id[3].min, &id[3].extent, nullptr);
     if ((r = check_shapes(uc, args, 4))) return r;
+    }
     const int OW = od[1].extent, OH = od[2].extent, OB = od[3].extent, FW = fd[1].extent, FH = fd[2].extent;
     const bool empty = C <= 0 || OW <= 0 || OH <= 0 || OB <= 0;
-    if (!empty) {
+    if (!SHALLOW && !empty) {
         int mn, ex;
         check_covers(uc, args[0], 0, 0, CIN);
         if (FW > 0 && FH > 0) {
@@ -708,7 +761,7 @@ int dw_entry(halide_buffer_t *input, uint8_t input_zero, halide_buffer_t *filter
             check_covers(uc, args[0], 2, mn, ex);
         }
     }
-    if (!BCAST) check_host_aligned(uc, args[0], DV);
+    if (!BCAST && !SHALLOW) check_host_aligned(uc, args[0], DV);
     DeviceCtx ctx;
     if ((r = to_device(uc, &ctx, args, 4))) return r;
     if (empty) {
@@ -717,26 +770,31 @@ int dw_entry(halide_buffer_t *input, uint8_t input_zero, halide_buffer_t *filter
     }
     DwGeom g = {};
     g.C = C, g.OW = OW, g.OH = OH, g.OB = OB;
-    g.in_sx = id[1].stride, g.in_sy = id[2].stride, g.in_sb = id[3].stride;
+    g.in_sx = SHALLOW ? input_stride_x : id[1].stride, g.in_sy = id[2].stride, g.in_sb = id[3].stride;
+    g.D = SHALLOW ? std::max(fd[0].extent, 1) : 0;
     g.o_sx = od[1].stride, g.o_sy = od[2].stride, g.o_sb = od[3].stride;
     g.f_sx = fd[1].stride, g.f_sy = fd[2].stride;
     g.sx = stride_x, g.sy = stride_y, g.dx = dilation_x, g.dy = dilation_y, g.FW = FW, g.FH = FH;
     g.az = input_zero, g.fz = filter_zero;
     g.q = {output_multiplier, output_shift, output_zero, output_min, output_max};
-    g.in = dev_ptr<uint8_t>(input) + ((long)od[1].min * stride_x - id[1].min) * g.in_sx + ((long)od[2].min * stride_y - id[2].min) * g.in_sy;
+    g.in = dev_ptr<uint8_t>(input) + ((long)od[2].min * stride_y - id[2].min) * g.in_sy;
+    if (SHALLOW) g.in += (0L - id[1].min) * id[1].stride;   // x = 0 of the input; dimension 0 starts at 0 on both sides
+    else g.in += ((long)od[1].min * stride_x - id[1].min) * g.in_sx;
     g.filt = dev_ptr<uint8_t>(filter), g.bias = dev_ptr<int32_t>(bias) - bd[0].min, g.out = dev_ptr<uint8_t>(output);
     const double bytes = (double)OW * OH * OB * C * 2 + (double)C * (FW * FH + 4);
     unsigned blocks;
     const long threads = (long)((C + 3) / 4) * OW * ((OH + DW_ROWS - 1) / DW_ROWS) * OB;
-    if (GENERAL || !dw_vector(threads, BCAST || (uintptr_t)g.in % 4 == 0, env_int("HLMI_HANNK_DW_VECTOR"))) {
+    bool aligned = BCAST || (uintptr_t)g.in % 4 == 0;
+    if (SHALLOW) aligned = aligned && C % 4 == 0 && ((long)dilation_x * input_stride_x) % 4 == 0 && g.in_sy % 4 == 0 && g.in_sb % 4 == 0;
+    if (GENERAL || !dw_vector(threads, aligned, env_int("HLMI_HANNK_DW_VECTOR"))) {
         if ((r = blocks_ok(uc, table.md.name, (long)C * OW * OH * OB, &blocks))) return r;
         timing_note_bytes(bytes);
-        HLMI_LAUNCH(uc, "hannk_dw_general", ctx.stream, hannk_dw_general<BCAST>, dim3(blocks), dim3(256), 0, g);
+        HLMI_LAUNCH(uc, "hannk_dw_general", ctx.stream, (hannk_dw_general<BCAST, SHALLOW>), dim3(blocks), dim3(256), 0, g);
     } else {
         if ((r = blocks_ok(uc, table.md.name, threads, &blocks))) return r;
         timing_note_bytes(bytes);
-        if (FW == 3 && FH == 3) HLMI_LAUNCH(uc, "hannk_dw", ctx.stream, (hannk_dw<true, BCAST>), dim3(blocks), dim3(256), 0, g);
-        else HLMI_LAUNCH(uc, "hannk_dw", ctx.stream, (hannk_dw<false, BCAST>), dim3(blocks), dim3(256), 0, g);
+        if (FW == 3 && FH == 3) HLMI_LAUNCH(uc, "hannk_dw", ctx.stream, (hannk_dw<true, BCAST, SHALLOW>), dim3(blocks), dim3(256), 0, g);
+        else HLMI_LAUNCH(uc, "hannk_dw", ctx.stream, (hannk_dw<false, BCAST, SHALLOW>), dim3(blocks), dim3(256), 0, g);
     }
     mark_output_written(output);
     return 0;
@@ -778,6 +836,14 @@ int depthwise_conv_broadcast_uint8(halide_buffer_t *input, uint8_t input_zero, h
     return dw_entry<true, false>(input, input_zero, filter, filter_zero, bias, stride_x, stride_y, dilation_x, dilation_y, input_stride_x, output_multiplier,
                                  output_shift, output_zero, output_min, output_max, output);
 }
+int depthwise_conv_shallow_uint8(halide_buffer_t *input, uint8_t input_zero, halide_buffer_t *filter, uint8_t filter_zero, halide_buffer_t *bias,
+                                 int32_t stride_x, int32_t stride_y, int32_t dilation_x, int32_t dilation_y, int32_t input_stride_x,
+                                 int32_t output_multiplier, int32_t output_shift, uint8_t output_zero, uint8_t output_min, uint8_t output_max,
+                                 halide_buffer_t *output) {
+    return dw_entry<false, false, true>(input, input_zero, filter, filter_zero, bias, stride_x, stride_y, dilation_x, dilation_y, input_stride_x,
+                                        output_multiplier, output_shift, output_zero, output_min, output_max, output);
+}
+HLMI_HANNK_ENTRY(depthwise_conv_shallow_uint8, dws_table)
 HLMI_HANNK_ENTRY(tile_conv_filter_uint8, tile_table)
 HLMI_HANNK_ENTRY(conv_u8_u8_u8, conv_u8_table)
 HLMI_HANNK_ENTRY(conv_u8_u8_i16, conv_i16_table)
@@ -795,6 +861,7 @@ extern "C" int hlmi_hannk_general(const char *name, void **argv) {
     if (!strcmp(name, "conv_u8_u8_i16")) return argv_call(conv_entry<true, true>, argv);
     if (!strcmp(name, "depthwise_conv_uint8")) return argv_call(dw_entry<false, true>, argv);
     if (!strcmp(name, "depthwise_conv_broadcast_uint8")) return argv_call(dw_entry<true, true>, argv);
+    if (!strcmp(name, "depthwise_conv_shallow_uint8")) return argv_call(dw_entry<false, true, true>, argv);
     return hannk_nn_general(name, argv);   // the pooling, reduction, elementwise and normalisation ops
 }
 

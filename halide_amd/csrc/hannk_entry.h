@@ -1,4 +1,4 @@
-// hannk_entry.h — what the entry points of apps/hannk's op library share on the host side (hannk_conv.hip, hannk_nn.hip): the lanes-1
+// hannk_entry.h — what the entry points of apps/hannk's op library share on the host side (hannk_conv.hip, hannk_nn.hip, hannk_program.hip): the lanes-1
 // types of their argument tables and the constraint checks in the reference's words.
 #pragma once
 
@@ -46,5 +46,39 @@ inline void check_dim(void *uc, const char *buffer, const halide_buffer_t *b, in
         check_equal(uc, what, have[k], expect, *want[k]);
     }
 }
+// check_shape for a buffer whose dimension 0 may have any stride (the generator's dim(0).set_stride(Expr())): the same extents and
+// sizes, recorded under the same name, with the stride constraint taken out
+inline void check_shape_any_stride0(void *uc, const BufArg &a) {
+    halide_dimension_t dims[4];
+    halide_buffer_t copy = *a.buf;
+    const int nd = std::min(a.buf->dimensions, 4);
+    for (int d = 0; d < nd; d++) dims[d] = a.buf->dim[d];
+    if (nd > 0) dims[0].stride = 1;
+    copy.dim = dims;
+    const BufArg b = {a.name, &copy, a.type, a.dims, a.is_output};
+    check_shape(uc, b);
+}
+// the no_bounds_query ops: an unallocated buffer is checked like any other, its type first (check_type_and_dims would take it
+// for a query and rewrite the type)
+inline int check_unallocated_types(void *uc, const BufArg *args, int n) {
+    for (int i = 0; i < n; i++)
+        if (!buffer_is_real(args[i].buf) && buf_type_abi(args[i].buf) != args[i].type) {
+            char t0[16], t1[16];
+            return report(uc, halide_error_code_bad_type, "%s buffer %s has type %s but type of the buffer passed in is %s", args[i].is_output ? "Output" : "Input",
+                          args[i].name, type_name(args[i].type, t0), type_name(buf_type_abi(args[i].buf), t1));
+        }
+    return 0;
+}
+// ... and after every other check has passed, its missing host pointer ends the call (asserts_host_non_null): before anything is
+// allocated for it
+inline int check_unallocated_host(void *uc, const BufArg *args, int n) {
+    for (int i = 0; i < n; i++)
+        if (!buffer_is_real(args[i].buf)) {
+            if (int r = checks_done(uc)) return r;
+            return report(uc, halide_error_code_host_is_null, "%s buffer %s host pointer is null", args[i].is_output ? "Output" : "Input", args[i].name);
+        }
+    return 0;
+}
+inline long elem_offset(const halide_buffer_t *b, int d, long coord) { return (coord - b->dim[d].min) * (long)b->dim[d].stride; }
 }  // namespace hannk_entry
 }  // namespace hlmi

@@ -1,5 +1,6 @@
 // hannk_math.h — the fixed-point helpers of apps/hannk/halide/common_halide.cpp, each restated in the type Halide gives it (DESIGN.md
-// §5.12 for the epilogue, §5.13 for the approx_* helpers), shared by hannk_conv.hip and hannk_nn.hip.  Host and device.
+// §5.12 for the epilogue, §5.13 for the approx_* helpers, §5.14 for the Elementwise interpreter), shared by hannk_conv.hip, hannk_nn.hip and
+// hannk_program.hip.  Host and device.
 //
 // Conventions: a value of a type below 32 bits travels in an int32_t and is wrapped (wrap<BITS>) or saturated (sat<BITS>) wherever
 // Halide's type does so; i32 arithmetic wraps through uint32_t.  Shifts: the result has the left operand's type; a negative signed
@@ -107,6 +108,85 @@ __host__ __device__ inline int32_t approx_reciprocal(int q, int32_t x) {
 template<int TB>
 __host__ __device__ inline int32_t approx_reciprocal_sqrt(int q, int32_t x) {
     return approx_exp2<32, TB>(q, wrap<32>(-(int64_t)approx_log2<32>(14, x, 0)), 15);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- approx_logistic, approx_tanh
+// common_halide.cpp:177-226, as the Elementwise generator instantiates them: x and the result are i16, q_x is a
+// run-time signed count of CW bits.  A shift by q_x runs at the wider of its operand's and the count's width (match_bits,
+// src/IROperator.cpp:2742-2747): CW = 16 in the generator, where q_x is the i16 expression input2 + arg3; CW = 32 in the reference's own
+// test, where it is the i32 Var y.  The constant log_q = 11 reaches approx_exp2 as an i32 immediate in both.
+// x >> c of a BITS-bit signed x, signed count
+template<int BITS>
+__host__ __device__ inline int32_t shr(int32_t a, int32_t c) { return shl<BITS>(a, c == INT32_MIN ? 0x7fffffff : -c); }
+// rounding_shift_right(a, s) of an i16 a with a signed i16 count (lower_rounding_shift_right: (a >> s) + (s > 0 & (a >> sat_sub(s, 1))))
+__host__ __device__ inline int32_t rounding_shift_right16(int32_t a, int32_t s) {
+    if (s <= 0) return shl<16>(a, -s);
+    return wrap<16>((int64_t)shr<16>(a, s) + (shr<16>(a, s - 1) & 1));
+}
+// approx_exp2(16, x, q_x, Int(32)) of an i16 x with a signed count
+template<int CW>
+__host__ __device__ inline int32_t approx_exp2_q16(int32_t x, int32_t q_x) {
+    const int32_t floor_x = shr<CW>(x, q_x);                                          // cast to i32: the value as it is
+    const int32_t e = shl<32>(1, wrap<32>((int64_t)floor_x + 16));
+    const int32_t d = wrap<16>((int64_t)x - shl<32>(floor_x, q_x));                   // floor_x is an i32: a 32-bit shift whatever CW
+    const int32_t frac1 = shl<16>(d, wrap<16>(15 - (int32_t)wrap<16>(q_x)));
+    const int32_t frac2 = mul2x<16>(frac1, frac1), frac3 = mul2x<16>(frac2, frac1);
+    int32_t poly = wrap<16>((int64_t)mul2x<16>(2592, frac3) + mul2x<16>(7363, frac2) + mul2x<16>(22812, frac1));
+    poly = shl<32>(poly, 16);
+    return sat<32>((int64_t)e + mul2x<32>(e, poly));
+}
+// approx_log2_exp2_plus_or_minus_one(q, x, sign, q_x, Int(16)): sign = 1 approx_log2p1_exp2, sign = -1 approx_log2m1_exp2
+template<int CW>
+__host__ __device__ inline int32_t approx_log2pm1_exp2(int q, int32_t x, int sign, int32_t q_x) {
+    const int32_t one_plus = wrap<32>((int64_t)sign * 65536 + approx_exp2_q16<CW>(x, q_x));
+    const int32_t raw = approx_log2<16>(q, one_plus, 16);
+    const int32_t line = sat<16>(rounding_shift_right(x, wrap<16>((int64_t)wrap<16>(q_x) - q)));   // the widened x: an i32 shift
+    return shr<CW>(x, q_x) < 14 ? raw : line;
+}
+constexpr int LOG2_E_Q14 = 23637;   // lround(1.442695f * 2^14)
+template<int CW>
+__host__ __device__ inline int32_t approx_logistic(int q, int32_t x, int32_t q_x) {
+    const int32_t x2 = mul2x<16>(x, -LOG2_E_Q14);
+    const int32_t log2_d = approx_log2pm1_exp2<CW>(11, x2, 1, wrap<CW>((int64_t)q_x - 1));
+    return approx_exp2<16, 16>(q, wrap<16>(-(int64_t)log2_d), 11);
+}
+template<int CW>
+__host__ __device__ inline int32_t approx_tanh(int q, int32_t x, int32_t q_x) {
+    const int32_t x2 = mul2x<16>(x, LOG2_E_Q14);
+    const int32_t ax = wrap<16>(x2 < 0 ? -(int64_t)x2 : x2), c = wrap<CW>((int64_t)q_x - 2);
+    const int32_t log2_n = approx_log2pm1_exp2<CW>(11, ax, -1, c), log2_d = approx_log2pm1_exp2<CW>(11, ax, 1, c);
+    const int32_t abs_out = approx_exp2<16, 16>(q, wrap<16>((int64_t)log2_n - log2_d), 11);
+    return x2 < 0 ? wrap<16>(-(int64_t)abs_out) : x2 == 0 ? 0 : abs_out;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the Elementwise interpreter
+// elementwise_generator.cpp:165-177: one instruction on i16 slots; a = slot[arg1], s2 = slot[arg2], arg3 and arg4 the i16 immediates.
+// Noop and any code outside 1 .. 10 give 0 (the reference leaves the slot undefined).
+constexpr int EW_MAX_INSTRUCTIONS = 20, EW_INPUTS = 5, EW_SLOTS = EW_INPUTS + EW_MAX_INSTRUCTIONS + 1;
+__host__ __device__ inline int32_t elementwise_op(int op, int32_t a, int32_t s2, int32_t arg3, int32_t arg4) {
+    const int32_t b = wrap<16>((int64_t)s2 + arg3);
+    switch (op) {
+    case 1: return sat<16>((int64_t)a + b);
+    case 2: return sat<16>((int64_t)a - b);
+    case 3: return sat<16>((int64_t)mul2x<16>(a, b) + arg4);
+    case 4: {
+        // i16_sat(rounding_shift_right(widening_mul(a, b), u32(u16(arg4)))): lower_rounding_mul_shift_right's last resort, the only
+        // one open to a run-time count (src/FindIntrinsics.cpp:1568-1575)
+        const uint32_t s = (uint32_t)arg4 & 0xffffu;
+        const int32_t p = a * b;
+        return sat<16>(s == 0 ? p : s > 31 ? 0 : (p >> s) + ((p >> (s - 1)) & 1));
+    }
+    case 5: return rounding_shift_right16(a, b);
+    case 6: return a < b ? a : b;
+    case 7: return a > b ? a : b;
+    case 8: {
+        const int32_t v = a < arg4 ? a : arg4;
+        return v > arg3 ? v : arg3;
+    }
+    case 9: return rounding_shift_right16(approx_logistic<16>(15, a, b), wrap<16>(15 - (int64_t)arg4));
+    case 10: return rounding_shift_right16(approx_tanh<16>(15, a, b), wrap<16>(15 - (int64_t)arg4));
+    default: return 0;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- the ops' element rules

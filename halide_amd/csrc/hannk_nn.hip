@@ -469,41 +469,6 @@ const ArgTable softmax_table("softmax_uint8", {L(in_buf("input", T_U8, 2)), L(sc
                                                L(scalar_i16("output_multiplier")), L(scalar_u16("output_shift")), L(out_buf("output", T_U8, 2))});
 const ArgTable l2_table("l2_normalization_uint8", {L(in_buf("input", T_U8, 2)), L(scalar_u8("input_zero")), L(out_buf("output", T_U8, 2))});
 
-// check_shape for a buffer whose dimension 0 may have any stride (the generator's dim(0).set_stride(Expr())): the same extents and
-// sizes, recorded under the same name, with the stride constraint taken out
-void check_shape_any_stride0(void *uc, const BufArg &a) {
-    halide_dimension_t dims[4];
-    halide_buffer_t copy = *a.buf;
-    const int nd = std::min(a.buf->dimensions, 4);
-    for (int d = 0; d < nd; d++) dims[d] = a.buf->dim[d];
-    if (nd > 0) dims[0].stride = 1;
-    copy.dim = dims;
-    const BufArg b = {a.name, &copy, a.type, a.dims, a.is_output};
-    check_shape(uc, b);
-}
-// the four no_bounds_query ops: an unallocated buffer is checked like any other, its type first (check_type_and_dims would take it
-// for a query and rewrite the type)
-int check_unallocated_types(void *uc, const BufArg *args, int n) {
-    for (int i = 0; i < n; i++)
-        if (!buffer_is_real(args[i].buf) && buf_type_abi(args[i].buf) != args[i].type) {
-            char t0[16], t1[16];
-            return report(uc, halide_error_code_bad_type, "%s buffer %s has type %s but type of the buffer passed in is %s", args[i].is_output ? "Output" : "Input",
-                          args[i].name, type_name(args[i].type, t0), type_name(buf_type_abi(args[i].buf), t1));
-        }
-    return 0;
-}
-// ... and after every other check has passed, its missing host pointer ends the call (asserts_host_non_null): before anything is
-// allocated for it
-int check_unallocated_host(void *uc, const BufArg *args, int n) {
-    for (int i = 0; i < n; i++)
-        if (!buffer_is_real(args[i].buf)) {
-            if (int r = checks_done(uc)) return r;
-            return report(uc, halide_error_code_host_is_null, "%s buffer %s host pointer is null", args[i].is_output ? "Output" : "Input", args[i].name);
-        }
-    return 0;
-}
-long elem_offset(const halide_buffer_t *b, int d, long coord) { return (coord - b->dim[d].min) * (long)b->dim[d].stride; }
-
 // ---------------------------------------------------------------------------------------------------------------- host: pools
 // ---- the plan of a pool call.  Where the input allows dword taps (pointer and x, y, b strides multiples of 4) and the output has a
 // workgroup of quads for every compute unit (POOL_MIN_QUADS, as depthwise_conv_uint8's DW_MIN_THREADS), hannk_pool4.  Below that the one-thread-per-output kernel
@@ -834,7 +799,7 @@ int hlmi::hannk_nn_general(const char *name, void **argv) {
     if (!strcmp(name, "mul_uint8_uint8_uint8")) return argv_call(mul_entry<true>, argv);
     if (!strcmp(name, "softmax_uint8")) return argv_call(softmax_entry<true>, argv);
     if (!strcmp(name, "l2_normalization_uint8")) return argv_call(l2_entry<true>, argv);
-    return -1;
+    return hannk_program_general(name, argv);   // the elementwise programs, copy, fill and upsample_channels
 }
 
 // x, out: host pointers to n elements.  One launch.

@@ -477,7 +477,7 @@ extern "C" int hlmi_debug_resnet50_maxpool(halide_buffer_t *input, int32_t k, in
 extern "C" int hlmi_debug_resnet50_tail(halide_buffer_t *input, halide_buffer_t *fc_weights, halide_buffer_t *fc_bias, halide_buffer_t *output);
 
 // hannk_conv.hip: the named entry point of apps/hannk's op library ("tile_conv_filter_uint8", "conv_u8_u8_u8", "conv_u8_u8_i16",
-// "depthwise_conv_uint8", "depthwise_conv_broadcast_uint8") in argv form with one thread per output running the contract's loops as
+// "depthwise_conv_uint8", "depthwise_conv_broadcast_uint8", "depthwise_conv_shallow_uint8") in argv form with one thread per output running the contract's loops as
 // written, for the tests (default == general byte for byte) and for bench_apps.py.  -1 for an unknown name.  Per call: no mode is
 // kept anywhere.
 extern "C" int hlmi_hannk_general(const char *name, void **argv);
@@ -498,6 +498,16 @@ HLMI_LOCAL int hannk_nn_general(const char *name, void **argv);
 // fn 0 = approx_log2(q, x, q_x, Int(bits)), 1 = approx_exp2(q, x, q_x, Int(bits)) of an i32 x, 2 = approx_reciprocal(q, x, Int(bits)),
 // 3 = approx_reciprocal_sqrt(q, x, Int(bits)); bits is 16 or 32; out: int32_t[n].  Returns 0, -1 = bad argument, < -1 = HIP error.
 extern "C" int hlmi_debug_hannk_approx(int fn, int32_t q, const int32_t *x, size_t n, int32_t q_x, int32_t bits, int32_t *out);
+
+// hannk_program.hip: the elementwise programs and the data movers ("elementwise_5xuint8_1xuint8", "elementwise_5xint16_1xuint8int16",
+// "copy_uint8_uint8", "fill_uint8", "upsample_channels_uint8") with one thread per output: what hannk_nn_general forwards the names it
+// does not know to.  -1 for an unknown name.
+HLMI_LOCAL int hannk_program_general(const char *name, void **argv);
+// hannk_program.hip, test hook: the device's approx_log2p1_exp2 (fn 0), approx_log2m1_exp2 (1), approx_logistic (2) and approx_tanh (3)
+// of hannk_math.h in Int(16), over host arrays of n elements: x the i16 argument, q the result's precision, q_x the argument's, each as
+// int32; width 16 or 32 is the width of the count q_x; out: int32_t[n].  One launch.  Returns 0, -1 = bad argument,
+// < -1 = HIP error.
+extern "C" int hlmi_debug_hannk_program_approx(int fn, const int32_t *x, const int32_t *q, const int32_t *q_x, size_t n, int32_t width, int32_t *out);
 
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;

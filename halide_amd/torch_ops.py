@@ -1024,3 +1024,120 @@ def _(input, in_scale, beta, out_scale, out_zero, axis):
 @hannk_l2_normalization.register_fake
 def _(input, input_zero, axis):
     return torch.empty_like(input)
+
+
+# apps/hannk's elementwise programs, pad and upsample_channels: uint8 (int16 for the LSTM program) tensors, the programs
+# built on the host as the interpreter builds them (hl.hannk_*_program, hl.ElementwiseAssembler).
+def _hannk_program_call(name, inputs, program):
+    if not 1 <= len(inputs) <= 5:
+        raise RuntimeError(f"{name}: one to five inputs")
+    dtype = inputs[0].dtype
+    if dtype not in (torch.uint8, torch.int16) or any(t.dtype != dtype for t in inputs):
+        raise TypeError(f"{name}: the inputs are all uint8 or all int16")
+    shape = torch.broadcast_shapes(*[t.shape for t in inputs])
+    n = shape[-1] if len(shape) else 1
+    rows = [t.broadcast_to(shape).contiguous().reshape(-1, n) for t in inputs]
+    prog = hl.Buffer(np.ascontiguousarray(program.detach().cpu().numpy(), np.int16).reshape(-1, 5))
+    outs = [torch.empty_like(rows[0], dtype=torch.uint8)] + ([torch.empty_like(rows[0])] if dtype == torch.int16 else [])
+    with _Wrapped(*rows, *outs) as bufs:
+        ins = bufs[:len(rows)] + [bufs[len(rows) - 1]] * (5 - len(rows))
+        (hl.elementwise_5xint16_1xuint8int16 if dtype == torch.int16 else hl.elementwise_5xuint8_1xuint8)(*ins, prog, *bufs[len(rows):])
+    return [o.reshape(shape) for o in outs]
+
+
+@torch.library.custom_op("hlmi::hannk_elementwise", mutates_args=())
+def hannk_elementwise(inputs: list[torch.Tensor], program: torch.Tensor) -> list[torch.Tensor]:
+    """ElementwiseProgramOp: one to five uint8 tensors -> [uint8]; one to five int16 tensors -> [uint8, int16]; program an (n, 5) int16
+    tensor (hl.ElementwiseAssembler), read on the host."""
+    return _hannk_program_call("hannk_elementwise", inputs, program)
+
+
+@torch.library.custom_op("hlmi::hannk_logistic", mutates_args=())
+def hannk_logistic(input: torch.Tensor, in_scale: float, in_zero: int) -> torch.Tensor:
+    """UnaryOp Logistic: uint8 -> uint8 with scale 1 / 256 and zero point 0"""
+    _hannk_check("hannk_logistic", input)
+    return _hannk_program_call("hannk_logistic", [input], torch.from_numpy(hl.hannk_logistic_program(in_scale, in_zero)))[0]
+
+
+@torch.library.custom_op("hlmi::hannk_tanh", mutates_args=())
+def hannk_tanh(input: torch.Tensor, in_scale: float, in_zero: int) -> torch.Tensor:
+    """UnaryOp Tanh: uint8 -> uint8 with scale 1 / 128 and zero point 128"""
+    _hannk_check("hannk_tanh", input)
+    return _hannk_program_call("hannk_tanh", [input], torch.from_numpy(hl.hannk_tanh_program(in_scale, in_zero)))[0]
+
+
+def _hannk_pad_shape(input, padding):
+    if input.dim() != 4 or len(padding) != 8 or any(p < 0 for p in padding):
+        raise RuntimeError("hannk_pad: a (B, H, W, C) tensor and eight paddings >= 0: (before, after) of B, H, W, C")
+    return tuple(input.shape[a] + padding[2 * a] + padding[2 * a + 1] for a in range(4))
+
+
+@torch.library.custom_op("hlmi::hannk_pad", mutates_args=())
+def hannk_pad(input: torch.Tensor, padding: list[int], pad_value: int) -> torch.Tensor:
+    """PadOp: (B, H, W, C) uint8, `padding` = (before, after) of B, H, W, C: the borders by fill_uint8, the rest by one copy_uint8_uint8
+    (which pads the channel itself where 3 channels become 4)"""
+    _hannk_check("hannk_pad", input)
+    out = torch.empty(_hannk_pad_shape(input, padding), dtype=torch.uint8, device=input.device)
+    src = input.contiguous()
+    imin = [padding[2 * (3 - d)] for d in range(4)]            # Halide dimension d is axis 3 - d
+    imax = [imin[d] + src.shape[3 - d] - 1 for d in range(4)]
+    omin, omax = [0] * 4, [out.shape[3 - d] - 1 for d in range(4)]
+
+    def on_crop(call):
+        view = out[tuple(slice(omin[3 - ax], omax[3 - ax] + 1) for ax in range(4))]
+        with _Wrapped(src, view) as (a, o):
+            a.set_min(*imin)
+            o.set_min(*omin)
+            call(a, o)
+
+    fill_min_dim = 1 if src.shape[3] == 3 and out.shape[3] == 4 else 0
+    for d in range(3, fill_min_dim - 1, -1):
+        lo, hi = omin[d], omax[d]
+        if lo < imin[d]:
+            omin[d], omax[d] = lo, imin[d] - 1
+            on_crop(lambda a, o: hl.fill_uint8(pad_value, o))
+        if hi > imax[d]:
+            omin[d], omax[d] = imax[d] + 1, hi
+            on_crop(lambda a, o: hl.fill_uint8(pad_value, o))
+        omin[d], omax[d] = max(lo, imin[d]), min(hi, imax[d])
+    on_crop(lambda a, o: hl.copy_uint8_uint8(a, pad_value, o))
+    return out
+
+
+@torch.library.custom_op("hlmi::hannk_upsample_channels", mutates_args=())
+def hannk_upsample_channels(input: torch.Tensor, factor: int) -> torch.Tensor:
+    """(B, H, W, C) uint8 -> (B, H, W, C * factor): channel c of the result is channel c // factor of the input"""
+    _hannk_check("hannk_upsample_channels", input)
+    if input.dim() != 4 or factor < 1:
+        raise RuntimeError("hannk_upsample_channels: a (B, H, W, C) tensor and a factor >= 1")
+    out = torch.empty(tuple(input.shape[:3]) + (input.shape[3] * factor,), dtype=torch.uint8, device=input.device)
+    with _Wrapped(input.contiguous(), out) as (a, o):
+        hl.upsample_channels_uint8(a, factor, o)
+    return out
+
+
+@hannk_elementwise.register_fake
+def _(inputs, program):
+    shape = torch.broadcast_shapes(*[t.shape for t in inputs])
+    outs = [inputs[0].new_empty(shape, dtype=torch.uint8)]
+    return outs + ([inputs[0].new_empty(shape, dtype=torch.int16)] if inputs[0].dtype == torch.int16 else [])
+
+
+@hannk_logistic.register_fake
+def _(input, in_scale, in_zero):
+    return torch.empty_like(input)
+
+
+@hannk_tanh.register_fake
+def _(input, in_scale, in_zero):
+    return torch.empty_like(input)
+
+
+@hannk_pad.register_fake
+def _(input, padding, pad_value):
+    return input.new_empty(_hannk_pad_shape(input, padding))
+
+
+@hannk_upsample_channels.register_fake
+def _(input, factor):
+    return input.new_empty(tuple(input.shape[:3]) + (input.shape[3] * factor,))
