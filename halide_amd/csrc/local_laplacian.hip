@@ -2435,260 +2435,24 @@ struct Up0HArgs {
 constexpr int U0H_PF = 4;      // rows in flight per wave
 constexpr int U0H_T2 = 68;     // row stride of the level-2 tile
 // EM1: plane 0 of level 1 holds outLPyramid[1] (ll_down01e<.., EM1>); phase 1 is one load per tile value (needs fuse2)
+// ROWS1 (with EM1 and fuse2 only; the kernel ll_up0r): no level-1 tile.  outGPyramid[1] of a coarse row is formed in the row loop, in
+// registers, when a wave's output rows reach it — a lane makes its own coarse column from the stored outLPyramid[1] value (requested
+// with the frame rows) and four taps of the level-2 tile, and takes the columns beside it from the lanes beside it (one wave shift
+// each, with bound_ctrl off: lanes 0 and 63 keep `old`, their outer column, which the wave formed for all its coarse rows beforehand
+// into a few floats of LDS of its own).  The horizontal lerps of a coarse row are formed once and kept for the four output rows
+// that use them.  Phase 1, its barrier and U0_TS x (RU + 2) floats of LDS go; every operation and operand stays.
+// The body is local_laplacian_up0h_body.h, shared as text (see there).
 template<bool NT, bool EM1, int CH = 2>  // CH: tile values a thread requests at a time in the two tile phases (1: 102.0, 2: 101.1, 4: 102.4 us per
                                          // frame on one stream — 4 costs occupancy: 124 VGPRs against 66)
 __global__ __launch_bounds__(256) void ll_up0h(Up0HArgs ph, Geometry gm) {
-    const Up0Args &p = ph.u;
-    LL_RESIDENCY(1);
-    extern __shared__ float s_out1[];
-    // tiles in row-major order, a contiguous run of them per XCD (blocks are dealt round-robin over the 8 XCDs): a tile's
-    // 130 x (RU + 2) coarse window overlaps its neighbours' by two columns / rows, and its 130-float rows start one float before a
-    // 512-byte boundary — 6 lines for 4 of payload, the outer two shared with the neighbour tile: same L2 now (131.5 -> 118.1 MB
-    // fetched per 4K frame)
-    int bx, by;
-    {
-        const int b = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x, nb8 = (int)(gridDim.x * gridDim.y) >> 3;
-        const int lb = b < (nb8 << 3) ? (b & 7) * nb8 + (b >> 3) : b;
-        by = lb / (int)gridDim.x, bx = lb - by * (int)gridDim.x;
-    }
-    const int X0 = p.ox0 + bx * 256;                       // even
-    const int Yw0 = p.oy0 + by * (2 * p.RU);
-    const int Yw1 = min(Yw0 + 2 * p.RU, p.oy0 + p.oh) - 1;
-    const int cx0 = (X0 >> 1) - 1, cy0 = dev::fdiv2(Yw0 - 1);
-    const int th = dev::fdiv2(Yw1 + 1) - cy0 + 1;
-    float *const s_out2 = s_out1 + U0_TS * (p.RU + 2);
-    const int cx1 = min(cx0 + U0_TW - 1, p.rx1_1);                               // last level-1 column of the tile
-    const int c2x0 = dev::fdiv2(cx0 - 1), c2y0 = dev::fdiv2(cy0 - 1);             // level-2 window the level-1 tile's upsampling reads
-    // The two tile phases below are each a handful of values per thread, and a value takes two DEPENDENT memory round trips
-    // (inGPyramid -> which planes -> their bilinear taps).  As per-element loops they ran those trips element after element — and
-    // every workgroup of the launch (one round of resident workgroups) sat in that prologue at the same time, the memory system idle.
-    // Round 5: CH elements per thread at a time, all first loads, then all gathers, then the arithmetic (outl_value's and up_at's
-    // operations in their order): two trips per chunk.  Worth ~1 % of the frame: the resident workgroups of a CU already interleave
-    // their prologues.  Every load is `uniform base + 32-bit byte offset` (the workspace offsets of this path are < 4 GB): as
-    // 64-bit element indices the address arithmetic was 60 % of the 148 VALU instructions a tile value cost, and the tile values
-    // 45 % of the launch's instructions.
-    // The four taps of an upsampled value are f(yb, xb), f(yb, xb + 1) and the same pair one row on (fdiv2(v + 1) = fdiv2(v - 1) + 1):
-    // two unaligned 8-byte loads from two byte offsets.  Rows are numbered from the tile's first one, so every row x stride product
-    // is (small) x (stride < 2^24, the host checks) = one full-rate v_mul_u32_u24 on top of a scalar base; e / tile width is a
-    // multiplication by ceil(2^22 / width), exact while e x width < 2^22 (130 x 302 rows x 130 at the largest tile LDS can hold).
-    struct Taps32 {
-        uint32_t b, a;             // byte offsets of f(yb, xb) and f(yb + 1, xb) inside a plane
-    };
-    auto mul24 = [](uint32_t a, uint32_t b) { return (uint32_t)__umul24(a, b); };
-    auto tap_bytes = [&](uint32_t row0, int y0, int lox, int ws, int X, int Y) {   // row0 = (y0 - loy) * ws (uniform), y0 <= fdiv2(Y - 1)
-        Taps32 t;
-        t.b = (row0 + mul24((uint32_t)(dev::fdiv2(Y - 1) - y0), (uint32_t)ws) + (uint32_t)(dev::fdiv2(X - 1) - lox)) << 2;
-        t.a = t.b + ((uint32_t)ws << 2);
-        return t;
-    };
-    auto taps_at = [](const float *base, uint32_t plane_bytes, const Taps32 &t) {
-        const F2U lo = ld_su<F2U>(base, plane_bytes + t.b), hi = ld_su<F2U>(base, plane_bytes + t.a);
-        UpTaps r;
-        r.bb = lo.x, r.ba = lo.y, r.ab = hi.x, r.aa = hi.y;
-        return r;
-    };
-    const uint32_t ps1b = (uint32_t)p.ps1 * 4u, ps2b = (uint32_t)p.ps2 * 4u, ps3b = (uint32_t)ph.ps3 * 4u;
-    if (ph.fuse2) {
-        const int n2x = dev::fdiv2(cx1 + 1) - c2x0 + 1, n2y = dev::fdiv2(cy0 + th) - c2y0 + 1, n2 = n2x * n2y;
-        const uint32_t m2 = (4194304u + (uint32_t)n2x - 1u) / (uint32_t)n2x;
-        const int c3y0 = dev::fdiv2(c2y0 - 1);
-        const uint32_t row2 = (uint32_t)((c2y0 - p.loy2) * p.ws2), row3 = (uint32_t)((c3y0 - ph.loy3) * ph.ws3);
-        for (int e0 = threadIdx.x; e0 < n2; e0 += 256 * CH) {
-            int X2[CH], Y2[CH];
-            uint32_t ti[CH];
-            bool ok[CH];
-            uint32_t ob[CH];
-            Taps32 t3[CH];
-            float inG[CH], lf[CH], ga[CH], gb[CH];
-            UpTaps o3[CH], t0[CH], t1[CH];
-#pragma unroll
-            for (int i = 0; i < CH; i++) {
-                const int e = e0 + 256 * i;
-                const uint32_t ec = (uint32_t)min(e, n2 - 1), ty = mul24(ec, m2) >> 22, tx = ec - mul24(ty, (uint32_t)n2x);
-                ok[i] = e < n2, ti[i] = mul24(ty, U0H_T2) + tx;
-                X2[i] = c2x0 + (int)tx, Y2[i] = c2y0 + (int)ty;
-                ob[i] = (row2 + mul24(ty, (uint32_t)p.ws2) + (uint32_t)(X2[i] - p.lox2)) << 2;
-                inG[i] = ld_su<float>(p.g2, (uint32_t)gm.K * ps2b + ob[i]);
-                t3[i] = tap_bytes(row3, c3y0, ph.lox3, ph.ws3, X2[i], Y2[i]);
-                o3[i] = taps_at(ph.out3, 0u, t3[i]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < CH; i++) {
-                const float level = inG[i] * gm.Km1;
-                const int li = dev::clampi((int)level, 0, gm.K - 2);
-                lf[i] = level - (float)li;
-                ga[i] = ld_su<float>(p.g2, (uint32_t)li * ps2b + ob[i]), gb[i] = ld_su<float>(p.g2, (uint32_t)(li + 1) * ps2b + ob[i]);
-                t0[i] = taps_at(ph.g3, (uint32_t)li * ps3b, t3[i]);
-                t1[i] = taps_at(ph.g3, (uint32_t)(li + 1) * ps3b, t3[i]);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < CH; i++) {
-                // outGPyramid[2] = upsample(outGPyramid[3]) + outLPyramid[2]   (:76-79), exactly as ll_up computes it
-                const float l0 = ga[i] - up_from(t0[i], X2[i], Y2[i]), l1 = gb[i] - up_from(t1[i], X2[i], Y2[i]);
-                const float outL = dev::mad2(1.0f - lf[i], l0, lf[i], l1);
-                if (ok[i]) s_out2[ti[i]] = up_from(o3[i], X2[i], Y2[i]) + outL;
-            }
-        }
-        __syncthreads();
-    }
-    {
-        const int n1 = U0_TW * th;
-        constexpr uint32_t M1 = (4194304u + U0_TW - 1) / U0_TW;
-        const uint32_t row1 = (uint32_t)((cy0 - p.loy1) * p.ws1), row2 = (uint32_t)((c2y0 - p.loy2) * p.ws2);
-        if constexpr (EM1) {
-            for (int e0 = threadIdx.x; e0 < n1; e0 += 256 * CH) {
-                // outGPyramid[1] = upsample(outGPyramid[2]) + outLPyramid[1]   (:76-79): the stored value and up_at on the LDS tile
-                int cx[CH], cy[CH];
-                uint32_t ti[CH];
-                bool ok[CH];
-                float outL[CH];
-#pragma unroll
-                for (int i = 0; i < CH; i++) {
-                    const int e = e0 + 256 * i;
-                    const uint32_t ec = (uint32_t)min(e, n1 - 1), ty = mul24(ec, M1) >> 22, tx = ec - mul24(ty, U0_TW);
-                    ok[i] = e < n1 && cx0 + (int)tx <= p.rx1_1, ti[i] = mul24(ty, U0_TS) + tx;
-                    cx[i] = min(cx0 + (int)tx, p.rx1_1), cy[i] = cy0 + (int)ty;
-                    outL[i] = ld_su<float>(p.g1, (row1 + mul24(ty, (uint32_t)p.ws1) + (uint32_t)(cx[i] - p.lox1)) << 2);
-                }
-#pragma unroll
-                for (int i = 0; i < CH; i++) {
-                    const float *q = s_out2 + mul24((uint32_t)(dev::fdiv2(cy[i] - 1) - c2y0), U0H_T2) + (uint32_t)(dev::fdiv2(cx[i] - 1) - c2x0);
-                    UpTaps t;
-                    t.bb = q[0], t.ba = q[1], t.ab = q[U0H_T2], t.aa = q[U0H_T2 + 1];
-                    if (ok[i]) s_out1[ti[i]] = up_from(t, cx[i], cy[i]) + outL[i];
-                }
-            }
-        } else {
-            for (int e0 = threadIdx.x; e0 < n1; e0 += 256 * CH) {
-                int cx[CH], cy[CH];
-                uint32_t ti[CH];
-                bool ok[CH];
-                Taps32 t2[CH];
-                float inG[CH], lf[CH], ga[CH], gb[CH];
-                UpTaps o2[CH], t0[CH], t1[CH];
-#pragma unroll
-                for (int i = 0; i < CH; i++) {
-                    const int e = e0 + 256 * i;
-                    const uint32_t ec = (uint32_t)min(e, n1 - 1), ty = mul24(ec, M1) >> 22, tx = ec - mul24(ty, U0_TW);
-                    ok[i] = e < n1 && cx0 + (int)tx <= p.rx1_1, ti[i] = mul24(ty, U0_TS) + tx;
-                    cx[i] = min(cx0 + (int)tx, p.rx1_1), cy[i] = cy0 + (int)ty;      // columns right of R_1 are not tile values: their threads re-read its last one
-                    const uint32_t ob = (row1 + mul24(ty, (uint32_t)p.ws1) + (uint32_t)(cx[i] - p.lox1)) << 2;
-                    // level 1 as ll_down01e stored it: plane 0 / 1 = gPyramid[1](., ., li / li + 1) of the pixel's own li, plane K = inGPyramid[1]
-                    inG[i] = ld_su<float>(p.g1, (uint32_t)gm.K * ps1b + ob), ga[i] = ld_su<float>(p.g1, ob), gb[i] = ld_su<float>(p.g1, ps1b + ob);
-                    t2[i] = tap_bytes(row2, c2y0, p.lox2, p.ws2, cx[i], cy[i]);
-                    if (!ph.fuse2) o2[i] = taps_at(p.out2, 0u, t2[i]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < CH; i++) {
-                    const float level = inG[i] * gm.Km1;
-                    const int li = dev::clampi((int)level, 0, gm.K - 2);
-                    lf[i] = level - (float)li;
-                    t0[i] = taps_at(p.g2, (uint32_t)li * ps2b, t2[i]);
-                    t1[i] = taps_at(p.g2, (uint32_t)(li + 1) * ps2b, t2[i]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int i = 0; i < CH; i++) {
-                    // outGPyramid[1] = upsample(outGPyramid[2]) + outLPyramid[1]   (:76-79), exactly as ll_up computes it
-                    const float l0 = ga[i] - up_from(t0[i], cx[i], cy[i]), l1 = gb[i] - up_from(t1[i], cx[i], cy[i]);
-                    const float outL = dev::mad2(1.0f - lf[i], l0, lf[i], l1);
-                    float up2;
-                    if (ph.fuse2) {   // up_at on the LDS tile: the same taps, weights and lerps
-                        const float *q = s_out2 + mul24((uint32_t)(dev::fdiv2(cy[i] - 1) - c2y0), U0H_T2) + (uint32_t)(dev::fdiv2(cx[i] - 1) - c2x0);
-                        UpTaps t;
-                        t.bb = q[0], t.ba = q[1], t.ab = q[U0H_T2], t.aa = q[U0H_T2 + 1];
-                        up2 = up_from(t, cx[i], cy[i]);
-                    } else {
-                        up2 = up_from(o2[i], cx[i], cy[i]);
-                    }
-                    if (ok[i]) s_out1[ti[i]] = up2 + outL;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int x = bx * 256 + (wave & 1) * 128 + 2 * lane;  // output storage column of the lane's pair
-    const int y0 = by * (2 * p.RU) + (wave >> 1) * p.RU;
-    if (y0 >= p.oh || x >= p.ow) return;
-    const int y1 = min(y0 + p.RU, p.oh);
-    const int X = p.ox0 + x;                                              // even
-    uint32_t inb = (uint32_t)(X - gm.ix0) * 2u, outb = (uint32_t)x * 2u, l0b = (uint32_t)(X - gm.ix0) * 4u;
-    // fma canon: the contracted product is the one with `zero` (dev::mad2) — f[c] * 3/4 for even X, f[c+1] * 1/4 for odd X
-    auto hl0 = [](float rm, float r0) {   // lerp(f[c], f[c-1], 1/4): X even
-        return dev::CANON_FMA ? __builtin_fmaf(r0, 0.75f, rm * 0.25f) : __builtin_fmaf(rm, 0.25f, r0 * 0.75f);
-    };
-    auto hl1 = [](float r0, float rp) { return __builtin_fmaf(rp, 0.25f, r0 * 0.75f); };  // lerp(f[c+1], f[c], 3/4): X odd
-    auto vl = [](float uq, float ut, float wq, float wt) {   // as in ll_up0f
-        return dev::CANON_FMA ? __builtin_fmaf(uq, wq, ut * wt) : __builtin_fmaf(uq, 0.25f, ut * 0.75f);
-    };
-    struct Frame {
-        ushort2 c0, c1, c2;
-        float2 l0;
-    };
-    // The lane's byte offsets are loop invariants: hoisted out of the row loop as 64-bit values they cost a v_lshl_add_u64 per load
-    // and store (7 per row); redefined in place per use (an empty asm) they stay 32-bit and every access is `row base in SGPRs +
-    // VGPR offset`.
-    auto fresh = [](uint32_t &v) {
-        asm volatile("" : "+v"(v));
-        return v;
-    };
-    auto load_frame = [&](int y, Frame &f) {
-        const int yc = min(y, y1 - 1);
-        const uint16_t *irow = p.in + (long)(p.oy0 + yc - gm.iy0) * p.in_sy;
-        const uint32_t ib = fresh(inb);
-        f.c0 = ld_frame2<NT>(irow + p.gco[0], ib), f.c1 = ld_frame2<NT>(irow + p.gco[1], ib), f.c2 = ld_frame2<NT>(irow + p.gco[2], ib);
-        {
-            const f2 *const lp = reinterpret_cast<const f2 *>(reinterpret_cast<const char *>(ph.outl0 + (size_t)yc * ph.l0_ws) + fresh(l0b));
-            const f2 v = NT ? __builtin_nontemporal_load(lp) : *lp;
-            f.l0 = make_float2(v.x, v.y);
-        }
-    };
-    auto finish = [&](int y, const Frame &f) {
-        const int Y = p.oy0 + min(y, y1 - 1);
-        const int ya = dev::fdiv2(Y + 1), yb = dev::fdiv2(Y - 1);
-        const bool yodd = dev::fmod2(Y) != 0;  // wave-uniform
-        // q: the coarse row whose weight is 1/4; fma canon: q = row ya (`zero`), t = row yb (`one`) with weights wq, wt (see ll_up0f)
-        const int yq = (dev::CANON_FMA || yodd) ? ya : yb, yt = (dev::CANON_FMA || yodd) ? yb : ya;
-        const float wq = yodd ? 0.25f : 0.75f, wt = yodd ? 0.75f : 0.25f;
-        const float *oa = s_out1 + (yq - cy0) * U0_TS + (wave & 1) * 64 + lane;
-        const float *ob = s_out1 + (yt - cy0) * U0_TS + (wave & 1) * 64 + lane;
-        const float ax = oa[0], ay = oa[1], az = oa[2], bx = ob[0], by = ob[1], bz = ob[2];
-        const float uo[2] = {vl(hl0(ax, ay), hl0(bx, by), wq, wt), vl(hl1(ay, az), hl1(by, bz), wq, wt)};
-        const float outL[2] = {f.l0.x, f.l0.y};
-        const uint16_t ch[3][2] = {{f.c0.x, f.c0.y}, {f.c1.x, f.c1.y}, {f.c2.x, f.c2.y}};
-        uint16_t res[3][2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const float gray = gray_from(ch[0][i], ch[1][i], ch[2][i]);
-            const float og = (uo[i] + outL[i]) + 0.01f;
-            const float gr = gray + 0.01f;
-            const float n[3] = {(float)ch[0][i] * og, (float)ch[1][i] * og, (float)ch[2][i] * og};
-            float q[3];
-            div3_by(n, gr, q);
-#pragma unroll
-            for (int c = 0; c < 3; c++) res[c][i] = (uint16_t)__builtin_amdgcn_fmed3f(q[c], 0.0f, 65535.0f);  // q is never NaN
-        }
-        if (y < y1) {
-            uint16_t *orow = p.out + (long)y * p.out_sy;
-#pragma unroll
-            for (int c = 0; c < 3; c++) st_frame2<NT>(reinterpret_cast<char *>(orow + (long)c * p.out_sc) + fresh(outb), res[c][0], res[c][1]);
-        }
-    };
-    Frame f[U0H_PF];
-#pragma unroll
-    for (int i = 0; i < U0H_PF; i++) load_frame(y0 + i, f[i]);
-    for (int y = y0; y < y1; y += U0H_PF) {
-#pragma unroll
-        for (int i = 0; i < U0H_PF; i++) {
-            const Frame cur = f[i];
-            load_frame(y + U0H_PF + i, f[i]);
-            finish(y + i, cur);
-        }
-    }
+    constexpr bool ROWS1 = false;
+#include "local_laplacian_up0h_body.h"
+}
+template<bool NT>
+__global__ __launch_bounds__(256) void ll_up0r(Up0HArgs ph, Geometry gm) {
+    constexpr bool EM1 = true, ROWS1 = true;
+    constexpr int CH = 2;
+#include "local_laplacian_up0h_body.h"
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2709,8 +2473,9 @@ const ArgTable ll_table("local_laplacian", {
 //                                                           else none: strips down to level J-1)           test_hip_repeated_calls_follow_new_contents
 //   UPCHAIN_FROM  3 if FUSE_FROM is 4, else 0               first level ll_up_multi collapses (1 .. J-2;   test_hip_pyramid_levels_match_oracle
 //                                                           else FUSE_FROM)
-//   RU            ll_up0h: 32 (EMIT1: 24) on a frame queue, rows per wave of the level-0 kernel            test_hip_emit_launch_geometries_match_oracle
-//                 else 8; fused ll_up0f: 32 / 16; else 8    (clamped to 1 .. 300, dev_clamp_ru)
+//   RU            ll_up0h: 32 (EMIT1: 24; UP1_ROWS: 64) on  rows per wave of the level-0 kernel            test_hip_emit_launch_geometries_match_oracle
+//                 a frame queue, else 8; fused ll_up0f:     (clamped to 1 .. 300, dev_clamp_ru)
+//                 32 / 16; else 8
 //   UNITS0        ll_down01e on a frame queue: 10 x the     resident-wave target of the level-1 kernel     test_hip_fused_levels_1_and_2_match_oracle,
 //                 stream's CUs; otherwise 8 x the device's                                                 test_hip_emit_launch_geometries_match_oracle
 //   NO_VEC        0                                         1: the scalar frame-access kernels only        none
@@ -2724,6 +2489,9 @@ const ArgTable ll_table("local_laplacian", {
 //   EMIT1         on a frame queue where d0.lds + 3 x       ll_down01e stores outLPyramid[1] as ONE plane   tests/test_local_laplacian_outl1.py
 //                 up0_lds <= 160 KB (RU, when unset, is     of level 1 instead of three, ll_up0h adds it
 //                 chosen to fit: 24); otherwise off         (1: on any stream, whatever the budget; 0: off)
+//   UP1_ROWS      on where EMIT1 is on, on a frame queue    ll_up0r: outGPyramid[1] formed in ll_up0h's row   tests/test_local_laplacian_up0_rows.py
+//                 (RU, when unset, is then 64)              loop, in registers, no level-1 tile in LDS
+//                                                           (1: wherever EMIT1 is on; 0: off)
 //   CHAIN_FIT     on where EMIT1 is on and the CU has the   ll_down_strip2 / ll_down_multi / ll_up_multi     tests/test_local_laplacian_chain.py
 //                 LDS left (see ll_plan); otherwise off     instances of at most 56 VGPRs, which fit beside
 //                                                           one ll_down01e and three ll_up0h workgroups
@@ -2731,7 +2499,7 @@ const ArgTable ll_table("local_laplacian", {
 // Compile-time (csrc/Makefile EXTRA): HLMI_LL_CHAIN_PRIO (0) — s_setprio at the top of the three chain kernels; the whole GPU suite
 // runs on such a build through HLMI_LIB.
 struct LlSwitches {
-    std::optional<int> fuse_from, upchain_from, ru, units0, no_vec, emit, nt, fuse_up2, d01_exch, d01_pad_lds, no_lut_cache, emit1, chain_fit;
+    std::optional<int> fuse_from, upchain_from, ru, units0, no_vec, emit, nt, fuse_up2, d01_exch, d01_pad_lds, no_lut_cache, emit1, chain_fit, up1_rows;
 };
 LlSwitches ll_switches() {
     const auto get = env_int;
@@ -2740,7 +2508,7 @@ LlSwitches ll_switches() {
     s.ru = get("HLMI_LL_RU"), s.units0 = get("HLMI_LL_UNITS0"), s.no_vec = get("HLMI_LL_NO_VEC");
     s.emit = get("HLMI_LL_EMIT"), s.nt = get("HLMI_LL_NT"), s.fuse_up2 = get("HLMI_LL_FUSE_UP2");
     s.d01_exch = get("HLMI_LL_D01_EXCH"), s.d01_pad_lds = get("HLMI_LL_D01_PAD_LDS"), s.no_lut_cache = get("HLMI_LL_NO_LUT_CACHE");
-    s.emit1 = get("HLMI_LL_EMIT1"), s.chain_fit = get("HLMI_LL_CHAIN_FIT");
+    s.emit1 = get("HLMI_LL_EMIT1"), s.chain_fit = get("HLMI_LL_CHAIN_FIT"), s.up1_rows = get("HLMI_LL_UP1_ROWS");
     return s;
 }
 
@@ -2774,6 +2542,7 @@ struct LlPlan {
     bool b1;           // beta == 1
     bool fast, fuse1, fuse2, emit, nt;
     bool emit1;        // level 1 is stored as ONE plane, outLPyramid[1] (ll_down01e / ll_up0h <.., EM1>), not as three
+    bool up1_rows;     // ... and ll_up0r adds it in its row loop, in registers: no level-1 tile in LDS (ll_up0h_body<.., ROWS1>)
     bool d01;         // levels 1 and 2 in one walk of the input (ll_down01e / ll_down01f), no ll_down_strip:1
     bool strip2;       // levels 3 and 4 in one launch (ll_down_strip2), no ll_down_strip:2 / :3
     bool chain_fit;    // ll_down_strip2, ll_down_multi and ll_up_multi run their <= 56-VGPR instances
@@ -2932,17 +2701,31 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
     constexpr size_t kCuLds = 160 * 1024, kLdsGranule = 1280;   // gfx950
     constexpr int WPB = D0_THREADS / 64;
     auto lds_alloc = [](size_t bytes) { return (bytes + kLdsGranule - 1) / kLdsGranule * kLdsGranule; };
-    auto up0h_lds = [](int ru) { return sizeof(float) * ((size_t)U0_TS * (ru + 2) + (size_t)U0H_T2 * (ru / 2 + 4)); };
+    // ll_up0h: the level-1 tile and the level-2 tile; ll_up0r (rows1): the level-2 tile and, per wave, both outer columns of its coarse rows
+    auto up0h_lds = [](int ru, bool rows1) {
+        return sizeof(float) * ((rows1 ? (size_t)(256 / 64) * 2 * (ru / 2 + 2) : (size_t)U0_TS * (ru + 2)) + (size_t)U0H_T2 * (ru / 2 + 4));
+    };
     // ll_down01e's LDS: the table, the level-1 -> 2 window state of the four waves and the published rows of three, the EM1 part
     const size_t d01_lds_exch = sizeof(float) * ((nlut + 1) & ~1) + sizeof(float2) * D01_STATE * (2 * WPB - 1);
+    // up1_rows: ll_up0r instead of ll_up0h<.., EM1> — outGPyramid[1] is formed in the row loop, in registers, and the level-1 tile
+    // (131 x (RU + 2) floats, 13.6 of the workgroup's 18 KB at RU 24), the tile phase that fills it and its barrier go; the level-2
+    // tile and 2 x (RU / 2 + 2) floats per wave remain: 6 016 bytes at RU 32, 10 880 at 64.  47 VGPRs, so still three workgroups
+    // beside ll_down01e and a chain workgroup.  With the tile gone RU is free again: four frame queues at 4K, parent's library /
+    // this one with the switch off / on at RU 24 / 32 / 48 / 64, two rounds alternating: 124.4, 124.7 / 124.6, 124.5 / 125.4, 125.5 /
+    // 126.9, 126.4 / 126.6, 126.0 / 128.5, 129.0 Gpx/s (profiles/r26_up1_rows_speed_ab.txt) — 64, where 102 400 + 3 x 11 520 =
+    // 136 960 bytes.  HLMI_LL_UP1_ROWS unset: on where emit1 is on, on a frame queue; 1: wherever emit1 is on; 0: off.
+    constexpr int kRows1Ru = 64;
     pl.emit1 = false;
+    bool rows1 = false;
     {
-        const int e1 = sw.emit1.value_or(-1);
+        const int e1 = sw.emit1.value_or(-1), u1 = sw.up1_rows.value_or(-1);
         if (pl.fuse2 && (e1 > 0 || (e1 < 0 && partitioned && kEmit1Default))) {
+            rows1 = u1 > 0 || (u1 < 0 && partitioned);
             const size_t d0 = lds_alloc(d01_lds_exch + d01_em1_lds_bytes());
-            auto fits = [&](int ru) { return d0 + 3 * lds_alloc(up0h_lds(ru)) <= kCuLds; };
+            auto fits = [&](int ru) { return d0 + 3 * lds_alloc(up0h_lds(ru, rows1)) <= kCuLds; };
             int ru = RU;
             if (partitioned && !sw.ru) {
+                if (rows1) ru = kRows1Ru;
                 ru &= ~3;
                 while (ru > 8 && !fits(ru)) ru -= 4;
             }
@@ -2950,6 +2733,7 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
             if (pl.emit1) RU = ru;
         }
     }
+    pl.up1_rows = pl.emit1 && rows1;
     p.RU = RU;
     // levels 3 and 4 from level 2 in one launch (ll_down_strip2) when the chain would otherwise run ll_down_strip:2 and :3
     // (one stream: 111.6 -> 105.1 us per frame back to back, 123 -> 116.6 for one call + sync; four frame queues 75-77 -> 72-76)
@@ -3021,12 +2805,13 @@ void ll_plan(LlPlan &pl, const halide_buffer_t *input, const halide_buffer_t *ou
     }
     // ll_down_strip: enough waves to fill the chip on the big levels, short strips on the small ones
     pl.units_strip = 16 * device_cus;
-    pl.up0_lds = emit   ? sizeof(float) * ((size_t)U0_TS * (RU + 2) + (size_t)U0H_T2 * (RU / 2 + 4))
+    pl.up0_lds = emit   ? up0h_lds(RU, pl.up1_rows)
                  : fast ? lut_sh + (fuse1 ? ((lut_lds && (nlut & 1)) ? 4 : 0) + sizeof(float) * U0_TS * (RU + 2) : 0)
                         : lut_sh;
     // chain_fit: with frames in flight the three short launches between the two big kernels find their CUs full — one ll_down01e
     // workgroup (312 VGPRs allocated) and three of ll_up0h (3 x 48) leave 512 - 456 = 56 registers per lane, and of the LDS what
-    // d0.lds + 3 x up0_lds leave of 160 KB (3 840 bytes at 4K) — and wait for an ll_up0h workgroup or two to leave first.  Their
+    // d0.lds + 3 x up0_lds leave of 160 KB (4K: 3 840 bytes with ll_up0h<.., EM1> at RU 24, 26 880 with ll_up0r at RU 64) —
+    // and wait for an ll_up0h workgroup or two to leave first.  Their
     // FIT instances keep within 56 VGPRs (no AGPRs, no scratch: `make resources` prints every instance's) by having less in
     // flight at once; the plan picks them where the LDS of ll_down_multi and ll_up_multi fits that rest too.  An unset switch
     // means on where emit1 is on (a frame queue): the stream that owns the device has no such neighbours and keeps the instances
@@ -3277,6 +3062,12 @@ int ll_stage_up0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st)
         ph.u = p, ph.outl0 = b.outl0, ph.l0_ws = gm.ix1 - gm.ix0 + 1;
         ph.fuse2 = pl.fuse2 ? 1 : 0;
         ph.g3 = b.g[3], ph.out3 = b.outg[3], ph.lox3 = lv[3].lox, ph.loy3 = lv[3].loy, ph.ws3 = lv[3].ws, ph.ps3 = lv[3].ps;
+        if (pl.up1_rows) {
+            return with_flags([&](auto NT) -> int {
+                HLMI_LAUNCH(uc, "ll_up0r", st, (ll_up0r<NT.value>), grid, block, pl.up0_lds, ph, gm);
+                return 0;
+            }, pl.nt);
+        }
         return with_flags([&](auto NT, auto E1) -> int {
             HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0h<NT.value, E1.value>), grid, block, pl.up0_lds, ph, gm);
             return 0;
