@@ -1860,6 +1860,178 @@ def hannk_upsample_channels(input, factor) -> np.ndarray:
     return out.numpy()
 
 
+# apps/hannk's data movement: what the interpreter does with Buffer::copy_from on re-viewed buffers, and GatherOp.  The two
+# entry points are library extensions (no metadata); the ops below build their views with numpy, whose axes are the Halide dimensions reversed.
+HANNK_MOVE_KERNELS = ("none", "rows", "transposing", "general")
+
+
+def hannk_copy_from(src, dst, general=False) -> int:
+    """Halide::Runtime::Buffer::copy_from: dst's elements inside src's box take src's values.  Two Buffers of the same rank (<= 8) and element
+    size (1, 2, 4, 8 bytes), any strides; `general` forces the one-thread-per-element kernel (hlmi_hannk_general)."""
+    if general:
+        argv = (C.c_void_p * 2)(C.cast(_as_ptr(src), C.c_void_p), C.cast(_as_ptr(dst), C.c_void_p))
+        fn = lib.hlmi_hannk_general
+        fn.restype, fn.argtypes = C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]
+        return _check(fn(b"hannk_copy_from", argv))
+    fn = lib.hlmi_hannk_copy_from
+    fn.restype, fn.argtypes = C.c_int, [_BP, _BP]
+    return _check(fn(_as_ptr(src), _as_ptr(dst)))
+
+
+def hannk_gather_buffers(src, indices, axis, dst) -> int:
+    """GatherOp::execute with batch_dims == 0 on Buffers: `axis` is a Halide dimension of src, indices int32 of rank 0 .. 2, dst of rank
+    src.rank + indices.rank - 1.  An index outside src's dimension leaves its slice of dst unwritten and raises HalideError -8."""
+    fn = lib.hlmi_hannk_gather
+    fn.restype, fn.argtypes = C.c_int, [_BP, _BP, C.c_int, _BP]
+    return _check(fn(_as_ptr(src), _as_ptr(indices), int(axis), _as_ptr(dst)))
+
+
+def debug_hannk_move_plan(src, dst, general=False) -> dict:
+    """What hannk_copy_from's plan chooses for two Buffers (only their types and dimensions are read; no device is needed): the kernel, one
+    of HANNK_MOVE_KERNELS, and the number of dimensions left after dropping extent-1 dimensions and merging."""
+    out = (C.c_int32 * 2)()
+    f = lib.hlmi_debug_hannk_move_plan
+    f.restype, f.argtypes = C.c_int, [_BP, _BP, C.c_int32, C.POINTER(C.c_int32)]
+    rc = f(_as_ptr(src), _as_ptr(dst), int(bool(general)), out)
+    if rc != 0:
+        raise ValueError(f"hlmi_debug_hannk_move_plan: {'dst aliases itself' if rc == -8 else 'bad arguments'}")
+    return {"kernel": HANNK_MOVE_KERNELS[out[0]], "rank": int(out[1])}
+
+
+def _hannk_movable(a):
+    a = np.ascontiguousarray(a)
+    if a.dtype not in _TYPE_OF:
+        raise TypeError(f"unsupported dtype {a.dtype}")
+    return a
+
+
+def _hannk_copy_views(src_view, dst_view, general=False):
+    d = Buffer(dst_view)
+    hannk_copy_from(Buffer(src_view), d, general)
+    d.numpy()
+
+
+def hannk_transpose(input, perm, general=False) -> np.ndarray:
+    """TransposeOp::execute: np.transpose(input, perm) as one copy_from into the output re-viewed in the input's order"""
+    input = _hannk_movable(input)
+    perm = [int(p) for p in perm]
+    if sorted(perm) != list(range(input.ndim)):
+        raise ValueError(f"{perm} is no permutation of {input.ndim} axes")
+    out = np.zeros(tuple(input.shape[p] for p in perm), input.dtype)
+    _hannk_copy_views(input, out.transpose(np.argsort(perm)), general)
+    return out
+
+
+def _hannk_block_views(space, depth, block):
+    """(B, H, W, C) and (B, H / block, W / block, block * block * C) as two rank-6 views of one shape (ops.cpp:1607-1625)"""
+    b, h, w, c = space.shape
+    if block < 1 or h % block or w % block or depth.shape != (b, h // block, w // block, block * block * c):
+        raise ValueError("the block size divides height and width, and depth = block^2 * channels")
+    s6 = space.reshape(b, h // block, block, w // block, block, c)
+    d6 = depth.reshape(b, h // block, w // block, block, block, c).transpose(0, 1, 3, 2, 4, 5)
+    return s6, d6
+
+
+def hannk_space_to_depth(input, block_size, general=False) -> np.ndarray:
+    """SpaceToDepth: (B, H, W, C) -> (B, H / block, W / block, block^2 * C), one copy_from over rank-6 views"""
+    input = _hannk_movable(input)
+    block = int(block_size)
+    if input.ndim != 4 or block < 1 or input.shape[1] % block or input.shape[2] % block:
+        raise ValueError("a (B, H, W, C) array whose height and width the block size divides")
+    b, h, w, c = input.shape
+    out = np.zeros((b, h // block, w // block, block * block * c), input.dtype)
+    s6, d6 = _hannk_block_views(input, out, block)
+    _hannk_copy_views(s6, d6, general)
+    return out
+
+
+def hannk_depth_to_space(input, block_size, general=False) -> np.ndarray:
+    """DepthToSpace: (B, H, W, block^2 * C) -> (B, H * block, W * block, C)"""
+    input = _hannk_movable(input)
+    block = int(block_size)
+    if input.ndim != 4 or block < 1 or input.shape[3] % (block * block):
+        raise ValueError("a (B, H, W, C) array whose channel count the squared block size divides")
+    b, h, w, c = input.shape
+    out = np.zeros((b, h * block, w * block, c // (block * block)), input.dtype)
+    s6, d6 = _hannk_block_views(out, input, block)
+    _hannk_copy_views(d6, s6, general)
+    return out
+
+
+def hannk_requantize(input, q_in, q_out, activation=None) -> np.ndarray:
+    """try_requantize (ops.cpp:487-504) on a uint8 array: add_uint8(in * 1 + in * 0) from q_in = (scale, zero) to q_out"""
+    input = np.ascontiguousarray(input, np.uint8)
+    return hannk_add(input, q_in, input, q_in, q_out, activation, sign2=0)
+
+
+def hannk_concatenation(inputs, axis, quantization=None, general=False) -> np.ndarray:
+    """ConcatenationOp::execute: every input goes into its crop of the output through requantize_or_copy.  `quantization` = [(scale, zero) of
+    each input ..., (scale, zero) of the output] sends uint8 pieces through the add kernel, equal scales or not, as the reference does;
+    without it the pieces are copied."""
+    inputs = [_hannk_movable(a) for a in inputs]
+    nd = inputs[0].ndim
+    axis = int(axis) % nd
+    out = np.zeros(tuple(sum(a.shape[d] for a in inputs) if d == axis else inputs[0].shape[d] for d in range(nd)), inputs[0].dtype)
+    at = 0
+    for i, a in enumerate(inputs):
+        if a.dtype != out.dtype or any(a.shape[d] != out.shape[d] for d in range(nd) if d != axis):
+            raise ValueError("the inputs share dtype and every extent but the axis'")
+        piece = out[tuple(slice(at, at + a.shape[axis]) if d == axis else slice(None) for d in range(nd))]
+        if quantization is not None and out.dtype == np.dtype(np.uint8):
+            piece[...] = hannk_requantize(a, quantization[i], quantization[-1])
+        else:
+            _hannk_copy_views(a, piece, general)
+        at += a.shape[axis]
+    return out
+
+
+def hannk_split(input, sizes, axis, quantization=None, general=False) -> list:
+    """SplitOp::execute: `sizes` an int (that many equal pieces) or the pieces' extents along `axis`; `quantization` = [(scale, zero) of the
+    input, (scale, zero) of each output ...] as for hannk_concatenation."""
+    input = _hannk_movable(input)
+    axis = int(axis) % input.ndim
+    n = input.shape[axis]
+    if np.isscalar(sizes):
+        if int(sizes) < 1 or n % int(sizes):
+            raise ValueError(f"{n} elements do not split into {sizes} equal pieces")
+        sizes = [n // int(sizes)] * int(sizes)
+    sizes = [int(v) for v in sizes]
+    if sum(sizes) != n or any(v < 0 for v in sizes):
+        raise ValueError(f"pieces of {sizes} do not add up to {n}")
+    outs, at = [], 0
+    for i, size in enumerate(sizes):
+        piece = input[tuple(slice(at, at + size) if d == axis else slice(None) for d in range(input.ndim))]
+        if quantization is not None and input.dtype == np.dtype(np.uint8):
+            outs.append(hannk_requantize(piece, quantization[0], quantization[1 + i]))
+        else:
+            out = np.zeros(piece.shape, input.dtype)
+            _hannk_copy_views(piece, out, general)
+            outs.append(out)
+        at += size
+    return outs
+
+
+def hannk_gather(input, indices, axis=0) -> np.ndarray:
+    """GatherOp::execute: np.take(input, indices, axis) for int32 indices of rank 0 .. 2 in one launch"""
+    input = _hannk_movable(input)
+    indices = np.require(indices, np.int32, "C")   # (ascontiguousarray would make a scalar index a vector)
+    axis = int(axis) % input.ndim
+    out = Buffer(np.zeros(input.shape[:axis] + indices.shape + input.shape[axis + 1:], input.dtype))
+    hannk_gather_buffers(Buffer(input), Buffer(indices), input.ndim - 1 - axis, out)
+    return out.numpy()
+
+
+def hannk_fully_connected(input, weights, bias, input_zero, filter_zero, multiplier, shift, output_zero=0, output_min=0, output_max=255) -> np.ndarray:
+    """lower_tflite_fullyconnected: input of any rank flattened to (N, CI), weights (CO, CI) u8, bias int32 (CO,) -> (N, CO): the conv op on
+    a 1 x 1 image"""
+    weights = np.ascontiguousarray(weights, np.uint8)
+    co, ci = weights.shape
+    flat = np.ascontiguousarray(input, np.uint8).reshape(-1, ci)
+    out = hannk_conv2d(flat.reshape(-1, 1, 1, ci), weights.reshape(co, 1, 1, ci), bias, input_zero, filter_zero, 1, 1, 0, multiplier, shift, output_zero,
+                       output_min, output_max)
+    return out.reshape(-1, co)
+
+
 def lens_blur(left_im, right_im, slices, focus_depth, blur_radius_scale, aperture_samples, final) -> int:
     return _check(_fn["lens_blur"](_as_ptr(left_im), _as_ptr(right_im), int(slices), int(focus_depth), float(blur_radius_scale),
                         int(aperture_samples), _as_ptr(final)))

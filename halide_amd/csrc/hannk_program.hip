@@ -783,7 +783,7 @@ int hlmi::hannk_program_general(const char *name, void **argv) {
     if (!strcmp(name, "copy_uint8_uint8")) return argv_call(copy_entry<true>, argv);
     if (!strcmp(name, "fill_uint8")) return argv_call(fill_entry<true>, argv);
     if (!strcmp(name, "upsample_channels_uint8")) return argv_call(upsample_entry<true>, argv);
-    return -1;
+    return hannk_copy_general(name, argv);   // copy_from and gather
 }
 
 // x, q, q_x, out: host pointers to n elements.  One launch.

@@ -509,6 +509,22 @@ HLMI_LOCAL int hannk_program_general(const char *name, void **argv);
 // < -1 = HIP error.
 extern "C" int hlmi_debug_hannk_program_approx(int fn, const int32_t *x, const int32_t *q, const int32_t *q_x, size_t n, int32_t width, int32_t *out);
 
+// hannk_move.hip: the movement the interpreter does with Buffer::copy_from, as library extensions without argument table, _argv or _metadata.
+// hlmi_hannk_copy_from: Halide::Runtime::Buffer::copy_from: same rank (<= 8) and element size (1, 2, 4, 8 bytes), the intersection of the two
+// boxes, any strides on either side.  A dst whose distinct indices share an element through a stride of 0 is refused (-8); no other
+// overlap of dst with itself (strides (1, 1), a row stride below the row's extent) is looked for: such a dst is the caller's error and its
+// elements end up holding any one of the values written to them.  hlmi_hannk_gather: GatherOp::execute with batch_dims == 0, indices int32 of
+// rank 0 .. 2; an index outside the source's dimension `axis` leaves its slice of dst unwritten and the call returns -8.
+extern "C" int hlmi_hannk_copy_from(const halide_buffer_t *src, halide_buffer_t *dst);
+extern "C" int hlmi_hannk_gather(const halide_buffer_t *src, const halide_buffer_t *indices, int axis, halide_buffer_t *dst);
+// "hannk_copy_from" (argv: src, dst) and "hannk_gather" (argv: src, indices, &axis, dst) with one thread per element: what hannk_program_general
+// forwards the names it does not know to.  -1 for an unknown name.
+HLMI_LOCAL int hannk_copy_general(const char *name, void **argv);
+// hannk_move.hip, no device needed: what copy_from's plan chooses for two buffers (only type, dimensions and dim[] are read): out = {kernel:
+// 0 nothing to copy, 1 rows, 2 transposing, 3 general; dimensions left after dropping and merging}.  general != 0: as under hlmi_hannk_general.
+// Returns 0, -1 = bad argument, -8 = dst aliases itself.
+extern "C" int hlmi_debug_hannk_move_plan(const halide_buffer_t *src, const halide_buffer_t *dst, int32_t general, int32_t *out);
+
 inline int floor_div(int a, int b) {  // b > 0 ; Halide integer division rounds toward -inf (src/IR.h:145-166)
     int q = a / b, r = a % b;
     return (r != 0 && r < 0) ? q - 1 : q;

@@ -1141,3 +1141,179 @@ def _(input, padding, pad_value):
 @hannk_upsample_channels.register_fake
 def _(input, factor):
     return input.new_empty(tuple(input.shape[:3]) + (input.shape[3] * factor,))
+
+
+# apps/hannk's data movement: one hlmi_hannk_copy_from over two views of the tensors' memory, or one hlmi_hannk_gather.  Any
+# dtype of 1, 2, 4 or 8 bytes this module wraps; nothing is synchronised except by gather, whose indices are device data (its flag is read back).
+class _Views:
+    """_Wrapped for views: any strides, the innermost included"""
+
+    def __init__(self, *tensors):
+        self.tensors, self.bufs = tensors, []
+
+    def __enter__(self):
+        for t in self.tensors:      # every tensor is checked before any is wrapped: a refusal leaves nothing to detach
+            if not t.is_cuda:
+                raise RuntimeError("hlmi ops need tensors on the GPU (there is no CPU implementation)")
+            if t.dtype not in _NP:
+                raise TypeError(f"unsupported dtype {t.dtype}")
+        for t in self.tensors:
+            self.bufs.append(hl.Buffer.wrap_device(t.data_ptr(), _NP[t.dtype], list(reversed(t.shape)), list(reversed(t.stride()))))
+        s = torch.cuda.current_stream(self.tensors[0].device).cuda_stream
+        hl.set_stream(s if s else 1)
+        hl.set_gpu_device(self.tensors[0].device.index or 0)
+        return self.bufs
+
+    def __exit__(self, *exc):
+        hl.set_stream(None)
+        for b in self.bufs:
+            b.device_detach()
+        return False
+
+
+def _hannk_copy(src_view, dst_view):
+    with _Views(src_view, dst_view) as (s, d):
+        hl.hannk_copy_from(s, d)
+
+
+def _hannk_perm(name, input, perm):
+    perm = [int(p) for p in perm]
+    if sorted(perm) != list(range(input.dim())):
+        raise RuntimeError(f"{name}: {perm} is no permutation of {input.dim()} axes")
+    return perm
+
+
+@torch.library.custom_op("hlmi::hannk_transpose", mutates_args=())
+def hannk_transpose(input: torch.Tensor, perm: list[int]) -> torch.Tensor:
+    """TransposeOp: input.permute(perm) as a dense tensor, one copy_from into the output viewed in the input's order"""
+    perm = _hannk_perm("hannk_transpose", input, perm)
+    out = torch.empty([input.shape[p] for p in perm], dtype=input.dtype, device=input.device)
+    _hannk_copy(input, out.permute([perm.index(a) for a in range(len(perm))]))
+    return out
+
+
+def _hannk_block_shape(name, input, block, to_depth):
+    if input.dim() != 4 or block < 1:
+        raise RuntimeError(f"{name}: a (B, H, W, C) tensor and a block size >= 1")
+    b, h, w, c = input.shape
+    if to_depth:
+        if h % block or w % block:
+            raise RuntimeError(f"{name}: the block size {block} divides neither {h} nor {w}")
+        return (b, h // block, w // block, c * block * block)
+    if c % (block * block):
+        raise RuntimeError(f"{name}: {block}^2 does not divide {c} channels")
+    return (b, h * block, w * block, c // (block * block))
+
+
+def _hannk_block_views(space, depth, block):
+    b, h, w, c = space.shape
+    s6 = space.view(b, h // block, block, w // block, block, c)
+    d6 = depth.view(b, h // block, w // block, block, block, c).permute(0, 1, 3, 2, 4, 5)
+    return s6, d6
+
+
+@torch.library.custom_op("hlmi::hannk_space_to_depth", mutates_args=())
+def hannk_space_to_depth(input: torch.Tensor, block_size: int) -> torch.Tensor:
+    """(B, H, W, C) -> (B, H / block, W / block, block^2 * C)"""
+    out = torch.empty(_hannk_block_shape("hannk_space_to_depth", input, block_size, True), dtype=input.dtype, device=input.device)
+    s6, d6 = _hannk_block_views(input.contiguous(), out, block_size)
+    _hannk_copy(s6, d6)
+    return out
+
+
+@torch.library.custom_op("hlmi::hannk_depth_to_space", mutates_args=())
+def hannk_depth_to_space(input: torch.Tensor, block_size: int) -> torch.Tensor:
+    """(B, H, W, block^2 * C) -> (B, H * block, W * block, C)"""
+    out = torch.empty(_hannk_block_shape("hannk_depth_to_space", input, block_size, False), dtype=input.dtype, device=input.device)
+    s6, d6 = _hannk_block_views(out, input.contiguous(), block_size)
+    _hannk_copy(d6, s6)
+    return out
+
+
+def _hannk_gather_shape(input, indices, axis):
+    if input.dim() < 1 or indices.dim() > 2 or not -input.dim() <= axis < input.dim():
+        raise RuntimeError("hannk_gather: indices of rank 0 .. 2 and an axis of the input")
+    axis %= input.dim()
+    return axis, tuple(input.shape[:axis]) + tuple(indices.shape) + tuple(input.shape[axis + 1:])
+
+
+@torch.library.custom_op("hlmi::hannk_gather", mutates_args=())
+def hannk_gather(input: torch.Tensor, indices: torch.Tensor, axis: int) -> torch.Tensor:
+    """GatherOp: torch.index_select generalised to int32 indices of rank 0 .. 2; an index outside the axis raises (HalideError -8) after the
+    other slices were written.  The one op here that waits for the device: the kernel's out-of-range flag is read back."""
+    if indices.dtype != torch.int32:
+        raise TypeError("hannk_gather: indices are int32")
+    axis, shape = _hannk_gather_shape(input, indices, axis)
+    out = torch.zeros(shape, dtype=input.dtype, device=input.device)
+    with _Views(input, indices, out) as (a, i, o):
+        hl.hannk_gather_buffers(a, i, input.dim() - 1 - axis, o)
+    return out
+
+
+def _hannk_concat_shape(inputs, axis):
+    if not inputs or not -inputs[0].dim() <= axis < inputs[0].dim():
+        raise RuntimeError("hannk_concatenation: at least one input and an axis of it")
+    axis %= inputs[0].dim()
+    first = inputs[0]
+    for t in inputs:
+        if t.dtype != first.dtype or t.dim() != first.dim() or any(t.shape[d] != first.shape[d] for d in range(first.dim()) if d != axis):
+            raise RuntimeError("hannk_concatenation: the inputs share dtype and every extent but the axis'")
+    return axis, tuple(sum(t.shape[d] for t in inputs) if d == axis else first.shape[d] for d in range(first.dim()))
+
+
+@torch.library.custom_op("hlmi::hannk_concatenation", mutates_args=())
+def hannk_concatenation(inputs: list[torch.Tensor], axis: int) -> torch.Tensor:
+    """ConcatenationOp's copying half: every input into its crop of the output, one copy_from each (pieces of different quantisation go
+    through hannk_add first, as hl.hannk_concatenation does)"""
+    axis, shape = _hannk_concat_shape(inputs, axis)
+    out = torch.empty(shape, dtype=inputs[0].dtype, device=inputs[0].device)
+    at = 0
+    for t in inputs:
+        if t.shape[axis]:
+            _hannk_copy(t, out.narrow(axis, at, t.shape[axis]))
+        at += t.shape[axis]
+    return out
+
+
+@torch.library.custom_op("hlmi::hannk_fully_connected", mutates_args=())
+def hannk_fully_connected(input: torch.Tensor, weights: torch.Tensor, bias: torch.Tensor, input_zero: int, filter_zero: int, multiplier: int,
+                          shift: int, output_zero: int, output_min: int, output_max: int) -> torch.Tensor:
+    """lower_tflite_fullyconnected: input of any rank flattened to (N, CI), weights (CO, CI) uint8, bias (CO,) int32 -> (N, CO) uint8: the conv
+    op on a 1 x 1 image"""
+    _hannk_check("hannk_fully_connected", input, weights)
+    if weights.dim() != 2 or input.numel() % weights.shape[1]:
+        raise RuntimeError("hannk_fully_connected: weights are (CO, CI) and CI divides the input")
+    co, ci = weights.shape
+    out = hannk_conv2d(input.reshape(-1, 1, 1, ci), weights.reshape(co, 1, 1, ci), bias, input_zero, filter_zero, [1, 1], [1, 1], [0, 0], multiplier,
+                       shift, output_zero, output_min, output_max, False)
+    return out.reshape(-1, co)
+
+
+@hannk_transpose.register_fake
+def _(input, perm):
+    return input.new_empty([input.shape[p] for p in _hannk_perm("hannk_transpose", input, perm)])
+
+
+@hannk_space_to_depth.register_fake
+def _(input, block_size):
+    return input.new_empty(_hannk_block_shape("hannk_space_to_depth", input, block_size, True))
+
+
+@hannk_depth_to_space.register_fake
+def _(input, block_size):
+    return input.new_empty(_hannk_block_shape("hannk_depth_to_space", input, block_size, False))
+
+
+@hannk_gather.register_fake
+def _(input, indices, axis):
+    return input.new_empty(_hannk_gather_shape(input, indices, axis)[1])
+
+
+@hannk_concatenation.register_fake
+def _(inputs, axis):
+    return inputs[0].new_empty(_hannk_concat_shape(inputs, axis)[1])
+
+
+@hannk_fully_connected.register_fake
+def _(input, weights, bias, input_zero, filter_zero, multiplier, shift, output_zero, output_min, output_max):
+    return input.new_empty((input.numel() // weights.shape[1], weights.shape[0]))
