@@ -7,7 +7,7 @@ is backend-neutral: prepare() / run() issue it on the device, tests/hannk_model_
 plain-C checkers.  `model.tensors` lists the graph's tensors followed by the ones the lowering adds (padded conv inputs, tiled filters,
 programs); one allocation per tensor, no planner, no aliasing except RESHAPE of a dense tensor, which is a view.
 
-Lowering follows interpreter/ops.cpp and lower.cpp; the parameter derivations are the hl.hannk_* helpers'.  Of ConvOp::execute's
+Lowering follows interpreter/ops.cpp and lower.cpp; the parameter derivations are the hannk.hannk_* helpers'.  Of ConvOp::execute's
 reshapes (the x/y fusion of 1 x 1 filters and the x/y swap, ops.cpp:879-898) none is kept: the conv kernels here tile output pixels
 as one flat index, so neither changes which kernel runs.  The shallow depthwise variant is not chosen by the lowering."""
 from __future__ import annotations
@@ -18,6 +18,7 @@ from collections import namedtuple
 import numpy as np
 
 import halide_amd as hl
+from halide_amd import hannk
 from halide_amd import tflite_reader as tfl
 
 View = namedtuple("View", "tensor offset mins extents strides")
@@ -80,21 +81,15 @@ class HannkModel:
     def _rank2(self, i, like=None):
         """tensor i as an [x, y] operand: dimension 0 and everything outside it; against `like` (the full shape) extent-1 dimensions
         are broadcast with a stride of 0, as elementwise_loop_nest<2> does"""
-        shape = list(self.tensors[i].shape)
-        full = list(shape if like is None else like)
-        shape += [1] * (len(full) - len(shape))
-        n0 = full[0] if full else 1
-        rest = int(np.prod(full[1:], dtype=np.int64)) if len(full) > 1 else 1
-        s0 = 1 if (shape[0] if shape else 1) == n0 else 0
-        if s0 == 0 and (shape[0] if shape else 1) != 1:
-            raise NotImplementedError("hannk_model: operands that do not broadcast")
-        if shape[1:] == full[1:]:
-            s1 = shape[0] if shape else 1
-        elif all(e == 1 for e in shape[1:]):
-            s1 = 0
-        else:
+        shape = self.tensors[i].shape[::-1]
+        try:
+            rule = hannk.hannk_rank2_rule(shape, shape if like is None else tuple(like)[::-1])
+        except ValueError:
+            raise NotImplementedError("hannk_model: operands that do not broadcast") from None
+        if rule is None:
             raise NotImplementedError("hannk_model: broadcasting of some but not all outer dimensions")
-        return View(i, 0, (0, 0), (n0, rest), (s0, s1))
+        rows, n, s0, s1 = rule
+        return View(i, 0, (0, 0), (n, rows), (s0, s1))
 
     def _piece(self, i, axis, at, size):
         """the crop [at, at + size) of tensor i along Halide dimension `axis`, as an [x, y] view: the dimensions up to the axis are one row"""
@@ -106,8 +101,8 @@ class HannkModel:
     # ------------------------------------------------------------------------------------------------------------ shared pieces
     def _requant(self, src, qin, dst, qout, activation=None):
         """requantize_or_copy's quantised branch: add_uint8(in * 1 + in * 0)"""
-        m1, m2 = hl.hannk_add_multipliers(qin[0], qin[0], qout[0], 0)
-        lo, hi = hl.hannk_output_range(activation, qout[1], qout[0])
+        m1, m2 = hannk.hannk_add_multipliers(qin[0], qin[0], qout[0], 0)
+        lo, hi = hannk.hannk_output_range(activation, qout[1], qout[0])
         self.plan.append(Step("add_uint8_uint8", (src, qin[1], m1, src, qin[1], m2, qout[1], lo, hi, dst)))
 
     def _move(self, i_src, src, i_dst, dst):
@@ -141,12 +136,12 @@ class HannkModel:
         before, need = [], []
         for k in range(2):
             eff = (filt[k] - 1) * dilation[k] + 1
-            before.append(hl.hannk_compute_padding(attrs["stride"][k], size[k], eff, out[k]) if attrs["padding"] == "same" else 0)
+            before.append(hannk.hannk_compute_padding(attrs["stride"][k], size[k], eff, out[k]) if attrs["padding"] == "same" else 0)
             need.append((out[k] - 1) * attrs["stride"][k] + eff)
         return tuple(before), tuple(need)
 
     def _multiply_params(self, a, b, c):
-        m, e = hl.hannk_int_float(_f32(a) * _f32(b) / _f32(c), 32)
+        m, e = hannk.hannk_int_float(_f32(a) * _f32(b) / _f32(c), 32)
         return m, -e
 
     # ------------------------------------------------------------------------------------------------------------ lowerings
@@ -165,8 +160,8 @@ class HannkModel:
             xin = View(x, 0, (0, 0, 0, 0), (ci, 1, 1, n), (1, ci, ci, ci))
             oview = View(out, 0, (0, 0, 0, 0), (co, 1, 1, n), (1, co, co, co))
             a = {"stride": (1, 1), "dilation": (1, 1), "padding": "valid", "activation": a["activation"]}
-            if ci % hl.HANNK_VECTOR_REDUCTION:
-                p = self._new((_round_up(ci, hl.HANNK_VECTOR_REDUCTION), 1, 1, n))
+            if ci % hannk.HANNK_VECTOR_REDUCTION:
+                p = self._new((_round_up(ci, hannk.HANNK_VECTOR_REDUCTION), 1, 1, n))
                 whole = self._whole(p)
                 self.plan.append(Step("fill_uint8", (zi, whole)))
                 self.plan.append(Step("copy_uint8_uint8", (xin, zi, whole)))
@@ -177,11 +172,11 @@ class HannkModel:
             oview = self._whole(out, 4)
             _, w, h, _ = self._whole(x, 4).extents
             before, need = self._window(a, (w, h), (fw, fh), oview.extents[1:3], a["dilation"])
-            xin = self._padded(x, zi, hl.HANNK_VECTOR_REDUCTION, before, need)
+            xin = self._padded(x, zi, hannk.HANNK_VECTOR_REDUCTION, before, need)
         tiled = self._new((4, 16, -(-ci // 4), -(-co // 16), fw, fh))
         self.setup.append(Step("tile_conv_filter_uint8", (self._whole(f, 4), zf, zf, self._whole(tiled))))
         m, shift = self._multiply_params(si, sf, so)
-        lo, hi = hl.hannk_output_range(a["activation"], zo, so)
+        lo, hi = hannk.hannk_output_range(a["activation"], zo, so)
         self.plan.append(Step("conv_u8_u8_u8", (xin, zi, self._whole(tiled), zf, self._whole(bias), a["stride"][0], a["stride"][1], a["dilation"][0],
                                                 a["dilation"][1], m, shift, zo, lo, hi, oview)))
 
@@ -207,9 +202,9 @@ class HannkModel:
             x = up
         oview = self._whole(out, 4)
         before, need = self._window(a, (w, h), (fw, fh), oview.extents[1:3], a["dilation"])
-        xin = self._padded(x, zi, 1 if broadcast else hl.HANNK_DEPTHWISE_VECTOR, before, need)
+        xin = self._padded(x, zi, 1 if broadcast else hannk.HANNK_DEPTHWISE_VECTOR, before, need)
         m, shift = self._multiply_params(si, sf, so)
-        lo, hi = hl.hannk_output_range(a["activation"], zo, so)
+        lo, hi = hannk.hannk_output_range(a["activation"], zo, so)
         name = "depthwise_conv_broadcast_uint8" if broadcast else "depthwise_conv_uint8"
         self.plan.append(Step(name, (xin, zi, self._whole(f3), zf, self._whole(bias), a["stride"][0], a["stride"][1], a["dilation"][0], a["dilation"][1],
                                      0, m, shift, zo, lo, hi, oview)))
@@ -221,7 +216,7 @@ class HannkModel:
         _, w, h, _ = self._whole(x, 4).extents
         oview = self._whole(out, 4)
         before, _ = self._window(a, (w, h), a["filter"], oview.extents[1:3])
-        lo, hi = hl.hannk_output_range(a["activation"], zo, so)
+        lo, hi = hannk.hannk_output_range(a["activation"], zo, so)
         xin = self._whole(x, 4)._replace(mins=(0, before[0], before[1], 0))
         self.plan.append(Step(name, (xin, a["stride"][0], a["stride"][1], a["filter"][0], a["filter"][1], lo, hi, oview)))
 
@@ -237,12 +232,12 @@ class HannkModel:
         (s1, z1), (s2, z2), (so, zo) = self._q(i1), self._q(i2), self._q(out)
         full = self.tensors[out].shape
         a, b, o = self._rank2(i1, full), self._rank2(i2, full), self._rank2(out)
-        lo, hi = hl.hannk_output_range(op.attrs.get("activation"), zo, so)
+        lo, hi = hannk.hannk_output_range(op.attrs.get("activation"), zo, so)
         if mul:
-            m, shift = hl.hannk_mul_params(s1, s2, so)
+            m, shift = hannk.hannk_mul_params(s1, s2, so)
             self.plan.append(Step("mul_uint8_uint8_uint8", (a, z1, b, z2, zo, m, shift, lo, hi, o)))
         else:
-            m1, m2 = hl.hannk_add_multipliers(s1, s2, so, sign2)
+            m1, m2 = hannk.hannk_add_multipliers(s1, s2, so, sign2)
             self.plan.append(Step("add_uint8_uint8", (a, z1, m1, b, z2, m2, zo, lo, hi, o)))
 
     def _lower_add(self, op):
@@ -256,8 +251,8 @@ class HannkModel:
 
     def _activation(self, op, activation):      # try_requantize with the activation's range
         x, out = op.inputs[0], op.outputs[0]
-        m1, m2 = hl.hannk_add_multipliers(self._q(x)[0], self._q(x)[0], self._q(out)[0], 0)
-        lo, hi = hl.hannk_output_range(activation, self._q(out)[1], self._q(out)[0])
+        m1, m2 = hannk.hannk_add_multipliers(self._q(x)[0], self._q(x)[0], self._q(out)[0], 0)
+        lo, hi = hannk.hannk_output_range(activation, self._q(out)[1], self._q(out)[0])
         v = self._rank2(x)
         self.plan.append(Step("add_uint8_uint8", (v, self._q(x)[1], m1, v, self._q(x)[1], m2, self._q(out)[1], lo, hi, self._rank2(out))))
 
@@ -277,14 +272,14 @@ class HannkModel:
         self.plan.append(Step("elementwise_5xuint8_1xuint8", (v, v, v, v, v, self._whole(p), self._rank2(out))))
 
     def _lower_logistic(self, op):
-        self._program(op, hl.hannk_logistic_program(*self._q(op.inputs[0])))
+        self._program(op, hannk.hannk_logistic_program(*self._q(op.inputs[0])))
 
     def _lower_tanh(self, op):
-        self._program(op, hl.hannk_tanh_program(*self._q(op.inputs[0])))
+        self._program(op, hannk.hannk_tanh_program(*self._q(op.inputs[0])))
 
     def _lower_softmax(self, op):
         x, out = op.inputs[0], op.outputs[0]
-        bm, bs, om, osh = hl.hannk_softmax_params(self._q(x)[0], op.attrs["beta"], self._q(out)[0])
+        bm, bs, om, osh = hannk.hannk_softmax_params(self._q(x)[0], op.attrs["beta"], self._q(out)[0])
         self.plan.append(Step("softmax_uint8", (self._rank2(x), bm, bs, self._q(out)[1], om, osh, self._rank2(out))))
 
     def _lower_l2_normalization(self, op):
@@ -346,13 +341,11 @@ class HannkModel:
         self.plan.append(Step("hannk_copy_from", (self._whole(x), View(out, 0, (0,) * r, self.tensors[x].shape, tuple(strides)))))
 
     def _block_views(self, space, depth, block):
-        c, w, h, b = self.tensors[space].shape
-        s = np.empty((b, h, w, c), np.uint8)
-        d = np.empty((b, h // block, w // block, block * block * c), np.uint8)
-        s6 = s.reshape(b, h // block, block, w // block, block, c)
-        d6 = d.reshape(b, h // block, w // block, block, block, c).transpose(0, 1, 3, 2, 4, 5)
-        mk = lambda t, v: View(t, 0, (0,) * 6, v.shape[::-1], v.strides[::-1])      # noqa: E731  (uint8: byte strides are element strides)
-        return mk(space, s6), mk(depth, d6)
+        """the two rank-6 views of hannk_block_views in Halide order: the space tensor dense, the depth tensor's dense strides permuted"""
+        space6, depth6, perm = hannk.hannk_block_views(self.tensors[space].shape[::-1], block)
+        dstr = _dense(depth6[::-1])[::-1]
+        return (View(space, 0, (0,) * 6, space6[::-1], tuple(_dense(space6[::-1]))),
+                View(depth, 0, (0,) * 6, tuple(depth6[p] for p in perm)[::-1], tuple(dstr[p] for p in perm)[::-1]))
 
     def _lower_space_to_depth(self, op):
         s6, d6 = self._block_views(op.inputs[0], op.outputs[0], op.attrs["block_size"])
@@ -405,9 +398,9 @@ class HannkModel:
     def _bind(self, step):
         args = [self._buffer(a) if isinstance(a, View) else int(a) for a in step.args]
         if step.name == "hannk_copy_from":
-            return lambda: hl.hannk_copy_from(args[0], args[1])
+            return lambda: hannk.hannk_copy_from(args[0], args[1])
         if step.name == "hannk_gather":
-            return lambda: hl.hannk_gather_buffers(*args)
+            return lambda: hannk.hannk_gather_buffers(*args)
         fn = hl._fn[step.name]
         cargs = [a.ptr if isinstance(a, hl.Buffer) else a for a in args]
         return lambda: hl._check(fn(*cargs))

@@ -841,9 +841,12 @@ def _hannk_pad(input, zero, channel_multiple, padding):
     return torch.nn.functional.pad(input, (0, cp - c, padding[0], padding[0], padding[1], padding[1]), value=zero).contiguous()
 
 
-def _hannk_out_hw(input, fh, fw, stride, dilation, padding):
-    return (hl.hannk_conv_out_extent(input.shape[1], fh, stride[1], dilation[1], padding[1]),
-            hl.hannk_conv_out_extent(input.shape[2], fw, stride[0], dilation[0], padding[0]))
+def _hannk_rule(name, rule, *args, **kwargs):
+    """a shape rule of halide_amd/hannk.py for the op `name` and its register_fake twin: its refusal as the RuntimeError torch ops raise"""
+    try:
+        return rule(*args, **kwargs)
+    except ValueError as e:
+        raise RuntimeError(f"{name}: {e}") from None
 
 
 @torch.library.custom_op("hlmi::hannk_conv2d", mutates_args=())
@@ -853,13 +856,11 @@ def hannk_conv2d(input: torch.Tensor, filter: torch.Tensor, bias: torch.Tensor, 
     """apps/hannk conv: input (B, H, W, CI) uint8, filter (CO, FH, FW, CI) uint8, bias (CO,) int32 -> (B, OH, OW, CO) uint8, or int16 with
     out_int16; stride, dilation and padding are (x, y) pairs, the padding is input_zero."""
     _hannk_check("hannk_conv2d", input, filter)
+    _, multiple, shape = _hannk_rule("hannk_conv2d", hl.hannk_conv_shape, input.shape, filter.shape, stride, dilation, padding)
     co, fh, fw, ci = filter.shape
-    if input.shape[3] != ci:
-        raise RuntimeError(f"hannk_conv2d: the input has {input.shape[3]} channels, the filter {ci}")
-    padded = _hannk_pad(input, input_zero, hl.HANNK_VECTOR_REDUCTION, padding)
+    padded = _hannk_pad(input, input_zero, multiple, padding)
     tiled = torch.empty((fh, fw, -(-co // 16), -(-ci // 4), 16, 4), dtype=torch.uint8, device=input.device)
-    oh, ow = _hannk_out_hw(input, fh, fw, stride, dilation, padding)
-    out = torch.empty((input.shape[0], oh, ow, co), dtype=torch.int16 if out_int16 else torch.uint8, device=input.device)
+    out = torch.empty(shape, dtype=torch.int16 if out_int16 else torch.uint8, device=input.device)
     with _Wrapped(padded, filter.contiguous(), tiled, bias.contiguous(), out) as (a, f, t, b, o):
         hl.tile_conv_filter_uint8(f, filter_zero, filter_zero, t)
         (hl.conv_u8_u8_i16 if out_int16 else hl.conv_u8_u8_u8)(a, input_zero, t, filter_zero, b, stride, dilation, multiplier, shift, output_zero,
@@ -874,13 +875,10 @@ def hannk_depthwise_conv2d(input: torch.Tensor, filter: torch.Tensor, bias: torc
     """apps/hannk depthwise conv: input (B, H, W, C) uint8, filter (FH, FW, C) uint8, bias (C,) int32 -> (B, OH, OW, C) uint8; an input of
     one channel under a filter of several is broadcast."""
     _hannk_check("hannk_depthwise_conv2d", input, filter)
-    fh, fw, c = filter.shape
-    broadcast = input.shape[3] == 1 and c > 1
-    if not broadcast and input.shape[3] != c:
-        raise RuntimeError(f"hannk_depthwise_conv2d: the input has {input.shape[3]} channels, the filter {c}")
-    padded = _hannk_pad(input, input_zero, 1 if broadcast else hl.HANNK_DEPTHWISE_VECTOR, padding)
-    oh, ow = _hannk_out_hw(input, fh, fw, stride, dilation, padding)
-    out = torch.empty((input.shape[0], oh, ow, c), dtype=torch.uint8, device=input.device)
+    broadcast, multiple, shape = _hannk_rule("hannk_depthwise_conv2d", hl.hannk_conv_shape, input.shape, filter.shape, stride, dilation, padding,
+                                             depthwise=True)
+    padded = _hannk_pad(input, input_zero, multiple, padding)
+    out = torch.empty(shape, dtype=torch.uint8, device=input.device)
     with _Wrapped(padded, filter.contiguous(), bias.contiguous(), out) as (a, f, b, o):
         (hl.depthwise_conv_broadcast_uint8 if broadcast else hl.depthwise_conv_uint8)(a, input_zero, f, filter_zero, b, stride, dilation, multiplier,
                                                                                      shift, output_zero, output_min, output_max, o)
@@ -889,27 +887,17 @@ def hannk_depthwise_conv2d(input: torch.Tensor, filter: torch.Tensor, bias: torc
 
 @hannk_conv2d.register_fake
 def _(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, multiplier, shift, output_zero, output_min, output_max, out_int16):
-    oh, ow = _hannk_out_hw(input, filter.shape[1], filter.shape[2], stride, dilation, padding)
-    return input.new_empty((input.shape[0], oh, ow, filter.shape[0]), dtype=torch.int16 if out_int16 else torch.uint8)
+    shape = _hannk_rule("hannk_conv2d", hl.hannk_conv_shape, input.shape, filter.shape, stride, dilation, padding)[2]
+    return input.new_empty(shape, dtype=torch.int16 if out_int16 else torch.uint8)
 
 
 @hannk_depthwise_conv2d.register_fake
 def _(input, filter, bias, input_zero, filter_zero, stride, dilation, padding, multiplier, shift, output_zero, output_min, output_max):
-    oh, ow = _hannk_out_hw(input, filter.shape[0], filter.shape[1], stride, dilation, padding)
-    return input.new_empty((input.shape[0], oh, ow, filter.shape[2]))
+    return input.new_empty(_hannk_rule("hannk_depthwise_conv2d", hl.hannk_conv_shape, input.shape, filter.shape, stride, dilation, padding, depthwise=True)[2])
 
 
 # apps/hannk's pooling, mean, add, mul, softmax and L2 normalisation on uint8 tensors (NHWC where the op is spatial), parameters derived
-# from float scales as the interpreter's ops.cpp derives them (hl.hannk_* have the derivations).
-def _hannk_pool_out(input, filter, stride, padding):
-    h, w = input.shape[1], input.shape[2]
-    if padding == "same":
-        return -(-h // stride[1]), -(-w // stride[0])
-    if padding == "valid":
-        return (h - filter[1]) // stride[1] + 1, (w - filter[0]) // stride[0] + 1
-    raise RuntimeError("hannk_pool2d: padding is 'same' or 'valid'")
-
-
+# from float scales as the interpreter's ops.cpp derives them (halide_amd/hannk.py has the derivations and every op's shape rule).
 @torch.library.custom_op("hlmi::hannk_pool2d", mutates_args=())
 def hannk_pool2d(input: torch.Tensor, kind: str, filter: list[int], stride: list[int], padding: str, output_min: int, output_max: int) -> torch.Tensor:
     """Pool2DOp: input (B, H, W, C) uint8 -> (B, OH, OW, C) uint8; kind "average" or "max", filter and stride (x, y) pairs, padding "same" or
@@ -917,8 +905,8 @@ def hannk_pool2d(input: torch.Tensor, kind: str, filter: list[int], stride: list
     _hannk_check("hannk_pool2d", input)
     if kind not in ("average", "max"):
         raise RuntimeError("hannk_pool2d: kind is 'average' or 'max'")
-    oh, ow = _hannk_pool_out(input, filter, stride, padding)
-    out = torch.empty((input.shape[0], oh, ow, input.shape[3]), dtype=torch.uint8, device=input.device)
+    _, oh, ow, _ = shape = _hannk_rule("hannk_pool2d", hl.hannk_pool_shape, input.shape, filter, stride, padding)
+    out = torch.empty(shape, dtype=torch.uint8, device=input.device)
     with _Wrapped(input.contiguous(), out) as (a, o):
         a.set_min(0, hl.hannk_compute_padding(stride[0], input.shape[2], filter[0], ow), hl.hannk_compute_padding(stride[1], input.shape[1], filter[1], oh), 0)
         (hl.average_pool_uint8 if kind == "average" else hl.max_pool_uint8)(a, stride, filter, output_min, output_max, o)
@@ -929,16 +917,11 @@ def hannk_pool2d(input: torch.Tensor, kind: str, filter: list[int], stride: list
 def hannk_mean(input: torch.Tensor, axes: list[int]) -> torch.Tensor:
     """ReductionOp (Mean): input uint8 of rank <= 4, the reduced axes kept with extent 1"""
     _hannk_check("hannk_mean", input)
-    nd = input.dim()
-    red = sorted({a % nd for a in axes})
-    in4 = input.contiguous().reshape((1,) * (4 - nd) + tuple(input.shape))
-    extents = [1] * 4
-    for a in red:
-        extents[3 - (a + 4 - nd)] = in4.shape[a + 4 - nd]
-    out = torch.empty(tuple(1 if a - (4 - nd) in red else in4.shape[a] for a in range(4)), dtype=torch.uint8, device=input.device)
-    with _Wrapped(in4, out) as (a, o):
-        hl.mean_uint8(a, [0, 0, 0, 0], extents, o)
-    return out.reshape(tuple(1 if a in red else input.shape[a] for a in range(nd)))
+    in4, box, out4, kept, _ = _hannk_rule("hannk_mean", hl.hannk_mean_shapes, input.shape, axes)
+    out = torch.empty(out4, dtype=torch.uint8, device=input.device)
+    with _Wrapped(input.contiguous().reshape(in4), out) as (a, o):
+        hl.mean_uint8(a, *box, o)
+    return out.reshape(kept)
 
 
 def _hannk_rank2_pair(name, in1, in2):
@@ -996,21 +979,15 @@ def hannk_l2_normalization(input: torch.Tensor, input_zero: int, axis: int) -> t
 
 @hannk_pool2d.register_fake
 def _(input, kind, filter, stride, padding, output_min, output_max):
-    oh, ow = _hannk_pool_out(input, filter, stride, padding)
-    return input.new_empty((input.shape[0], oh, ow, input.shape[3]))
+    return input.new_empty(_hannk_rule("hannk_pool2d", hl.hannk_pool_shape, input.shape, filter, stride, padding))
 
 
 @hannk_mean.register_fake
 def _(input, axes):
-    red = {a % input.dim() for a in axes}
-    return input.new_empty(tuple(1 if a in red else input.shape[a] for a in range(input.dim())))
+    return input.new_empty(_hannk_rule("hannk_mean", hl.hannk_mean_shapes, input.shape, axes)[3])
 
 
 @hannk_add.register_fake
-def _(in1, scale1, zero1, in2, scale2, zero2, out_scale, out_zero, activation):
-    return in1.new_empty(torch.broadcast_shapes(in1.shape, in2.shape))
-
-
 @hannk_mul.register_fake
 def _(in1, scale1, zero1, in2, scale2, zero2, out_scale, out_zero, activation):
     return in1.new_empty(torch.broadcast_shapes(in1.shape, in2.shape))
@@ -1066,41 +1043,28 @@ def hannk_tanh(input: torch.Tensor, in_scale: float, in_zero: int) -> torch.Tens
     return _hannk_program_call("hannk_tanh", [input], torch.from_numpy(hl.hannk_tanh_program(in_scale, in_zero)))[0]
 
 
-def _hannk_pad_shape(input, padding):
-    if input.dim() != 4 or len(padding) != 8 or any(p < 0 for p in padding):
-        raise RuntimeError("hannk_pad: a (B, H, W, C) tensor and eight paddings >= 0: (before, after) of B, H, W, C")
-    return tuple(input.shape[a] + padding[2 * a] + padding[2 * a + 1] for a in range(4))
+def _hannk_pad_boxes(input, padding):
+    if len(padding) != 8:
+        raise RuntimeError("hannk_pad: eight paddings: (before, after) of B, H, W, C")
+    return _hannk_rule("hannk_pad", hl.hannk_pad_boxes, input.shape, list(zip(padding[::2], padding[1::2])))
 
 
 @torch.library.custom_op("hlmi::hannk_pad", mutates_args=())
 def hannk_pad(input: torch.Tensor, padding: list[int], pad_value: int) -> torch.Tensor:
-    """PadOp: (B, H, W, C) uint8, `padding` = (before, after) of B, H, W, C: the borders by fill_uint8, the rest by one copy_uint8_uint8
-    (which pads the channel itself where 3 channels become 4)"""
+    """PadOp: (B, H, W, C) uint8, `padding` = (before, after) of B, H, W, C: one fill_uint8 or copy_uint8_uint8 per box of hl.hannk_pad_boxes
+    (the borders filled, the rest one copy, which pads the channel itself where 3 channels become 4)"""
     _hannk_check("hannk_pad", input)
-    out = torch.empty(_hannk_pad_shape(input, padding), dtype=torch.uint8, device=input.device)
+    shape, imin, boxes = _hannk_pad_boxes(input, padding)
+    out = torch.empty(shape, dtype=torch.uint8, device=input.device)
     src = input.contiguous()
-    imin = [padding[2 * (3 - d)] for d in range(4)]            # Halide dimension d is axis 3 - d
-    imax = [imin[d] + src.shape[3 - d] - 1 for d in range(4)]
-    omin, omax = [0] * 4, [out.shape[3 - d] - 1 for d in range(4)]
-
-    def on_crop(call):
-        view = out[tuple(slice(omin[3 - ax], omax[3 - ax] + 1) for ax in range(4))]
-        with _Wrapped(src, view) as (a, o):
+    for kind, omin, omax in boxes:
+        with _Wrapped(src, out[hl.hannk_box_slices(omin, omax)]) as (a, o):
             a.set_min(*imin)
             o.set_min(*omin)
-            call(a, o)
-
-    fill_min_dim = 1 if src.shape[3] == 3 and out.shape[3] == 4 else 0
-    for d in range(3, fill_min_dim - 1, -1):
-        lo, hi = omin[d], omax[d]
-        if lo < imin[d]:
-            omin[d], omax[d] = lo, imin[d] - 1
-            on_crop(lambda a, o: hl.fill_uint8(pad_value, o))
-        if hi > imax[d]:
-            omin[d], omax[d] = imax[d] + 1, hi
-            on_crop(lambda a, o: hl.fill_uint8(pad_value, o))
-        omin[d], omax[d] = max(lo, imin[d]), min(hi, imax[d])
-    on_crop(lambda a, o: hl.copy_uint8_uint8(a, pad_value, o))
+            if kind == "fill":
+                hl.fill_uint8(pad_value, o)
+            else:
+                hl.copy_uint8_uint8(a, pad_value, o)
     return out
 
 
@@ -1124,10 +1088,6 @@ def _(inputs, program):
 
 
 @hannk_logistic.register_fake
-def _(input, in_scale, in_zero):
-    return torch.empty_like(input)
-
-
 @hannk_tanh.register_fake
 def _(input, in_scale, in_zero):
     return torch.empty_like(input)
@@ -1135,7 +1095,7 @@ def _(input, in_scale, in_zero):
 
 @hannk_pad.register_fake
 def _(input, padding, pad_value):
-    return input.new_empty(_hannk_pad_shape(input, padding))
+    return input.new_empty(_hannk_pad_boxes(input, padding)[0])
 
 
 @hannk_upsample_channels.register_fake
@@ -1176,65 +1136,35 @@ def _hannk_copy(src_view, dst_view):
         hl.hannk_copy_from(s, d)
 
 
-def _hannk_perm(name, input, perm):
-    perm = [int(p) for p in perm]
-    if sorted(perm) != list(range(input.dim())):
-        raise RuntimeError(f"{name}: {perm} is no permutation of {input.dim()} axes")
-    return perm
-
-
 @torch.library.custom_op("hlmi::hannk_transpose", mutates_args=())
 def hannk_transpose(input: torch.Tensor, perm: list[int]) -> torch.Tensor:
     """TransposeOp: input.permute(perm) as a dense tensor, one copy_from into the output viewed in the input's order"""
-    perm = _hannk_perm("hannk_transpose", input, perm)
+    inverse = _hannk_rule("hannk_transpose", hl.hannk_inverse_perm, perm, input.dim())
     out = torch.empty([input.shape[p] for p in perm], dtype=input.dtype, device=input.device)
-    _hannk_copy(input, out.permute([perm.index(a) for a in range(len(perm))]))
+    _hannk_copy(input, out.permute(inverse))
     return out
 
 
-def _hannk_block_shape(name, input, block, to_depth):
-    if input.dim() != 4 or block < 1:
-        raise RuntimeError(f"{name}: a (B, H, W, C) tensor and a block size >= 1")
-    b, h, w, c = input.shape
-    if to_depth:
-        if h % block or w % block:
-            raise RuntimeError(f"{name}: the block size {block} divides neither {h} nor {w}")
-        return (b, h // block, w // block, c * block * block)
-    if c % (block * block):
-        raise RuntimeError(f"{name}: {block}^2 does not divide {c} channels")
-    return (b, h * block, w * block, c // (block * block))
-
-
 def _hannk_block_views(space, depth, block):
-    b, h, w, c = space.shape
-    s6 = space.view(b, h // block, block, w // block, block, c)
-    d6 = depth.view(b, h // block, w // block, block, block, c).permute(0, 1, 3, 2, 4, 5)
-    return s6, d6
+    space6, depth6, perm = hl.hannk_block_views(space.shape, block)
+    return space.view(space6), depth.view(depth6).permute(perm)
 
 
 @torch.library.custom_op("hlmi::hannk_space_to_depth", mutates_args=())
 def hannk_space_to_depth(input: torch.Tensor, block_size: int) -> torch.Tensor:
     """(B, H, W, C) -> (B, H / block, W / block, block^2 * C)"""
-    out = torch.empty(_hannk_block_shape("hannk_space_to_depth", input, block_size, True), dtype=input.dtype, device=input.device)
-    s6, d6 = _hannk_block_views(input.contiguous(), out, block_size)
-    _hannk_copy(s6, d6)
+    out = torch.empty(_hannk_rule("hannk_space_to_depth", hl.hannk_block_shape, input.shape, block_size, True), dtype=input.dtype, device=input.device)
+    _hannk_copy(*_hannk_block_views(input.contiguous(), out, block_size))
     return out
 
 
 @torch.library.custom_op("hlmi::hannk_depth_to_space", mutates_args=())
 def hannk_depth_to_space(input: torch.Tensor, block_size: int) -> torch.Tensor:
     """(B, H, W, block^2 * C) -> (B, H * block, W * block, C)"""
-    out = torch.empty(_hannk_block_shape("hannk_depth_to_space", input, block_size, False), dtype=input.dtype, device=input.device)
+    out = torch.empty(_hannk_rule("hannk_depth_to_space", hl.hannk_block_shape, input.shape, block_size, False), dtype=input.dtype, device=input.device)
     s6, d6 = _hannk_block_views(out, input.contiguous(), block_size)
     _hannk_copy(d6, s6)
     return out
-
-
-def _hannk_gather_shape(input, indices, axis):
-    if input.dim() < 1 or indices.dim() > 2 or not -input.dim() <= axis < input.dim():
-        raise RuntimeError("hannk_gather: indices of rank 0 .. 2 and an axis of the input")
-    axis %= input.dim()
-    return axis, tuple(input.shape[:axis]) + tuple(indices.shape) + tuple(input.shape[axis + 1:])
 
 
 @torch.library.custom_op("hlmi::hannk_gather", mutates_args=())
@@ -1243,7 +1173,7 @@ def hannk_gather(input: torch.Tensor, indices: torch.Tensor, axis: int) -> torch
     other slices were written.  The one op here that waits for the device: the kernel's out-of-range flag is read back."""
     if indices.dtype != torch.int32:
         raise TypeError("hannk_gather: indices are int32")
-    axis, shape = _hannk_gather_shape(input, indices, axis)
+    axis, shape = _hannk_rule("hannk_gather", hl.hannk_gather_shape, input.shape, indices.shape, axis)
     out = torch.zeros(shape, dtype=input.dtype, device=input.device)
     with _Views(input, indices, out) as (a, i, o):
         hl.hannk_gather_buffers(a, i, input.dim() - 1 - axis, o)
@@ -1251,14 +1181,9 @@ def hannk_gather(input: torch.Tensor, indices: torch.Tensor, axis: int) -> torch
 
 
 def _hannk_concat_shape(inputs, axis):
-    if not inputs or not -inputs[0].dim() <= axis < inputs[0].dim():
-        raise RuntimeError("hannk_concatenation: at least one input and an axis of it")
-    axis %= inputs[0].dim()
-    first = inputs[0]
-    for t in inputs:
-        if t.dtype != first.dtype or t.dim() != first.dim() or any(t.shape[d] != first.shape[d] for d in range(first.dim()) if d != axis):
-            raise RuntimeError("hannk_concatenation: the inputs share dtype and every extent but the axis'")
-    return axis, tuple(sum(t.shape[d] for t in inputs) if d == axis else first.shape[d] for d in range(first.dim()))
+    if any(t.dtype != inputs[0].dtype for t in inputs):
+        raise RuntimeError("hannk_concatenation: the inputs share dtype and every extent but the axis'")
+    return _hannk_rule("hannk_concatenation", hl.hannk_concat_shape, [t.shape for t in inputs], axis)
 
 
 @torch.library.custom_op("hlmi::hannk_concatenation", mutates_args=())
@@ -1291,22 +1216,23 @@ def hannk_fully_connected(input: torch.Tensor, weights: torch.Tensor, bias: torc
 
 @hannk_transpose.register_fake
 def _(input, perm):
-    return input.new_empty([input.shape[p] for p in _hannk_perm("hannk_transpose", input, perm)])
+    _hannk_rule("hannk_transpose", hl.hannk_inverse_perm, perm, input.dim())
+    return input.new_empty([input.shape[p] for p in perm])
 
 
 @hannk_space_to_depth.register_fake
 def _(input, block_size):
-    return input.new_empty(_hannk_block_shape("hannk_space_to_depth", input, block_size, True))
+    return input.new_empty(_hannk_rule("hannk_space_to_depth", hl.hannk_block_shape, input.shape, block_size, True))
 
 
 @hannk_depth_to_space.register_fake
 def _(input, block_size):
-    return input.new_empty(_hannk_block_shape("hannk_depth_to_space", input, block_size, False))
+    return input.new_empty(_hannk_rule("hannk_depth_to_space", hl.hannk_block_shape, input.shape, block_size, False))
 
 
 @hannk_gather.register_fake
 def _(input, indices, axis):
-    return input.new_empty(_hannk_gather_shape(input, indices, axis)[1])
+    return input.new_empty(_hannk_rule("hannk_gather", hl.hannk_gather_shape, input.shape, indices.shape, axis)[1])
 
 
 @hannk_concatenation.register_fake
