@@ -588,7 +588,7 @@ def fuzz_linear_algebra(rng):
     with random a and b and in a third of the cases a handful of special values, against tests/cpp/linear_algebra_check.c
     (tests/linear_algebra_checker.py) in the library's canonical form.  Bit for bit, NaN for NaN; the bytes around every buffer must
     come back unchanged."""
-    import linear_algebra_checker as la
+    from linear_algebra_checker import f32 as la
     la.set_canon(hl.canon_fma())
     name = la.NAMES[int(rng.integers(0, len(la.NAMES)))]
     general = rng.random() < 0.3
@@ -675,10 +675,10 @@ def fuzz_linear_algebra(rng):
 def fuzz_linear_algebra_f64(rng):
     """One of the twelve f64 pipelines of apps/linear_algebra, drawn as fuzz_linear_algebra draws the f32 ones (vectors 0 .. 3000, matrix
     extents 1 .. 200 within the variant's squareness rule, either path, device allocations with a column stride and a pointer offset
-    of 0 or 8 bytes, a third of the cases in place, a third with special values), against tests/cpp/linear_algebra_f64_check.c
-    (tests/linear_algebra_f64_checker.py) in the library's canonical form.  Bit for bit, NaN for NaN; the bytes around every buffer
+    of 0 or 8 bytes, a third of the cases in place, a third with special values), against the ld_* half of tests/cpp/linear_algebra_check.c
+    (tests/linear_algebra_checker.py) in the library's canonical form.  Bit for bit, NaN for NaN; the bytes around every buffer
     must come back unchanged."""
-    import linear_algebra_f64_checker as ld
+    from linear_algebra_checker import f64 as ld
     f64 = np.float64
     ld.set_canon(hl.canon_fma())
     name = ld.NAMES[int(rng.integers(0, len(ld.NAMES)))]
@@ -1144,7 +1144,7 @@ CASES["compositing"] = fuzz_compositing   # integer throughout: its checker (tes
 CASES["hexagon_benchmarks"] = fuzz_hexagon_benchmarks   # all six entry points; integer throughout (tests/hexagon_benchmarks_checker.py)
 CASES["mat_mul"] = fuzz_mat_mul   # sized and general paths; one chain in both canonical forms (tests/mat_mul_checker.py)
 CASES["linear_algebra"] = fuzz_linear_algebra   # all twelve entry points, both paths (tests/linear_algebra_checker.py)
-CASES["linear_algebra_f64"] = fuzz_linear_algebra_f64   # the f64 half, both paths (tests/linear_algebra_f64_checker.py)
+CASES["linear_algebra_f64"] = fuzz_linear_algebra_f64   # the f64 half, both paths (tests/linear_algebra_checker.py)
 CASES["fft"] = fuzz_fft   # all four kinds, both paths (tests/fft_checker.py)
 CASES["hannk_conv"] = fuzz_hannk_conv   # both output types, both paths, split-K; integer throughout (tests/hannk_checker.py)
 CASES["hannk_depthwise"] = fuzz_hannk_depthwise   # both variants, both paths

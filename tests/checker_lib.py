@@ -1,11 +1,14 @@
-"""ctypes bindings to the plain-C checkers of the pipelines oracle/ does not restate (tests/cpp/*_check.c: resize, gaussian_blur,
-linear_blur / simple_blur) — TEST INFRASTRUCTURE ONLY, the sibling of oracle_lib.py.
+"""The plain-C checkers of the pipelines oracle/ does not restate (tests/cpp/*_check.c) — TEST INFRASTRUCTURE ONLY, the sibling of
+oracle_lib.py.
 
-The one place that knows the build line, the ctypes signatures and the canonical-form switch.  The files compile together into
-one shared object, once per process, in a temporary directory; tests/test_*.py and scripts/fuzz_parity.py both come here.  A
-further checker costs its C file, a line in SOURCES and its bindings below.  Imports neither the product nor torch."""
+Checker is the one place that knows how a checker object comes to exist: the build line, the temporary directory, the load, and the
+canonical-form switch of an object with float forms.  Every *_checker.py declares one Checker and keeps its ctypes signatures, name
+tables and numpy conveniences; the bindings of resize, gaussian_blur and linear_blur / simple_blur, three files in one object, are
+below.  tests/test_*.py and scripts/fuzz_parity.py both come here.  A further checker-held pipeline costs its C file, a Checker and
+its bindings.  Imports neither the product nor torch."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -15,33 +18,72 @@ import threading
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("check_canon.c", "resize_check.c", "gaussian_blur_check.c", "linear_blur_check.c")
 
 RESIZE_KERNELS = ("box", "linear", "cubic", "lanczos")        # rc_* take the index
 RESIZE_TAPS = {"box": 1, "linear": 2, "cubic": 4, "lanczos": 6}
 RESIZE_TYPE_INDEX = {"float32": 0, "uint8": 1, "uint16": 2}   # rc_resize's `type`
 
-_lock = threading.Lock()
-_lib = []
 f32 = np.float32
 
 
-def lib():
-    """The loaded shared object (the raw ctypes library), built on the first call.  -Wl,-Bsymbolic: the object holds its own
-    o_canon_fma (check_canon.c) beside liboracle.so's in the same process."""
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_checkers"), "libcheckers.so")
-            subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", so]
-                           + [os.path.join(ROOT, "tests", "cpp", s) for s in SOURCES] + ["-lm"], check=True)
-            _lib.append(_bind(C.CDLL(so)))
-    return _lib[0]
+def host_has_fma():
+    """whether gcc may emit the FMA instruction for fmaf / fma (-mfma: the same correctly rounded operation, five times as fast at
+    1024^3 as the call into libm)"""
+    try:
+        with open("/proc/cpuinfo") as f:
+            return any(line.startswith("flags") and " fma " in line + " " for line in f)
+    except OSError:
+        return False
+
+
+class Checker:
+    """One shared object of tests/cpp/ `sources`, built with -O2 -Wall -Werror and `flags` on first use, once per process, under one
+    lock, in a temporary directory; `bind(L)` sets its ctypes signatures.  float_forms: the object evaluates the canonical float forms
+    of oracle/oracle_common.h, so it is built with check_canon.c and -ffp-contract=off, holds an o_canon_fma of its own beside
+    liboracle.so's and every other checker's in the same process (-Wl,-Bsymbolic), and has the switch below."""
+    _lock = threading.Lock()
+
+    def __init__(self, name, sources, bind, float_forms=False, flags=()):
+        self.name, self.bind, self.float_forms, self._lib = name, bind, float_forms, None
+        self.sources = (("check_canon.c",) if float_forms else ()) + tuple(sources)
+        self.flags = list(flags) + (["-ffp-contract=off", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle")] if float_forms else [])
+
+    def lib(self):
+        """The loaded shared object (the raw ctypes library)."""
+        with Checker._lock:
+            if self._lib is None:
+                so = os.path.join(tempfile.mkdtemp(prefix=f"hlmi_{self.name}_checker"), f"lib{self.name}.so")
+                subprocess.run(["gcc", "-O2", "-Wall", "-Werror", *self.flags, "-shared", "-fPIC", "-o", so]
+                               + [os.path.join(ROOT, "tests", "cpp", s) for s in self.sources] + ["-lm"], check=True)
+                L = C.CDLL(so)
+                if self.float_forms:
+                    L.ck_set_canon.argtypes = [C.c_int]
+                    L.ck_get_canon.restype = C.c_int
+                self.bind(L)
+                self._lib = L
+        return self._lib
+
+    def set_canon(self, fma: int) -> None:
+        """The object's canonical form: 0 = one rounding per operator, 1 = mul+add pairs contracted into fma.  One switch for every
+        checker in the object; every other object's, and the oracle's (oracle_lib.set_canon), is a separate one."""
+        self.lib().ck_set_canon(int(fma))
+
+    def get_canon(self) -> int:
+        return int(self.lib().ck_get_canon())
+
+    @contextlib.contextmanager
+    def canon(self, fma: int):
+        """with xx.canon(0): ...   — evaluates the object's checkers in the given form, then restores the one in force."""
+        prev = self.get_canon()
+        self.set_canon(fma)
+        try:
+            yield self
+        finally:
+            self.set_canon(prev)
 
 
 def _bind(L):
     I, F, P = C.c_int, C.c_float, C.c_void_p
-    L.ck_set_canon.argtypes = [I]
-    L.ck_get_canon.restype = I
     L.rc_halide_sin.restype = F
     L.rc_halide_sin.argtypes = [F]
     L.rc_sin_array.argtypes = [P, P, C.c_size_t]
@@ -62,34 +104,10 @@ def _bind(L):
     L.lc_blur.argtypes = [I, P, I, I, I, I, I, I, I, P, I, I, I, I]
     for fn in (L.lc_to_linear, L.lc_to_srgb):
         fn.restype, fn.argtypes = F, [F]
-    return L
 
 
-# ---------------------------------------------------------------------------------------------------- the canonical form
-def set_canon(fma: int) -> None:
-    """The checkers' canonical form (oracle/oracle_common.h): 0 = one rounding per operator, 1 = mul+add pairs contracted into
-    fma.  One switch for all of them; the oracle's (oracle_lib.set_canon) is a separate one."""
-    lib().ck_set_canon(int(fma))
-
-
-def get_canon() -> int:
-    return int(lib().ck_get_canon())
-
-
-class canon:
-    """with checker_lib.canon(0): ...   — evaluates the checkers in the given form, then restores the one in force."""
-
-    def __init__(self, fma: int):
-        self.fma = int(fma)
-
-    def __enter__(self):
-        self.prev = get_canon()
-        set_canon(self.fma)
-        return self
-
-    def __exit__(self, *exc):
-        set_canon(self.prev)
-        return False
+checker = Checker("resize_blur", ("resize_check.c", "gaussian_blur_check.c", "linear_blur_check.c"), _bind, float_forms=True)
+lib, set_canon, get_canon, canon = checker.lib, checker.set_canon, checker.get_canon, checker.canon
 
 
 class _Checker:

@@ -1,45 +1,31 @@
-"""ctypes bindings to tests/cpp/compositing_check.c, the plain-C checker of compositing — TEST INFRASTRUCTURE ONLY, the sibling of
-wavelet_checker.py.
+"""ctypes bindings to tests/cpp/compositing_check.c, the plain-C checker of compositing — TEST INFRASTRUCTURE ONLY.
 
-The checker is one file of integer arithmetic: it needs neither check_canon.c nor a canonical-form switch.  It is built into a
-shared object of its own, once per process, in a temporary directory; tests/test_compositing.py and scripts/fuzz_parity.py both come
-here.  Imports neither the product nor torch."""
+The checker is one file of integer arithmetic: a checker_lib.Checker without float forms, so without a canonical-form switch.
+tests/test_compositing.py and scripts/fuzz_parity.py both come here.  Imports neither the product nor torch."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("compositing_check.c",)
+from checker_lib import Checker
+
 OPS = ("over", "atop", "xor", "in", "out")   # op code = index
 LAYERS, NOPS = 6, 5
-
-_lock = threading.Lock()
-_lib = []
 u8, u16 = np.uint8, np.uint16
 
 
-def lib():
-    """The loaded shared object (the raw ctypes library), built on the first call."""
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_compositing_checker"), "libcompositingcheck.so")
-            subprocess.run(["gcc", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so] + [os.path.join(ROOT, "tests", "cpp", s) for s in SOURCES], check=True)
-            L = C.CDLL(so)
-            P = C.c_void_p
-            L.cc_scale16.restype, L.cc_scale16.argtypes = C.c_uint16, [C.c_uint16, C.c_uint8]
-            L.cc_scale16_div255.restype, L.cc_scale16_div255.argtypes = C.c_uint16, [C.c_uint16, C.c_uint8]
-            L.cc_scale8.restype, L.cc_scale8.argtypes = C.c_uint8, [C.c_uint8, C.c_uint8]
-            L.cc_divide.restype, L.cc_divide.argtypes = C.c_uint16, [C.c_uint16, C.c_uint8]
-            L.cc_scale16_sweep.restype, L.cc_scale16_sweep.argtypes = None, [P, P, P, P, C.c_size_t]
-            L.cc_compositing.restype, L.cc_compositing.argtypes = None, [C.POINTER(P), P, P, C.c_int, C.c_int]
-            _lib.append(L)
-    return _lib[0]
+def _bind(L):
+    P = C.c_void_p
+    L.cc_scale16.restype, L.cc_scale16.argtypes = C.c_uint16, [C.c_uint16, C.c_uint8]
+    L.cc_scale16_div255.restype, L.cc_scale16_div255.argtypes = C.c_uint16, [C.c_uint16, C.c_uint8]
+    L.cc_scale8.restype, L.cc_scale8.argtypes = C.c_uint8, [C.c_uint8, C.c_uint8]
+    L.cc_divide.restype, L.cc_divide.argtypes = C.c_uint16, [C.c_uint16, C.c_uint8]
+    L.cc_scale16_sweep.restype, L.cc_scale16_sweep.argtypes = None, [P, P, P, P, C.c_size_t]
+    L.cc_compositing.restype, L.cc_compositing.argtypes = None, [C.POINTER(P), P, P, C.c_int, C.c_int]
+
+
+lib = Checker("compositing", ("compositing_check.c",), _bind).lib
 
 
 def scale16(a, s) -> int:

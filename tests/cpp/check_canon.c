@@ -1,5 +1,5 @@
-/* check_canon.c — the one canonical-form switch of the plain-C checkers (resize_check.c, gaussian_blur_check.c,
- * linear_blur_check.c), which tests/checker_lib.py links into one shared object.  o_canon_fma is the form that
+/* check_canon.c — the canonical-form switch of a plain-C checker object with float forms (resize_check.c, gaussian_blur_check.c and
+ * linear_blur_check.c in one object; wavelet, fft, linear_algebra, resnet50 in one each): tests/checker_lib.py links a copy into each.  o_canon_fma is the form that
  * oracle/oracle_common.h's helpers read; the object is linked with -Wl,-Bsymbolic, so it is this definition and not
  * liboracle.so's that the checkers see when both are loaded. */
 int o_canon_fma = 1;

@@ -1,6 +1,6 @@
 /* compositing_check.c — the checker of compositing: apps/compositing/compositing_generator.cpp:25-154 restated in plain C in its
  * INTEGER form (the branch of a target without a GPU feature: uint16 colour, uint8 alpha), every value held in the type the
- * generator gives it so that additions wrap where the generator's do.  tests/compositing_checker.py holds the build line and drives
+ * generator gives it so that additions wrap where the generator's do.  tests/compositing_checker.py declares the object (tests/checker_lib.py builds it) and drives
  * this file through ctypes.  No float operation anywhere: there is no canonical form to choose.
  *
  *   premultiply_alpha :34-37     C[i] = widening_mul(v_i, a): u16(v_i) * u16(a); A = a

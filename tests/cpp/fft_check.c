@@ -1,7 +1,7 @@
 /* fft_check.c — the checker of the four 2-D f32 transforms of apps/fft (c2c forward, c2c inverse, r2c, c2r): the arithmetic of
  * fft.cpp, complex.h and fft_generator.cpp restated in plain C, one rounding per operator (no contraction by the compiler), the fused
- * operations written out.  tests/fft_checker.py holds the build line: it links this file with check_canon.c into a shared object of
- * its own and drives it through ctypes.  The derivation, line by line:
+ * operations written out.  tests/fft_checker.py declares the object: tests/checker_lib.py links this file with check_canon.c into a shared object of
+ * its own, and fft_checker.py drives it through ctypes.  The derivation, line by line:
  *
  * complex.h:77-104.  (a + b), (a - b) work per component.  a * b = (a.re b.re - a.im b.im, a.re b.im + a.im b.re): a difference and a
  *   sum of two products.  In form 1 (oracle/oracle_common.h) the first product of each is the one fused: re = mulsub(a.re, b.re,

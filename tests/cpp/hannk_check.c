@@ -1,7 +1,7 @@
 /* hannk_check.c — plain-C restatement of the contract of the hannk convolution ops, written from the ALGORITHM sections
  * of the reference's generators (apps/hannk/halide/conv_generator.cpp:84-159 and :341-350, depthwise_conv_generator.cpp:66-135,
  * common_halide.cpp:228-248) and the lowering of the run-time rounding shift (src/FindIntrinsics.cpp:1331-1345); nothing of their
- * schedules.  TEST INFRASTRUCTURE ONLY: built by tests/hannk_checker.py into a shared object of its own; shares no code with the product.
+ * schedules.  TEST INFRASTRUCTURE ONLY: built with hannk_program_check.c into one shared object, declared by tests/hannk_checker.py; shares no code with the product.
  *
  * Every buffer comes as a pointer to its element at (min0, min1, ...), its mins, extents and element strides, dimension 0 first.
  * Sums are uint32_t: they wrap modulo 2^32 like the contract's int32. */

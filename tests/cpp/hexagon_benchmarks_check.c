@@ -6,7 +6,7 @@
  *   hb_<name>_verify   from the matching verify() of process.h: the window gathered tap by tap, the median by selection, the sums in
  *                      an int16_t or int32_t accumulator
  *
- * tests/hexagon_benchmarks_checker.py holds the build line and drives this file through ctypes; tests/test_hexagon_benchmarks.py
+ * tests/hexagon_benchmarks_checker.py declares the object (tests/checker_lib.py builds it) and drives this file through ctypes; tests/test_hexagon_benchmarks.py
  * holds the two to each other and to numpy.  Integer arithmetic only: there is no canonical form to choose.  Wrapping is written
  * out (a sum formed in uint32_t, narrowed through uint16_t), never left to a signed overflow.
  *

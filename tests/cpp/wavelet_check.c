@@ -1,6 +1,6 @@
 /* wavelet_check.c — the checker of haar_x, inverse_haar_x, daubechies_x and inverse_daubechies_x: the arithmetic of apps/wavelet
  * restated in plain C, one rounding per operator (no contraction by the compiler), the fused operations written out.
- * tests/wavelet_checker.py holds the build line: it links this file with check_canon.c into a shared object of its own and drives
+ * tests/wavelet_checker.py declares the object (tests/checker_lib.py links this file with check_canon.c into a shared object of its own) and drives
  * it through ctypes.  Written from the generators' text, `in` being repeat_edge of the input over the buffer's own min and extent
  * in every dimension:
  *

@@ -1,74 +1,33 @@
-"""ctypes bindings to tests/cpp/fft_check.c, the plain-C checker of the four 2-D transforms of apps/fft — TEST INFRASTRUCTURE ONLY,
-the sibling of wavelet_checker.py.
+"""ctypes bindings to tests/cpp/fft_check.c, the plain-C checker of the four 2-D transforms of apps/fft — TEST INFRASTRUCTURE ONLY.
 
-The checker is built with tests/cpp/check_canon.c into a shared object of its own, with checker_lib.py's build line, once per
-process, in a temporary directory; tests/test_fft.py and scripts/fuzz_parity.py both come here.  Its canonical-form switch is its
-own copy of check_canon.c's (-Wl,-Bsymbolic).  Imports neither the product nor torch: use_twiddles() takes the address of the
-library's table function from whoever has loaded the library."""
+A checker_lib.Checker with float forms: a shared object and a canonical-form switch of its own.  tests/test_fft.py and
+scripts/fuzz_parity.py both come here.  Imports neither the product nor torch: use_twiddles() takes the address of the library's
+table function from whoever has loaded the library."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("check_canon.c", "fft_check.c")
+from checker_lib import Checker
+
 KINDS = ("c2c_forward", "c2c_inverse", "r2c", "c2r")
 V = 8   # FC_V
-
-_lock = threading.Lock()
-_lib = []
 f32 = np.float32
 
 
-def lib():
-    """The loaded shared object (the raw ctypes library), built on the first call."""
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_fft_checker"), "libfftcheck.so")
-            subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"),
-                            "-o", so] + [os.path.join(ROOT, "tests", "cpp", s) for s in SOURCES] + ["-lm"], check=True)
-            L = C.CDLL(so)
-            I, P = C.c_int, C.c_void_p
-            L.ck_set_canon.argtypes = [I]
-            L.ck_get_canon.restype = I
-            L.fc_twiddles.restype, L.fc_twiddles.argtypes = None, [I, I, C.c_float, P]
-            L.fc_set_twiddle_fn.restype, L.fc_set_twiddle_fn.argtypes = None, [P]
-            L.fc_radix_factor.argtypes = [I, P]
-            L.fc_size_ok.argtypes = [I]
-            L.fc_zip_width.argtypes = [I, I, I, I]
-            L.fc_fft2d.argtypes = [I, I, I, C.c_float, I, P, C.c_long, P, C.c_long]
-            _lib.append(L)
-    return _lib[0]
+def _bind(L):
+    I, P = C.c_int, C.c_void_p
+    L.fc_twiddles.restype, L.fc_twiddles.argtypes = None, [I, I, C.c_float, P]
+    L.fc_set_twiddle_fn.restype, L.fc_set_twiddle_fn.argtypes = None, [P]
+    L.fc_radix_factor.argtypes = [I, P]
+    L.fc_size_ok.argtypes = [I]
+    L.fc_zip_width.argtypes = [I, I, I, I]
+    L.fc_fft2d.argtypes = [I, I, I, C.c_float, I, P, C.c_long, P, C.c_long]
 
 
-def set_canon(fma: int) -> None:
-    """The checker's canonical form (oracle/oracle_common.h): 0 = one rounding per operator, 1 = mul+add pairs contracted."""
-    lib().ck_set_canon(int(fma))
-
-
-def get_canon() -> int:
-    return int(lib().ck_get_canon())
-
-
-class canon:
-    """with fft_checker.canon(0): ...   — evaluates the checker in the given form, then restores the one in force."""
-
-    def __init__(self, fma: int):
-        self.fma = int(fma)
-
-    def __enter__(self):
-        self.prev = get_canon()
-        set_canon(self.fma)
-        return self
-
-    def __exit__(self, *exc):
-        set_canon(self.prev)
-        return False
+checker = Checker("fft", ("fft_check.c",), _bind, float_forms=True)
+lib, set_canon, get_canon, canon = checker.lib, checker.set_canon, checker.get_canon, checker.canon
 
 
 def use_twiddles(fn_address) -> None:

@@ -1,6 +1,7 @@
-"""ctypes bindings to tests/cpp/hannk_check.c, the plain-C checker of the hannk convolution ops — TEST INFRASTRUCTURE ONLY, the sibling of
-resnet50_checker.py.  Built into a shared object of its own, once per process, in a temporary directory.  Imports neither the product nor
-torch.
+"""ctypes bindings to tests/cpp/hannk_check.c, the plain-C checker of the hannk convolution ops — TEST INFRASTRUCTURE ONLY.  Declares the one checker_lib.Checker of
+the three hannk checkers (hannk_check.c and hannk_program_check.c, which includes hannk_nn_check.c: hk_*, hkn_* and hkp_* in one object,
+integer throughout, no canonical-form switch) with all its signatures; hannk_nn_checker.py and hannk_program_checker.py take `lib` and the
+argument helpers from here.  Imports neither the product nor torch.
 
 Arrays are the Halide dimensions reversed, the innermost axis dense, the outer ones possibly padded (strides are read from the array): an
 activation [c, x, y, b] is an array of shape (B, H, W, C), the tiled filter [4, 16, ci / 4, co / 16, fx, fy] one of shape
@@ -8,40 +9,43 @@ activation [c, x, y, b] is an array of shape (B, H, W, C), the tiled filter [4, 
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from checker_lib import Checker
+
 VECTOR_REDUCTION, ACCUM_VECTOR_SIZE, DEPTHWISE_VECTOR = 4, 16, 16
 
-_lock = threading.Lock()
-_lib = []
+
+def _bind(L):
+    I, P, N, U = C.c_int32, C.c_void_p, C.c_long, C.c_uint8                 # hannk_check.c
+    L.hk_multiply_2x_high.restype, L.hk_multiply_2x_high.argtypes = I, [I, I]
+    L.hk_rounding_shift_right.restype, L.hk_rounding_shift_right.argtypes = I, [I, I]
+    L.hk_quantize_i16.restype, L.hk_quantize_i16.argtypes = C.c_int16, [I, I, I]
+    L.hk_quantize_and_relu_u8.restype, L.hk_quantize_and_relu_u8.argtypes = U, [I, I, I, U, U, U]
+    L.hk_quantize.restype, L.hk_quantize.argtypes = None, [C.c_int, P, N, I, I, U, U, U, P]
+    L.hk_tile_filter.restype, L.hk_tile_filter.argtypes = None, [P, P, P, P, U, U, P, P, P, P]
+    L.hk_conv.restype = None
+    L.hk_conv.argtypes = [P, P, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P] + [C.c_int] * 5 + [U, U, I, I, U, U, U]
+    L.hk_depthwise.restype = None
+    L.hk_depthwise.argtypes = [P, P, P, P, P, C.c_int, C.c_int, P, P, P, P, P] + [C.c_int] * 5 + [U, U, I, I, U, U, U]
+    I = C.c_int                                                               # hannk_nn_check.c
+    L.hkn_approx.restype, L.hkn_approx.argtypes = None, [I, I, P, N, I, I, P]
+    L.hkn_pool.restype, L.hkn_pool.argtypes = None, [I, P, P, P, P, P, P, P, P, I, I, I, I, I, I]
+    L.hkn_mean.restype, L.hkn_mean.argtypes = None, [P] * 9
+    L.hkn_add.restype, L.hkn_add.argtypes = None, [P, P, P, I, I, P, P, P, I, I, I, I, I, P, P, P, P]
+    L.hkn_mul.restype, L.hkn_mul.argtypes = None, [P, P, P, I, P, P, P, I, I, C.c_int32, C.c_uint32, I, I, P, P, P, P]
+    L.hkn_softmax.restype, L.hkn_softmax.argtypes = None, [P, P, P, P, I, C.c_uint, I, I, C.c_uint, P, P, P, P]
+    L.hkn_l2_normalization.restype, L.hkn_l2_normalization.argtypes = None, [P, P, P, P, I, P, P, P, P]
+    L.hkp_approx.restype, L.hkp_approx.argtypes = None, [I, P, P, P, N, I, P]   # hannk_program_check.c
+    L.hkp_op.restype, L.hkp_op.argtypes = None, [I, P, P, P, P, N, P]
+    L.hkp_elementwise.restype, L.hkp_elementwise.argtypes = I, [I, P, P, P, P, I, P, N, P, N, I, I]
+    L.hkp_copy.restype, L.hkp_copy.argtypes = None, [P, P, P, P, I, P, P, P, P]
+    L.hkp_upsample_channels.restype, L.hkp_upsample_channels.argtypes = None, [P, P, P, I, P, P, P, P]
+    L.hkp_depthwise_shallow.restype, L.hkp_depthwise_shallow.argtypes = None, [P, I, I, P, I, I, I, P, P, I, I, I] + [I] * 6 + [C.c_int32, C.c_int32, I, I, I]
 
 
-def lib():
-    """The loaded shared object (the raw ctypes library), built on the first call."""
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_hannk_checker"), "libhannkcheck.so")
-            subprocess.run(["gcc", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "cpp", "hannk_check.c")], check=True)
-            L = C.CDLL(so)
-            I, P, N, U = C.c_int32, C.c_void_p, C.c_long, C.c_uint8
-            L.hk_multiply_2x_high.restype, L.hk_multiply_2x_high.argtypes = I, [I, I]
-            L.hk_rounding_shift_right.restype, L.hk_rounding_shift_right.argtypes = I, [I, I]
-            L.hk_quantize_i16.restype, L.hk_quantize_i16.argtypes = C.c_int16, [I, I, I]
-            L.hk_quantize_and_relu_u8.restype, L.hk_quantize_and_relu_u8.argtypes = U, [I, I, I, U, U, U]
-            L.hk_quantize.restype, L.hk_quantize.argtypes = None, [C.c_int, P, N, I, I, U, U, U, P]
-            L.hk_tile_filter.restype, L.hk_tile_filter.argtypes = None, [P, P, P, P, U, U, P, P, P, P]
-            L.hk_conv.restype = None
-            L.hk_conv.argtypes = [P, P, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P] + [C.c_int] * 5 + [U, U, I, I, U, U, U]
-            L.hk_depthwise.restype = None
-            L.hk_depthwise.argtypes = [P, P, P, P, P, C.c_int, C.c_int, P, P, P, P, P] + [C.c_int] * 5 + [U, U, I, I, U, U, U]
-            _lib.append(L)
-    return _lib[0]
+lib = Checker("hannk", ("hannk_check.c", "hannk_program_check.c"), _bind).lib
 
 
 def _ints(v):

@@ -1,5 +1,5 @@
 """The evaluator of halide_amd.hannk_model's plans: walks model.setup and model.plan on numpy arrays.  Generator steps go through the plain-C
-checkers of the same name (hannk_checker, hannk_nn_checker, hannk_program_checker); fill, copy_from and gather are numpy (as_strided views and
+checkers of the same name (hannk_checker, hannk_nn_checker, hannk_program_checker: three modules over one object); fill, copy_from and gather are numpy (as_strided views and
 np.take).  Independent of the HIP code; of the package it reads the plan and nothing else."""
 import numpy as np
 

@@ -1,58 +1,16 @@
 """ctypes bindings to tests/cpp/hannk_nn_check.c, the plain-C checker of hannk's pooling, mean, add, mul, softmax and l2_normalization ops
-and of the approx_* helpers — TEST INFRASTRUCTURE ONLY, the sibling of hannk_checker.py.  Built into a shared object of its own, once per
-process, in a temporary directory.  Imports neither the product nor torch.
+and of the approx_* helpers — TEST INFRASTRUCTURE ONLY.  The hkn_* half of hannk_checker.py's one object.  Imports neither the product
+nor torch.
 
 Arrays are the Halide dimensions reversed: an activation [c, x, y, b] is an array of shape (B, H, W, C), a rank-2 operand [x, y] one of
 shape (rows, n).  Strides are read from the arrays (a transposed or broadcast view is passed as it is); `mins` are Halide-ordered."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from hannk_checker import _estrides, _extents, _ints, _longs, lib
+
 FNS = {"approx_log2": 0, "approx_exp2": 1, "approx_reciprocal": 2, "approx_reciprocal_sqrt": 3}
-
-_lock = threading.Lock()
-_lib = []
-
-
-def lib():
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_hannk_nn_checker"), "libhannknncheck.so")
-            subprocess.run(["gcc", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "cpp", "hannk_nn_check.c")], check=True)
-            L = C.CDLL(so)
-            I, P, N = C.c_int, C.c_void_p, C.c_long
-            L.hkn_approx.restype, L.hkn_approx.argtypes = None, [I, I, P, N, I, I, P]
-            L.hkn_pool.restype, L.hkn_pool.argtypes = None, [I, P, P, P, P, P, P, P, P, I, I, I, I, I, I]
-            L.hkn_mean.restype, L.hkn_mean.argtypes = None, [P] * 9
-            L.hkn_add.restype, L.hkn_add.argtypes = None, [P, P, P, I, I, P, P, P, I, I, I, I, I, P, P, P, P]
-            L.hkn_mul.restype, L.hkn_mul.argtypes = None, [P, P, P, I, P, P, P, I, I, C.c_int32, C.c_uint32, I, I, P, P, P, P]
-            L.hkn_softmax.restype, L.hkn_softmax.argtypes = None, [P, P, P, P, I, C.c_uint, I, I, C.c_uint, P, P, P, P]
-            L.hkn_l2_normalization.restype, L.hkn_l2_normalization.argtypes = None, [P, P, P, P, I, P, P, P, P]
-            _lib.append(L)
-    return _lib[0]
-
-
-def _ints(v):
-    return (C.c_int * len(v))(*[int(x) for x in v])
-
-
-def _longs(v):
-    return (C.c_long * len(v))(*[int(x) for x in v])
-
-
-def _estrides(a):
-    return [s // a.itemsize for s in a.strides[::-1]]
-
-
-def _extents(a):
-    return list(a.shape[::-1])
 
 
 def _u8(a):

@@ -1,53 +1,18 @@
 """ctypes bindings to tests/cpp/hannk_program_check.c, the plain-C checker of hannk's Elementwise interpreter, its approx_logistic / approx_tanh
-helpers, copy, upsample_channels and the shallow depthwise variant — TEST INFRASTRUCTURE ONLY, the sibling of hannk_nn_checker.py.  Built into a shared object of its own,
-once per process, in a temporary directory.  Imports neither the product nor torch.
+helpers, copy, upsample_channels and the shallow depthwise variant — TEST INFRASTRUCTURE ONLY.  The hkp_* half of hannk_checker.py's one object.
+Imports neither the product nor torch.
 
 Arrays are the Halide dimensions reversed: a rank-2 operand [x, y] is an array of shape (rows, n), an activation [c, x, y, b] one of shape
 (B, H, W, C).  Strides are read from the arrays (a broadcast view is passed as it is); `mins` are Halide-ordered."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from hannk_checker import _estrides, _ints, _longs, lib
+
 FNS = {"approx_log2p1_exp2": 0, "approx_log2m1_exp2": 1, "approx_logistic": 2, "approx_tanh": 3}
-
-_lock = threading.Lock()
-_lib = []
-
-
-def lib():
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_hannk_program_checker"), "libhannkprogramcheck.so")
-            subprocess.run(["gcc", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so, os.path.join(ROOT, "tests", "cpp", "hannk_program_check.c")], check=True)
-            L = C.CDLL(so)
-            I, P, N = C.c_int, C.c_void_p, C.c_long
-            L.hkp_approx.restype, L.hkp_approx.argtypes = None, [I, P, P, P, N, I, P]
-            L.hkp_op.restype, L.hkp_op.argtypes = None, [I, P, P, P, P, N, P]
-            L.hkp_elementwise.restype, L.hkp_elementwise.argtypes = I, [I, P, P, P, P, I, P, N, P, N, I, I]
-            L.hkp_copy.restype, L.hkp_copy.argtypes = None, [P, P, P, P, I, P, P, P, P]
-            L.hkp_upsample_channels.restype, L.hkp_upsample_channels.argtypes = None, [P, P, P, I, P, P, P, P]
-            L.hkp_depthwise_shallow.restype, L.hkp_depthwise_shallow.argtypes = None, [P, I, I, P, I, I, I, P, P, I, I, I] + [I] * 6 + [C.c_int32, C.c_int32, I, I, I]
-            _lib.append(L)
-    return _lib[0]
-
-
-def _ints(v):
-    return (C.c_int * len(v))(*[int(x) for x in v])
-
-
-def _longs(v):
-    return (C.c_long * len(v))(*[int(x) for x in v])
-
-
-def _estrides(a):
-    return [s // a.itemsize for s in a.strides[::-1]]
 
 
 def _i32(v, shape):

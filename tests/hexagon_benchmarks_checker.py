@@ -1,47 +1,33 @@
 """ctypes bindings to tests/cpp/hexagon_benchmarks_check.c, the plain-C checker of the six filters of apps/hexagon_benchmarks — TEST
-INFRASTRUCTURE ONLY, the sibling of compositing_checker.py.
+INFRASTRUCTURE ONLY.
 
-The checker is one file of integer arithmetic: it needs neither check_canon.c nor a canonical-form switch.  It is built into a
-shared object of its own, once per process, in a temporary directory; tests/test_hexagon_benchmarks.py and scripts/fuzz_parity.py
-both come here.  Imports neither the product nor torch."""
+The checker is one file of integer arithmetic: a checker_lib.Checker without float forms, so without a canonical-form switch.
+tests/test_hexagon_benchmarks.py and scripts/fuzz_parity.py both come here.  Imports neither the product nor torch."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 
 import numpy as np
 
+from checker_lib import Checker
 from parity_helpers import DevArray
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("hexagon_benchmarks_check.c",)
 NAMES = ("conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel")
 MASKED = ("conv3x3a16", "conv3x3a32")
 HALO = {n: (2 if n == "gaussian5x5" else 1) for n in NAMES}
 DRIVER_MASK = np.array([[1, -4, 7], [2, -5, 8], [3, -6, 9]], np.int8)   # [i][j] = mask(j, i), as process.h fills it
 
-_lock = threading.Lock()
-_lib = []
+
+def _bind(L):
+    P, I, G = C.c_void_p, C.c_int, C.c_long
+    for n in NAMES:
+        for f in (getattr(L, "hb_" + n), getattr(L, "hb_" + n + "_verify")):
+            f.restype = None
+            f.argtypes = [P, I, I, G] + ([P] if n in MASKED else []) + [P, I, I, I, I]
+    L.hb_conv3x3_sum.restype, L.hb_conv3x3_sum.argtypes = None, [P, I, I, G, P, P, I, I, I, I]
 
 
-def lib():
-    """The loaded shared object (the raw ctypes library), built on the first call."""
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_hexagon_benchmarks_checker"), "libhexagonbenchmarkscheck.so")
-            subprocess.run(["gcc", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-o", so] + [os.path.join(ROOT, "tests", "cpp", s) for s in SOURCES], check=True)
-            L = C.CDLL(so)
-            P, I, G = C.c_void_p, C.c_int, C.c_long
-            for n in NAMES:
-                for f in (getattr(L, "hb_" + n), getattr(L, "hb_" + n + "_verify")):
-                    f.restype = None
-                    f.argtypes = [P, I, I, G] + ([P] if n in MASKED else []) + [P, I, I, I, I]
-            L.hb_conv3x3_sum.restype, L.hb_conv3x3_sum.argtypes = None, [P, I, I, G, P, P, I, I, I, I]
-            _lib.append(L)
-    return _lib[0]
+lib = Checker("hexagon_benchmarks", ("hexagon_benchmarks_check.c",), _bind).lib
 
 
 def _plane(image):

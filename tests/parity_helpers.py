@@ -25,8 +25,9 @@ def gpu_present():
 
 def same_bits(got, want, what):
     """bit patterns, not values: -0 is not 0, and a NaN equals itself"""
-    assert got.shape == want.shape, what
-    bits = {4: np.uint32, 2: np.uint16, 1: np.uint8}[got.itemsize]
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    bits = {8: np.uint64, 4: np.uint32, 2: np.uint16, 1: np.uint8}[got.itemsize]
     bad = got.view(bits) != want.view(bits)
     assert not bad.any(), f"{what}: {np.count_nonzero(bad)} of {got.size} differ, first at {tuple(np.argwhere(bad)[0])}"
 
@@ -34,10 +35,12 @@ def same_bits(got, want, what):
 def same_bits_or_nan(got, want, what):
     """same_bits, except where the oracle has a NaN: there the library must have a NaN, and nothing else is compared (sign and
     payload of a NaN that an operation produces belong to the processor)"""
-    assert got.shape == want.shape and got.dtype == want.dtype == np.float32, what
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype and got.dtype in (np.float32, np.float64), what
+    bits = np.uint32 if got.dtype == np.float32 else np.uint64
     nan = np.isnan(want)
     assert np.isnan(got[nan]).all(), f"{what}: {np.count_nonzero(~np.isnan(got[nan]))} of the oracle's {np.count_nonzero(nan)} NaNs are numbers"
-    bad = (got.view(np.uint32) != want.view(np.uint32)) & ~nan
+    bad = (got.view(bits) != want.view(bits)) & ~nan
     assert not bad.any(), f"{what}: {np.count_nonzero(bad)} of {got.size} differ, first at {tuple(np.argwhere(bad)[0])}"
 
 
@@ -50,7 +53,8 @@ def kernel_const(hip_file, name):
     return int(m.group(1))
 
 
-SENTINEL = {np.dtype(np.uint8): 0xA5, np.dtype(np.uint16): 0xA5C3, np.dtype(np.float32): np.float32(-1234.5)}
+SENTINEL = {np.dtype(np.uint8): 0xA5, np.dtype(np.uint16): 0xA5C3, np.dtype(np.float32): np.float32(-1234.5),
+            np.dtype(np.float64): np.float64(-1234.5)}
 
 
 class _Strided:
@@ -201,7 +205,7 @@ def call_argv(hl, name, *args):
         if a.kind != 0:
             argv[j] = None if v is None else C.cast(v.ptr, C.c_void_p)
         else:
-            keep.append({(2, 32): C.c_float, (0, 32): C.c_int32}[(a.type.code, a.type.bits)](v))
+            keep.append({(2, 32): C.c_float, (2, 64): C.c_double, (0, 32): C.c_int32}[(a.type.code, a.type.bits)](v))
             argv[j] = C.cast(C.pointer(keep[-1]), C.c_void_p)
     return fn(argv)
 

@@ -1,78 +1,35 @@
-"""ctypes bindings to tests/cpp/resnet50_check.c, the plain-C checker of apps/resnet_50 — TEST INFRASTRUCTURE ONLY, the sibling of
-mat_mul_checker.py.
+"""ctypes bindings to tests/cpp/resnet50_check.c, the plain-C checker of apps/resnet_50 — TEST INFRASTRUCTURE ONLY.
 
-Built with tests/cpp/check_canon.c into a shared object of its own, once per process, in a temporary directory, with
--ffp-contract=off and OpenMP; where the host has the FMA instruction the compiler may emit it for fmaf (-mfma, as mat_mul_checker.py).
-Its canonical-form switch is its own copy of check_canon.c's.  Imports neither the product nor torch.
+A checker_lib.Checker with float forms (a shared object and a canonical-form switch of its own), built with OpenMP; where the host
+has the FMA instruction the compiler may emit it for fmaf (-mfma).  Imports neither the product nor torch.
 
 Arrays are the Halide dimensions reversed, float32, the innermost axis dense, rows and planes possibly padded: an activation (c, x, y) is
 an array of shape (H, W, C), convolution weights (co, kx, ky, ci) one of shape (CI, KH, KW, CO), fc weights (n, c) one of shape (C, N)."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 
 import numpy as np
 
-from mat_mul_checker import host_has_fma
+from checker_lib import Checker, host_has_fma
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("check_canon.c", "resnet50_check.c")
 MODES = ("raw", "scaled", "scaled_relu", "residual_relu")
 NCONV = 53
-
-_lock = threading.Lock()
-_lib = []
 f32 = np.float32
 
 
-def lib():
-    """The loaded shared object (the raw ctypes library), built on the first call."""
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_resnet50_checker"), "librn50check.so")
-            flags = ["-O2", "-ftree-vectorize", "-ffp-contract=off", "-fopenmp", "-Wall", "-Werror"] + (["-mfma"] if host_has_fma() else [])
-            subprocess.run(["gcc"] + flags + ["-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", so]
-                           + [os.path.join(ROOT, "tests", "cpp", s) for s in SOURCES] + ["-lm"], check=True)
-            L = C.CDLL(so)
-            I, P, N = C.c_int, C.c_void_p, C.c_long
-            L.ck_set_canon.argtypes = [I]
-            L.ck_get_canon.restype = I
-            L.rn_out_extent.restype, L.rn_out_extent.argtypes = I, [I, I, I, I]
-            L.rn_conv.restype, L.rn_conv.argtypes = None, [P, N, N, P, N, N, N, P, P, P, P, P, N, N, P, N, N] + [I] * 9
-            L.rn_maxpool.restype, L.rn_maxpool.argtypes = None, [P, N, N, P, N, N] + [I] * 6
-            L.rn_tail.restype, L.rn_tail.argtypes = None, [P, N, N, I, I, I, P, N, P, I, P, P, P, P]
-            L.rn_network.restype, L.rn_network.argtypes = None, [P, P, P, P, P, P, P]
-            _lib.append(L)
-    return _lib[0]
+def _bind(L):
+    I, P, N = C.c_int, C.c_void_p, C.c_long
+    L.rn_out_extent.restype, L.rn_out_extent.argtypes = I, [I, I, I, I]
+    L.rn_conv.restype, L.rn_conv.argtypes = None, [P, N, N, P, N, N, N, P, P, P, P, P, N, N, P, N, N] + [I] * 9
+    L.rn_maxpool.restype, L.rn_maxpool.argtypes = None, [P, N, N, P, N, N] + [I] * 6
+    L.rn_tail.restype, L.rn_tail.argtypes = None, [P, N, N, I, I, I, P, N, P, I, P, P, P, P]
+    L.rn_network.restype, L.rn_network.argtypes = None, [P, P, P, P, P, P, P]
 
 
-def set_canon(fma: int) -> None:
-    """The checker's canonical form (oracle/oracle_common.h): 0 = one rounding per operator, 1 = mul+add pairs contracted."""
-    lib().ck_set_canon(int(fma))
-
-
-def get_canon() -> int:
-    return int(lib().ck_get_canon())
-
-
-class canon:
-    """with resnet50_checker.canon(0): ...   — evaluates the checker in the given form, then restores the one in force."""
-
-    def __init__(self, fma: int):
-        self.fma = int(fma)
-
-    def __enter__(self):
-        self.prev = get_canon()
-        set_canon(self.fma)
-        return self
-
-    def __exit__(self, *exc):
-        set_canon(self.prev)
-        return False
+checker = Checker("resnet50", ("resnet50_check.c",), _bind, float_forms=True,
+                  flags=["-ftree-vectorize", "-fopenmp"] + (["-mfma"] if host_has_fma() else []))
+lib, set_canon, get_canon, canon = checker.lib, checker.set_canon, checker.get_canon, checker.canon
 
 
 def out_extent(size, k, stride, pad):

@@ -1,5 +1,6 @@
-"""tests/checker_lib.py itself: the plain-C checkers build once into one object, and its one canonical-form switch restores
-itself and reaches each of them.  CPU only; needs neither the product library nor a GPU."""
+"""tests/checker_lib.py itself: a Checker builds once; the resize / gaussian_blur / linear_blur checkers are one object whose one
+canonical-form switch restores itself and reaches each of them; another object's switch restores itself too and moves independently.
+CPU only; needs neither the product library nor a GPU."""
 import numpy as np
 import pytest
 
@@ -26,6 +27,34 @@ def test_canon_restores_the_form_in_force():
         with checker_lib.canon(1 - before):
             raise KeyError("on the way out")
     assert checker_lib.get_canon() == before
+
+
+def test_a_checker_builds_once_and_binds():
+    import wavelet_checker
+    second = checker_lib.Checker("second", ("wavelet_check.c",), wavelet_checker._bind, float_forms=True)
+    first = second.lib()
+    assert second.lib() is first and first is not wavelet_checker.lib() and first is not checker_lib.lib()
+    assert first.wc_constant.restype is wavelet_checker.lib().wc_constant.restype and first.ck_get_canon.restype is not None
+    plain = checker_lib.Checker("plain", ("compositing_check.c",), lambda L: None)
+    assert plain.lib() is plain.lib() and not hasattr(plain.lib(), "ck_set_canon")
+
+
+def test_canon_restores_on_a_second_object_and_the_switches_are_independent():
+    import wavelet_checker as wc
+    mine, theirs = checker_lib.get_canon(), wc.get_canon()
+    with wc.canon(1 - theirs):
+        assert wc.get_canon() == 1 - theirs and checker_lib.get_canon() == mine
+        with checker_lib.canon(1 - mine):
+            assert checker_lib.get_canon() == 1 - mine and wc.get_canon() == 1 - theirs
+        assert checker_lib.get_canon() == mine and wc.get_canon() == 1 - theirs
+    assert wc.get_canon() == theirs
+    with pytest.raises(KeyError):
+        with wc.canon(1 - theirs):
+            raise KeyError("on the way out")
+    assert wc.get_canon() == theirs and checker_lib.get_canon() == mine
+    wc.set_canon(1 - theirs)
+    assert checker_lib.get_canon() == mine
+    wc.set_canon(theirs)
 
 
 # Inputs on which the separately built checkers of the parent commit already give different bits in the two forms (measured there):

@@ -19,10 +19,11 @@ import threading
 import numpy as np
 import pytest
 
-import linear_algebra_checker as la
-from linear_algebra_checker import Arr
+from linear_algebra_checker import f32 as la
 from parity_helpers import ROOT, call_argv, call_direct, kernel_const, load_fuzz_parity
 from parity_helpers import gpu_present as _gpu_present, launches as _launches, same_bits as _same, same_bits_or_nan as _same_or_nan
+
+Arr = la.Arr
 
 f32, f64, u32 = np.float32, np.float64, np.uint32
 HIP = "linear_algebra.hip"

@@ -2,7 +2,7 @@
 dger, dgemm x 4), the hblas_d* interface over them (include/hlmi_blas.h), the Python calls and the torch ops.
 
 The contract is restated in include/hlmi_pipelines.h and DESIGN.md 5.10 and, derived from the generators at T = double, in the header of
-the checker tests/cpp/linear_algebra_f64_check.c (bound by tests/linear_algebra_f64_checker.py).  The CPU tests hold the checker to
+the checker tests/cpp/linear_algebra_check.c (its ld_* half, bound by tests/linear_algebra_checker.py).  The CPU tests hold the checker to
 independent evaluations (numpy float64 where every partial result is exact, libm's fma and Python's float operators one output at a time
 elsewhere, both canonical forms), show that the inputs used on the GPU tell V = 4 from 2, 8 and a sequential sum, state the -0 traps in
 numbers, hold the checker to the reference's own acceptance (compareScalars in double against numpy.longdouble at N = 768) and the
@@ -20,10 +20,11 @@ import threading
 import numpy as np
 import pytest
 
-import linear_algebra_f64_checker as ld
-from linear_algebra_f64_checker import Arr, call_argv, same_bits as _same, same_bits_or_nan as _same_or_nan
-from parity_helpers import ROOT, call_direct, kernel_const, load_fuzz_parity
-from parity_helpers import gpu_present as _gpu_present, launches as _launches
+from linear_algebra_checker import f64 as ld
+from parity_helpers import ROOT, call_argv, call_direct, kernel_const, load_fuzz_parity
+from parity_helpers import gpu_present as _gpu_present, launches as _launches, same_bits as _same, same_bits_or_nan as _same_or_nan
+
+Arr = ld.Arr
 
 f32, f64, u64, ext = np.float32, np.float64, np.uint64, np.longdouble
 HIP = "linear_algebra_f64.hip"
@@ -1235,7 +1236,7 @@ def test_seeded_fuzz_slice_of_linear_algebra_f64(on_stream):
 
 @pytest.mark.gpu
 def test_two_host_threads_call_an_s_and_a_d_routine_at_once(hl, canon_lib):
-    import linear_algebra_checker as la
+    from linear_algebra_checker import f32 as la
     rng = np.random.default_rng(5)
     A32, B32, C32 = ((rng.random(s, dtype=f32) * 2 - 1).astype(f32) for s in ((70, 96), (65, 70), (65, 96)))
     with la.canon(hl.canon_fma()):

@@ -1,70 +1,30 @@
 """ctypes bindings to tests/cpp/wavelet_check.c, the plain-C checker of haar_x, inverse_haar_x, daubechies_x and
-inverse_daubechies_x — TEST INFRASTRUCTURE ONLY, the sibling of checker_lib.py.
+inverse_daubechies_x — TEST INFRASTRUCTURE ONLY.
 
-The checker is built with tests/cpp/check_canon.c into a shared object of its own, with checker_lib.py's build line, once per
-process, in a temporary directory; tests/test_wavelet.py and scripts/fuzz_parity.py both come here.  Its canonical-form switch is
-its own copy of check_canon.c's (-Wl,-Bsymbolic), separate from checker_lib's and the oracle's.  Imports neither the product nor
-torch."""
+A checker_lib.Checker with float forms: a shared object of its own, with a canonical-form switch of its own, separate from every
+other checker's and the oracle's.  tests/test_wavelet.py and scripts/fuzz_parity.py both come here.  Imports neither the product
+nor torch."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
-import tempfile
-import threading
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = ("check_canon.c", "wavelet_check.c")
-NAMES = ("haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x")
+from checker_lib import Checker
 
-_lock = threading.Lock()
-_lib = []
+NAMES = ("haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x")
 f32 = np.float32
 
 
-def lib():
-    """The loaded shared object (the raw ctypes library), built on the first call."""
-    with _lock:
-        if not _lib:
-            so = os.path.join(tempfile.mkdtemp(prefix="hlmi_wavelet_checker"), "libwaveletcheck.so")
-            subprocess.run(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-Wl,-Bsymbolic", "-I", os.path.join(ROOT, "oracle"), "-o", so]
-                           + [os.path.join(ROOT, "tests", "cpp", s) for s in SOURCES] + ["-lm"], check=True)
-            L = C.CDLL(so)
-            I, P = C.c_int, C.c_void_p
-            L.ck_set_canon.argtypes = [I]
-            L.ck_get_canon.restype = I
-            L.wc_constant.restype, L.wc_constant.argtypes = C.c_float, [I]
-            L.wc_forward.argtypes = [I, P, I, I, I, I, P, I, I, I, I, I, I]
-            L.wc_inverse.argtypes = [I, P, I, I, I, I, I, I, P, I, I, I, I]
-            _lib.append(L)
-    return _lib[0]
+def _bind(L):
+    I, P = C.c_int, C.c_void_p
+    L.wc_constant.restype, L.wc_constant.argtypes = C.c_float, [I]
+    L.wc_forward.argtypes = [I, P, I, I, I, I, P, I, I, I, I, I, I]
+    L.wc_inverse.argtypes = [I, P, I, I, I, I, I, I, P, I, I, I, I]
 
 
-def set_canon(fma: int) -> None:
-    """The checker's canonical form (oracle/oracle_common.h): 0 = one rounding per operator, 1 = mul+add pairs contracted."""
-    lib().ck_set_canon(int(fma))
-
-
-def get_canon() -> int:
-    return int(lib().ck_get_canon())
-
-
-class canon:
-    """with wavelet_checker.canon(0): ...   — evaluates the checker in the given form, then restores the one in force."""
-
-    def __init__(self, fma: int):
-        self.fma = int(fma)
-
-    def __enter__(self):
-        self.prev = get_canon()
-        set_canon(self.fma)
-        return self
-
-    def __exit__(self, *exc):
-        set_canon(self.prev)
-        return False
+checker = Checker("wavelet", ("wavelet_check.c",), _bind, float_forms=True)
+lib, set_canon, get_canon, canon = checker.lib, checker.set_canon, checker.get_canon, checker.canon
 
 
 def constants():
