@@ -482,6 +482,54 @@ def run(only=(), samples=5, sink=None, cpu=False, batched=True):
                      {"alg_bytes": nbytes, "kernels_ms": kernels(call, o), "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, o)},
                       "fused_not_slower": bool(t <= tg)})
 
+    # ---- reaction_diffusion: the app's own 1024x1024x3 state (apps/HelloWasm/app/core.cpp) and 4096x4096x3, whose 201 MB do not fit the
+    #      on-die caches: one update, render, update + render, and hlmi_reaction_diffusion_run of 16 steps under each steps-per-launch
+    #      instance (HLMI_RD_STEPS_PER_LAUNCH = 1, 2, 4) and under the hook (one thread per output, one launch per step).  Compulsory
+    #      traffic: 24 B/px per update, 16 B/px per render; the yardstick is membench's copy rate of the same run.
+    if not only or "reaction_diffusion" in only:
+        for W, H in ((1024, 1024), (4096, 4096)):
+            s, n = hl.Buffer(rng.random((3, H, W), dtype=np.float32)), hl.Buffer(np.zeros((3, H, W), np.float32))
+            pix = hl.Buffer(np.zeros((H, W), np.uint32))
+            s.copy_to_device()
+            mouse = (W // 2, H // 2)
+            iters = 50 if W == 1024 else 10
+
+            def line(name, what, call, general, out, nbytes, extra=None):
+                t = timed(call, out, iters)
+                clock = last_clock[0]
+                tg = timed(general, out, iters)
+                last_clock[0] = clock
+                emit(name, f"apps/HelloWasm {what}, f32 {W}x{H}x3", t, W * H, "hbm", nbytes / t / 1e9, HBM_PEAK_GBS, "GB/s",
+                     {"alg_bytes": nbytes, "kernels_ms": kernels(call, out), "general_path": {"ms_per_call": round(tg * 1e3, 4), "kernels_ms": kernels(general, out)},
+                      "fused_not_slower": bool(t <= tg), **(extra or {})})
+
+            line("reaction_diffusion_update", "reaction_diffusion_update", lambda: hl.reaction_diffusion_update(s, *mouse, 7, n),
+                 lambda: hl.debug_reaction_diffusion_general("reaction_diffusion_update", s, *mouse, 7, out=n), n, 24 * W * H)
+            line("reaction_diffusion_render", "reaction_diffusion_render", lambda: hl.reaction_diffusion_render(s, pix),
+                 lambda: hl.debug_reaction_diffusion_general("reaction_diffusion_render", s, render=pix), pix, 16 * W * H)
+            line("reaction_diffusion_update_render", "reaction_diffusion_update + reaction_diffusion_render, two calls against run of one step",
+                 lambda: hl.reaction_diffusion_run(s, *mouse, 7, 1, n, pix),
+                 lambda: (hl.reaction_diffusion_update(s, *mouse, 7, n), hl.reaction_diffusion_render(n, pix)), pix, 28 * W * H)
+            before = os.environ.get("HLMI_RD_STEPS_PER_LAUNCH")
+            try:
+                for S in ("plan", 1, 2, 4):
+                    if S == "plan":
+                        os.environ.pop("HLMI_RD_STEPS_PER_LAUNCH", None)
+                    else:
+                        os.environ["HLMI_RD_STEPS_PER_LAUNCH"] = str(S)
+                    for with_render in (False, True):
+                        r = pix if with_render else None
+                        line(f"reaction_diffusion_run16_{S}{'_render' if with_render else ''}",
+                             f"hlmi_reaction_diffusion_run, 16 steps, steps per launch {S}{', rendered' if with_render else ''}",
+                             lambda: hl.reaction_diffusion_run(s, *mouse, 7, 16, n, r),
+                             lambda: hl.debug_reaction_diffusion_general("run", s, *mouse, 7, 16, n, r), n, (16 * 24 + (4 if with_render else 0)) * W * H,
+                             {"steps": 16, "steps_per_launch": S})
+            finally:
+                if before is None:
+                    os.environ.pop("HLMI_RD_STEPS_PER_LAUNCH", None)
+                else:
+                    os.environ["HLMI_RD_STEPS_PER_LAUNCH"] = before
+
     # ---- compositing: six u8 RGBA layers and five op codes at 1536x2560 (the generator's estimate and the size of the image the
     #      reference's test feeds apps/compositing/process.cpp) and at 7680x4320, with the driver's blobs and op codes {4, 3, 2, 1, 0}
     #      (process.cpp:33-51) over a noise input.  Compulsory traffic: 24 B/px read, 4 B/px written; the yardstick is membench's copy

@@ -466,6 +466,7 @@ _fn = {name: _bind(name) for name in
         "camera_pipe"] + [f"resize_{k}_{t}_{d}" for k in RESIZE_KERNELS for t in _RESIZE_TYPES for d in ("up", "down")]
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
        + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]
+       + ["reaction_diffusion_init", "reaction_diffusion_update", "reaction_diffusion_render"]
        + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"] + ["resnet50"]
        + ["fft_forward_r2c", "fft_inverse_c2r", "fft_forward_c2c", "fft_inverse_c2c"]
        + ["halide_scopy_impl", "halide_sscal_impl", "halide_saxpy_impl", "halide_sdot", "halide_sasum", "halide_sgemv_notrans",
@@ -715,6 +716,47 @@ def debug_wavelet_general(name: str, input, output) -> int:
     fn.restype = C.c_int
     fn.argtypes = [C.c_char_p, _BP, _BP]
     return _check(fn(name.encode(), _as_ptr(input), _as_ptr(output)))
+
+
+def reaction_diffusion_init(output) -> int:
+    """apps/HelloWasm reaction_diffusion: f32 [W,H,C] = random_float() hashed over the coordinates; any output region."""
+    return _check(_fn["reaction_diffusion_init"](_as_ptr(output)))
+
+
+def reaction_diffusion_update(state, mouse_x, mouse_y, frame, new_state) -> int:
+    """apps/HelloWasm reaction_diffusion: one time step, f32 [W,H,3] -> f32 [W,H,3]; new_state must hold the state's edge rows and
+    columns and the clobber box around the mouse (include/hlmi_pipelines.h)."""
+    return _check(_fn["reaction_diffusion_update"](_as_ptr(state), int(mouse_x), int(mouse_y), int(frame), _as_ptr(new_state)))
+
+
+def reaction_diffusion_render(state, render) -> int:
+    """apps/HelloWasm reaction_diffusion: f32 [W,H,3] -> u32 [W,H], the contour colours packed B | G << 8 | R << 16 | 255 << 24."""
+    return _check(_fn["reaction_diffusion_render"](_as_ptr(state), _as_ptr(render)))
+
+
+def _rd_int32(v):
+    return (int(v) + 2 ** 31) % 2 ** 32 - 2 ** 31
+
+
+def reaction_diffusion_run(state, mouse_x, mouse_y, frame0, steps, new_state, render=None) -> int:
+    """`steps` updates with frames frame0 .. frame0 + steps - 1 from state into new_state and, render given, one render of the final
+    state: what that many reaction_diffusion_update calls and one reaction_diffusion_render give, in as few launches as the plan
+    allows (the switch HLMI_RD_STEPS_PER_LAUNCH = 1, 2, 4 overrides its steps per launch)."""
+    fn = lib.hlmi_reaction_diffusion_run
+    fn.restype = C.c_int
+    fn.argtypes = [_BP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _BP, _BP]
+    return _check(fn(_as_ptr(state), int(mouse_x), int(mouse_y), _rd_int32(frame0), int(steps), _as_ptr(new_state), None if render is None else _as_ptr(render)))
+
+
+def debug_reaction_diffusion_general(name: str, state=None, mouse_x=0, mouse_y=0, frame=0, steps=1, out=None, render=None) -> int:
+    """Test and measurement hook: "reaction_diffusion_init" (out), "reaction_diffusion_update" (state, mouse_x, mouse_y, frame, out),
+    "reaction_diffusion_render" (state, render) or "run" (reaction_diffusion_run's arguments, out = new_state) with one thread per
+    output and, for "run", one launch per step."""
+    fn = lib.hlmi_reaction_diffusion_general
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, _BP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _BP, _BP]
+    p = lambda b: None if b is None else _as_ptr(b)
+    return _check(fn(name.encode(), p(state), int(mouse_x), int(mouse_y), _rd_int32(frame), int(steps), p(out), p(render)))
 
 
 def compositing(layers, ops, output) -> int:

@@ -419,6 +419,13 @@ extern "C" int hlmi_linear_blur_general(const char *name, halide_buffer_t *input
 // is kept anywhere.
 extern "C" int hlmi_wavelet_general(const char *name, halide_buffer_t *in, halide_buffer_t *out);
 
+// reaction_diffusion.hip: "reaction_diffusion_init" (reads `out`), "reaction_diffusion_update" (state, mouse_x, mouse_y, frame, out),
+// "reaction_diffusion_render" (state, render) or "run" (hlmi_reaction_diffusion_run's arguments, out = new_state) with one thread per
+// output, every tap a clamped load from global memory and, for "run", one launch per step and a separate render, for the tests
+// (default == general bit for bit) and for bench_apps.py.  Arguments a name does not read are ignored.  Per call: no mode is kept.
+extern "C" int hlmi_reaction_diffusion_general(const char *name, halide_buffer_t *state, int32_t mouse_x, int32_t mouse_y, int32_t frame, int32_t steps,
+                                               halide_buffer_t *out, halide_buffer_t *render);
+
 // compositing.hip: the same call with one thread per pixel and byte loads, written from the operator table of hlmi_pipelines.h, for
 // the tests (default == general bit for bit) and for bench_apps.py.  Per call: no mode is kept anywhere.
 extern "C" int hlmi_compositing_general(halide_buffer_t *layer_rgba_0, halide_buffer_t *layer_rgba_1, halide_buffer_t *layer_rgba_2,

@@ -314,6 +314,66 @@ def inverse_daubechies_x(input: torch.Tensor) -> torch.Tensor:
     return _wavelet_inverse("inverse_daubechies_x", hl.inverse_daubechies_x, input)
 
 
+def _rd_state_check(name, state):
+    if state.dim() != 3 or state.shape[0] != 3 or state.dtype != torch.float32:
+        raise TypeError(f"{name} takes a (3, H, W) float32 tensor")
+
+
+def _rd_pixels(t):
+    """the u32 halide buffer over an int32 tensor of packed pixels (torch has no arithmetic on uint32: the bits are what matters)"""
+    return hl.Buffer.wrap_device(t.data_ptr(), np.uint32, list(reversed(t.shape)), list(reversed(t.stride())))
+
+
+@torch.library.custom_op("hlmi::reaction_diffusion_init", mutates_args=())
+def reaction_diffusion_init(height: int, width: int, device: torch.device) -> torch.Tensor:
+    """apps/HelloWasm reaction_diffusion: a (3, height, width) float32 state of random_float() hashed over the coordinates."""
+    out = torch.empty((3, height, width), dtype=torch.float32, device=device)
+    with _Wrapped(out) as (o,):
+        hl.reaction_diffusion_init(o)
+    return out
+
+
+@torch.library.custom_op("hlmi::reaction_diffusion_update", mutates_args=())
+def reaction_diffusion_update(state: torch.Tensor, mouse_x: int, mouse_y: int, frame: int) -> torch.Tensor:
+    """apps/HelloWasm reaction_diffusion: one time step, (3, H, W) float32 -> (3, H, W) float32."""
+    _rd_state_check("reaction_diffusion_update", state)
+    out = torch.empty(tuple(state.shape), dtype=torch.float32, device=state.device)
+    with _Wrapped(state, out) as (a, o):
+        hl.reaction_diffusion_update(a, mouse_x, mouse_y, frame, o)
+    return out
+
+
+@torch.library.custom_op("hlmi::reaction_diffusion_render", mutates_args=())
+def reaction_diffusion_render(state: torch.Tensor) -> torch.Tensor:
+    """apps/HelloWasm reaction_diffusion: (3, H, W) float32 -> (H, W) int32 holding the packed pixels' 32 bits, B | G << 8 | R << 16 |
+    255 << 24."""
+    _rd_state_check("reaction_diffusion_render", state)
+    out = torch.empty(tuple(state.shape[1:]), dtype=torch.int32, device=state.device)
+    with _Wrapped(state) as (a,):
+        p = _rd_pixels(out)
+        try:
+            hl.reaction_diffusion_render(a, p)
+        finally:
+            p.device_detach()
+    return out
+
+
+@torch.library.custom_op("hlmi::reaction_diffusion_run", mutates_args=())
+def reaction_diffusion_run(state: torch.Tensor, mouse_x: int, mouse_y: int, frame0: int, steps: int) -> tuple[torch.Tensor, torch.Tensor]:
+    """`steps` updates with frames frame0 .. frame0 + steps - 1 and one render of the final state: the new (3, H, W) float32 state and the
+    (H, W) int32 packed pixels, in as few launches as the library's plan allows."""
+    _rd_state_check("reaction_diffusion_run", state)
+    out = torch.empty(tuple(state.shape), dtype=torch.float32, device=state.device)
+    pix = torch.empty(tuple(state.shape[1:]), dtype=torch.int32, device=state.device)
+    with _Wrapped(state, out) as (a, o):
+        p = _rd_pixels(pix)
+        try:
+            hl.reaction_diffusion_run(a, mouse_x, mouse_y, frame0, steps, o, p)
+        finally:
+            p.device_detach()
+    return out, pix
+
+
 @torch.library.custom_op("hlmi::compositing", mutates_args=())
 def compositing(layers: list[torch.Tensor], ops: torch.Tensor) -> torch.Tensor:
     """apps/compositing: six (4, H, W) uint8 layers and five int32 op codes (0 over, 1 atop, 2 xor, 3 in, 4 out; any other code skips
@@ -717,6 +777,26 @@ def _(input):
 @inverse_daubechies_x.register_fake
 def _(input):
     return input.new_empty((input.shape[1], 2 * input.shape[2]))
+
+
+@reaction_diffusion_init.register_fake
+def _(height, width, device):
+    return torch.empty((3, height, width), dtype=torch.float32, device=device)
+
+
+@reaction_diffusion_update.register_fake
+def _(state, mouse_x, mouse_y, frame):
+    return state.new_empty(tuple(state.shape))
+
+
+@reaction_diffusion_render.register_fake
+def _(state):
+    return state.new_empty(tuple(state.shape[1:]), dtype=torch.int32)
+
+
+@reaction_diffusion_run.register_fake
+def _(state, mouse_x, mouse_y, frame0, steps):
+    return state.new_empty(tuple(state.shape)), state.new_empty(tuple(state.shape[1:]), dtype=torch.int32)
 
 
 @compositing.register_fake

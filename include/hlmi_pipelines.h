@@ -340,6 +340,44 @@ HLMI_DECLARE_AUX(daubechies_x)
 int inverse_daubechies_x(struct halide_buffer_t *in, struct halide_buffer_t *out);
 HLMI_DECLARE_AUX(inverse_daubechies_x)
 
+/* apps/HelloWasm/generator/reaction_diffusion_generator.cpp — a three-channel reaction-diffusion simulation, one update per frame.
+ * reaction_diffusion_init (:10-12): output f32 [x, y, c] = random_float(), any region.
+ * reaction_diffusion_update (:34-105): state, new_state f32 [x, y, c], c pinned to [0, 3) on both (-8).  The pure stage: with in =
+ * repeat_edge(state) over the state's own min and extent, blur = ((in(x-2) + in(x-1) + in(x) + in(x+1) + in(x+2)) + (the same in y))
+ * * 0.1f per channel, each five-tap sum left to right; R, G, B = blur * (0.5f + (0.5f * blur) * (3 - 2 * blur)); dR = B * ((1 - R) - G),
+ * dG = (1 - B) * (R - G), dB = (((1 - B) + (2 * G) * R) - R) - G; boost = 5 * max(0, 1.f - float(mx * mx + my * my) * 0.001f) + 1 with
+ * mx = mouse_x - x, my = mouse_y - y in wrapping int32; R += (dR * 0.14f) * boost, G += (dG * 0.05f) * boost, B += (dB * 0.065f) * boost;
+ * each clamped to [0, 1] as max(min(v, 1), 0).  Then, in this order: row state.min(1) and row state.max(1) = random_float(frame) * 0.2f
+ * (hashed over c and x), column state.min(0) and column state.max(0) (hashed over c and y), each over the output's range in the other
+ * dimension; then every pixel of the box x in [clamp(mouse_x - 10, 0, W - 1), clamp(mouse_x + 10, 0, W - 1)], y alike with H — W and
+ * H the state's EXTENTS, the coordinates absolute whatever the mins — with float(dx * dx + dy * dy) < 100.0f becomes 0.25f * (n(x, y) +
+ * n(x + 1, y) + n(x + 1, y + 1) + n(x, y + 1)), n = random_float(frame) hashed over c, y, x.  Float forms as in
+ * oracle/oracle_common.h; the contracted one fuses (0.5f * blur) * (3 - 2 blur) + 0.5f, 3 - 2 * blur, (2 * G) * R + (1 - B),
+ * 1 - d2 * 0.001f, 5 * max + 1 and the three rate products into their adds.  new_state must hold the two rows, the two columns and the
+ * clobber box (-4); the pure stage is defined for any output region.  An empty state under an output that is not empty: -4.  Bounds
+ * query: new_state grows to hold its own region and what the updates write, state keeps x and y as passed; both get channels [0, 3).
+ * The frame counter is an int32 hashed as uint32.
+ * reaction_diffusion_render (:150-174): state f32 [x, y, c] -> render u32 [x, y]; k = min(((s * (1.01f - s)) * 4)^4, 1) per channel,
+ * R = min(k0, (k1 + k2) * 0.5f), G = clamp(((k1 + k0) + k2) * 0.5f, 0, 1), B = max(k0, max(k1, k2)), each cast<uint32_t>(ch * 255) &
+ * 0xff, packed B | G << 8 | R << 16 | 255 << 24.  The state must cover render's x and y and channels [0, 3) (-4).  A NaN state has no
+ * defined cast.  No estimates and no _auto_schedule twins: the reference has none.
+ * The random hash (src/Random.cpp) is restated in halide_amd/csrc/hlmi_random.h; the call ids and definition tags it is fed are
+ * derived by reading the reference and are NOT confirmed against a Halide build. */
+int reaction_diffusion_init(struct halide_buffer_t *output);
+HLMI_DECLARE_AUX(reaction_diffusion_init)
+int reaction_diffusion_update(struct halide_buffer_t *state, int32_t mouse_x, int32_t mouse_y, int32_t frame, struct halide_buffer_t *new_state);
+HLMI_DECLARE_AUX(reaction_diffusion_update)
+int reaction_diffusion_render(struct halide_buffer_t *state, struct halide_buffer_t *render);
+HLMI_DECLARE_AUX(reaction_diffusion_render)
+/* Library extension (no argument table, _argv or _metadata): `steps` >= 1 updates with frames frame0 .. frame0 + steps - 1 (wrapping
+ * int32) from state into new_state, then, render non-null, one render of the final state: bit for bit what that many calls of
+ * reaction_diffusion_update and one of reaction_diffusion_render produce, in as few launches as the plan allows.  state and
+ * new_state (and render) have the same box in x and y, state is not modified, state and new_state do not overlap; steps < 1, unequal
+ * boxes or an overlap: -8.  Intermediate states live in new_state and in the stream's workspace.  The switch
+ * HLMI_RD_STEPS_PER_LAUNCH (1, 2, 4) overrides the plan's steps per launch. */
+int hlmi_reaction_diffusion_run(struct halide_buffer_t *state, int32_t mouse_x, int32_t mouse_y, int32_t frame0, int32_t steps,
+                                struct halide_buffer_t *new_state, struct halide_buffer_t *render);
+
 /* apps/compositing/compositing_generator.cpp:17-23,25-154 — Porter-Duff blending of six u8 RGBA layers [W,H,4] by five run-time
  * op codes (int32 [5]) into u8 [W,H,4]: a small interpreter.  THE CONTRACT IS THE GENERATOR'S INTEGER FORM (the branch a target
  * without a GPU feature takes, and what the reference's own test runs): the float form normalises by 255.0f / alpha, which at

@@ -438,6 +438,79 @@ def fuzz_wavelet(rng):
     return desc, r == 0 and same(np.ascontiguousarray(o.numpy()), want)
 
 
+def fuzz_reaction_diffusion(rng):
+    """One of reaction_diffusion_init, reaction_diffusion_update, reaction_diffusion_render and hlmi_reaction_diffusion_run on a random
+    frame (mins, strides, mouse inside, on the border or far outside, frame numbers up to the int32 wrap), on either path and, for run,
+    under a random HLMI_RD_STEPS_PER_LAUNCH, against tests/cpp/reaction_diffusion_check.c (tests/reaction_diffusion_checker.py).
+    Frames reach several 64 x 32 tiles; update also takes outputs larger than the frame."""
+    import reaction_diffusion_checker as rdc
+    rdc.set_canon(hl.canon_fma())
+    what = ("init", "update", "render", "run")[int(rng.integers(0, 4))]
+    general = bool(rng.integers(0, 2))
+    w, h = rdim(rng, 1, 200), rdim(rng, 1, 100)
+    mins = (0, 0) if rng.random() < 0.5 else (int(rng.integers(-9, 1)), int(rng.integers(-5, 1)))
+    fn = hl.lib.hlmi_reaction_diffusion_general
+    fn.restype, fn.argtypes = hl.C.c_int, [hl.C.c_char_p, hl._BP, hl.C.c_int32, hl.C.c_int32, hl.C.c_int32, hl.C.c_int32, hl._BP, hl._BP]
+    if what == "init":
+        nc, oc = int(rng.integers(1, 5)), int(rng.integers(-2, 3))
+        o = hl.Buffer(_strided_rows(rng, (nc, h, w)), mins=mins + (oc,))
+        r = fn(b"reaction_diffusion_init", None, 0, 0, 0, 0, o.ptr, None) if general else hl._fn["reaction_diffusion_init"](o.ptr)
+        return f"init{' general' if general else ''} {(w, h, nc)} min {mins + (oc,)} -> {r}", r == 0 and same(np.ascontiguousarray(o.numpy()), rdc.init((nc, h, w), mins + (oc,)))
+    vals = rng.random((3, h, w), dtype=f32) * f32(2) - f32(0.5)
+    src = _strided_rows(rng, vals.shape)
+    src[...] = vals
+    a = hl.Buffer(src, mins=mins + (0,))
+    if what == "render":
+        vals = np.clip(vals, 0, 1)
+        src[...] = vals
+        o = hl.Buffer(np.ascontiguousarray(_strided_rows(rng, (h, w))).astype(np.uint32), mins=mins)
+        r = fn(b"reaction_diffusion_render", a.ptr, 0, 0, 0, 0, None, o.ptr) if general else hl._fn["reaction_diffusion_render"](a.ptr, o.ptr)
+        return f"render{' general' if general else ''} {(w, h)} min {mins} -> {r}", r == 0 and np.array_equal(np.ascontiguousarray(o.numpy()), rdc.render(vals))
+    # a mouse whose clobber box the frame holds: the box is in extent coordinates, the frame starts at mins <= 0
+    far = rng.random() < 0.3
+    mouse = (int(rng.integers(-10, w + mins[0] - 10)) if w + mins[0] > 0 else -1000, int(rng.integers(-10, h + mins[1] - 10)) if h + mins[1] > 0 else -1000)
+    if far:
+        mouse = (-1000 - int(rng.integers(0, 2 ** 30)), mouse[1])
+    box = rdc.clobber_box(w, h, *mouse)
+    if box[1] > mins[0] + w - 1 or box[3] > mins[1] + h - 1:
+        mouse = (-1000, -1000)   # the degenerate box at (0, 0): held, mins <= 0
+        if mins[0] + w - 1 < 0 or mins[1] + h - 1 < 0:
+            mins = (0, 0)
+            a = hl.Buffer(src, mins=(0, 0, 0))
+    frame = int(rng.choice([0, 1, 77, 2 ** 31 - 2, -2 ** 31, -5]))
+    if what == "update":
+        grow = (0, 0, 0, 0) if rng.random() < 0.6 else tuple(int(v) for v in rng.integers(0, 6, 4))
+        out_shape, out_min = (3, h + grow[1] + grow[3], w + grow[0] + grow[2]), (mins[0] - grow[0], mins[1] - grow[1])
+        o = hl.Buffer(_strided_rows(rng, out_shape), mins=out_min + (0,))
+        want = rdc.update(vals, *mouse, frame, state_min=mins, out_shape=out_shape, out_min=out_min)
+        r = (fn(b"reaction_diffusion_update", a.ptr, mouse[0], mouse[1], frame, 0, o.ptr, None) if general
+             else hl._fn["reaction_diffusion_update"](a.ptr, mouse[0], mouse[1], frame, o.ptr))
+        return (f"update{' general' if general else ''} {(w, h)} min {mins} mouse {mouse} frame {frame} out {out_shape[::-1]} min {out_min} -> {r}",
+                r == 0 and same(np.ascontiguousarray(o.numpy()), want))
+    steps, S = int(rng.integers(1, 10)), int(rng.choice([0, 1, 2, 4]))   # 0: the switch unset, the plan's choice
+    with_render = bool(rng.integers(0, 2))
+    o = hl.Buffer(_strided_rows(rng, vals.shape), mins=mins + (0,))
+    p = hl.Buffer(np.zeros((h, w), np.uint32), mins=mins) if with_render else None
+    want = rdc.run(vals, *mouse, frame, steps, state_min=mins)
+    before = os.environ.get("HLMI_RD_STEPS_PER_LAUNCH")
+    os.environ.pop("HLMI_RD_STEPS_PER_LAUNCH", None)
+    if S:
+        os.environ["HLMI_RD_STEPS_PER_LAUNCH"] = str(S)
+    try:
+        if general:
+            r = fn(b"run", a.ptr, mouse[0], mouse[1], frame, steps, o.ptr, p.ptr if p else None)
+        else:
+            run = hl.lib.hlmi_reaction_diffusion_run
+            run.restype, run.argtypes = hl.C.c_int, [hl._BP, hl.C.c_int32, hl.C.c_int32, hl.C.c_int32, hl.C.c_int32, hl._BP, hl._BP]
+            r = run(a.ptr, mouse[0], mouse[1], frame, steps, o.ptr, p.ptr if p else None)
+    finally:
+        os.environ.pop("HLMI_RD_STEPS_PER_LAUNCH", None)
+        if before is not None:
+            os.environ["HLMI_RD_STEPS_PER_LAUNCH"] = before
+    ok = r == 0 and same(np.ascontiguousarray(o.numpy()), want) and (p is None or np.array_equal(np.ascontiguousarray(p.numpy()), rdc.render(want)))
+    return f"run{' general' if general else ''} S {S} steps {steps} {(w, h)} min {mins} mouse {mouse} frame0 {frame} render {with_render} -> {r}", ok
+
+
 def _u8_view(rng, shape):
     """a zeroed uint8 (C, H, W) view inside one allocation: dense, or with longer rows, planes further apart (channel strides that
     are no multiple of 4 among them) and a first element that is not the allocation's"""
@@ -1139,6 +1212,7 @@ CASES = {k[5:]: v for k, v in list(globals().items()) if k.startswith("case_")}
 CASES["resize"] = fuzz_resize   # these three: their checkers are not oracle/'s (tests/checker_lib.py)
 CASES["gaussian_blur"] = fuzz_gaussian_blur
 CASES["linear_blur"] = fuzz_linear_blur   # both entry points
+CASES["reaction_diffusion"] = fuzz_reaction_diffusion   # init, update, render and run; its checker has a module of its own
 CASES["wavelet"] = fuzz_wavelet   # all four entry points; its checker has a module of its own (tests/wavelet_checker.py)
 CASES["compositing"] = fuzz_compositing   # integer throughout: its checker (tests/compositing_checker.py) has no canonical form
 CASES["hexagon_benchmarks"] = fuzz_hexagon_benchmarks   # all six entry points; integer throughout (tests/hexagon_benchmarks_checker.py)
