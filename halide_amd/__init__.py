@@ -467,7 +467,7 @@ _fn = {name: _bind(name) for name in
        + ["gaussian_blur_direct"] + [f"gaussian_blur_{u}_{d}_{f}" for u in (2, 3, 4) for d in (1, 2, 3) for f in (2, 4, 8, 16)]
        + ["linear_blur", "simple_blur"] + ["haar_x", "inverse_haar_x", "daubechies_x", "inverse_daubechies_x"] + ["compositing"]
        + ["reaction_diffusion_init", "reaction_diffusion_update", "reaction_diffusion_render"]
-       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"] + ["resnet50"]
+       + ["conv3x3a16", "conv3x3a32", "dilate3x3", "median3x3", "gaussian5x5", "sobel"] + ["mat_mul"] + ["resnet50", "resnet50_batch"]
        + ["fft_forward_r2c", "fft_inverse_c2r", "fft_forward_c2c", "fft_inverse_c2c"]
        + ["halide_scopy_impl", "halide_sscal_impl", "halide_saxpy_impl", "halide_sdot", "halide_sasum", "halide_sgemv_notrans",
           "halide_sgemv_trans", "halide_sger_impl", "halide_sgemm_notrans", "halide_sgemm_transA", "halide_sgemm_transB",
@@ -910,6 +910,74 @@ def debug_resnet50_tail(input, fc_weights, fc_bias, output) -> int:
     fn = lib.hlmi_debug_resnet50_tail
     fn.restype, fn.argtypes = C.c_int, [_BP] * 4
     return _check(fn(*[_as_ptr(b) for b in (input, fc_weights, fc_bias, output)]))
+
+
+# resnet50_batch, a library extension (the reference's generator has no batch dimension): N images per call, each bit for bit what
+# resnet50 gives it.  Arrays: images (N, 224, 224, 3), output (N, 1000).
+def resnet50_batch(input, params, output) -> int:
+    """f32 [3, 224, 224, N] and resnet50's 267 parameters -> [<= 1000, N]: column n is what resnet50 writes for image n, bit for bit.
+    The image range is `output`'s dimension 1; any N >= 1 runs in chunks of 64 images (HLMI_RN50_BATCH_CHUNK = 1 .. 64 overrides)."""
+    return _check(_fn["resnet50_batch"](*_resnet50_args(input, params, output)))
+
+
+def debug_resnet50_batch_general(input, params, output) -> int:
+    """Test and measurement hook: resnet50_batch with every convolution on the one-thread-per-output kernel."""
+    fn = lib.hlmi_resnet50_batch_general
+    fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_void_p)]
+    args = _resnet50_args(input, params, output)
+    return _check(fn((C.c_void_p * len(args))(*[None if a is None else C.cast(a, C.c_void_p) for a in args])))
+
+
+# `variant` of the batched layer hook: the plan's choice, the general kernel, then each MFMA tile instance (co x pixels) in turn
+RESNET50_LAYER_VARIANTS = ("plan", "general", "mfma_64x64", "mfma_64x128")
+RESNET50_LAUNCH_NAMES = ("resnet50_conv_mfma", "resnet50_conv_general", "resnet50_maxpool", "resnet50_avgpool", "resnet50_fc", "resnet50_softmax",
+                         "resnet50_conv_mfma_wide")
+
+
+def debug_resnet50_layer_batch(input, weights, gamma, beta, mu, sig, residual, stride, pad, mode, output, variant=0) -> int:
+    """debug_resnet50_layer over N images: input [CI, W, H, N], residual and output [CO, OW, OH, N]; variant: an index into or a name of
+    RESNET50_LAYER_VARIANTS (an unknown index is refused with -8)."""
+    fn = lib.hlmi_debug_resnet50_layer_batch
+    fn.restype, fn.argtypes = C.c_int, [_BP] * 7 + [C.c_int32] * 4 + [_BP]
+    mode = RESNET50_LAYER_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    variant = RESNET50_LAYER_VARIANTS.index(variant) if isinstance(variant, str) else int(variant)
+    return _check(fn(*[_as_ptr(b) for b in (input, weights, gamma, beta, mu, sig, residual)], int(stride), int(pad), mode, variant, _as_ptr(output)))
+
+
+def debug_resnet50_maxpool_batch(input, k, stride, pad, output) -> int:
+    """debug_resnet50_maxpool over N images: [C, W, H, N] -> [C, OW, OH, N]."""
+    fn = lib.hlmi_debug_resnet50_maxpool_batch
+    fn.restype, fn.argtypes = C.c_int, [_BP, C.c_int32, C.c_int32, C.c_int32, _BP]
+    return _check(fn(_as_ptr(input), int(k), int(stride), int(pad), _as_ptr(output)))
+
+
+def debug_resnet50_tail_batch(input, fc_weights, fc_bias, output) -> int:
+    """debug_resnet50_tail over N images: [C, W, H, N] -> [classes, N]."""
+    fn = lib.hlmi_debug_resnet50_tail_batch
+    fn.restype, fn.argtypes = C.c_int, [_BP] * 4
+    return _check(fn(*[_as_ptr(b) for b in (input, fc_weights, fc_bias, output)]))
+
+
+def debug_resnet50_batch_plan(n, general=False) -> dict:
+    """The launch plan of resnet50_batch for n images, without a device: {"chunk": images per run of the plan in force, "chunks": one list
+    per run, each of 57 steps {"name", "grid": (x, y), "tile": (co, pixels) or None}}."""
+    fn = lib.hlmi_debug_resnet50_batch_plan
+    fn.restype, fn.argtypes = C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    if n < 1:
+        raise ValueError("debug_resnet50_batch_plan takes n >= 1")
+    chunk, steps = C.c_int32(0), (C.c_int32 * (64 * 5))()
+
+    def run(images):
+        count = fn(images, int(bool(general)), C.byref(chunk), steps)
+        if count < 0:
+            _check(count)
+        return [{"name": RESNET50_LAUNCH_NAMES[steps[5 * i]], "grid": (steps[5 * i + 1], steps[5 * i + 2]),
+                 "tile": (steps[5 * i + 3], steps[5 * i + 4]) if steps[5 * i + 3] else None} for i in range(count)]
+
+    first = run(n)   # the first run of the batch: min(n, chunk) images, and the chunk size in force
+    size = chunk.value
+    full, rest = divmod(n, size)
+    return {"chunk": size, "chunks": [first] * max(full, 1) + ([run(rest)] if full and rest else [])}
 
 
 def _resnet50_keys():

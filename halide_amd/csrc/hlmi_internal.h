@@ -482,6 +482,20 @@ extern "C" int hlmi_debug_resnet50_layer(halide_buffer_t *input, halide_buffer_t
 // resnet50.hip: the max pool (k x k window) and the tail (mean over W x H, fc with weights [N, C] and bias [N], softmax) at any size
 extern "C" int hlmi_debug_resnet50_maxpool(halide_buffer_t *input, int32_t k, int32_t stride, int32_t pad, halide_buffer_t *output);
 extern "C" int hlmi_debug_resnet50_tail(halide_buffer_t *input, halide_buffer_t *fc_weights, halide_buffer_t *fc_bias, halide_buffer_t *output);
+// resnet50.hip, the batched siblings (resnet50_batch is a library extension: the reference has no such generator).  The whole call on the
+// general kernel; the layer hook over N images, input [CI, W, H, N], residual and output [CO, OW, OH, N], with `variant` 0 = the plan's
+// choice, 1 = the general kernel, 2 = the 64 x 64 MFMA tile, 3 = the 64 x 128 one, anything else -8; the pool hook [C, W, H, N] ->
+// [C, OW, OH, N]; the tail hook [C, W, H, N] -> [classes, N].
+extern "C" int hlmi_resnet50_batch_general(void **argv);
+extern "C" int hlmi_debug_resnet50_layer_batch(halide_buffer_t *input, halide_buffer_t *weights, halide_buffer_t *gamma, halide_buffer_t *beta,
+                                               halide_buffer_t *mu, halide_buffer_t *sig, halide_buffer_t *residual, int32_t stride, int32_t pad, int32_t mode,
+                                               int32_t variant, halide_buffer_t *output);
+extern "C" int hlmi_debug_resnet50_maxpool_batch(halide_buffer_t *input, int32_t k, int32_t stride, int32_t pad, halide_buffer_t *output);
+extern "C" int hlmi_debug_resnet50_tail_batch(halide_buffer_t *input, halide_buffer_t *fc_weights, halide_buffer_t *fc_bias, halide_buffer_t *output);
+// resnet50.hip, no device needed: the 57 launches of the first run of a batch of n_images >= 1 images (min(n_images, *chunk) of them) as steps[57][5] = (launch: 0
+// resnet50_conv_mfma, 1 resnet50_conv_general, 2 resnet50_maxpool, 3 resnet50_avgpool, 4 resnet50_fc, 5 resnet50_softmax, 6
+// resnet50_conv_mfma_wide; grid x; grid y; tile co; tile pixels) and *chunk = the images per run in force.  Returns the step count.
+extern "C" int hlmi_debug_resnet50_batch_plan(int32_t n_images, int32_t general_only, int32_t *chunk, int32_t *steps);
 
 // hannk_conv.hip: the named entry point of apps/hannk's op library ("tile_conv_filter_uint8", "conv_u8_u8_u8", "conv_u8_u8_i16",
 // "depthwise_conv_uint8", "depthwise_conv_broadcast_uint8", "depthwise_conv_shallow_uint8") in argv form with one thread per output running the contract's loops as

@@ -449,6 +449,24 @@ def resnet50(input: torch.Tensor, params: list[torch.Tensor]) -> torch.Tensor:
     return out
 
 
+@torch.library.custom_op("hlmi::resnet50_batch", mutates_args=())
+def resnet50_batch(input: torch.Tensor, params: list[torch.Tensor]) -> torch.Tensor:
+    """resnet50 over N images per call (a library extension: the reference's generator has no batch dimension): (N, 224, 224, 3)
+    float32 images in the layout resnet50 takes for one, the same 267 parameters -> (N, 1000) float32; row n is bit for bit what
+    resnet50 gives image n.  float32 only."""
+    if len(params) != len(hl.RESNET50_PARAM_NAMES):
+        raise TypeError(f"resnet50_batch takes {len(hl.RESNET50_PARAM_NAMES)} parameters, not {len(params)}")
+    for t in (input, *params):
+        if t.dtype != torch.float32:
+            raise TypeError("resnet50_batch takes float32 tensors only")
+    if input.dim() != 4 or tuple(input.shape[1:]) != (224, 224, 3) or input.shape[0] < 1:
+        raise TypeError("resnet50_batch takes (N, 224, 224, 3) images, N >= 1")
+    out = torch.empty((input.shape[0], 1000), dtype=torch.float32, device=input.device)
+    with _Wrapped(input, *params, out) as bufs:
+        hl.resnet50_batch(bufs[0], bufs[1:-1], bufs[-1])
+    return out
+
+
 @torch.library.custom_op("hlmi::fft2d", mutates_args=())
 def fft2d(input: torch.Tensor, kind: str, gain: float) -> torch.Tensor:
     """apps/fft at any allowed size: kind "c2c_forward" / "c2c_inverse" take and return a complex array, "r2c" takes a real (N1, N0)
@@ -812,6 +830,11 @@ def _(A, B):
 @resnet50.register_fake
 def _(input, params):
     return input.new_empty((1000,))
+
+
+@resnet50_batch.register_fake
+def _(input, params):
+    return input.new_empty((input.shape[0], 1000))
 
 
 @fft2d.register_fake

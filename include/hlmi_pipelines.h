@@ -617,6 +617,22 @@ HLMI_DECLARE_AUX(halide_dgemm_transAB)
 int resnet50(HLMI_RN50_INPUTS(HLMI_RN50_PARAM) struct halide_buffer_t *final_output);
 HLMI_DECLARE_AUX(resnet50)
 
+/* resnet50_batch — a LIBRARY EXTENSION: the reference has no such generator (its resnet_50 has no batch dimension).  resnet50 over N images
+ * per call; the same 269 buffers in the same order, two of them with one more dimension:
+ *   input [3, 224, 224, N];   final_output [<= 1000, N];   the 267 parameter buffers exactly as resnet50 takes them.
+ * Contract: column n of final_output holds, bit for bit and NaN for NaN, what resnet50 writes for image n of input, in both canonical
+ * float forms.  Every chain, epilogue, pool, fc and softmax step of image n is resnet50's; no operation mixes two images.
+ * Protocol: resnet50's, with one more range, the images [bmin, bmin + N): dimension 1 of final_output where that buffer is known (real,
+ * or a query with a shape), else dimension 3 of input where that is known, else [0, 1).  input must cover that range in dimension 3 (-4)
+ * and may be larger or padded in any dimension; the class box of final_output (dimension 0) keeps resnet50's rule.  A bounds query
+ * answers every box, the image range included.  Checks and return codes are resnet50's, in its order.
+ * Any N >= 1 runs as ceil(N / C) runs of the launch plan over at most C images each, in order on the call's stream; C is 64 unless
+ * HLMI_RN50_BATCH_CHUNK (1 .. 64, read once per call; any other value is refused with -8) says otherwise.  The rule that every element
+ * of a buffer lies within 2^31 - 1 elements of its first (-5) applies PER CHUNK to input and final_output — C images and C columns,
+ * whatever N is — and to every other buffer as a whole. */
+int resnet50_batch(HLMI_RN50_INPUTS(HLMI_RN50_PARAM) struct halide_buffer_t *final_output);
+HLMI_DECLARE_AUX(resnet50_batch)
+
 /* apps/camera_pipe/camera_pipe_generator.cpp:219-228,622 — raw u16 Bayer -> u8 [W,H,3]. */
 int camera_pipe(struct halide_buffer_t *input, struct halide_buffer_t *matrix_3200,
                 struct halide_buffer_t *matrix_7000, float color_temp, float gamma, float contrast,
