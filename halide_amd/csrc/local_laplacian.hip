@@ -290,26 +290,120 @@ __device__ __forceinline__ T pick4(T x, T y, T z, T w, int s) {
 // five alternating runs each): non-temporal input loads in both kernels, outLPyramid[0] stores and loads, output stores; the
 // level-1 and level-2 planes stay cached (non-temporal: slower).  On a stream that owns the device they cost 2-3 %, so the
 // kernels take it as a template parameter and the host asks the runtime which kind of stream it is on.
+//
+// Since the one-plane level 1 and ll_up0r the hint is no longer one boolean: ll_down01e, ll_up0h, ll_up0r (and ll_down_strip2's
+// chain_fit instances) take a MemPolicy, one flavour per ACCESS CLASS.  A policy is a word of hex digits, digit i = the flavour of
+// class i:
+//   digit  class                                                              bytes per lane   frame-queue policy
+//   0      in_down  input loads of ll_down01e (load_raw)                      8                sc1 (was nt: +4.1 %)
+//   1      in_up    input loads of the up kernel (load_frame)                 4                nt
+//   2      l0_st    outLPyramid[0] stores of ll_down01e (emit_store)          16               nt
+//   3      l0_ld    outLPyramid[0] loads of the up kernel (load_frame)        8                nt
+//   4      out_st   output stores of the up kernel (st_frame2)                4                nt
+//   5      l1_st    outLPyramid[1] stores of ll_down01e (em1_store)           8                plain
+//   6      l1_ld    outLPyramid[1] loads of the up kernel (load_row1, s_edge) 4                plain
+//   7      l2_st    level-2 plane stores of ll_down01e                        4                plain
+//   8      l23_ld   level-2 / 3 loads of ll_down_strip2 (chain_fit) and of    16 / 4 and 8     plain
+//                   the up kernel's phase 0
+// Flavours: 0 plain, 1 nt (__builtin_nontemporal_*), 2 sc1 (a raw buffer access with the sc1 bit: the compiler counts it in vmcnt
+// like the other two, which the kernels' hand-placed waits rely on).  On gfx950 nt and sc1 loads bypass the CU's L1 only; plain and
+// nt stores keep the line in the XCD's L2, an sc1 store drops it — at the price of one fabric write per store instruction, which is
+// what a plain store costs only at 16 bytes per lane (8 bytes: 2.7 x, 4 bytes: 6 x per byte): st_flavour refuses sc1 below 16 bytes.
+// The device-stream policy is all plain (the former NT = false); the frame-queue policy is HLMI_LL_POLICY, by default the word
+// below.  Other words are built as variant libraries (make VARIANT=_pol<hex> EXTRA=-DHLMI_LL_POLICY=0x<hex>) and measured by
+// scripts/ll_mem_policy_sweep.py; profiles/NOTES.md ("memory policy per access class") has the sweep.  With the word 0x11111 the
+// kernels compile to the instructions they had under NT = true.  Measured from there on four frame queues (4K noise, bench.py, the
+// parent's library before every run, two calls of three runs): in_down sc1 126.1 -> 131.6 and 131.5 -> 136.4 Gpx/s (+4.1 %, every
+// run above the parent's maximum in both calls) — the one word that met the rule, and the default; in_down plain +1.8 %, l0_st sc1
+// +1.5 .. 2.0 %, l23_ld sc1 +1.0 .. 1.6 %, each inside the parent's spread, and none of them adds to in_down sc1 (0x11212 +2.3 %,
+// 0x200011112 +3.1 %, 0x200011212 +1.2 %).  Losers: in_up plain / sc1 -1 %, out_st plain -2 %, l0_ld plain / sc1 and l0_st plain 0,
+// l1_st nt -0.7 .. -1.6 %, l1_ld nt -2 %, l2_st nt -2.5 .. -3 %, l23_ld nt -5 %.
+enum MemFlavour : unsigned { MF_PLAIN = 0, MF_NT = 1, MF_SC1 = 2 };
+template<unsigned long long W>
+struct MemPolicy {
+    static constexpr unsigned long long word = W;
+    static constexpr MemFlavour digit(int i) { return (MemFlavour)((W >> (4 * i)) & 0xfull); }
+    static constexpr MemFlavour in_down = digit(0), in_up = digit(1), l0_st = digit(2), l0_ld = digit(3), out_st = digit(4),
+                                l1_st = digit(5), l1_ld = digit(6), l2_st = digit(7), l23_ld = digit(8);
+    static_assert((W >> 36) == 0 && in_down <= MF_SC1 && in_up <= MF_SC1 && l0_st <= MF_SC1 && l0_ld <= MF_SC1 && out_st <= MF_SC1 &&
+                  l1_st <= MF_SC1 && l1_ld <= MF_SC1 && l2_st <= MF_SC1 && l23_ld <= MF_SC1, "nine classes, flavours 0 .. 2");
+};
+#ifndef HLMI_LL_POLICY
+#define HLMI_LL_POLICY 0x000011112
+#endif
+using LlDeviceStreamPolicy = MemPolicy<0>;
+using LlFrameQueuePolicy = MemPolicy<HLMI_LL_POLICY>;
+template<bool FRAME_QUEUE>
+using LlPolicyOf = std::conditional_t<FRAME_QUEUE, LlFrameQueuePolicy, LlDeviceStreamPolicy>;
+
+// sc1 accesses: `wave-uniform base + 32-bit byte offset` through a raw buffer descriptor over the base (no stride, no bound below
+// 4 GB: the same addresses the plain form reaches)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t sc1_rsrc(const void *ubase) {
+    const uint64_t a = (uint64_t)(size_t)ubase;
+    const uint64_t u = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a) |
+                       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(a >> 32)) << 32);
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>((size_t)u), 0, -1, 0x00027000);
+}
+constexpr int AUX_SC1 = 16;   // gfx940+: aux bit 0 = sc0, bit 1 = nt, bit 4 = sc1
+// V: a 4-, 8- or 16-byte scalar or vector.  ubase / byte_off: see sc1_rsrc; plain and nt read ubase + byte_off as one pointer.
+template<MemFlavour F, typename V>
+__device__ __forceinline__ V ld_flavour(const void *ubase, uint32_t byte_off) {
+    static_assert(sizeof(V) == 4 || sizeof(V) == 8 || sizeof(V) == 16, "vector loads of one, two or four dwords");
+    if constexpr (F == MF_SC1) {
+        typedef uint32_t u2_t __attribute__((ext_vector_type(2)));
+        typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
+        if constexpr (sizeof(V) == 4) return __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b32(sc1_rsrc(ubase), (int)byte_off, 0, AUX_SC1));
+        else if constexpr (sizeof(V) == 8) return __builtin_bit_cast(V, (u2_t)__builtin_amdgcn_raw_buffer_load_b64(sc1_rsrc(ubase), (int)byte_off, 0, AUX_SC1));
+        else return __builtin_bit_cast(V, (u4_t)__builtin_amdgcn_raw_buffer_load_b128(sc1_rsrc(ubase), (int)byte_off, 0, AUX_SC1));
+    } else {
+        const V *q = reinterpret_cast<const V *>(reinterpret_cast<const char *>(ubase) + byte_off);
+        if constexpr (F == MF_NT) return __builtin_nontemporal_load(q);
+        else return *q;
+    }
+}
+template<MemFlavour F, typename V>
+__device__ __forceinline__ void st_flavour(V v, void *ubase, uint32_t byte_off) {
+    static_assert(F != MF_SC1 || sizeof(V) >= 16, "an sc1 store below 16 bytes per lane is one fabric write per 4 or 8 bytes");
+    if constexpr (F == MF_SC1) {
+        typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4_t, v), sc1_rsrc(ubase), (int)byte_off, 0, AUX_SC1);
+    } else {
+        V *q = reinterpret_cast<V *>(reinterpret_cast<char *>(ubase) + byte_off);
+        if constexpr (F == MF_NT) __builtin_nontemporal_store(v, q);
+        else *q = v;
+    }
+}
+
 typedef unsigned short us4_t __attribute__((ext_vector_type(4)));
-template<bool NT = false>
+template<MemFlavour F = MF_PLAIN>
 __device__ __forceinline__ ushort4 ld_frame4(const uint16_t *p) {
-    if (NT) {
+    static_assert(F != MF_SC1, "sc1: the (uniform base, byte offset) form below");
+    if (F == MF_NT) {
         us4_t v = __builtin_nontemporal_load(reinterpret_cast<const us4_t *>(p));
         return make_ushort4(v.x, v.y, v.z, v.w);
     }
     return *reinterpret_cast<const ushort4 *>(p);
 }
-template<bool NT = false>
+template<MemFlavour F>
+__device__ __forceinline__ ushort4 ld_frame4(const uint16_t *ubase, uint32_t byte_off) {
+    const us4_t v = ld_flavour<F, us4_t>(ubase, byte_off);
+    return make_ushort4(v.x, v.y, v.z, v.w);
+}
+template<MemFlavour F = MF_PLAIN>
 __device__ __forceinline__ ushort2 ld_frame2(const void *sbase, uint32_t byte_off) {
-    const uint32_t *q = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(sbase) + byte_off);
-    const uint32_t w = NT ? __builtin_nontemporal_load(q) : *q;
+    uint32_t w;
+    if constexpr (F == MF_SC1) {
+        w = ld_flavour<F, uint32_t>(sbase, byte_off);
+    } else {
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(sbase) + byte_off);
+        w = F == MF_NT ? __builtin_nontemporal_load(q) : *q;
+    }
     return make_ushort2((uint16_t)(w & 0xffffu), (uint16_t)(w >> 16));
 }
-template<bool NT = false>
+template<MemFlavour F = MF_PLAIN>
 __device__ __forceinline__ void st_frame2(void *p, uint16_t a, uint16_t b) {
     const uint32_t w = (uint32_t)a | ((uint32_t)b << 16);
-    if (NT) __builtin_nontemporal_store(w, reinterpret_cast<uint32_t *>(p));
-    else *reinterpret_cast<uint32_t *>(p) = w;
+    st_flavour<F>(w, p, 0u);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -321,13 +415,17 @@ struct Levels {
     float v[MAX_K];      // level_k = k * (1 / (levels - 1))  (:41), kernel-argument (scalar) operands
 };
 
-template<bool VEC, bool NT = false>
+template<bool VEC, MemFlavour F = MF_PLAIN>
 __device__ __forceinline__ void load_raw(Raw &r, const uint16_t *__restrict__ rp, long co0, long co1, long co2,
                                          int oq, const int (&xo)[4]) {
-    if (VEC) {
-        r.c0 = ld_frame4<NT>(rp + co0 + oq);
-        r.c1 = ld_frame4<NT>(rp + co1 + oq);
-        r.c2 = ld_frame4<NT>(rp + co2 + oq);
+    if constexpr (VEC && F == MF_SC1) {   // rp and the channel offsets are wave-uniform, the quad's column is the lane's
+        r.c0 = ld_frame4<F>(rp + co0, 2u * (uint32_t)oq);
+        r.c1 = ld_frame4<F>(rp + co1, 2u * (uint32_t)oq);
+        r.c2 = ld_frame4<F>(rp + co2, 2u * (uint32_t)oq);
+    } else if (VEC) {
+        r.c0 = ld_frame4<F>(rp + co0 + oq);
+        r.c1 = ld_frame4<F>(rp + co1 + oq);
+        r.c2 = ld_frame4<F>(rp + co2 + oq);
     } else {
         r.c0 = make_ushort4(rp[co0 + xo[0]], rp[co0 + xo[1]], rp[co0 + xo[2]], rp[co0 + xo[3]]);
         r.c1 = make_ushort4(rp[co1 + xo[0]], rp[co1 + xo[1]], rp[co1 + xo[2]], rp[co1 + xo[3]]);
@@ -948,7 +1046,7 @@ __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementw
 __device__ __forceinline__ f2 mad_2(f2 a, f2 b, f2 c) { return dev::CANON_FMA ? fma2(a, b, c) : a * b + c; }
 __device__ __forceinline__ f2 mad2_2(f2 a, f2 b, f2 c, f2 d) { return dev::CANON_FMA ? fma2(a, b, c * d) : a * b + c * d; }
 
-template<bool ODD0, bool ODD1, bool B1, bool EXCH, bool NT, bool EM1>
+template<bool ODD0, bool ODD1, bool B1, bool EXCH, class MP, bool EM1>
 __global__ __launch_bounds__(D0_THREADS, EM1 ? 1 : 2) void ll_down01e(D01EArgs pe, Geometry gm, Levels lev) {
     const D01Args &p = pe.d;
     LL_RESIDENCY(0);
@@ -1025,7 +1123,7 @@ __global__ __launch_bounds__(D0_THREADS, EM1 ? 1 : 2) void ll_down01e(D01EArgs p
     constexpr bool EDGE = decltype(edge_tag)::value;
     auto load_row = [&](Raw &r, int y_abs) {
         const uint16_t *rp = p.in + (long)(dev::clampi(y_abs - gm.iy0, 0, ih)) * p.in_sy;
-        load_raw<true, NT>(r, rp, p.co0, p.co1, p.co2, qs.oq, xo);
+        load_raw<true, MP::in_down>(r, rp, p.co0, p.co1, p.co2, qs.oq, xo);
     };
     auto u16s = [&](const ushort4 &c, uint16_t (&o)[4]) {
         const uint2 w = __builtin_bit_cast(uint2, c);
@@ -1217,9 +1315,13 @@ __global__ __launch_bounds__(D0_THREADS, EM1 ? 1 : 2) void ll_down01e(D01EArgs p
     auto emit_store = [&](int y, const float (&r)[4]) {
         if (em_ok && y >= pe.oy0 && y < pe.oy0 + pe.oh) {
             typedef float f4_t __attribute__((ext_vector_type(4)));
-            f4_t *const dst = reinterpret_cast<f4_t *>(em_col + (size_t)(y - pe.oy0) * iw);
-            if (NT) __builtin_nontemporal_store(f4_t{r[0], r[1], r[2], r[3]}, dst);
-            else *dst = f4_t{r[0], r[1], r[2], r[3]};
+            if constexpr (MP::l0_st == MF_SC1) {   // the row is wave-uniform, the quad's column the lane's
+                st_flavour<MP::l0_st>(f4_t{r[0], r[1], r[2], r[3]}, pe.outl0 + (size_t)(y - pe.oy0) * iw, 4u * (uint32_t)(q0 - gm.ix0));
+            } else {
+                f4_t *const dst = reinterpret_cast<f4_t *>(em_col + (size_t)(y - pe.oy0) * iw);
+                if (MP::l0_st == MF_NT) __builtin_nontemporal_store(f4_t{r[0], r[1], r[2], r[3]}, dst);
+                else *dst = f4_t{r[0], r[1], r[2], r[3]};
+            }
         }
     };
     // ---- what the collapse of level 1 reads at the lane's two coarse pixels of one level-1 row (:63-72): gPyramid[1](., ., li1),
@@ -1259,8 +1361,13 @@ __global__ __launch_bounds__(D0_THREADS, EM1 ? 1 : 2) void ll_down01e(D01EArgs p
         if (e1_ok) {
             const int y = 2 * U - 1 - p.loy1;
             float *drow = p.g1 + (long)y * p.ws1 + off1;
-            if (y >= 0 && y < p.h1) *reinterpret_cast<float2 *>(drow) = vo;
-            if (y + 1 >= 0 && y + 1 < p.h1) *reinterpret_cast<float2 *>(drow + p.ws1) = ve;
+            if constexpr (MP::l1_st == MF_PLAIN) {
+                if (y >= 0 && y < p.h1) *reinterpret_cast<float2 *>(drow) = vo;
+                if (y + 1 >= 0 && y + 1 < p.h1) *reinterpret_cast<float2 *>(drow + p.ws1) = ve;
+            } else {
+                if (y >= 0 && y < p.h1) st_flavour<MP::l1_st>(f2{vo.x, vo.y}, drow, 0u);
+                if (y + 1 >= 0 && y + 1 < p.h1) st_flavour<MP::l1_st>(f2{ve.x, ve.y}, drow + p.ws1, 0u);
+            }
         }
     };
     L1Row dl_o0 = {}, dl_o1 = {}, dl_e = {};   // EM1 delay line: level-1 rows 2U - 1, 2U + 1 and 2U at the step that completes level-2 row U
@@ -1321,7 +1428,7 @@ __global__ __launch_bounds__(D0_THREADS, EM1 ? 1 : 2) void ll_down01e(D01EArgs p
                     const float py = lane_prev(r.y), nx = lane_next(r.x);
                     o = down4_tail(py, r.x, r.y, nx);
                 }
-                if (out2 && st2_ok) d2[(size_t)k * p.ps2] = o;
+                if (out2 && st2_ok) st_flavour<MP::l2_st>(o, d2 + (size_t)k * p.ps2, 0u);
                 st2[(2 * k + 1) * 64] = c;
                 if (EM1 && k < KCH) {
                     ringU[(2 * k) * 64] = o;
@@ -1484,7 +1591,7 @@ __global__ __launch_bounds__(D0_THREADS, EM1 ? 1 : 2) void ll_down01e(D01EArgs p
                 const float py = lane_prev(r.y), nx = lane_next(r.x);
                 o = down4_tail(py, r.x, r.y, nx);
             }
-            if (st2_ok) d2[(size_t)k * p.ps2] = o;
+            if (st2_ok) st_flavour<MP::l2_st>(o, d2 + (size_t)k * p.ps2, 0u);
             if (EM1 && k < KCH) ring[(2 * k + (B & 1)) * 64] = o;
         }
         if (EM1) {
@@ -1637,7 +1744,10 @@ __global__ __launch_bounds__(256) void ll_down_strip2(Strip2Args p) {
     const uint32_t lane_off = 4u * (uint32_t)qs.oq;
     auto request = [&](int i) {
         const size_t row = (size_t)dev::clampi(2 * T0 - 1 + i - p.sloy, 0, p.sh - 1) * p.sws;
-        return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(su + row) + lane_off);
+        // FIT: the frame-queue policy's flavour of the level-2 / 3 loads (MemPolicy, above ld_frame4)
+        typedef float f4_t __attribute__((ext_vector_type(4)));
+        const f4_t v = ld_flavour<LlPolicyOf<FIT>::l23_ld, f4_t>(su + row, lane_off);
+        return make_float4(v.x, v.y, v.z, v.w);
     };
     auto select = [&](float4 &v) {
         v = make_float4(pick4(v.x, v.y, v.z, v.w, qs.sel[0]), pick4(v.x, v.y, v.z, v.w, qs.sel[1]),
@@ -2207,9 +2317,18 @@ __global__ __launch_bounds__(256) void ll_up0(Up0Args p, Geometry gm) {
 //     correctly-rounded refinement per numerator (div3_by below)
 struct __attribute__((packed, aligned(4))) F2U { float x, y; };
 struct __attribute__((packed, aligned(4))) F3U { float x, y, z; };
-template<typename T>
+template<typename T, MemFlavour F = MF_PLAIN>
 __device__ __forceinline__ T ld_su(const void *sbase, uint32_t byte_off) {  // sbase wave-uniform
-    return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(sbase) + byte_off);
+    if constexpr (F == MF_PLAIN) {
+        return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(sbase) + byte_off);
+    } else if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, ld_flavour<F, uint32_t>(sbase, byte_off));
+    } else {
+        static_assert(sizeof(T) == 8, "float and F2U");
+        typedef f2 f2u_t __attribute__((aligned(4)));   // F2U's alignment
+        if constexpr (F == MF_SC1) return __builtin_bit_cast(T, ld_flavour<F, f2>(sbase, byte_off));
+        else return __builtin_bit_cast(T, (f2)__builtin_nontemporal_load(reinterpret_cast<const f2u_t *>(reinterpret_cast<const char *>(sbase) + byte_off)));
+    }
 }
 
 // q[i] = n[i] / d, correctly rounded (identical to IEEE `/` up to the sign of a zero quotient, which the u16 cast
@@ -2442,13 +2561,13 @@ constexpr int U0H_T2 = 68;     // row stride of the level-2 tile
 // into a few floats of LDS of its own).  The horizontal lerps of a coarse row are formed once and kept for the four output rows
 // that use them.  Phase 1, its barrier and U0_TS x (RU + 2) floats of LDS go; every operation and operand stays.
 // The body is local_laplacian_up0h_body.h, shared as text (see there).
-template<bool NT, bool EM1, int CH = 2>  // CH: tile values a thread requests at a time in the two tile phases (1: 102.0, 2: 101.1, 4: 102.4 us per
+template<class MP, bool EM1, int CH = 2>  // CH: tile values a thread requests at a time in the two tile phases (1: 102.0, 2: 101.1, 4: 102.4 us per
                                          // frame on one stream — 4 costs occupancy: 124 VGPRs against 66)
 __global__ __launch_bounds__(256) void ll_up0h(Up0HArgs ph, Geometry gm) {
     constexpr bool ROWS1 = false;
 #include "local_laplacian_up0h_body.h"
 }
-template<bool NT>
+template<class MP>
 __global__ __launch_bounds__(256) void ll_up0r(Up0HArgs ph, Geometry gm) {
     constexpr bool EM1 = true, ROWS1 = true;
     constexpr int CH = 2;
@@ -2480,7 +2599,8 @@ const ArgTable ll_table("local_laplacian", {
 //                 stream's CUs; otherwise 8 x the device's                                                 test_hip_emit_launch_geometries_match_oracle
 //   NO_VEC        0                                         1: the scalar frame-access kernels only        none
 //   EMIT          1                                         0: ll_down01f / ll_up0f (materialised level 1) test_hip_emit_and_materialised_dataflows_match_oracle
-//   NT            1 on a frame queue, else 0                non-temporal frame / outLPyramid[0] accesses   test_hip_emit_launch_geometries_match_oracle
+//   NT            1 on a frame queue, else 0                the frame-queue MemPolicy (a flavour per       test_hip_emit_launch_geometries_match_oracle,
+//                                                           access class, above ld_frame4; 0: all plain)   tests/test_local_laplacian_mem_policy.py
 //   FUSE_UP2      1                                         ll_up0h collapses level 2 (0: ll_up:2 launch)  test_hip_emit_launch_geometries_match_oracle
 //   D01_EXCH      1                                         ll_down01* units swap seam rows through LDS    test_hip_fused_levels_1_and_2_match_oracle
 //   D01_PAD_LDS   ll_down01e on a frame queue: -1 (one      bytes of unused LDS per ll_down01* workgroup   none (scripts/residency_probe.py)
@@ -2930,7 +3050,8 @@ int ll_stage_down0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t s
     dim3 grid((a.nunits + WPB - 1) / WPB);
     if (pl.emit) {
         // input read once; outLPyramid[0] (4 B per output pixel), three level-1 planes and K + 1 level-2 planes written
-        // (emit1: one level-1 plane, outLPyramid[1])
+        // (emit1: one level-1 plane, outLPyramid[1]).  MemPolicy classes of these bytes, with the frame-queue flavour: in_down (sc1: the
+        // loads pass the CU's L1 by and mark nothing as streaming, +4.1 % against nt), l0_st (nt), l1_st and l2_st (plain)
         timing_note_bytes(6.0 * iw * (gm.iy1 - gm.iy0 + 1) + 4.0 * iw * f.oh + 4.0 * (pl.emit1 ? 1.0 : 3.0) * d.w * d.h +
                           4.0 * (levels + 1) * e.w * e.h);
         D01EArgs ae;
@@ -2938,7 +3059,7 @@ int ll_stage_down0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t s
         ae.nsx_magic = a.nsx == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)a.nsx + 1ull);
         ae.last2 = e.loy + e.h - 1;
         return with_flags([&](auto O0, auto O1, auto B, auto EX, auto NT, auto E1) -> int {
-            HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0.value, O1.value, B.value, EX.value, NT.value, E1.value>), grid, block, pl.d0.lds, ae,
+            HLMI_LAUNCH(uc, "ll_down01", st, (ll_down01e<O0.value, O1.value, B.value, EX.value, LlPolicyOf<NT.value>, E1.value>), grid, block, pl.d0.lds, ae,
                         gm, lev);
             return 0;
         }, d.odd, e.odd, pl.b1, pl.d0.exch, pl.nt, pl.emit1);
@@ -3056,7 +3177,8 @@ int ll_stage_up0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st)
     if (pl.emit) {
         // input read + output written (u16 x 3 channels), outLPyramid[0] read, three planes of level 1, per level-2 pixel two
         // planes of g_2 + outG_2
-        // (emit1: one plane of level 1, outLPyramid[1])
+        // (emit1: one plane of level 1, outLPyramid[1]).  MemPolicy classes of these bytes, with the frame-queue flavour: in_up, l0_ld
+        // and out_st (nt), l1_ld and l23_ld (plain)
         timing_note_bytes(2.0 * (3 + nc) * ow * oh + 4.0 * ow * oh + 4.0 * (pl.emit1 ? 1.0 : 3.0) * n1 + 4.0 * 3.0 * n2);
         Up0HArgs ph;
         ph.u = p, ph.outl0 = b.outl0, ph.l0_ws = gm.ix1 - gm.ix0 + 1;
@@ -3064,12 +3186,12 @@ int ll_stage_up0(void *uc, const LlPlan &pl, const LlBuffers &b, hipStream_t st)
         ph.g3 = b.g[3], ph.out3 = b.outg[3], ph.lox3 = lv[3].lox, ph.loy3 = lv[3].loy, ph.ws3 = lv[3].ws, ph.ps3 = lv[3].ps;
         if (pl.up1_rows) {
             return with_flags([&](auto NT) -> int {
-                HLMI_LAUNCH(uc, "ll_up0r", st, (ll_up0r<NT.value>), grid, block, pl.up0_lds, ph, gm);
+                HLMI_LAUNCH(uc, "ll_up0r", st, (ll_up0r<LlPolicyOf<NT.value>>), grid, block, pl.up0_lds, ph, gm);
                 return 0;
             }, pl.nt);
         }
         return with_flags([&](auto NT, auto E1) -> int {
-            HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0h<NT.value, E1.value>), grid, block, pl.up0_lds, ph, gm);
+            HLMI_LAUNCH(uc, "ll_up0", st, (ll_up0h<LlPolicyOf<NT.value>, E1.value>), grid, block, pl.up0_lds, ph, gm);
             return 0;
         }, pl.nt, pl.emit1);
     }

@@ -1,6 +1,8 @@
 // The body of ll_up0h and ll_up0r (local_laplacian.hip), included into both kernels: the text between the braces of
-//     template<bool NT, bool EM1, int CH> __global__ void ll_up0h(Up0HArgs ph, Geometry gm)      with ROWS1 = false
-//     template<bool NT>                   __global__ void ll_up0r(Up0HArgs ph, Geometry gm)      with EM1 = ROWS1 = true, CH = 2
+//     template<class MP, bool EM1, int CH> __global__ void ll_up0h(Up0HArgs ph, Geometry gm)     with ROWS1 = false
+//     template<class MP>                   __global__ void ll_up0r(Up0HArgs ph, Geometry gm)     with EM1 = ROWS1 = true, CH = 2
+// MP: the MemPolicy (local_laplacian.hip, above ld_frame4) — the flavours of the input and outLPyramid[0] loads and the output stores of
+// the row loop, of the outLPyramid[1] loads (EM1) and of phase 0's level-2 / 3 loads.  The three-plane phase 1 (EM1 off) stays plain.
 // It is text and not a function the two kernels call because ll_up0h must compile to the instructions it had before ll_up0r
 // existed (the stream that owns the device runs it): as an inlined function the compiler commutes operands and schedules otherwise.
     static_assert(EM1 || !ROWS1, "ROWS1 adds the stored outLPyramid[1] plane");
@@ -59,6 +61,12 @@
         const uint32_t m2 = (4194304u + (uint32_t)n2x - 1u) / (uint32_t)n2x;
         const int c3y0 = dev::fdiv2(c2y0 - 1);
         const uint32_t row2 = (uint32_t)((c2y0 - p.loy2) * p.ws2), row3 = (uint32_t)((c3y0 - ph.loy3) * ph.ws3);
+        auto taps23 = [](const float *base, uint32_t plane_bytes, const Taps32 &t) {   // taps_at with the policy's flavour
+            const F2U lo = ld_su<F2U, MP::l23_ld>(base, plane_bytes + t.b), hi = ld_su<F2U, MP::l23_ld>(base, plane_bytes + t.a);
+            UpTaps r;
+            r.bb = lo.x, r.ba = lo.y, r.ab = hi.x, r.aa = hi.y;
+            return r;
+        };
         for (int e0 = threadIdx.x; e0 < n2; e0 += 256 * CH) {
             int X2[CH], Y2[CH];
             uint32_t ti[CH];
@@ -74,9 +82,9 @@
                 ok[i] = e < n2, ti[i] = mul24(ty, U0H_T2) + tx;
                 X2[i] = c2x0 + (int)tx, Y2[i] = c2y0 + (int)ty;
                 ob[i] = (row2 + mul24(ty, (uint32_t)p.ws2) + (uint32_t)(X2[i] - p.lox2)) << 2;
-                inG[i] = ld_su<float>(p.g2, (uint32_t)gm.K * ps2b + ob[i]);
+                inG[i] = ld_su<float, MP::l23_ld>(p.g2, (uint32_t)gm.K * ps2b + ob[i]);
                 t3[i] = tap_bytes(row3, c3y0, ph.lox3, ph.ws3, X2[i], Y2[i]);
-                o3[i] = taps_at(ph.out3, 0u, t3[i]);
+                o3[i] = taps23(ph.out3, 0u, t3[i]);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -84,9 +92,9 @@
                 const float level = inG[i] * gm.Km1;
                 const int li = dev::clampi((int)level, 0, gm.K - 2);
                 lf[i] = level - (float)li;
-                ga[i] = ld_su<float>(p.g2, (uint32_t)li * ps2b + ob[i]), gb[i] = ld_su<float>(p.g2, (uint32_t)(li + 1) * ps2b + ob[i]);
-                t0[i] = taps_at(ph.g3, (uint32_t)li * ps3b, t3[i]);
-                t1[i] = taps_at(ph.g3, (uint32_t)(li + 1) * ps3b, t3[i]);
+                ga[i] = ld_su<float, MP::l23_ld>(p.g2, (uint32_t)li * ps2b + ob[i]), gb[i] = ld_su<float, MP::l23_ld>(p.g2, (uint32_t)(li + 1) * ps2b + ob[i]);
+                t0[i] = taps23(ph.g3, (uint32_t)li * ps3b, t3[i]);
+                t1[i] = taps23(ph.g3, (uint32_t)(li + 1) * ps3b, t3[i]);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -116,7 +124,7 @@
                     const uint32_t ec = (uint32_t)min(e, n1 - 1), ty = mul24(ec, M1) >> 22, tx = ec - mul24(ty, U0_TW);
                     ok[i] = e < n1 && cx0 + (int)tx <= p.rx1_1, ti[i] = mul24(ty, U0_TS) + tx;
                     cx[i] = min(cx0 + (int)tx, p.rx1_1), cy[i] = cy0 + (int)ty;
-                    outL[i] = ld_su<float>(p.g1, (row1 + mul24(ty, (uint32_t)p.ws1) + (uint32_t)(cx[i] - p.lox1)) << 2);
+                    outL[i] = ld_su<float, MP::l1_ld>(p.g1, (row1 + mul24(ty, (uint32_t)p.ws1) + (uint32_t)(cx[i] - p.lox1)) << 2);
                 }
 #pragma unroll
                 for (int i = 0; i < CH; i++) {
@@ -208,10 +216,13 @@
         const int yc = min(y, y1 - 1);
         const uint16_t *irow = p.in + (long)(p.oy0 + yc - gm.iy0) * p.in_sy;
         const uint32_t ib = fresh(inb);
-        f.c0 = ld_frame2<NT>(irow + p.gco[0], ib), f.c1 = ld_frame2<NT>(irow + p.gco[1], ib), f.c2 = ld_frame2<NT>(irow + p.gco[2], ib);
-        {
+        f.c0 = ld_frame2<MP::in_up>(irow + p.gco[0], ib), f.c1 = ld_frame2<MP::in_up>(irow + p.gco[1], ib), f.c2 = ld_frame2<MP::in_up>(irow + p.gco[2], ib);
+        if constexpr (MP::l0_ld == MF_SC1) {
+            const f2 v = ld_flavour<MF_SC1, f2>(ph.outl0 + (size_t)yc * ph.l0_ws, ROWS1 ? 2u * fresh(inb) : fresh(l0b));
+            f.l0 = make_float2(v.x, v.y);
+        } else {
             const f2 *const lp = reinterpret_cast<const f2 *>(reinterpret_cast<const char *>(ph.outl0 + (size_t)yc * ph.l0_ws) + (ROWS1 ? 2u * fresh(inb) : fresh(l0b)));   // ROWS1: one loop register less
-            const f2 v = NT ? __builtin_nontemporal_load(lp) : *lp;
+            const f2 v = MP::l0_ld == MF_NT ? __builtin_nontemporal_load(lp) : *lp;
             f.l0 = make_float2(v.x, v.y);
         }
     };
@@ -244,7 +255,7 @@
             if (y < y1) {
                 uint16_t *orow = p.out + (long)y * p.out_sy;
 #pragma unroll
-                for (int c = 0; c < 3; c++) st_frame2<NT>(reinterpret_cast<char *>(orow + (long)c * p.out_sc) + fresh(outb), res[c][0], res[c][1]);
+                for (int c = 0; c < 3; c++) st_frame2<MP::out_st>(reinterpret_cast<char *>(orow + (long)c * p.out_sc) + fresh(outb), res[c][0], res[c][1]);
             }
         };
         Frame f[U0H_PF];
@@ -279,7 +290,7 @@
             if (y < y1 && live) {
                 uint16_t *orow = p.out + (long)y * p.out_sy;
 #pragma unroll
-                for (int c = 0; c < 3; c++) st_frame2<NT>(reinterpret_cast<char *>(orow + (long)c * p.out_sc) + fresh(outb), res[c][0], res[c][1]);
+                for (int c = 0; c < 3; c++) st_frame2<MP::out_st>(reinterpret_cast<char *>(orow + (long)c * p.out_sc) + fresh(outb), res[c][0], res[c][1]);
             }
         };
         // Output rows Y = 2m - 1 and 2m lerp coarse rows m - 1 and m: a wave meets a new coarse row at every odd Y.  It keeps the
@@ -303,7 +314,7 @@
             const uint32_t row1 = (uint32_t)((m0 - p.loy1) * p.ws1);
             for (int e = lane; e < 2 * (mlast - m0 + 1); e += 64) {
                 const int m = m0 + (e >> 1), cx = (e & 1) ? min(c0 + 64, p.rx1_1) : c0 - 1;
-                const float outL = ld_su<float>(p.g1, (row1 + mul24((uint32_t)(e >> 1), (uint32_t)p.ws1) + (uint32_t)(cx - p.lox1)) << 2);
+                const float outL = ld_su<float, MP::l1_ld>(p.g1, (row1 + mul24((uint32_t)(e >> 1), (uint32_t)p.ws1) + (uint32_t)(cx - p.lox1)) << 2);
                 s_edge[e] = g1_at(s_out2 + mul24((uint32_t)(dev::fdiv2(m - 1) - c2y0), U0H_T2) + (dev::fdiv2(cx - 1) - c2x0), outL, cx, m);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -311,7 +322,7 @@
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
         auto load_row1 = [&](int m, float &l) {
-            l = ld_su<float>(p.g1 + (long)(min(m, mlast) - p.loy1) * p.ws1, fresh(c1b));   // row base wave-uniform
+            l = ld_su<float, MP::l1_ld>(p.g1 + (long)(min(m, mlast) - p.loy1) * p.ws1, fresh(c1b));   // row base wave-uniform
         };
         auto coarse_row = [&](int m, float l, float (&h)[2]) {
             const int mc = min(m, mlast);

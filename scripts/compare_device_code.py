@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device code of two builds of the library, object by object:
 
-    python scripts/compare_device_code.py <parent>/build/csrc build/csrc          (and .../csrc_nofma for the other form)
+    python scripts/compare_device_code.py <parent>/build/csrc build/csrc [OLD=NEW ...]     (and .../csrc_nofma for the other form)
 
 An object whose code object (the gfx950 entry of its .hip_fatbin section) is byte-identical says so.  Otherwise every symbol of the
 code object is compared by name: a kernel's machine code and its 64-byte kernel descriptor (VGPRs, AGPRs, SGPRs, scratch, LDS and
@@ -45,6 +45,15 @@ def digest(obj):
         d = {n: (t, sec, size, hashlib.sha256(body(n, off, size)).hexdigest()) for n, (t, sec, off, size) in syms.items() if not n.startswith("__hip_cuid_")}
         return hashlib.sha256(raw).hexdigest(), d
 a, b = sys.argv[1], sys.argv[2]
+# further arguments OLD=NEW: substrings of the second build's symbol names rewritten before the comparison, for a change that renames a
+# template argument and nothing else (e.g. NS_9MemPolicyILy69905EEE=Lb1E: the policy type where the parent had `bool NT = true`)
+renames = [r.split("=", 1) for r in sys.argv[3:]]
+def renamed(d):
+    out = {}
+    for n, v in d.items():
+        for old, new in renames: n = n.replace(old, new)
+        out[n] = v
+    return out
 bad = 0
 for f in sorted(os.listdir(a)):
     if not f.endswith(".o") or f == "resources.o": continue
@@ -53,6 +62,7 @@ for f in sorted(os.listdir(a)):
     except subprocess.CalledProcessError: 
         print(f"{f}: no device code"); continue
     hb, db = digest(pb)
+    db = renamed(db)
     if ha == hb:
         print(f"{f}: code object byte-identical ({len([n for n in da if n.endswith('.kd')])} kernels)"); continue
     ka, kb = {n for n in da if n.endswith(".kd")}, {n for n in db if n.endswith(".kd")}
